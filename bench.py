@@ -10,7 +10,7 @@ of the replicated scene and the step also exchanges the parameter gradients over
 Workload at N=1 (BASELINE.json metric "rasterized Gaussians/s fwd+bwd @1600x1200"):
 S3 = configs[2] stand-in: 1.5 M surfels on the faces of a 6x4x3 m room, 1600x1200, SH degree 3.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (re-exec through
 torch.distributed.run on 127.0.0.1); under torch.distributed.run it uses the ranks it is given.
@@ -48,6 +48,7 @@ from g4splat_amd.benchlib import (HBM_PEAK_GBS, SIMDS, STRONG_VIEWS, WORKLOADS, 
 from g4splat_amd import benchlib  # noqa: E402
 
 TRAINED_INFO = {}      # workload -> what trained_scene.scene_trained reported (printed under config.trained_scene)
+DUMP_ROWS, DUMP_PIXELS, DUMP_SEED = 65536, 262144, 20240   # --dump-outputs: sample sizes and the seed that picks them
 
 
 def parse_args(argv=None):
@@ -75,6 +76,11 @@ def parse_args(argv=None):
     ap.add_argument("--presized", action="store_true",
                     help="use g4s_rasterizer_forward_presized (no host read-back; extension) instead of the "
                          "reference-shaped forward -- for the step-time comparison in DESIGN.md, not the default")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the headline passes, write what the last timed step returned to its caller (forward maps, "
+                         "radii, num_rendered, gradients; rank 0) as DIR/<name>.npy in float32 / float64: per-Gaussian "
+                         "arrays on a fixed seeded sample of at most %d rows, the maps on one of at most %d pixels "
+                         "(< 64 MB in all), so that two builds can be compared output for output" % (DUMP_ROWS, DUMP_PIXELS))
     return ap.parse_args(argv)
 
 
@@ -221,6 +227,8 @@ def main():
 
     pstate = None
     pipe = None
+    last_step = [] if args.dump_outputs else None   # --dump-outputs: [forward outputs, backward outputs] of the latest step
+    dump_idx = dump_indices(P, N, device) if args.dump_outputs else None
     vis_union = torch.zeros((P,), dtype=torch.bool, device=device) if strong else None
 
     def views_of_step(i):
@@ -271,12 +279,14 @@ def main():
             out = dict(grad_out, accumulate="first", view_stats=side)
             if prepack:  # ... and so do the rows this rank sends to the owners, already in the all_to_all's layout
                 out["packed"] = reducer.prepack(radii > 0)
-        _C.rasterize_gaussians_backward(bg, dev["means3D"], radii, empty, dev["scales"], dev["rotations"],
-                                        1.0, empty, cam["view"], cam["proj"], cam["tanfovx"], cam["tanfovy"],
-                                        dL_dcolor, dL_dothers, dev["sh"], D, cam["campos"], geom, R, binning,
-                                        img, False, out=out)
+        grads = _C.rasterize_gaussians_backward(bg, dev["means3D"], radii, empty, dev["scales"], dev["rotations"],
+                                                1.0, empty, cam["view"], cam["proj"], cam["tanfovx"], cam["tanfovy"],
+                                                dL_dcolor, dL_dothers, dev["sh"], D, cam["campos"], geom, R, binning,
+                                                img, False, out=out)
         if dist is not None:
             exchange_step(radii)
+        if last_step is not None:
+            last_step[:] = [fw, grads]
         return [(R, radii)]
 
     def step_strong(i):
@@ -323,10 +333,12 @@ def main():
                 out["accumulate"] = True if j > 0 else "first"
                 if j > 0:
                     out["after"] = pipe.previous_view_done
-                _C.rasterize_gaussians_backward(bg, dev["means3D"], radii, empty, dev["scales"], dev["rotations"],
-                                                1.0, empty, cam["view"], cam["proj"], cam["tanfovx"],
-                                                cam["tanfovy"], dL_dcolor, dL_dothers, dev["sh"], D, cam["campos"],
-                                                fw[4], fw[0], fw[5], fw[6], False, out=out)
+                grads = _C.rasterize_gaussians_backward(bg, dev["means3D"], radii, empty, dev["scales"], dev["rotations"],
+                                                        1.0, empty, cam["view"], cam["proj"], cam["tanfovx"],
+                                                        cam["tanfovy"], dL_dcolor, dL_dothers, dev["sh"], D, cam["campos"],
+                                                        fw[4], fw[0], fw[5], fw[6], False, out=out)
+                if last_step is not None and j == L - 1:
+                    last_step[:] = [fw, grads]   # the parameter gradients are the step's sums (views of the bucket)
                 res.append((fw[0], radii))
         pipe.join()
         if dist is not None:
@@ -505,6 +517,9 @@ def main():
             break
     head = pick_headline(attempts)
     mem1 = torch.cuda.memory_stats(device)
+    dumped = None
+    if last_step is not None:  # the headline's last step, sampled on the GPU (the presized forward returns a capacity, no count)
+        dumped = sample_outputs(*last_step, *dump_idx, P, N, with_count=not (strong or args.presized))
 
     # Sustained throughput: the same step, issued back to back right behind the headline pass (no pause anywhere), for
     # >= --sustained-seconds and >= 500 steps; the engine clock is sampled from sysfs on the way.
@@ -689,10 +704,55 @@ def main():
         trained_scene=TRAINED_INFO.get(args.workload)))
     if lib_options:
         out["library_options"] = lib_options  # (an A/B run: not the library's defaults)
+    if dumped is not None:
+        write_outputs(args.dump_outputs, dumped)
     print(json.dumps(out))
     sys.stdout.flush()
     if dist is not None:
         dist.destroy_process_group()
+
+
+GRAD_NAMES = ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dtransMat", "dL_dsh", "dL_dscales",
+              "dL_drotations")  # rasterize_gaussians_backward's outputs, in order
+
+
+def dump_indices(P, N, device):
+    """--dump-outputs: the Gaussian rows and pixels that are written, the same in every run (DUMP_SEED); None = all."""
+    import torch
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    rows = torch.randperm(P, generator=g)[:DUMP_ROWS].sort().values.to(device) if P > DUMP_ROWS else None
+    pix = torch.randperm(N, generator=g)[:DUMP_PIXELS].sort().values.to(device) if N > DUMP_PIXELS else None
+    return rows, pix
+
+
+def sample_outputs(fw, grads, rows, pix, P, N, with_count=True):
+    """--dump-outputs: what the caller of one step receives (the forward's maps, radii and count, the backward's
+    gradients), reduced on the device to the fixed sample and copied out of the buffers the next steps overwrite."""
+    import torch
+    R, color, others, radii = fw[:4]
+
+    def pick(t, dim, idx):
+        return (t if idx is None else t.index_select(dim, idx)).to(torch.float32, copy=True)
+
+    out = {"color": pick(color.reshape(color.shape[0], N), 1, pix), "others": pick(others.reshape(others.shape[0], N), 1, pix),
+           "radii": pick(radii, 0, rows)}
+    if with_count:
+        out["num_rendered"] = torch.tensor([int(R)], dtype=torch.float64)
+    for name, t in zip(GRAD_NAMES, grads):
+        if t is not None:
+            out[name] = pick(t.reshape(P, -1), 0, rows)
+    return out
+
+
+def write_outputs(path, dumped):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in dumped.items():
+        a = np.ascontiguousarray(t.cpu().numpy())
+        np.save(os.path.join(path, name + ".npy"), a)
+        total += a.nbytes
+    print(f"[bench] --dump-outputs: {len(dumped)} arrays, {total / 2**20:.1f} MiB -> {path}", file=sys.stderr)
 
 
 def run_views_in_flight(lib, _C, device, dev, dcams, P, W, H, D, Vs, Rs, K, steps, dL_dcolor, dL_dothers):

@@ -177,3 +177,37 @@ def test_the_line_at_eight_ranks_strong_scaling():
     assert "8 views per step over 8 GPU(s): 1 per GPU" in d["config"]["workload"]
     m.update(exchange="allreduce", backend="gloo")
     assert benchlib.assemble_line(m)["config"]["parallelism"] == "view-dp8+gloo-visible-rows-allreduce"
+
+
+def test_dump_outputs_is_a_fixed_sample_under_64_mb(tmp_path):
+    """--dump-outputs at S3's sizes (CPU tensors stand in for the device's): the same rows and pixels in every run, values
+    copied out of the step's buffers, float32 / float64 only, under 64 MB in all; small outputs are written whole."""
+    import numpy as np
+    import torch
+    assert bench.parse_args(["--dump-outputs", str(tmp_path)]).dump_outputs == str(tmp_path)
+    assert bench.parse_args([]).dump_outputs is None
+    P, W, H, M = 1_500_000, 1600, 1200, 16
+    N = W * H
+    g = torch.Generator().manual_seed(0)
+    fw = (5_549_638, torch.rand(3, H, W, generator=g), torch.rand(7, H, W, generator=g),
+          torch.randint(0, 40, (P,), generator=g, dtype=torch.int32))
+    grads = [torch.rand(P, *s, generator=g) for s in ((3,), (3,), (1,), (3,), (9,), (M, 3), (2,), (4,))]
+    rows, pix = bench.dump_indices(P, N, "cpu")
+    assert torch.equal(rows, bench.dump_indices(P, N, "cpu")[0]) and torch.equal(pix, bench.dump_indices(P, N, "cpu")[1])
+    got = bench.sample_outputs(fw, grads, rows, pix, P, N)
+    assert set(got) == {"color", "others", "radii", "num_rendered"} | set(bench.GRAD_NAMES)
+    assert torch.equal(got["color"], fw[1].reshape(3, N)[:, pix]) and torch.equal(got["others"], fw[2].reshape(7, N)[:, pix])
+    assert torch.equal(got["radii"], fw[3][rows].float()) and float(got["num_rendered"][0]) == 5_549_638
+    assert torch.equal(got["dL_dsh"], grads[5].reshape(P, -1)[rows])
+    grads[0].zero_()  # the next step overwrites the buffers: the sample keeps its values
+    assert got["dL_dmeans2D"].abs().sum() > 0
+    bench.write_outputs(str(tmp_path), got)
+    files = sorted(os.listdir(tmp_path))
+    assert files == sorted(n + ".npy" for n in got)
+    arrays = [np.load(tmp_path / f) for f in files]
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays)
+    assert sum(os.path.getsize(tmp_path / f) for f in files) < 64 * 2**20
+    small = bench.sample_outputs((7, fw[1][:, :4, :5], fw[2][:, :4, :5], fw[3][:100]), [t[:100] for t in grads],
+                                 *bench.dump_indices(100, 20, "cpu"), 100, 20, with_count=False)
+    assert "num_rendered" not in small and torch.equal(small["color"], fw[1][:, :4, :5].reshape(3, 20))
+    assert torch.equal(small["dL_drotations"], grads[7][:100])
