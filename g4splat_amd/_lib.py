@@ -119,6 +119,35 @@ def last_error():
     return load().g4s_last_error().decode()
 
 
+# ---- argument helpers of the library calls -----------------------------------------------------------------------
+def ptr(t):
+    """A tensor's device address as a `void*` argument (None -> NULL)."""
+    return c_p(t.data_ptr() if t is not None else 0)
+
+
+def ptrs(tensors):
+    """HOST array of the tensors' device addresses (None -> NULL)."""
+    return (c_p * len(tensors))(*[t.data_ptr() if t is not None else 0 for t in tensors])
+
+
+def array(ctype, values):
+    """HOST array of `ctype` (c_int, ctypes.c_longlong, ctypes.c_double, ...) from a list."""
+    return (ctype * len(values))(*values)
+
+
+def stream(dev):
+    """The current torch stream of device `dev` as the `void* stream` argument."""
+    import torch
+    return c_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def call(name, *args):
+    """lib.<name>(*args); a non-zero status raises RuntimeError with the library's last error."""
+    rc = getattr(load(), name)(*args)
+    if rc != 0:
+        raise RuntimeError(f"{name} failed ({rc}): {last_error()}")
+
+
 OPTION_UNSET = -2147483648  # G4S_OPTION_UNSET
 
 

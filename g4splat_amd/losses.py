@@ -7,8 +7,6 @@
 One call computes the three scalars AND d loss / d image (two tiled HIP kernels + a fixed-order reduction);
 the autograd backward only scales the stored gradient.  `Ll1` and `ssim` are returned for logging (detached,
 as the reference uses them).  No CPU path."""
-import ctypes
-
 import torch
 
 from . import _lib
@@ -31,13 +29,8 @@ class _Photometric(torch.autograd.Function):
             grad = torch.empty_like(x) if need_grad else None
             nws = lib.g4s_photometric_workspace(W, H)
             ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            rc = lib.g4s_photometric_loss(W, H, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(y.data_ptr()),
-                                          float(lambda_dssim), ctypes.c_void_p(out3.data_ptr()),
-                                          ctypes.c_void_p(grad.data_ptr() if need_grad else 0),
-                                          ctypes.c_void_p(ws.data_ptr()), nws, stream)
-        if rc != 0:
-            raise RuntimeError(f"photometric_loss failed ({rc}): {_lib.last_error()}")
+            _lib.call("g4s_photometric_loss", W, H, _lib.ptr(x), _lib.ptr(y), float(lambda_dssim), _lib.ptr(out3),
+                      _lib.ptr(grad), _lib.ptr(ws), nws, _lib.stream(dev))
         ctx.grad = grad
         ctx.mark_non_differentiable(out3)
         return out3[0].clone(), out3
@@ -71,12 +64,8 @@ class _GeometryRegularizers(torch.autograd.Function):
             out2 = torch.empty(2, dtype=torch.float32, device=dev)
             nws = lib.g4s_geometry_regularizers_workspace(W, H)
             ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-            rc = lib.g4s_geometry_regularizers_forward(
-                W, H, ctypes.c_void_p(rn.data_ptr()), ctypes.c_void_p(sn.data_ptr()), ctypes.c_void_p(rd.data_ptr()),
-                ctypes.c_void_p(out2.data_ptr()), ctypes.c_void_p(ws.data_ptr()), nws,
-                ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"geometry_regularizers failed ({rc}): {_lib.last_error()}")
+            _lib.call("g4s_geometry_regularizers_forward", W, H, _lib.ptr(rn), _lib.ptr(sn), _lib.ptr(rd), _lib.ptr(out2),
+                      _lib.ptr(ws), nws, _lib.stream(dev))
         ctx.save_for_backward(rn, sn)
         ctx.dist_shape = rend_dist.shape
         return out2
@@ -84,19 +73,14 @@ class _GeometryRegularizers(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_out2):
         rn, sn = ctx.saved_tensors
-        lib = _lib.load()
         dev = rn.device
         H, W = int(rn.size(1)), int(rn.size(2))
         g2 = g_out2.detach().float().contiguous()
         with torch.cuda.device(dev):
             d_rn, d_sn = torch.empty_like(rn), torch.empty_like(sn)
             d_rd = torch.empty(ctx.dist_shape, dtype=torch.float32, device=dev)
-            rc = lib.g4s_geometry_regularizers_backward(
-                W, H, ctypes.c_void_p(rn.data_ptr()), ctypes.c_void_p(sn.data_ptr()), ctypes.c_void_p(g2.data_ptr()),
-                ctypes.c_void_p(d_rn.data_ptr()), ctypes.c_void_p(d_sn.data_ptr()), ctypes.c_void_p(d_rd.data_ptr()),
-                ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"geometry_regularizers backward failed ({rc}): {_lib.last_error()}")
+            _lib.call("g4s_geometry_regularizers_backward", W, H, _lib.ptr(rn), _lib.ptr(sn), _lib.ptr(g2), _lib.ptr(d_rn),
+                      _lib.ptr(d_sn), _lib.ptr(d_rd), _lib.stream(dev))
         return d_rn, d_sn, d_rd
 
 

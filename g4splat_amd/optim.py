@@ -109,40 +109,37 @@ class FusedAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        lib = _lib.load()
         # (betas, eps, device) -> segments; the reference uses one setting for all groups => one launch per 8 tensors
         batches = self._batches(True, need_grad=False)
         if any(k[4] for k in batches) and not torch.cuda.is_current_stream_capturing():
             self.sync_lr()
         for (b1, b2, eps, dev, cap), items in batches.items():
             with torch.cuda.device(dev):
-                stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+                stream = _lib.stream(dev)
                 if cap:
                     lr_dev, _last, coef, dummy = self._dev_buffers((b1, b2, eps, dev, cap), len(items), dev)
                 for c, i in enumerate(range(0, len(items), 8)):
                     seg = items[i:i + 8]
-                    k = len(seg)
-                    ptr = lambda ts: (ctypes.c_void_p * k)(*[(t.data_ptr() if t is not None else 0) for t in ts])
                     if cap:
                         if all(s[1] is None for s in seg):
                             continue
                         live = [s[1] is not None for s in seg]
-                        rc = lib.g4s_adam_step_device(
-                            k, ptr([s[0] for s in seg]), ptr([s[1] for s in seg]),
-                            ptr([s[2]["exp_avg"] if ok else None for s, ok in zip(seg, live)]),
-                            ptr([s[2]["exp_avg_sq"] if ok else None for s, ok in zip(seg, live)]),
-                            (ctypes.c_longlong * k)(*[(s[0].numel() if ok else 0) for s, ok in zip(seg, live)]),
+                        _lib.call(
+                            "g4s_adam_step_device", len(seg), _lib.ptrs([s[0] for s in seg]), _lib.ptrs([s[1] for s in seg]),
+                            _lib.ptrs([s[2]["exp_avg"] if ok else None for s, ok in zip(seg, live)]),
+                            _lib.ptrs([s[2]["exp_avg_sq"] if ok else None for s, ok in zip(seg, live)]),
+                            _lib.array(ctypes.c_longlong, [(s[0].numel() if ok else 0) for s, ok in zip(seg, live)]),
                             ctypes.c_void_p(lr_dev.data_ptr() + 8 * i),
-                            ptr([s[2]["step"] if ok else dummy for s, ok in zip(seg, live)]),  # (no gradient: t stays)
+                            _lib.ptrs([s[2]["step"] if ok else dummy for s, ok in zip(seg, live)]),  # (no gradient: t stays)
                             ctypes.c_void_p(coef.data_ptr() + 64 * c), float(b1), float(b2), float(eps), stream)
                     else:
-                        rc = lib.g4s_adam_step(
-                            k, ptr([s[0] for s in seg]), ptr([s[1] for s in seg]), ptr([s[2]["exp_avg"] for s in seg]),
-                            ptr([s[2]["exp_avg_sq"] for s in seg]), (ctypes.c_longlong * k)(*[s[0].numel() for s in seg]),
-                            (ctypes.c_double * k)(*[s[3] for s in seg]), (ctypes.c_int * k)(*[int(s[2]["step"]) for s in seg]),
-                            float(b1), float(b2), float(eps), stream)
-                    if rc != 0:
-                        raise RuntimeError(f"g4s_adam_step failed ({rc}): {_lib.last_error()}")
+                        _lib.call(
+                            "g4s_adam_step", len(seg), _lib.ptrs([s[0] for s in seg]), _lib.ptrs([s[1] for s in seg]),
+                            _lib.ptrs([s[2]["exp_avg"] for s in seg]), _lib.ptrs([s[2]["exp_avg_sq"] for s in seg]),
+                            _lib.array(ctypes.c_longlong, [s[0].numel() for s in seg]),
+                            _lib.array(ctypes.c_double, [s[3] for s in seg]),
+                            _lib.array(ctypes.c_int, [int(s[2]["step"]) for s in seg]), float(b1), float(b2), float(eps),
+                            stream)
         return loss
 
 
@@ -167,53 +164,34 @@ def densify_stats(grad_mean2D, update_filter, xyz_gradient_accum, denom, radii=N
     r = radii.contiguous() if radii is not None else None
     if r is not None and (r.dtype != torch.int32 or r.numel() != P or max_radii2D.numel() != P):
         raise RuntimeError("densify_stats: radii must be int32 [P]")
-    lib = _lib.load()
     with torch.cuda.device(dev):
-        rc = lib.g4s_densify_stats(P, ctypes.c_void_p(g.data_ptr()), ctypes.c_void_p(f.data_ptr()),
-                                   ctypes.c_void_p(r.data_ptr() if r is not None else 0),
-                                   ctypes.c_void_p(xyz_gradient_accum.data_ptr()), ctypes.c_void_p(denom.data_ptr()),
-                                   ctypes.c_void_p(max_radii2D.data_ptr() if max_radii2D is not None else 0),
-                                   ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"g4s_densify_stats failed ({rc}): {_lib.last_error()}")
+        _lib.call("g4s_densify_stats", P, _lib.ptr(g), _lib.ptr(f), _lib.ptr(r), _lib.ptr(xyz_gradient_accum),
+                  _lib.ptr(denom), _lib.ptr(max_radii2D), _lib.stream(dev))
 
 
 class _Activations(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scaling, rotation, opacity):
-        lib = _lib.load()
         dev = scaling.device
         P = int(scaling.shape[0])
         s, r, o = scaling.detach().contiguous(), rotation.detach().contiguous(), opacity.detach().contiguous()
         with torch.cuda.device(dev):
             scales, rots, opac = torch.empty_like(s), torch.empty_like(r), torch.empty_like(o)
-            rc = lib.g4s_activations_forward(P, ctypes.c_void_p(s.data_ptr()), ctypes.c_void_p(r.data_ptr()),
-                                             ctypes.c_void_p(o.data_ptr()), ctypes.c_void_p(scales.data_ptr()),
-                                             ctypes.c_void_p(rots.data_ptr()), ctypes.c_void_p(opac.data_ptr()),
-                                             ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"g4s_activations_forward failed ({rc}): {_lib.last_error()}")
+            _lib.call("g4s_activations_forward", P, *map(_lib.ptr, (s, r, o, scales, rots, opac)), _lib.stream(dev))
         ctx.save_for_backward(scales, r, opac)
         return scales, rots, opac
 
     @staticmethod
     def backward(ctx, g_scales, g_rots, g_opac):
         scales, r, opac = ctx.saved_tensors
-        lib = _lib.load()
         dev = scales.device
         P = int(scales.shape[0])
         zero = lambda ref, g: torch.zeros_like(ref) if g is None else g.contiguous()
         gs, gr, go = zero(scales, g_scales), zero(r, g_rots), zero(opac, g_opac)
         with torch.cuda.device(dev):
             ds, dr, do = torch.empty_like(scales), torch.empty_like(r), torch.empty_like(opac)
-            rc = lib.g4s_activations_backward(P, ctypes.c_void_p(scales.data_ptr()), ctypes.c_void_p(r.data_ptr()),
-                                              ctypes.c_void_p(opac.data_ptr()), ctypes.c_void_p(gs.data_ptr()),
-                                              ctypes.c_void_p(gr.data_ptr()), ctypes.c_void_p(go.data_ptr()),
-                                              ctypes.c_void_p(ds.data_ptr()), ctypes.c_void_p(dr.data_ptr()),
-                                              ctypes.c_void_p(do.data_ptr()),
-                                              ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"g4s_activations_backward failed ({rc}): {_lib.last_error()}")
+            _lib.call("g4s_activations_backward", P, *map(_lib.ptr, (scales, r, opac, gs, gr, go, ds, dr, do)),
+                      _lib.stream(dev))
         return ds, dr, do
 
 
@@ -251,23 +229,16 @@ def compact_rows(keep, tensors, extra_rows=0):
     lib = _lib.load()
     keep_c = keep.contiguous()
     with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream(dev)
         nws = lib.g4s_compact_workspace(P)
         ws = torch.empty(nws, dtype=torch.uint8, device=dev)
         count = torch.zeros(1, dtype=torch.int32, device=dev)
-        rc = lib.g4s_compact_scan(P, ctypes.c_void_p(keep_c.data_ptr()), ctypes.c_void_p(count.data_ptr()),
-                                  ctypes.c_void_p(ws.data_ptr()), nws, stream)
-        if rc != 0:
-            raise RuntimeError(f"g4s_compact_scan failed ({rc}): {_lib.last_error()}")
+        _lib.call("g4s_compact_scan", P, _lib.ptr(keep_c), _lib.ptr(count), _lib.ptr(ws), nws, stream)
         n = int(count.item())
         out = [torch.empty((n + int(extra_rows),) + tuple(t.shape[1:]), dtype=torch.float32, device=dev) for t in src]
         k = len(src)
         if k and P and n > 0:  # (n == 0: nothing to copy, and empty outputs have no address)
             widths = [int(t[0].numel()) if t.ndim > 1 else 1 for t in src]
-            rc = lib.g4s_compact_gather(P, ctypes.c_void_p(keep_c.data_ptr()), ctypes.c_void_p(ws.data_ptr()), k,
-                                        (ctypes.c_void_p * k)(*[t.data_ptr() for t in src]),
-                                        (ctypes.c_void_p * k)(*[t.data_ptr() for t in out]), (ctypes.c_int * k)(*widths), 0,
-                                        stream)
-            if rc != 0:
-                raise RuntimeError(f"g4s_compact_gather failed ({rc}): {_lib.last_error()}")
+            _lib.call("g4s_compact_gather", P, _lib.ptr(keep_c), _lib.ptr(ws), k, _lib.ptrs(src), _lib.ptrs(out),
+                      _lib.array(ctypes.c_int, widths), 0, stream)
     return n, out

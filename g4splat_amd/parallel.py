@@ -10,11 +10,14 @@ restricted to the rows of Gaussians visible on some rank when those are a minori
 a norm per view, not the norm of a sum), visibility counts are summed, radii are max-reduced
 (train_with_refine_depth.py:583).
 """
+import contextlib
 import os
 from typing import Iterable, List, Optional, Sequence
 
 import torch
 import torch.distributed as dist
+
+from . import _lib
 
 
 def shard_views(views: Sequence, rank: int, world_size: int) -> List:
@@ -45,6 +48,93 @@ class GradientBucket:
                 p.grad = v  # optimizer.zero_grad(set_to_none=True) drops the views: re-attach
 
 
+class _HostRows:
+    """Row operations of the exchanges over float32 [P, w] tensors: torch indexing here (host tensors), the library's kernels
+    in _DeviceRows.  Buffers are row-major [n, W] (index_col: [n, W + 1], the index as int32 bits last) or, row_major=False,
+    segment after segment [n w_0 | n w_1 | ...]."""
+
+    def __init__(self, rows):
+        self.rows, self.widths, self.dev = rows, [int(r.shape[1]) for r in rows], rows[0].device
+        self.W = sum(self.widths)
+
+    def _parts(self, buf, n, row_major=True):
+        if row_major:
+            return buf[:n, :self.W].split(self.widths, dim=1)
+        return [s.view(n, w) for s, w in zip(buf[:n * self.W].split([n * w for w in self.widths]), self.widths)]
+
+    def pack(self, idx, buf, index_col=False, row_major=True):
+        """buf <- the rows `idx` (int64)."""
+        for r, part in zip(self.rows, self._parts(buf, idx.numel(), row_major)):
+            part.copy_(r.index_select(0, idx))
+        if index_col:
+            buf[:idx.numel(), self.W] = idx.to(torch.int32).view(torch.float32)
+
+    def unpack(self, idx, buf, row_major=True):
+        """The rows `idx` <- buf (overwrite)."""
+        for r, part in zip(self.rows, self._parts(buf, idx.numel(), row_major)):
+            r.index_copy_(0, idx, part)
+
+    def accumulate(self, buf, srcs, lo, hi, path, own_pos):
+        """Adds the rows of `buf` (row-major, index column) that arrived from the sources srcs = [(offset, count)] to the
+        owner's rows [lo, hi), source after source, in OwnerReduce.addition_order()'s `path`.  "rank": the zero-then-add
+        form -- the first `own_pos` sources into a zero shard, then the owner's rows, then the others."""
+        def add(targets, o, c, shift):
+            ridx = buf[o:o + c, self.W].contiguous().view(torch.int32).to(torch.int64) - shift
+            for t, part in zip(targets, self._parts(buf[o:o + c], c)):
+                t.index_add_(0, ridx, part)
+        if path != "rank":
+            for o, c in srcs:
+                add(self.rows, o, c, 0)
+            return
+        acc = [torch.zeros(hi - lo, w, dtype=r.dtype) for r, w in zip(self.rows, self.widths)]
+        for o, c in srcs[:own_pos]:
+            add(acc, o, c, lo)
+        for a, r in zip(acc, self.rows):
+            a += r[lo:hi]
+        for o, c in srcs[own_pos:]:
+            add(acc, o, c, lo)
+        for a, r in zip(acc, self.rows):
+            r[lo:hi] = a
+
+
+class _DeviceRows(_HostRows):
+    def __init__(self, rows):
+        super().__init__(rows)
+        if not all(r.is_contiguous() for r in rows):
+            raise RuntimeError("row views must be contiguous [P, w] tensors")
+
+    def _kernel(self, idx, n, buf, mode):
+        """g4s_pack_rows: mode 0 / 1 = pack / unpack segment after segment, 2 / 3 = row-major, 10 = row-major with the
+        index column, 15 = unpack row-major ADDING, the indices read from the buffer (idx None)."""
+        if n:
+            with torch.cuda.device(self.dev):
+                _lib.call("g4s_pack_rows", len(self.rows), _lib.ptrs(self.rows), _lib.array(_lib.c_i, self.widths),
+                          _lib.ptr(idx), int(n), _lib.ptr(buf), mode, _lib.stream(self.dev))
+
+    def pack(self, idx, buf, index_col=False, row_major=True):
+        self._kernel(idx, idx.numel(), buf, (2 if row_major else 0) | (8 if index_col else 0))
+
+    def unpack(self, idx, buf, row_major=True):
+        self._kernel(idx, idx.numel(), buf, 3 if row_major else 1)
+
+    def accumulate(self, buf, srcs, lo, hi, path, own_pos):
+        if path == "per_source":  # a launch per source touches only the rows that arrived, not the whole shard
+            for o, c in srcs:
+                self._kernel(None, c, buf[o:o + c], 15)
+            return
+        args = (len(self.rows), _lib.ptrs(self.rows), _lib.array(_lib.c_i, self.widths), len(srcs),
+                _lib.array(_lib.c_i, [o for o, _ in srcs]), _lib.array(_lib.c_i, [c for _, c in srcs]), _lib.ptr(buf), lo, hi)
+        with torch.cuda.device(self.dev):
+            if path == "rank":
+                _lib.call("g4s_accumulate_rows_ordered", *args, own_pos, _lib.stream(self.dev))
+            else:
+                _lib.call("g4s_accumulate_rows", *args, _lib.stream(self.dev))
+
+
+def _row_ops(rows):
+    return (_DeviceRows if rows[0].device.type == "cuda" else _HostRows)(rows)
+
+
 class RowSparseAllReduce:
     """SUM all-reduce of per-Gaussian rows that exchanges only the rows some rank can have touched.
 
@@ -63,6 +153,7 @@ class RowSparseAllReduce:
         self.flat, self.rows, self.group, self.compact_below = flat, list(row_views), group, compact_below
         self.P = self.rows[0].shape[0]
         self.widths = [int(r.shape[1]) for r in self.rows]
+        self._ops = _row_ops(self.rows)  # (one HIP kernel each way on a device instead of 2 x len(rows) index kernels)
         self.compact = None  # persistent packed buffer, allocated on first use (capacity: every row)
         self.last_rows = None  # rows exchanged by the last reduce() (P for the dense path); for reporting
         self.last_dense = False  # the last reduce() all-reduced `flat` as a whole (row views outside it are NOT reduced)
@@ -80,40 +171,9 @@ class RowSparseAllReduce:
             return
         if self.compact is None:
             self.compact = torch.empty(self.P * sum(self.widths), dtype=self.flat.dtype, device=self.flat.device)
-        total = n * sum(self.widths)
-        if self.flat.is_cuda:
-            # one HIP kernel each way (g4s_pack_rows) instead of 2 x len(rows) index kernels
-            self._pack(idx, n, unpack=0)
-            dist.all_reduce(self.compact[:total], op=dist.ReduceOp.SUM, group=self.group)
-            self._pack(idx, n, unpack=1)
-            return
-        off, parts = 0, []  # host tensors (gloo): plain torch indexing
-        for r, w in zip(self.rows, self.widths):
-            part = self.compact[off:off + n * w].view(n, w)
-            torch.index_select(r, 0, idx, out=part)
-            parts.append(part)
-            off += n * w
-        dist.all_reduce(self.compact[:off], op=dist.ReduceOp.SUM, group=self.group)
-        for r, part in zip(self.rows, parts):
-            r.index_copy_(0, idx, part)
-
-    def _pack(self, idx, n, unpack):
-        import ctypes
-        from . import _lib
-        lib = _lib.load()
-        k = len(self.rows)
-        for r in self.rows:
-            if not r.is_contiguous():
-                raise RuntimeError("RowSparseAllReduce: row views must be contiguous [P, k] tensors")
-        ptrs = (ctypes.c_void_p * k)(*[r.data_ptr() for r in self.rows])
-        widths = (ctypes.c_int * k)(*self.widths)
-        dev = self.flat.device
-        with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            rc = lib.g4s_pack_rows(k, ptrs, widths, ctypes.c_void_p(idx.data_ptr()), int(n),
-                                   ctypes.c_void_p(self.compact.data_ptr()), int(unpack), stream)
-        if rc != 0:
-            raise RuntimeError(f"g4s_pack_rows failed ({rc}): {_lib.last_error()}")
+        self._ops.pack(idx, self.compact, row_major=False)
+        dist.all_reduce(self.compact[:n * sum(self.widths)], op=dist.ReduceOp.SUM, group=self.group)
+        self._ops.unpack(idx, self.compact, row_major=False)
 
 
 class OwnerReduce:
@@ -154,6 +214,13 @@ class OwnerReduce:
 
     Valid while a rank's gradient rows are zero outside its `visible` set (pure render gradients)."""
 
+
+    # sources from which the one-launch accumulation (a read + write of the whole shard) beats a launch per source
+    # (read + write of the arrived rows only): measured at the metric size, tools/micro/owner_local_cost.py
+    ONE_LAUNCH_SOURCES = 4
+    # sources g4s_accumulate_rows_ordered takes (nsrc <= 8): with more, the owner's rows come first
+    ORDERED_SOURCES = 8
+
     def __init__(self, row_views: Sequence[torch.Tensor], group=None):
         self.rows, self.group = list(row_views), group
         for r in self.rows:
@@ -165,34 +232,33 @@ class OwnerReduce:
         self.widths = [int(r.shape[1]) for r in self.rows]
         self.width = sum(self.widths)
         self.shard = (self.P + self.world - 1) // self.world  # rows per owner (the last shard may be short)
-        dev = self.rows[0].device
-        self.dev = dev
+        self.dev = dev = self.rows[0].device
         self.hip = dev.type == "cuda"
+        self._ops = _row_ops(self.rows)
         self.even = self.P == self.world * self.shard  # equal shards: the reduced slices are gathered in place
         self.rccl = self.hip and dist.get_backend(group) == "nccl"
         W2 = self.world * self.world
-        with (torch.cuda.device(dev) if self.hip else _nullctx()):
+        with self._on_device():
             # ---- persistent state (LAB_NOTES.md: collectives on persistent buffers only)
             self._meta = torch.zeros(self.P + W2, dtype=torch.int32, device=dev)  # radii | count matrix [src, dst]
             self._max_radii = torch.zeros(self.P, dtype=torch.int32, device=dev)  # what max_radii returns
             # sparse gather of the reduced shards (rows visible on SOME rank only): union mask / index list / per-owner counts
             self._union = torch.zeros(self.P, dtype=torch.bool, device=dev)
             self._uidx = torch.empty(self.P, dtype=torch.int64, device=dev)
-            self._ucounts_host = (torch.zeros(self.world, dtype=torch.int32).pin_memory() if self.hip
-                                  else torch.zeros(self.world, dtype=torch.int32))
+            self._ucounts_host = torch.zeros(self.world, dtype=torch.int32, pin_memory=self.hip)
             self._gin = self._gout = None  # float32 [capacity, width], grown on demand
-            self._ragged_stage = {}  # (dtype, width) -> (stage, mine): all_gather_rows with ragged shards
             self._idx = torch.empty(self.P, dtype=torch.int64, device=dev)
             self._edges = torch.tensor([min(d * self.shard, self.P) for d in range(self.world + 1)], dtype=torch.int64,
                                        device=dev)
-            self._counts_host = (torch.zeros(W2, dtype=torch.int32).pin_memory() if self.hip
-                                 else torch.zeros(W2, dtype=torch.int32))
+            self._counts_host = torch.zeros(W2, dtype=torch.int32, pin_memory=self.hip)
             self._event = torch.cuda.Event() if self.hip else None
             self._send = self._recv = None  # float32 [capacity, width + 1], grown on demand (never shrunk)
-            self._gather = self._acc = None
-            if not self.even:  # ragged shards: all_gather of padded shards through a staging buffer
-                self._gather = torch.zeros(self.world * self.shard, self.width, device=dev)
-                self._acc = torch.zeros(self.shard, self.width, device=dev)
+            # ragged shards: all_gather of padded shards through a staging buffer per (dtype, width) -> (stage, mine); the
+            # one of the row tensors together is made here
+            self._ragged_stage = {}
+            if not self.even:
+                self._ragged_stage[(torch.float32, self.width)] = (torch.zeros(self.world * self.shard, self.width, device=dev),
+                                                                   torch.zeros(self.shard, self.width, device=dev))
         self._pending = False
         self._have_union = False
         # Gather only the rows some rank saw when they are a minority (sparse_below x P): on 2 / 4 ranks the union of the
@@ -202,9 +268,10 @@ class OwnerReduce:
         # g_1) + ...) + g_{N-1}, the owner's own rows in their place -- instead of "the owner's first, then the others".  That
         # is the order in which ONE process accumulating the same views one after the other sums them, so a step of N ranks
         # with one view each reproduces single-process gradient accumulation BIT FOR BIT (tests/test_gpu_dp.py, test_dp_gloo.py).
-        # Costs nothing: the same one-launch kernel with its additions reordered (up to 8 sources = 9 ranks; beyond, and
-        # with rank_order = False, the owner's rows come first).
+        # Costs nothing: the same one-launch kernel with its additions reordered (up to ORDERED_SOURCES sources; beyond, and
+        # with rank_order = False, the owner's rows come first -- `last_order` says which order the last finish() used).
         self.rank_order = True
+        self.last_order = None  # "rank" | "owner": the order of additions of the last finish() (addition_order())
         self.last_gather = None  # "dense" | "sparse": what the last finish(gather=True) did
         self._nonzero_static = hasattr(torch, "nonzero_static")
         # one RCCL group call for the per-tensor in-place gathers: probed ONCE, on a dummy tensor, and agreed on by all
@@ -216,10 +283,23 @@ class OwnerReduce:
         self._timers = {}
         self.last_bytes = {}  # bytes this rank sent / received in the last step's collectives, by piece
 
+    def _on_device(self):
+        return torch.cuda.device(self.dev) if self.hip else contextlib.nullcontext()
+
+    @contextlib.contextmanager
     def _timed(self, name):
-        """Context manager: with `timing` on, a pair of HIP events on the current stream around the piece `name` (the
-        torch collectives are synchronous ops: the current stream waits for them, so the pair brackets the collective)."""
-        return _EventPair(self, name) if (self.timing and self.hip) else _nullctx()
+        """With `timing` on, a pair of HIP events on the current stream around the piece `name` (the torch collectives are
+        synchronous ops: the current stream waits for them, so the pair brackets the collective)."""
+        if not (self.timing and self.hip):
+            yield
+            return
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(torch.cuda.current_stream(self.dev))
+        try:
+            yield
+        finally:
+            b.record(torch.cuda.current_stream(self.dev))
+            self._timers.setdefault(name, []).append((a, b))
 
     def read_timers(self, reset=True):
         """-> {piece: mean ms per step} of everything recorded since the last reset (synchronises on the events)."""
@@ -265,8 +345,6 @@ class OwnerReduce:
         d = self.rank if d is None else d
         return min(d * self.shard, self.P), min((d + 1) * self.shard, self.P)
 
-    _bounds = bounds
-
     @property
     def max_radii(self):
         """int32 [P]: MAX over the ranks of the radii handed to the last begin().  A persistent buffer of its own, filled
@@ -274,15 +352,29 @@ class OwnerReduce:
         longer."""
         return self._max_radii
 
-    def _buffer(self, which, rows):
-        buf = getattr(self, which)
+    def _grow(self, name, rows, cols):  # persistent float32 buffer [>= rows, cols]: grown on demand, never shrunk
+        buf = getattr(self, name)
         if buf is None or buf.shape[0] < rows:
-            cap = max(int(rows * 1.25) + 1024, 0 if buf is None else buf.shape[0])
-            with (torch.cuda.device(self.dev) if self.hip else _nullctx()):
-                buf = torch.empty(cap, self.width + 1, device=self.dev)
-            setattr(self, which, buf)
+            buf = torch.empty(max(int(rows * 1.25) + 1024, 0 if buf is None else buf.shape[0]), cols, device=self.dev)
+            setattr(self, name, buf)
             self.allocations += 1
         return buf
+
+    def _rows_kernel(self, idx, n, buf, mode):
+        """g4s_pack_rows over all row views in any `mode` (HIP devices; tests compare the backward's packed rows with it)."""
+        self._ops._kernel(idx, n, buf, mode)
+
+    def _nonzero_padded(self, mask, out):
+        """out (int64 [P]) <- the indices of `mask`, ascending, padded with P (older torch: nonzero() waits for the count)."""
+        if self._nonzero_static:
+            try:
+                torch.nonzero_static(mask, size=self.P, fill_value=self.P, out=out.view(self.P, 1))
+            except (TypeError, RuntimeError):
+                out.copy_(torch.nonzero_static(mask, size=self.P, fill_value=self.P).view(-1))
+        else:
+            nz = mask.nonzero(as_tuple=True)[0]
+            out.fill_(self.P)
+            out[:nz.numel()] = nz
 
     def prepack(self, visible: torch.Tensor):
         """-> (rows, block_offs) for `_C.rasterize_gaussians_backward(..., out={"accumulate": "first", "packed": ...})`: the
@@ -296,7 +388,7 @@ class OwnerReduce:
             raise RuntimeError("OwnerReduce.prepack(): the row tensors must be means3D 3 | sh 3M | opacity 1 | scales 2 | "
                                f"rotations 4 | view_stats 2, got widths {self.widths}")
         if getattr(self, "_packed_all", None) is None:
-            with (torch.cuda.device(self.dev) if self.hip else _nullctx()):
+            with self._on_device():
                 self._packed_all = torch.empty(self.P, self.width + 1, device=self.dev)
                 self._pad256 = torch.zeros((self.P + 255) // 256 * 256, dtype=torch.int32, device=self.dev)
                 self._block_offs = torch.zeros((self.P + 255) // 256, dtype=torch.int32, device=self.dev)
@@ -312,17 +404,9 @@ class OwnerReduce:
     def begin(self, visible: torch.Tensor, radii: Optional[torch.Tensor] = None):
         """`visible`: bool[P], the rows this rank's views can have touched (radii > 0, OR-ed over its views);
         `radii`: optional integer [P] tensor whose MAX over the ranks is wanted (max_radii after finish())."""
-        with (torch.cuda.device(self.dev) if self.hip else _nullctx()), self._timed("begin_local"):
+        with self._on_device(), self._timed("begin_local"):
             # fixed-size index list (padded with P, ascending => grouped by owner): the host does not wait for a count
-            if self._nonzero_static:
-                try:
-                    torch.nonzero_static(visible, size=self.P, fill_value=self.P, out=self._idx.view(self.P, 1))
-                except (TypeError, RuntimeError):
-                    self._idx.copy_(torch.nonzero_static(visible, size=self.P, fill_value=self.P).view(-1))
-            else:  # older torch: nonzero() synchronises on the count
-                nz = visible.nonzero(as_tuple=True)[0]
-                self._idx.fill_(self.P)
-                self._idx[:nz.numel()] = nz
+            self._nonzero_padded(visible, self._idx)
             # per-owner counts: the list is sorted, so owner d's rows are the range between two binary searches (a
             # scatter_add of 1.5 M ones onto 8 counters would serialise on them)
             pos = torch.searchsorted(self._idx, self._edges)
@@ -342,7 +426,7 @@ class OwnerReduce:
             tail = meta[self.P:].view(self.world, self.world)
             tail.zero_()
             tail[self.rank].copy_(pos[1:] - pos[:-1])
-        with (torch.cuda.device(self.dev) if self.hip else _nullctx()):
+        with self._on_device():
             with self._timed("max_all_reduce"):
                 dist.all_reduce(meta, op=dist.ReduceOp.MAX, group=self.group)  # radii MAX + the count matrix, one collective
             self.last_bytes["max_all_reduce"] = int(meta.numel() * 4 * 2 * (self.world - 1) / max(self.world, 1))
@@ -352,15 +436,7 @@ class OwnerReduce:
             if self._have_union:
                 with self._timed("begin_union"):
                     torch.ge(meta[:self.P], 1 << 30, out=self._union)
-                    if self._nonzero_static:
-                        try:
-                            torch.nonzero_static(self._union, size=self.P, fill_value=self.P, out=self._uidx.view(self.P, 1))
-                        except (TypeError, RuntimeError):
-                            self._uidx.copy_(torch.nonzero_static(self._union, size=self.P, fill_value=self.P).view(-1))
-                    else:
-                        nz = self._union.nonzero(as_tuple=True)[0]
-                        self._uidx.fill_(self.P)
-                        self._uidx[:nz.numel()] = nz
+                    self._nonzero_padded(self._union, self._uidx)
                     upos = torch.searchsorted(self._uidx, self._edges)
                     self._ucounts_dev = (upos[1:] - upos[:-1]).to(torch.int32)
                     self._ucounts_host.copy_(self._ucounts_dev, non_blocking=self.hip)
@@ -371,66 +447,25 @@ class OwnerReduce:
                 self._counts_host.copy_(meta[self.P:])
         self._pending = True
 
-    def _rows_kernel(self, idx, n, buf, mode):
-        """g4s_pack_rows over all row views (include/g4s_rasterizer.h): mode 10 = pack row-major + index column,
-        15 = unpack row-major, adding, indices from the buffer."""
-        import ctypes
-        from . import _lib
-        lib = _lib.load()
-        k = len(self.rows)
-        ptrs = (ctypes.c_void_p * k)(*[r.data_ptr() for r in self.rows])
-        widths = (ctypes.c_int * k)(*self.widths)
-        with torch.cuda.device(self.dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
-            rc = lib.g4s_pack_rows(k, ptrs, widths, ctypes.c_void_p(idx.data_ptr() if idx is not None else 0), int(n),
-                                   ctypes.c_void_p(buf.data_ptr()), int(mode), stream)
-        if rc != 0:
-            raise RuntimeError(f"g4s_pack_rows failed ({rc}): {_lib.last_error()}")
-
-    # sources from which the one-launch accumulation (a read + write of the whole shard) beats a launch per source
-    # (read + write of the arrived rows only): measured at the metric size, tools/micro/owner_local_cost.py
-    ONE_LAUNCH_SOURCES = 4
-
-    def _accumulate_kernel(self, offs, cnts, buf, own_pos=0):
-        """g4s_accumulate_rows[_ordered] (include/g4s_rasterizer.h): the rows of `buf` received from the sources (offs[i],
-        cnts[i]) are added to my shard of the row views, source after source, in one launch; own_pos > 0: my own rows take
-        that position in the order of additions (rank order)."""
-        import ctypes
-        from . import _lib
-        lib = _lib.load()
-        k, n = len(self.rows), len(offs)
-        ptrs = (ctypes.c_void_p * k)(*[r.data_ptr() for r in self.rows])
-        widths = (ctypes.c_int * k)(*self.widths)
-        lo, hi = self.bounds()
-        with torch.cuda.device(self.dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
-            if own_pos:
-                rc = lib.g4s_accumulate_rows_ordered(k, ptrs, widths, n, (ctypes.c_int * n)(*offs), (ctypes.c_int * n)(*cnts),
-                                                     ctypes.c_void_p(buf.data_ptr()), int(lo), int(hi), int(own_pos), stream)
-            else:
-                rc = lib.g4s_accumulate_rows(k, ptrs, widths, n, (ctypes.c_int * n)(*offs), (ctypes.c_int * n)(*cnts),
-                                             ctypes.c_void_p(buf.data_ptr()), int(lo), int(hi), stream)
-        if rc != 0:
-            raise RuntimeError(f"g4s_accumulate_rows failed ({rc}): {_lib.last_error()}")
+    @classmethod
+    def addition_order(cls, live: Sequence[int], rank: int, rank_order: bool = True):
+        """The owner's order of additions, for both backends.  `live`: the ranks (ascending, not `rank`) whose rows reached
+        owner `rank`.  -> (path, order).  path "rank": the owner's rows join the sum behind the lower sources (ordered
+        kernel / zero-then-add); "one_launch" / "per_source": they come first, one launch for all sources or one each.
+        order: "rank" if the sum is in rank order (owner first is, with no lower source; one source commutes), else "owner"."""
+        ordered = rank_order and len(live) <= cls.ORDERED_SOURCES
+        if ordered and len(live) >= 2 and live[0] < rank:
+            return "rank", "rank"
+        return ("one_launch" if len(live) >= cls.ONE_LAUNCH_SOURCES else "per_source"), ("rank" if ordered else "owner")
 
     def all_gather_rows(self, tensors: Sequence[torch.Tensor]):
         """All-gathers the owners' row ranges of contiguous [P, ...] tensors in place (equal shards), as one RCCL group
         where the backend can: on return every rank holds every owner's rows."""
-        lo, hi = self.bounds()
         if not self.even:
-            for t in tensors:  # ragged: padded staging buffer per tensor
-                w = t[0].numel() if t.ndim > 1 else 1
-                flat = t.view(self.P, w)
-                key = (t.dtype, w)
-                if key not in self._ragged_stage:  # persistent per (dtype, width): nothing is allocated per step
-                    self._ragged_stage[key] = (torch.zeros(self.world * self.shard, w, dtype=t.dtype, device=t.device),
-                                               torch.zeros(self.shard, w, dtype=t.dtype, device=t.device))
-                    self.allocations += 1
-                stage, mine = self._ragged_stage[key]
-                mine[:hi - lo] = flat[lo:hi]
-                dist.all_gather_into_tensor(stage.view(-1), mine.view(-1), group=self.group)
-                flat.copy_(stage[:self.P])
+            for t in tensors:
+                self._staged_gather([t])
             return
+        lo, hi = self.bounds()
 
         def issue():
             for t in tensors:
@@ -443,6 +478,25 @@ class OwnerReduce:
                 issue()
         else:
             issue()
+
+    def _staged_gather(self, tensors):
+        """Ragged shards: ONE all_gather of the owners' rows of `tensors` ([P, ...], one dtype), padded to `shard` rows in a
+        staging buffer per (dtype, width) -- rank d's rows land at d * shard + i = their global index."""
+        lo, hi = self.bounds()
+        flats = [t.view(self.P, -1) for t in tensors]
+        widths = [int(f.shape[1]) for f in flats]
+        key = (tensors[0].dtype, sum(widths))
+        if key not in self._ragged_stage:
+            t = tensors[0]
+            self._ragged_stage[key] = (torch.zeros(self.world * self.shard, key[1], dtype=t.dtype, device=t.device),
+                                       torch.zeros(self.shard, key[1], dtype=t.dtype, device=t.device))
+            self.allocations += 1
+        stage, mine = self._ragged_stage[key]
+        for f, part in zip(flats, mine[:hi - lo].split(widths, dim=1)):
+            part.copy_(f[lo:hi])
+        dist.all_gather_into_tensor(stage.view(-1), mine.view(-1), group=self.group)
+        for f, part in zip(flats, stage[:self.P].split(widths, dim=1)):
+            f.copy_(part)
 
     # ---- second half: rows to their owners, owners accumulate, (optionally) everybody gets every shard ------------
     def finish(self, gather: bool = True, prepacked: bool = False, gather_rows: Optional[Sequence[int]] = None):
@@ -473,157 +527,93 @@ class OwnerReduce:
         if self._event is not None:
             self._event.synchronize()  # recorded a whole backward ago: returns at once
         torch.bitwise_and(self._meta[:self.P], (1 << 30) - 1, out=self._max_radii)  # (the next begin() reuses _meta)
+        send, recv, a, b, total = self._send_plan()
+        with self._on_device():
+            in_rows = self._send_to_owners(send, recv, a, b, total, prepacked)
+            self._accumulate(recv, in_rows)
+            if gather:
+                self._gather_shards(gather_rows)
+
+    def _send_plan(self):
+        """Count matrix -> all_to_all splits (my own rows are neither packed nor sent: [a, b) of my `total` visible ones)."""
         mat = self._counts_host.view(self.world, self.world).tolist()
         send = [int(x) for x in mat[self.rank]]
         recv = [int(mat[s][self.rank]) for s in range(self.world)]
-        # rows this rank owns itself stay where they are: they are neither packed nor sent
         a = sum(send[:self.rank])
         b = a + send[self.rank]
         total = sum(send)
         self.last_rows_sent = total - send[self.rank]
-        send[self.rank] = 0
-        recv[self.rank] = 0
-        n, m = sum(send), sum(recv)
+        send[self.rank] = recv[self.rank] = 0
+        return send, recv, a, b, total
+
+    def _send_to_owners(self, send, recv, a, b, total, prepacked):
+        """ONE all_to_all of my visible rows, row-major with the index column (owner d's rows one range) -> received rows."""
         W = self.width
-        with (torch.cuda.device(self.dev) if self.hip else _nullctx()):
-            if prepacked:
-                # the backward's per-Gaussian kernel has written ALL of this rank's visible rows, in index order, into
-                # prepack()'s buffer: the rows for owner d are the range [sum(counts[:d]), + counts[d]) of it.  My own rows
-                # sit in the middle; all_to_all_single wants consecutive pieces, so they take part as a piece to myself (a
-                # device-local copy of 1 / world of the rows inside the collective) and are skipped below -- my
-                # contribution already sits in my slice of the row tensors.
-                if getattr(self, "_packed_all", None) is None:
-                    raise RuntimeError("OwnerReduce.finish(prepacked=True) without prepack()")
-                if getattr(self, "debug_checks", False) and total:
-                    # the rows were laid out by the backward from prepack()'s mask, the splits come from begin()'s: the
-                    # index column the backward wrote has to be begin()'s index list, row for row
-                    col = self._packed_all[:total, W].contiguous().view(torch.int32).to(torch.int64)
-                    if not torch.equal(col, self._idx[:total]):
-                        raise RuntimeError("OwnerReduce.finish(prepacked=True): the rows in prepack()'s buffer are not the rows "
-                                           "begin() counted (different `visible` masks, or the backward did not run with "
-                                           "out['packed'])")
-                send[self.rank] = recv[self.rank] = b - a
-                m = sum(recv)
-                in_rows = self._buffer("_recv", m)[:m]
-                with self._timed("all_to_all"):
-                    dist.all_to_all_single(in_rows, self._packed_all[:total], recv, send, group=self.group)
+        n, m = sum(send), sum(recv)
+        self.last_bytes["all_to_all_sent"] = n * (W + 1) * 4          # (through the links: my own piece excluded)
+        self.last_bytes["all_to_all_received"] = m * (W + 1) * 4
+        if prepacked:
+            # the backward's per-Gaussian kernel has written ALL of this rank's visible rows, in index order, into
+            # prepack()'s buffer: the rows for owner d are the range [sum(counts[:d]), + counts[d]) of it.  My own rows
+            # sit in the middle; all_to_all_single wants consecutive pieces, so they take part as a piece to myself (a
+            # device-local copy of 1 / world of the rows inside the collective) and are skipped by the accumulation --
+            # my contribution already sits in my slice of the row tensors.
+            if getattr(self, "_packed_all", None) is None:
+                raise RuntimeError("OwnerReduce.finish(prepacked=True) without prepack()")
+            if getattr(self, "debug_checks", False) and total:
+                # the rows were laid out by the backward from prepack()'s mask, the splits come from begin()'s: the
+                # index column the backward wrote has to be begin()'s index list, row for row
+                col = self._packed_all[:total, W].contiguous().view(torch.int32).to(torch.int64)
+                if not torch.equal(col, self._idx[:total]):
+                    raise RuntimeError("OwnerReduce.finish(prepacked=True): the rows in prepack()'s buffer are not the rows "
+                                       "begin() counted (different `visible` masks, or the backward did not run with "
+                                       "out['packed'])")
+            send[self.rank] = recv[self.rank] = b - a
+            m = sum(recv)
+            in_rows = self._grow("_recv", m, W + 1)[:m]
+            out_rows = self._packed_all[:total]
+        else:
+            in_rows = self._grow("_recv", m, W + 1)[:m]
+            out_rows = self._grow("_send", n, W + 1)[:n]
+            with self._timed("pack"):
+                self._ops.pack(self._idx[:a], out_rows[:a], index_col=True)
+                self._ops.pack(self._idx[b:total], out_rows[a:], index_col=True)
+        with self._timed("all_to_all"):
+            dist.all_to_all_single(in_rows, out_rows, recv, send, group=self.group)
+        return in_rows
+
+    def _accumulate(self, recv, in_rows):
+        """Owner: adds the other ranks' rows to my slice, source by source in addition_order()'s order (a source's rows are
+        distinct and ascend by index: begin()'s list is sorted, and so are the rows the backward packs)."""
+        srcs, live, o = [], [], 0
+        for s in range(self.world):
+            if recv[s] and s != self.rank:  # (prepacked: my own rows came back to me; they are already in place)
+                srcs.append((o, recv[s]))
+                live.append(s)
+            o += recv[s]
+        path, self.last_order = self.addition_order(live, self.rank, self.rank_order)
+        lo, hi = self.bounds()
+        with self._timed("accumulate"):
+            self._ops.accumulate(in_rows, srcs, lo, hi, path, sum(s < self.rank for s in live))
+
+    def _gather_shards(self, gather_rows):
+        """Every rank gets every reduced shard: sparse (small union of the visible sets) or dense (all or `gather_rows`)."""
+        if self._have_union:
+            cu = [int(x) for x in self._ucounts_host.tolist()]
+            if sum(cu) < self.sparse_below * self.P:
+                self._sparse_gather(cu)
+                return
+        self.last_gather = "dense"
+        rows = self.rows if gather_rows is None else [self.rows[i] for i in sorted(set(gather_rows))]
+        lo, hi = self.bounds()
+        Wg = sum(int(r.shape[1]) for r in rows)
+        self.last_bytes["all_gather_sent_per_peer"] = (hi - lo) * Wg * 4
+        self.last_bytes["all_gather_received"] = (self.P - (hi - lo)) * Wg * 4
+        with self._timed("all_gather"):
+            if len(rows) == len(self.rows) and not self.even:
+                self._staged_gather(self.rows)  # (one collective for all of them)
             else:
-                in_rows = self._buffer("_recv", m)[:m]
-                out_rows = self._buffer("_send", n)[:n]
-                # pack my visible rows, [n, width + 1] row-major: the rows for owner d are one contiguous range, and the
-                # last column carries the row index (int32 bits), so rows and indices travel in ONE all_to_all
-                if self.hip:
-                    with self._timed("pack"):
-                        if a:
-                            self._rows_kernel(self._idx[:a], a, out_rows[:a], 10)
-                        if total - b:
-                            self._rows_kernel(self._idx[b:total], total - b, out_rows[a:], 10)
-                else:
-                    idx = torch.cat((self._idx[:a], self._idx[b:total]))
-                    off = 0
-                    for r, w in zip(self.rows, self.widths):
-                        out_rows[:, off:off + w] = r.index_select(0, idx)
-                        off += w
-                    out_rows[:, W] = idx.to(torch.int32).view(torch.float32)
-                with self._timed("all_to_all"):
-                    dist.all_to_all_single(in_rows, out_rows, recv, send, group=self.group)
-            self.last_bytes["all_to_all_sent"] = n * (W + 1) * 4          # (through the links: my own piece excluded)
-            self.last_bytes["all_to_all_received"] = (m - recv[self.rank]) * (W + 1) * 4
-            # owner: my own contribution already sits in my slice; add the other ranks' rows to it, source by source (a
-            # source holds a row at most once => no duplicate indices inside one accumulation, and the order is fixed)
-            o = 0
-            with self._timed("accumulate"):
-                if self.hip:
-                    # one launch for all sources (g4s_accumulate_rows: the same additions in the same order as a launch
-                    # per source, one read + write of my shard instead of one per source); every source's rows ascend by
-                    # index -- the index list of begin() is sorted, and so are the rows the backward packs itself
-                    offs, cnts, own_pos = [], [], 0
-                    for s_ in range(self.world):
-                        if recv[s_] and s_ != self.rank:  # (prepacked: my own rows came back to me; they are already in place)
-                            offs.append(o)
-                            cnts.append(recv[s_])
-                            own_pos += 1 if s_ < self.rank else 0
-                        o += recv[s_]
-                    # rank order (see `rank_order`): my own rows join the sum behind the sources of lower rank.  With no such
-                    # source (own first is rank order) or a single source (two addends commute) the plain forms already are.
-                    ordered = self.rank_order and own_pos > 0 and 2 <= len(offs) <= 8
-                    if ordered:
-                        self._accumulate_kernel(offs, cnts, in_rows, own_pos)
-                    elif len(offs) >= self.ONE_LAUNCH_SOURCES:
-                        self._accumulate_kernel(offs, cnts, in_rows)
-                    else:  # few sources: a launch each touches only the rows that arrived, not the whole shard
-                        for o_, c_ in zip(offs, cnts):
-                            self._rows_kernel(None, c_, in_rows[o_:o_ + c_], 15)
-                else:
-                    lo_, hi_ = self.bounds()
-                    live = [s_ for s_ in range(self.world) if recv[s_] and s_ != self.rank]
-                    below = [s_ for s_ in live if s_ < self.rank]
-                    ordered = self.rank_order and below and len(live) >= 2
-                    # host tensors: the same order of additions as the device path (rank order: the sources below me into a
-                    # zero shard first, then my own rows, then the sources above me)
-                    acc = [torch.zeros(hi_ - lo_, w, dtype=r.dtype) for r, w in zip(self.rows, self.widths)] if ordered else None
-                    starts, o2 = {}, 0
-                    for s_ in range(self.world):
-                        starts[s_] = o2
-                        o2 += recv[s_]
-
-                    def add_source(s_, targets, shift):
-                        c, o_ = recv[s_], starts[s_]
-                        ridx = in_rows[o_:o_ + c, W].contiguous().view(torch.int32).to(torch.int64) - shift
-                        off = 0
-                        for r, w in zip(targets, self.widths):
-                            r.index_add_(0, ridx, in_rows[o_:o_ + c, off:off + w])
-                            off += w
-                    if ordered:
-                        for s_ in below:
-                            add_source(s_, acc, lo_)
-                        for a_, r in zip(acc, self.rows):
-                            a_ += r[lo_:hi_]
-                        for s_ in live:
-                            if s_ > self.rank:
-                                add_source(s_, acc, lo_)
-                        for a_, r in zip(acc, self.rows):
-                            r[lo_:hi_] = a_
-                    else:
-                        for s_ in live:
-                            add_source(s_, self.rows, 0)
-            if not gather:
-                return
-            # every rank gets every reduced shard
-            lo, hi = self.bounds()
-            if self._have_union:
-                cu = [int(x) for x in self._ucounts_host.tolist()]
-                if sum(cu) < self.sparse_below * self.P:
-                    self._sparse_gather(cu)
-                    return
-            self.last_gather = "dense"
-            if gather_rows is not None and len(set(gather_rows)) < len(self.rows):
-                sub = [self.rows[i] for i in sorted(set(gather_rows))]
-                Wg = sum(int(r.shape[1]) for r in sub)
-                self.last_bytes["all_gather_sent_per_peer"] = (hi - lo) * Wg * 4
-                self.last_bytes["all_gather_received"] = (self.P - (hi - lo)) * Wg * 4
-                with self._timed("all_gather"):
-                    self.all_gather_rows(sub)   # (ragged shards: per-tensor staging inside)
-                return
-            self.last_bytes["all_gather_sent_per_peer"] = (hi - lo) * W * 4
-            self.last_bytes["all_gather_received"] = (self.P - (hi - lo)) * W * 4
-            if self.even:
-                with self._timed("all_gather"):
-                    self.all_gather_rows(self.rows)
-                return
-            with self._timed("all_gather"):
-                off = 0
-                for r, w in zip(self.rows, self.widths):
-                    self._acc[:hi - lo, off:off + w] = r[lo:hi]
-                    off += w
-                dist.all_gather_into_tensor(self._gather.view(-1), self._acc.view(-1), group=self.group)
-                full = self._gather[:self.P]
-                # (shards are padded to `shard` rows: rank d's rows sit at [d * shard, d * shard + (hi_d - lo_d)) = their global index)
-                off = 0
-                for r, w in zip(self.rows, self.widths):
-                    r.copy_(full[:, off:off + w])
-                    off += w
-
+                self.all_gather_rows(rows)
 
     def _sparse_gather(self, cu):
         """Gather of the reduced shards restricted to the rows some rank saw (`cu[d]` of them in owner d's shard, the
@@ -633,70 +623,20 @@ class OwnerReduce:
         W = self.width
         me = self.rank
         maxc = max(cu)
-        offs = [0]
-        for c in cu:
-            offs.append(offs[-1] + c)
+        offs = [sum(cu[:d]) for d in range(self.world)]
         self.last_gather = "sparse"
         self.last_bytes["all_gather_sent_per_peer"] = maxc * W * 4
         self.last_bytes["all_gather_received"] = (self.world - 1) * maxc * W * 4
         if maxc == 0:
             return
-
-        def grow(name, rows):
-            buf = getattr(self, name)
-            if buf is None or buf.shape[0] < rows:
-                buf = torch.empty(max(int(rows * 1.25) + 1024, 0 if buf is None else buf.shape[0]), W, device=self.dev)
-                setattr(self, name, buf)
-                self.allocations += 1
-            return buf
-        gin = grow("_gin", maxc)[:maxc]
-        gout = grow("_gout", self.world * maxc)[:self.world * maxc]
+        gin = self._grow("_gin", maxc, W)[:maxc]
+        gout = self._grow("_gout", self.world * maxc, W)[:self.world * maxc]
         with self._timed("all_gather"):
-            mine = self._uidx[offs[me]:offs[me] + cu[me]]
-            if self.hip:
-                if cu[me]:
-                    self._rows_kernel(mine, cu[me], gin, 2)          # pack, row-major
-            else:
-                off = 0
-                for r, w in zip(self.rows, self.widths):
-                    gin[:cu[me], off:off + w] = r.index_select(0, mine)
-                    off += w
+            self._ops.pack(self._uidx[offs[me]:offs[me] + cu[me]], gin)
             dist.all_gather_into_tensor(gout.view(-1), gin.view(-1), group=self.group)
-            for s_ in range(self.world):
-                if s_ == me or cu[s_] == 0:
-                    continue
-                idx = self._uidx[offs[s_]:offs[s_] + cu[s_]]
-                part = gout[s_ * maxc:s_ * maxc + cu[s_]]
-                if self.hip:
-                    self._rows_kernel(idx, cu[s_], part, 3)          # unpack, row-major, overwrite
-                else:
-                    off = 0
-                    for r, w in zip(self.rows, self.widths):
-                        r.index_copy_(0, idx, part[:, off:off + w])
-                        off += w
-
-
-class _nullctx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
-
-
-class _EventPair:
-    def __init__(self, owner, name):
-        self.owner, self.name = owner, name
-
-    def __enter__(self):
-        self.a, self.b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        self.a.record(torch.cuda.current_stream(self.owner.dev))
-        return self
-
-    def __exit__(self, *exc):
-        self.b.record(torch.cuda.current_stream(self.owner.dev))
-        self.owner._timers.setdefault(self.name, []).append((self.a, self.b))
-        return False
+            for s in range(self.world):
+                if s != me:
+                    self._ops.unpack(self._uidx[offs[s]:offs[s] + cu[s]], gout[s * maxc:s * maxc + cu[s]])
 
 
 def adam_update_(p, g, m, v, lr, step, beta1=0.9, beta2=0.999, eps=1e-15):
@@ -753,18 +693,12 @@ class ShardedAdam:
         if hi > lo:
             if self.red.hip:
                 import ctypes
-                from . import _lib
-                lib = _lib.load()
                 k = len(ps)
-                ptr = lambda ts: (ctypes.c_void_p * k)(*[t.data_ptr() for t in ts])
                 with torch.cuda.device(self.red.dev):
-                    stream = ctypes.c_void_p(torch.cuda.current_stream(self.red.dev).cuda_stream)
-                    rc = lib.g4s_adam_step(k, ptr(ps), ptr(gs), ptr(self.exp_avg), ptr(self.exp_avg_sq),
-                                           (ctypes.c_longlong * k)(*[t.numel() for t in ps]),
-                                           (ctypes.c_double * k)(*self.lrs), (ctypes.c_int * k)(*([self.steps] * k)),
-                                           self.betas[0], self.betas[1], self.eps, stream)
-                if rc != 0:
-                    raise RuntimeError(f"g4s_adam_step failed ({rc}): {_lib.last_error()}")
+                    _lib.call("g4s_adam_step", k, _lib.ptrs(ps), _lib.ptrs(gs), _lib.ptrs(self.exp_avg), _lib.ptrs(self.exp_avg_sq),
+                              _lib.array(ctypes.c_longlong, [t.numel() for t in ps]), _lib.array(ctypes.c_double, self.lrs),
+                              _lib.array(ctypes.c_int, [self.steps] * k), self.betas[0], self.betas[1], self.eps,
+                              _lib.stream(self.red.dev))
             else:
                 for p, g, m, v, lr in zip(ps, gs, self.exp_avg, self.exp_avg_sq, self.lrs):
                     adam_update_(p, g, m, v, lr, self.steps, self.betas[0], self.betas[1], self.eps)
@@ -818,20 +752,11 @@ class ViewParallel:
             raise ValueError("exchange must be 'allreduce' or 'owner'")
         self.group = group
         self.exchange = exchange
-        self._owner = None
-        self._visible = None
         self.compact_below = compact_below  # RowSparseAllReduce threshold; 0.0 = always dense
-        self._reducer = self._side = None
-        self._pipe = self._pipe_key = None  # accumulate(): the ViewPipeline of the current (P, image size)
+        self._pipe = None     # accumulate(): the ViewPipeline of the current (P, image size)
         self._capacity = {}   # (P, W, H) -> instance capacity of the pipeline's PresizedStates; 0 = unknown: stay sequential
-        self._dirty = False   # something has been accumulated since zero()
         self.regrown = 0      # accumulate(): steps redone sequentially because a view outgrew the pipeline's capacity
-        self.bucket = GradientBucket(params)
-        n = self.bucket.params[0].shape[0]
-        dev = self.bucket.flat.device
-        self.grad_norm_sum = torch.zeros((n, 1), device=dev)
-        self.vis_count = torch.zeros((n, 1), device=dev)
-        self.max_radii = torch.zeros((n,), device=dev)
+        self.rebind(params)   # the bucket, the statistics, and the exchange built on first use
 
     @property
     def world_size(self):
@@ -967,18 +892,11 @@ class ViewParallel:
         their owners (`side`, rows bounds()) -- see ReplicatedDensification(defer_stats=True); the returned grad_norm_sum /
         vis_count are then valid for this rank's own rows only."""
         if dist.is_initialized() and self.world_size > 1 and self.exchange == "owner":
-            P = self.bucket.params[0].shape[0]
-            self._ensure_owner()
-            self._side[:, 0:1] = self.grad_norm_sum
-            self._side[:, 1:2] = self.vis_count
-            vis = self._visible if self._visible is not None else torch.zeros(P, dtype=torch.bool, device=self._side.device)
             # (a training loop that drives OwnerReduce itself calls begin() right after its forward, so that the size
             # exchange hides behind the backward -- bench.py does; here both halves run back to back)
-            self._owner.begin(vis, radii=self.max_radii.to(torch.int32))  # the radii MAX rides in the same collective
-            self._owner.finish(gather_rows=None if gather_stats else range(len(self.bucket.views)))
-            self.max_radii = self._owner.max_radii.to(self.max_radii.dtype)
-            self.grad_norm_sum, self.vis_count = self._side[:, 0:1].clone(), self._side[:, 1:2].clone()
-        elif dist.is_initialized() and self.world_size > 1:
+            self._owner_exchange(gather_rows=None if gather_stats else range(len(self.bucket.views)))
+            return self.stats_after_owner_step()
+        if dist.is_initialized() and self.world_size > 1:
             dist.all_reduce(self.max_radii, op=dist.ReduceOp.MAX, group=self.group)
             if self._reducer is None:
                 P = self.bucket.params[0].shape[0]
@@ -1013,13 +931,15 @@ class ViewParallel:
         `vp.stats_after_owner_step()`."""
         if self.exchange != "owner" or not dist.is_initialized():
             raise RuntimeError("ViewParallel.reduce_to_owners() needs exchange='owner' and an initialised process group")
+        self._owner_exchange(gather=False)
+
+    def _owner_exchange(self, **finish):
         own = self._ensure_owner()
-        P = self.bucket.params[0].shape[0]
         self._side[:, 0:1] = self.grad_norm_sum
         self._side[:, 1:2] = self.vis_count
-        vis = self._visible if self._visible is not None else torch.zeros(P, dtype=torch.bool, device=self._side.device)
-        own.begin(vis, radii=self.max_radii.to(torch.int32))
-        own.finish(gather=False)
+        vis = self._visible if self._visible is not None else torch.zeros(own.P, dtype=torch.bool, device=self._side.device)
+        own.begin(vis, radii=self.max_radii.to(torch.int32))  # the radii MAX rides in the same collective
+        own.finish(**finish)
 
     @property
     def side(self):

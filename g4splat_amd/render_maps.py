@@ -7,8 +7,6 @@
 One HIP kernel forward, one backward (instead of ~15 element-wise torch kernels each way); torch is
 plumbing (memory, stream, autograd graph).  No CPU path: host tensors raise like the rasterizer's.
 """
-import ctypes
-
 import torch
 
 from . import _lib
@@ -16,10 +14,6 @@ from . import _lib
 _NAMES = ("rend_alpha", "rend_normal", "rend_normal_cam", "rend_depth", "rend_dist", "surf_depth", "surf_normal",
           "surf_normal_cam")
 _CH = (1, 3, 3, 1, 1, 1, 3, 3)
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
 
 
 def _mat(t, dev):
@@ -45,11 +39,8 @@ class _RenderMaps(torch.autograd.Function):
             outs = [torch.empty((c, H, W), dtype=torch.float32, device=dev) for c in _CH]
             nws = lib.g4s_render_maps_workspace()
             ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            rc = lib.g4s_render_maps_forward(W, H, _ptr(am), _ptr(wvt), _ptr(fpt), float(depth_ratio),
-                                             *[_ptr(o) for o in outs], _ptr(ws), nws, stream)
-        if rc != 0:
-            raise RuntimeError(f"render_maps forward failed ({rc}): {_lib.last_error()}")
+            _lib.call("g4s_render_maps_forward", W, H, _lib.ptr(am), _lib.ptr(wvt), _lib.ptr(fpt), float(depth_ratio),
+                      *[_lib.ptr(o) for o in outs], _lib.ptr(ws), nws, _lib.stream(dev))
         ctx.save_for_backward(am, outs[5], wvt, fpt)
         ctx.depth_ratio = float(depth_ratio)
         return tuple(outs)
@@ -65,11 +56,8 @@ class _RenderMaps(torch.autograd.Function):
             g_allmap = torch.empty_like(am)
             nws = lib.g4s_render_maps_workspace()
             ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            rc = lib.g4s_render_maps_backward(W, H, _ptr(am), _ptr(surf_depth), _ptr(wvt), _ptr(fpt), ctx.depth_ratio,
-                                              *[_ptr(g) for g in gs], _ptr(g_allmap), _ptr(ws), nws, stream)
-        if rc != 0:
-            raise RuntimeError(f"render_maps backward failed ({rc}): {_lib.last_error()}")
+            _lib.call("g4s_render_maps_backward", W, H, _lib.ptr(am), _lib.ptr(surf_depth), _lib.ptr(wvt), _lib.ptr(fpt),
+                      ctx.depth_ratio, *[_lib.ptr(g) for g in gs], _lib.ptr(g_allmap), _lib.ptr(ws), nws, _lib.stream(dev))
         return g_allmap, None, None, None
 
 

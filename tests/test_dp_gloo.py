@@ -242,7 +242,7 @@ def _owner_worker(rank, world, port, q):
         red2.begin(vis)
         red2.finish()
         gathers.add(red2.last_gather)
-        out.append((P, frac, exact, ok, bool(torch.equal(flat, flat2)), red.last_rows_sent, int(vis.sum())))
+        out.append((P, frac, exact, ok, bool(torch.equal(flat, flat2)), red.last_rows_sent, int(vis.sum()), red.last_order))
     # only the radii of rows a rank FLAGS take part in the MAX (the reference updates max_radii2D under the
     # visibility filter, train_with_refine_depth.py:583), and debug_checks refuses a non-zero unflagged row
     P = 64
@@ -291,11 +291,35 @@ def test_owner_reduce_equals_dense_all_reduce(world):
         assert p.exitcode == 0
     for r in range(world):
         assert res[r][-2] == (True, True), res[r][-2]
-        for P, frac, exact, ok, same_again, sent, nvis in res[r][:-2]:
+        for P, frac, exact, ok, same_again, sent, nvis, order in res[r][:-2]:
             assert ok, (r, P, frac, exact)
+            assert order == "rank", (r, P, frac, order)  # (at most 7 sources: the sums are in rank order)
             assert same_again, (r, P, frac)       # (sparse gather with radii == dense gather without: the same bits)
             assert 0 <= sent <= nvis
         assert res[r][-1] == ["dense", "sparse"], res[r][-1]  # both forms of the gather ran (small and large unions)
+
+
+def test_owner_addition_order_is_decided_once():
+    """OwnerReduce.addition_order(), the one rule both backends follow, over every (world <= 10, rank, set of live
+    sources): the rank-ordered path exactly where the device code has always taken it (rank_order on, a source below the
+    owner, 2 to 8 sources), the one-launch / per-source split at ONE_LAUNCH_SOURCES otherwise, and the recorded order
+    "owner" exactly when more than 8 sources arrive or rank_order is off."""
+    _setup_paths()
+    from itertools import combinations
+    from g4splat_amd.parallel import OwnerReduce
+    assert OwnerReduce.ONE_LAUNCH_SOURCES == 4 and OwnerReduce.ORDERED_SOURCES == 8
+    for world in range(1, 11):
+        for rank in range(world):
+            others = [s for s in range(world) if s != rank]
+            for k in range(len(others) + 1):
+                for live in combinations(others, k):
+                    for rank_order in (True, False):
+                        path, order = OwnerReduce.addition_order(list(live), rank, rank_order)
+                        below = any(s < rank for s in live)
+                        assert (path == "rank") == (rank_order and below and 2 <= k <= 8), (world, rank, live, rank_order)
+                        if path != "rank":
+                            assert path == ("one_launch" if k >= 4 else "per_source"), (world, rank, live, rank_order)
+                        assert order == ("owner" if (not rank_order or k > 8) else "rank"), (world, rank, live, rank_order)
 
 
 def _zero1_worker(rank, world, port, q):
