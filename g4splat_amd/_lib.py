@@ -88,6 +88,14 @@ SIGNATURES = {
                                       c_p]),
     "g4s_render_maps_backward": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                        c_p, c_sz, c_p]),
+    "g4s_tsdf_blocks_per_pixel": (c_i, [c_i, c_i, c_p, c_f, c_f]),
+    "g4s_tsdf_workspace": (c_sz, [c_i, c_i, c_i, c_i]),
+    "g4s_tsdf_alloc_count": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_i, c_p, c_i, c_p, c_p, c_sz, c_p]),
+    "g4s_tsdf_merge": (c_i, [c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_sz, c_p]),
+    "g4s_tsdf_integrate": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_sz,
+                                 c_p]),
+    "g4s_tsdf_extract_count": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_sz, c_p]),
+    "g4s_tsdf_extract_emit": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_f, c_p, c_p, c_p, c_i, c_i, c_p, c_sz, c_p]),
 }
 
 _lib = None

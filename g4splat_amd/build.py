@@ -12,7 +12,7 @@ def needs_build():
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h")) or f == "Makefile"]
+    srcs = [os.path.join(d, f) for d, _, files in os.walk(CSRC) for f in files if f.endswith((".hip", ".h")) or f == "Makefile"]
     inc = os.path.join(_HERE, "..", "include")
     srcs += [os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h")]  # every public header is a Makefile dependency
     return any(os.path.getmtime(s) > t for s in srcs)

@@ -1,0 +1,264 @@
+"""Mesh extraction from a trained scene: TSDF fusion of rendered depth and marching cubes on the GPU.
+
+The counterpart of 2d-gaussian-splatting/utils/mesh_utils.py:73-182 (GaussianExtractor with open3d's
+ScalableTSDFVolume; called from render.py:57-106), over the C ABI of include/g4s_render_maps.h (TSDF section, which
+states the semantics).  Depth and colour maps stay on the device; the volume lives in device tensors that grow on the
+host's decision (the library never overflows or reallocates anything).
+
+    volume = TSDFVolume(voxel_size, sdf_trunc, depth_trunc, device)
+    volume.integrate(depth, rgb, camera)           # per view
+    mesh = volume.extract_triangle_mesh()          # TriangleMesh(vertices, vertex_colors, triangles), numpy
+"""
+import ctypes
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+from . import _lib
+
+VOXELS_PER_BLOCK = 512
+
+
+class TriangleMesh(NamedTuple):
+    vertices: np.ndarray       # [V,3] float32
+    vertex_colors: np.ndarray  # [V,3] float32, 0..1
+    triangles: np.ndarray      # [F,3] int32, indices into vertices
+
+
+def _to_np(x):
+    if isinstance(x, torch.Tensor):
+        return x.detach().cpu().numpy()
+    return np.asarray(x)
+
+
+def _projection_matrix(camera):
+    """The camera's projection_matrix (row-vector convention, = Proj^T), or the one of its FoV and clip planes."""
+    pm = getattr(camera, "projection_matrix", None)
+    if pm is not None:
+        return _to_np(pm).astype(np.float32)
+    from .synthetic import projection_matrix
+    return projection_matrix(getattr(camera, "znear", 0.01), getattr(camera, "zfar", 100.0), camera.FoVx,
+                             camera.FoVy).T.astype(np.float32)
+
+
+def camera_intrinsics(camera):
+    """(fx, fy, cx, cy) exactly as to_cam_open3d computes them (mesh_utils.py:45-60): projection_matrix @ ndc2pix in
+    float32 -- a centred camera gets cx = (W-1)/2."""
+    W, H = int(camera.image_width), int(camera.image_height)
+    ndc2pix = np.array([[W / 2, 0, 0, (W - 1) / 2], [0, H / 2, 0, (H - 1) / 2], [0, 0, 0, 1]], np.float32).T
+    intr = (_projection_matrix(camera) @ ndc2pix)[:3, :3].T
+    return np.array([intr[0, 0], intr[1, 1], intr[0, 2], intr[1, 2]], np.float32)
+
+
+def camera_extrinsic(camera):
+    """world -> camera 4x4, = world_view_transform.T (mesh_utils.py:62)."""
+    return np.ascontiguousarray(_to_np(camera.world_view_transform).astype(np.float32).T)
+
+
+def _host_f32(a):
+    a = np.ascontiguousarray(a, np.float32).reshape(-1)
+    return (ctypes.c_float * len(a))(*a.tolist())
+
+
+class TSDFVolume:
+    """Sparse TSDF volume of 8^3-voxel blocks on one HIP device (the legacy ScalableTSDFVolume with RGB8 colour, as the
+    reference configures it; semantics: include/g4s_render_maps.h).  `initial_blocks` sizes the voxel pool; it grows
+    (allocate larger, copy) whenever a view brings more new blocks than it holds."""
+
+    def __init__(self, voxel_size, sdf_trunc, depth_trunc, device="cuda", initial_blocks=4096):
+        if not (voxel_size > 0 and sdf_trunc > 0 and depth_trunc > 0):
+            raise ValueError("voxel_size, sdf_trunc, depth_trunc must be positive")
+        self.voxel_size, self.sdf_trunc, self.depth_trunc = float(voxel_size), float(sdf_trunc), float(depth_trunc)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("TSDFVolume needs a HIP device (there is no CPU path)")
+        self.num_blocks = 0
+        self.grows = 0
+        cap = max(1, int(initial_blocks))
+        self.keys = torch.zeros(1, dtype=torch.int64, device=self.device)   # sorted packed block keys [num_blocks]
+        self.slots = torch.zeros(1, dtype=torch.int32, device=self.device)  # pool slot of each key
+        self.tsdf = torch.empty(cap * VOXELS_PER_BLOCK, dtype=torch.float32, device=self.device)
+        self.weight = torch.empty_like(self.tsdf)
+        self.color = torch.empty(cap * VOXELS_PER_BLOCK * 3, dtype=torch.float32, device=self.device)
+        self._ws = torch.empty(0, dtype=torch.uint8, device=self.device)
+
+    @property
+    def pool_blocks(self):
+        return self.tsdf.numel() // VOXELS_PER_BLOCK
+
+    def _workspace(self, nbytes):
+        if self._ws.numel() < nbytes:
+            self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def _grow(self, need):
+        cap = max(need, 2 * self.pool_blocks)
+        extra = (cap - self.pool_blocks) * VOXELS_PER_BLOCK
+        self.tsdf = torch.cat([self.tsdf, self.tsdf.new_empty(extra)])
+        self.weight = torch.cat([self.weight, self.weight.new_empty(extra)])
+        self.color = torch.cat([self.color, self.color.new_empty(3 * extra)])
+        self.grows += 1
+
+    def integrate(self, depth, rgb, camera, mask=None):
+        """Fuse one view: depth [1,H,W] or [H,W], rgb [3,H,W] (0..1), mask [1,H,W] / [H,W] (< 0.5: ignored), all on
+        the volume's device; `camera` carries image_width / image_height / FoVx / FoVy / world_view_transform."""
+        lib = _lib.load()
+        W, H = int(camera.image_width), int(camera.image_height)
+        depth = self._map(depth, (H, W), "depth")
+        rgb = self._map(rgb, (3, H, W), "rgb")
+        mask = None if mask is None else self._map(mask, (H, W), "mask")
+        intr, ext = _host_f32(camera_intrinsics(camera)), _host_f32(camera_extrinsic(camera))
+        v, T, D = self.voxel_size, self.sdf_trunc, self.depth_trunc
+        cap = lib.g4s_tsdf_blocks_per_pixel(W, H, intr, v, T)
+        if cap < 0:
+            raise RuntimeError(f"g4s_tsdf_blocks_per_pixel failed ({cap}): {_lib.last_error()}")
+        with torch.cuda.device(self.device):
+            nws = lib.g4s_tsdf_workspace(W, H, cap, 0)
+            ws = self._workspace(nws)
+            st = _lib.stream(self.device)
+            counts = (ctypes.c_int * 2)()
+            _lib.call("g4s_tsdf_alloc_count", W, H, _lib.ptr(depth), _lib.ptr(mask), intr, ext, v, T, D, cap,
+                      _lib.ptr(self.keys), self.num_blocks, counts, _lib.ptr(ws), ws.numel(), st)
+            m, n_new = counts[0], counts[1]
+            n = self.num_blocks + n_new
+            if n > self.pool_blocks:  # capacity is decided here, before anything is written
+                self._grow(n)
+            if m > 0:  # the merge writes the new table and gives every touched block its slot
+                keys = torch.empty(n, dtype=torch.int64, device=self.device)
+                slots = torch.empty(n, dtype=torch.int32, device=self.device)
+                _lib.call("g4s_tsdf_merge", W, H, cap, _lib.ptr(self.keys), _lib.ptr(self.slots), self.num_blocks, m, n_new,
+                          _lib.ptr(keys), _lib.ptr(slots), _lib.ptr(self.tsdf), _lib.ptr(self.weight), _lib.ptr(self.color),
+                          self.pool_blocks, _lib.ptr(ws), ws.numel(), st)
+                self.keys, self.slots, self.num_blocks = keys, slots, n
+            if m > 0:
+                _lib.call("g4s_tsdf_integrate", W, H, _lib.ptr(depth), _lib.ptr(mask), _lib.ptr(rgb), intr, ext, v, T, D,
+                          cap, m, _lib.ptr(self.tsdf), _lib.ptr(self.weight), _lib.ptr(self.color), self.pool_blocks,
+                          _lib.ptr(ws), ws.numel(), st)
+        return m, n_new
+
+    def _map(self, t, shape, name):
+        if not isinstance(t, torch.Tensor) or t.device != self.device:
+            raise RuntimeError(f"{name} must be a tensor on {self.device}")
+        t = t.detach()
+        if t.dim() == len(shape) + 1 and t.size(0) == 1:
+            t = t[0]
+        if tuple(t.shape) != tuple(shape):
+            raise RuntimeError(f"{name} must have shape {shape} (got {tuple(t.shape)})")
+        return t.float().contiguous()
+
+    def table(self):
+        """(keys int64 [n], slots int32 [n]) of the allocated blocks, ascending key, on the host."""
+        n = self.num_blocks
+        return self.keys[:n].cpu().numpy(), self.slots[:n].cpu().numpy()
+
+    def voxels(self):
+        """(tsdf [n,512], weight [n,512], colour [n,512,3]) of the allocated blocks in table order, on the host."""
+        _, slots = self.table()
+        s = torch.as_tensor(slots, dtype=torch.int64, device=self.device)
+        return (self.tsdf.view(-1, VOXELS_PER_BLOCK)[s].cpu().numpy(), self.weight.view(-1, VOXELS_PER_BLOCK)[s].cpu().numpy(),
+                self.color.view(-1, VOXELS_PER_BLOCK, 3)[s].cpu().numpy())
+
+    def extract_triangle_mesh(self):
+        """Marching cubes over the volume (include/g4s_render_maps.h: indexed, oriented towards the cameras, in a
+        defined order; bit-identical between runs)."""
+        lib = _lib.load()
+        n = self.num_blocks
+        if n == 0:
+            return TriangleMesh(np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32))
+        with torch.cuda.device(self.device):
+            nws = lib.g4s_tsdf_workspace(0, 0, 0, n)
+            ws = self._workspace(nws)
+            st = _lib.stream(self.device)
+            totals = (ctypes.c_int * 2)()
+            _lib.call("g4s_tsdf_extract_count", _lib.ptr(self.keys), _lib.ptr(self.slots), n, _lib.ptr(self.tsdf),
+                      _lib.ptr(self.weight), self.pool_blocks, totals, _lib.ptr(ws), ws.numel(), st)
+            V, F = totals[0], totals[1]
+            verts = torch.empty((max(V, 1), 3), dtype=torch.float32, device=self.device)
+            cols = torch.empty_like(verts)
+            tris = torch.empty((max(F, 1), 3), dtype=torch.int32, device=self.device)
+            _lib.call("g4s_tsdf_extract_emit", _lib.ptr(self.keys), _lib.ptr(self.slots), n, _lib.ptr(self.tsdf),
+                      _lib.ptr(self.weight), _lib.ptr(self.color), self.pool_blocks, self.voxel_size, _lib.ptr(verts),
+                      _lib.ptr(cols), _lib.ptr(tris), V, F, _lib.ptr(ws), ws.numel(), st)
+            return TriangleMesh(verts[:V].cpu().numpy(), cols[:V].cpu().numpy(), tris[:F].cpu().numpy())
+
+
+def focus_point(c2ws):
+    """The point nearest (least squares) to every camera's optical axis: argmin_p sum_i |(I - d_i d_i^T)(p - o_i)|^2,
+    d_i the viewing direction (+z of the camera), o_i its centre."""
+    c2ws = np.asarray(c2ws, np.float64)
+    d, o = c2ws[:, :3, 2], c2ws[:, :3, 3]
+    d = d / np.linalg.norm(d, axis=1, keepdims=True)
+    M = np.eye(3)[None] - d[:, :, None] * d[:, None, :]
+    return np.linalg.solve(M.sum(0), (M @ o[:, :, None]).sum(0))[:, 0]
+
+
+class GaussianExtractor:
+    """mesh_utils.py:73-182 (`GaussianExtractor`): render the views, fuse them into a TSDF volume on the GPU, extract
+    the mesh.  `render(camera, gaussians, pipe=, bg_color=)` is gaussian_renderer.render."""
+
+    def __init__(self, gaussians, render, pipe, bg_color=None):
+        if bg_color is None:
+            bg_color = [0, 0, 0]
+        self.gaussians = gaussians
+        self.device = gaussians.get_xyz.device
+        self._render, self.pipe = render, pipe
+        self.background = torch.tensor(bg_color, dtype=torch.float32, device=self.device)
+        self.clean()
+
+    def render(self, camera):
+        return self._render(camera, self.gaussians, self.pipe, self.background)
+
+    @torch.no_grad()
+    def clean(self):
+        self.depthmaps, self.rgbmaps, self.viewpoint_stack = [], [], []
+
+    @torch.no_grad()
+    def reconstruction(self, viewpoint_stack):
+        """Render every view and keep surf_depth / render ON THE DEVICE (the reference moves them to the CPU)."""
+        self.clean()
+        self.viewpoint_stack = list(viewpoint_stack)
+        for cam in self.viewpoint_stack:
+            pkg = self.render(cam)
+            self.rgbmaps.append(pkg["render"].detach())
+            self.depthmaps.append(pkg["surf_depth"].detach())
+        self.estimate_bounding_sphere()
+
+    def estimate_bounding_sphere(self):
+        """center = the focus point of the cameras' optical axes, radius = the smallest camera distance to it
+        (render.py derives depth_trunc = 2 radius from it)."""
+        c2ws = np.array([np.linalg.inv(camera_extrinsic(cam).astype(np.float64)) for cam in self.viewpoint_stack])
+        center = focus_point(c2ws)
+        self.radius = float(np.linalg.norm(c2ws[:, :3, 3] - center, axis=-1).min())
+        self.center = torch.from_numpy(center).float().to(self.device)
+
+    @staticmethod
+    def _mask(cam, mask_backgrond):
+        m = getattr(cam, "gt_alpha_mask", None) if mask_backgrond else None
+        return m
+
+    @torch.no_grad()
+    def extract_mesh_bounded(self, voxel_size=0.004, sdf_trunc=0.02, depth_trunc=3, mask_backgrond=True):
+        """TSDF fusion of the maps of reconstruction() and marching cubes (the reference's spelling of the keyword)."""
+        volume = TSDFVolume(voxel_size, sdf_trunc, depth_trunc, self.device)
+        for cam, depth, rgb in zip(self.viewpoint_stack, self.depthmaps, self.rgbmaps):
+            m = self._mask(cam, mask_backgrond)
+            volume.integrate(depth, rgb, cam, None if m is None else m.to(self.device))
+        self.volume = volume
+        return volume.extract_triangle_mesh()
+
+    @torch.no_grad()
+    def extract_mesh_bounded_streaming(self, viewpoint_stack, voxel_size=0.004, sdf_trunc=0.02, depth_trunc=3,
+                                       mask_backgrond=True):
+        """Same mesh as reconstruction() + extract_mesh_bounded(), but every view is fused right after it is rendered:
+        no map is kept, so hundreds of full-resolution views need only one view's memory."""
+        self.clean()
+        self.viewpoint_stack = list(viewpoint_stack)
+        volume = TSDFVolume(voxel_size, sdf_trunc, depth_trunc, self.device)
+        for cam in self.viewpoint_stack:
+            pkg = self.render(cam)
+            m = self._mask(cam, mask_backgrond)
+            volume.integrate(pkg["surf_depth"], pkg["render"], cam, None if m is None else m.to(self.device))
+            del pkg
+        self.volume = volume
+        return volume.extract_triangle_mesh()

@@ -111,3 +111,57 @@ def read_gaussian_ply(path, max_sh_degree=3):
         "mip_filter": col(["mip_filter"]) if "mip_filter" in v else None,
     }
     return out
+
+
+def write_triangle_mesh(path, mesh):
+    """Binary little-endian PLY of a triangle mesh (what open3d's write_triangle_mesh produces for the reference's
+    TSDF meshes): `vertex` with x y z float and red green blue uchar, `face` with a uchar-counted int list
+    `vertex_indices`.  Colours in [0,1] are stored as round(255 c) after clamping."""
+    v = np.ascontiguousarray(mesh.vertices, np.float32).reshape(-1, 3)
+    c = np.asarray(mesh.vertex_colors, np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(mesh.triangles, np.int32).reshape(-1, 3)
+    vdt = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    vert = np.empty(len(v), vdt)
+    vert["x"], vert["y"], vert["z"] = v[:, 0], v[:, 1], v[:, 2]
+    q = np.rint(np.clip(np.nan_to_num(c), 0.0, 1.0) * 255.0).astype(np.uint8)
+    vert["red"], vert["green"], vert["blue"] = q[:, 0], q[:, 1], q[:, 2]
+    fdt = np.dtype([("n", "u1"), ("i", "<i4", (3,))])
+    face = np.empty(len(t), fdt)
+    face["n"], face["i"] = 3, t
+    header = ("ply\nformat binary_little_endian 1.0\n"
+              f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+              f"element face {len(t)}\nproperty list uchar int vertex_indices\nend_header\n")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(vert.tobytes())
+        f.write(face.tobytes())
+
+
+def read_triangle_mesh(path):
+    """-> (vertices [V,3] float32, vertex_colors [V,3] float32 in [0,1], triangles [F,3] int32) of a file written by
+    write_triangle_mesh (binary little endian, that exact layout)."""
+    with open(path, "rb") as f:
+        head = []
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: unterminated PLY header")
+            line = line.decode("ascii").strip()
+            if line == "end_header":
+                break
+            head.append(line.split())
+        if head[0] != ["ply"] or head[1][:2] != ["format", "binary_little_endian"]:
+            raise ValueError(f"{path}: not a binary little-endian PLY")
+        counts = {h[1]: int(h[2]) for h in head if h[0] == "element"}
+        nv, nf = counts.get("vertex", 0), counts.get("face", 0)
+        vdt = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+        vert = np.frombuffer(f.read(nv * vdt.itemsize), vdt, count=nv)
+        fdt = np.dtype([("n", "u1"), ("i", "<i4", (3,))])
+        face = np.frombuffer(f.read(nf * fdt.itemsize), fdt, count=nf)
+    if nf and not (face["n"] == 3).all():
+        raise ValueError(f"{path}: only triangles are supported")
+    v = np.stack([vert["x"], vert["y"], vert["z"]], 1).astype(np.float32)
+    c = np.stack([vert["red"], vert["green"], vert["blue"]], 1).astype(np.float32) / 255.0
+    return v.reshape(-1, 3), c.reshape(-1, 3), face["i"].astype(np.int32).reshape(-1, 3)

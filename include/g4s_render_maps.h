@@ -59,6 +59,97 @@ int g4s_render_maps_backward(int width, int height, const float* allmap, const f
                              const float* dL_surf_normal, const float* dL_surf_normal_cam, float* dL_dallmap,
                              char* workspace, size_t workspace_bytes, void* stream);
 
+/* =====================================================================================================================
+ * TSDF fusion of rendered depth maps and marching-cubes mesh extraction (g4splat_amd/csrc/tsdf/tsdf.hip).
+ *
+ * The step after training in the reference (2d-gaussian-splatting/utils/mesh_utils.py:73-182, GaussianExtractor with
+ * open3d's ScalableTSDFVolume; render.py:57-106).  Modelled on that volume as the reference configures it, but the
+ * semantics below are this library's own, stated exactly (tests/tsdf_ref.py restates them in numpy); nothing here is
+ * claimed bit-equal to open3d.  All arithmetic is float32, round-to-nearest-even, correctly rounded / and sqrt, no
+ * fused multiply-add (the library builds with -ffp-contract=off), evaluated left to right as written.
+ *
+ * Camera.  intrinsic = {fx, fy, cx, cy} as mesh_utils.py:45-70 (to_cam_open3d) derives them from
+ *   projection_matrix @ ndc2pix (a centred camera: cx = (W-1)/2).  extrinsic = 16 floats, row-major, world -> camera
+ *   = world_view_transform.T; rows 0..2 are used (E).  The camera -> world matrix C of the allocation is the rigid
+ *   inverse of E computed in double precision and rounded to float once: C = [E3^T | -(E3^T t)], each component of
+ *   E3^T t summed left to right.  Host pointers, read during the call.
+ * Inputs per view.  depth [H,W] float32: pixel valid iff 0 < d <= depth_trunc (and, with a mask [H,W], mask >= 0.5).
+ *   rgb [3,H,W] float32: each value is clamped to [0,1] (NaN -> 0), multiplied by 255 and truncated to an integer
+ *   0..255 -- the reference's uint8 cast of rgb*255, defined also outside [0,1].
+ * Volume.  Blocks of 8^3 voxels, voxel size v; voxel (i,j,k) (global integer coordinates) has its centre at
+ *   ((i,j,k) + 0.5) * v.  Block (bx,by,bz) holds voxels 8*(bx,by,bz) + (0..7)^3, stored x fastest (lane = x + 8y + 64z).
+ *   Key of a block: ((bx + 2^20) << 42) | ((by + 2^20) << 21) | (bz + 2^20), 64-bit; the table of the volume is the
+ *   ascending list of keys with the pool slot of each.  A voxel holds tsdf, weight, colour[3] (0..255) as float32.
+ *   Pool layout: tsdf[slot*512 + lane], weight[slot*512 + lane], colour[(slot*512 + lane)*3 + c].
+ * Allocation.  Per valid pixel (u,v) with depth d: rx = (u - cx) / fx, ry = (v - cy) / fy; for z in {d - sdf_trunc,
+ *   d + sdf_trunc} the camera point (rx*z, ry*z, z) is mapped by C (w_r = ((C_r0 x + C_r1 y) + C_r2 z) + C_r3) and
+ *   divided by the block size B = 8 * v, giving a and b.  A pixel with any |a_i| or |b_i| >= 1e6 (or NaN) allocates
+ *   nothing.  Otherwise the cells floor(a) .. floor(b) are walked by a 3-D DDA: start at floor(a); while the cell is not
+ *   floor(b), among the axes i whose cell differs from floor(b_i) take the smallest
+ *   t_i = ((cell_i + (b_i > a_i ? 1 : 0)) - a_i) / (b_i - a_i)  (ties: the lowest axis) and step that axis towards
+ *   floor(b_i).  Every visited block is allocated -- a superset of the blocks the segment meets (a corner crossing
+ *   visits one extra neighbour).  The walk stops after g4s_tsdf_blocks_per_pixel() blocks, a bound that exact
+ *   arithmetic never reaches.  New blocks get the slots n_blocks, n_blocks+1, ... in ascending key order; their voxels
+ *   start at tsdf = weight = colour = 0; voxel data never moves.
+ * Integration of one view, for every voxel of every block the view allocated or touched (the set from the walk):
+ *   p = voxel centre; (x,y,z) = E p (rows as above); skip unless z > 0; u = floor((fx*x)/z + cx + 0.5),
+ *   v = floor((fy*y)/z + cy + 0.5) (round half up), skip unless 0 <= u <= W-1, 0 <= v <= H-1 and pixel (u,v) valid;
+ *   a = (u - cx)/fx, b = (v - cy)/fy, sdf = (d - z) * sqrt((1 + a*a) + b*b); skip unless sdf > -sdf_trunc;
+ *   t = min(1, sdf/sdf_trunc); tsdf <- (tsdf*w + t)/(w + 1); colour_c <- (colour_c*w + q_c)/(w + 1); w <- w + 1.
+ * Extraction.  A voxel is valid iff its block is allocated and weight > 0.  A cube (lower corner voxel g, corners
+ *   g + {0,1}^3) is valid iff its eight corners are; its configuration has bit c set iff tsdf(corner c) < 0, corner
+ *   c = x | y << 1 | z << 2.  Each cube edge is owned by its lower-corner voxel; an edge carries a vertex iff its two
+ *   voxels are valid, their signs (tsdf < 0) differ, and a valid cube contains it.  Vertex: e = f0 / (f0 - f1) (f0 at
+ *   the owner), position ((g + 0.5) along the other axes, (g_a + 0.5) + e along the edge's axis) * v, colour
+ *   (c0 + e*(c1 - c0)) / 255 per channel.  Triangles come from g4splat_amd/csrc/tsdf/tsdf_mc_table.h (generated by
+ *   tools/gen_mc_table.py: crossing polygons walked over the cube faces, ambiguous faces separate the negative corners,
+ *   fan triangulation from a vertex whose diagonals cross the cube's interior) and face towards positive tsdf, i.e.
+ *   towards the cameras.
+ * Order.  Vertices: blocks in ascending key, voxels x fastest, edges +x, +y, +z.  Triangles: blocks in ascending key,
+ *   cubes (by lower corner) x fastest, the table's order.  No atomics anywhere: two runs are bit-identical.
+ *
+ * Sequence per view:  alloc_count (emits, sorts and uniques the keys, looks them up; reads back two counts) ->
+ * the caller makes room (pool_blocks >= n_blocks + n_new, table arrays of n_blocks + n_new) -> merge (writes the new
+ * table to keys_out / slots_out, which must not alias the old one) -> integrate.  The three calls share the workspace,
+ * and merge / integrate use what alloc_count left in it.  Extraction: extract_count (reads back vertex and triangle
+ * counts) -> extract_emit.  Keys are `long long` holding the unsigned packed value (bit 63 is always 0).
+ * Every argument is checked on the host before anything is launched; capacities are the caller's: no kernel grows or
+ * overflows anything.
+ */
+
+/* Key slots per pixel the allocation needs for this camera (>= 1), or a negative G4S_ERR_* for bad arguments. */
+int g4s_tsdf_blocks_per_pixel(int width, int height, const float* intrinsic, float voxel_size, float sdf_trunc);
+
+/* Bytes of device workspace for views of width x height with `blocks_per_pixel` key slots (width = 0: none) and for
+ * the extraction of a volume of n_blocks blocks: the larger of the two. */
+size_t g4s_tsdf_workspace(int width, int height, int blocks_per_pixel, int n_blocks);
+
+/* counts[0] = blocks the view touches, counts[1] = of those, blocks not yet in the table (host int[2]). */
+int g4s_tsdf_alloc_count(int width, int height, const float* depth, const float* mask, const float* intrinsic,
+                         const float* extrinsic, float voxel_size, float sdf_trunc, float depth_trunc, int blocks_per_pixel,
+                         const long long* keys, int n_blocks, int* counts, char* workspace, size_t workspace_bytes,
+                         void* stream);
+
+int g4s_tsdf_merge(int width, int height, int blocks_per_pixel, const long long* keys_in, const int* slots_in, int n_blocks,
+                   int n_touched, int n_new, long long* keys_out, int* slots_out, float* tsdf, float* weight, float* color,
+                   int pool_blocks, char* workspace, size_t workspace_bytes, void* stream);
+
+int g4s_tsdf_integrate(int width, int height, const float* depth, const float* mask, const float* rgb,
+                       const float* intrinsic, const float* extrinsic, float voxel_size, float sdf_trunc, float depth_trunc,
+                       int blocks_per_pixel, int n_touched, float* tsdf, float* weight, float* color, int pool_blocks,
+                       char* workspace, size_t workspace_bytes, void* stream);
+
+/* totals[0] = vertices, totals[1] = triangles of the mesh (host int[2]). */
+int g4s_tsdf_extract_count(const long long* keys, const int* slots, int n_blocks, const float* tsdf, const float* weight,
+                           int pool_blocks, int* totals, char* workspace, size_t workspace_bytes, void* stream);
+
+/* vertices [n_vertices,3], vertex_colors [n_vertices,3] (0..1), triangles [n_triangles,3]: the totals of extract_count
+ * on the same volume and workspace (nothing is written beyond them). */
+int g4s_tsdf_extract_emit(const long long* keys, const int* slots, int n_blocks, const float* tsdf, const float* weight,
+                          const float* color, int pool_blocks, float voxel_size, float* vertices, float* vertex_colors,
+                          int* triangles, int n_vertices, int n_triangles, char* workspace, size_t workspace_bytes,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

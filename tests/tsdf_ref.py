@@ -1,0 +1,291 @@
+"""numpy restatement of the TSDF fusion and marching-cubes contract (include/g4s_render_maps.h, TSDF section).
+
+Every float operation is float32 in the header's order, so the allocation, the slot order, the voxel values and the
+extracted mesh can be compared with the HIP library exactly.  Slow and simple: for tests only.
+"""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import gen_mc_table  # noqa: E402
+
+f32 = np.float32
+BIAS = 1 << 20
+COORD_LIMIT = f32(1.0e6)
+
+
+def pack_keys(b):
+    """[N,3] int block coordinates -> [N] int64 packed keys."""
+    b = np.asarray(b, np.int64) + BIAS
+    return (b[:, 0] << 42) | (b[:, 1] << 21) | b[:, 2]
+
+
+def unpack_keys(k):
+    k = np.asarray(k, np.int64)
+    return np.stack([(k >> 42) & 0x1FFFFF, (k >> 21) & 0x1FFFFF, k & 0x1FFFFF], 1) - BIAS
+
+
+def camera_to_world(E):
+    """C = rigid inverse of the 3x4 rows of E (row-major 16 floats), in double, rounded once."""
+    E = np.asarray(E, f32).reshape(4, 4)
+    C = np.zeros((3, 4), f32)
+    for r in range(3):
+        for k in range(3):
+            C[r, k] = E[k, r]
+        t = (float(E[0, r]) * float(E[0, 3]) + float(E[1, r]) * float(E[1, 3])) + float(E[2, r]) * float(E[2, 3])
+        C[r, 3] = f32(-t)
+    return C
+
+
+def _affine(M, x, y, z):
+    return [((M[r, 0] * x + M[r, 1] * y) + M[r, 2] * z) + M[r, 3] for r in range(3)]
+
+
+def blocks_per_pixel(W, H, intr, voxel_size, sdf_trunc):
+    fx, fy, cx, cy = (float(f32(v)) for v in intr)
+    rx = max(abs(-cx), abs(W - 1 - cx)) / fx
+    ry = max(abs(-cy), abs(H - 1 - cy)) / fy
+    length = 2.0 * float(f32(sdf_trunc)) * np.sqrt(1.0 + rx * rx + ry * ry) / (8.0 * float(f32(voxel_size)))
+    return 1 + 3 * (int(np.ceil(length * (1.0 + 1e-6))) + 1)
+
+
+def valid_pixels(depth, mask, depth_trunc):
+    d = np.asarray(depth, f32)
+    ok = (d > 0) & (d <= f32(depth_trunc))
+    if mask is not None:
+        ok &= np.asarray(mask, f32) >= f32(0.5)
+    return ok
+
+
+def view_blocks(depth, mask, intr, E, voxel_size, sdf_trunc, depth_trunc):
+    """Block coordinates the DDA of every valid pixel visits ([N,3], with repeats)."""
+    H, W = depth.shape
+    fx, fy, cx, cy = (f32(v) for v in intr)
+    T, bs = f32(sdf_trunc), f32(8.0) * f32(voxel_size)
+    cap = blocks_per_pixel(W, H, intr, voxel_size, sdf_trunc)
+    C = camera_to_world(E)
+    vy, vx = np.nonzero(valid_pixels(depth, mask, depth_trunc))
+    d = np.asarray(depth, f32)[vy, vx]
+    rx, ry = (vx.astype(f32) - cx) / fx, (vy.astype(f32) - cy) / fy
+    z0, z1 = d - T, d + T
+    a = np.stack(_affine(C, rx * z0, ry * z0, z0), 1) / bs
+    b = np.stack(_affine(C, rx * z1, ry * z1, z1), 1) / bs
+    ok = np.all((np.abs(a) < COORD_LIMIT) & (np.abs(b) < COORD_LIMIT), 1)
+    a, b = a[ok], b[ok]
+    cell, end = np.floor(a).astype(np.int64), np.floor(b).astype(np.int64)
+    dirv = b - a
+    step = np.where(end > cell, 1, -1)
+    out = [cell.copy()]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for _ in range(cap - 1):
+            live = np.any(cell != end, 1)
+            if not live.any():
+                break
+            t = ((cell + (step > 0)).astype(f32) - a) / dirv
+            t = np.where(cell != end, t, np.inf)
+            best = np.argmin(t, 1)  # first minimum: ties go to the lower axis
+            idx = np.nonzero(live)[0]
+            cell[idx, best[idx]] += step[idx, best[idx]]
+            out.append(cell[idx].copy())
+    return np.concatenate(out, 0)
+
+
+def quantise(rgb):
+    return np.floor(np.fmin(np.fmax(np.asarray(rgb, f32), f32(0)), f32(1)) * f32(255)).astype(f32)
+
+
+class RefVolume:
+    def __init__(self, voxel_size, sdf_trunc, depth_trunc):
+        self.v, self.T, self.depth_trunc = f32(voxel_size), f32(sdf_trunc), f32(depth_trunc)
+        self.keys = np.zeros(0, np.int64)   # sorted
+        self.slots = np.zeros(0, np.int32)  # table order
+        self.tsdf = np.zeros((0, 512), f32)
+        self.weight = np.zeros((0, 512), f32)
+        self.color = np.zeros((0, 512, 3), f32)
+
+    def integrate(self, depth, rgb, intr, E, mask=None):
+        depth = np.asarray(depth, f32)
+        H, W = depth.shape
+        blocks = view_blocks(depth, mask, intr, E, self.v, self.T, self.depth_trunc)
+        touched = np.unique(pack_keys(blocks)) if len(blocks) else np.zeros(0, np.int64)
+        new = np.setdiff1d(touched, self.keys)
+        n = len(self.keys)
+        new_slots = np.arange(n, n + len(new), dtype=np.int32)
+        keys = np.concatenate([self.keys, new])
+        slots = np.concatenate([self.slots, new_slots])
+        order = np.argsort(keys, kind="stable")
+        self.keys, self.slots = keys[order], slots[order]
+        self.tsdf = np.concatenate([self.tsdf, np.zeros((len(new), 512), f32)])
+        self.weight = np.concatenate([self.weight, np.zeros((len(new), 512), f32)])
+        self.color = np.concatenate([self.color, np.zeros((len(new), 512, 3), f32)])
+        if len(touched) == 0:
+            return
+        tslot = self.slots[np.searchsorted(self.keys, touched)]
+        lane = np.arange(512)
+        loc = np.stack([lane & 7, (lane >> 3) & 7, lane >> 6], 1)
+        g = (unpack_keys(touched)[:, None, :] * 8 + loc[None]).reshape(-1, 3)
+        slot = np.repeat(tslot, 512)
+        ln = np.tile(lane, len(touched))
+        p = (g.astype(f32) + f32(0.5)) * self.v
+        E4 = np.asarray(E, f32).reshape(4, 4)
+        x, y, z = _affine(E4, p[:, 0], p[:, 1], p[:, 2])
+        fx, fy, cx, cy = (f32(q) for q in intr)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            fu = np.floor((fx * x) / z + cx + f32(0.5))
+            fv = np.floor((fy * y) / z + cy + f32(0.5))
+        ok = (z > 0) & (fu >= 0) & (fu <= W - 1) & (fv >= 0) & (fv <= H - 1)
+        idx = np.nonzero(ok)[0]
+        u, v = fu[idx].astype(np.int64), fv[idx].astype(np.int64)
+        good = valid_pixels(depth, mask, self.depth_trunc)[v, u]
+        idx, u, v = idx[good], u[good], v[good]
+        d = depth[v, u]
+        a, b = (fu[idx] - cx) / fx, (fv[idx] - cy) / fy
+        sdf = (d - z[idx]) * np.sqrt((f32(1) + a * a) + b * b)
+        keep = sdf > -self.T
+        idx, u, v, sdf = idx[keep], u[keep], v[keep], sdf[keep]
+        t = np.fmin(f32(1), sdf / self.T)
+        s, l = slot[idx], ln[idx]
+        w = self.weight[s, l]
+        w1 = w + f32(1)
+        self.tsdf[s, l] = (self.tsdf[s, l] * w + t) / w1
+        q = quantise(np.asarray(rgb, f32)[:, v, u]).T
+        self.color[s, l] = (self.color[s, l] * w[:, None] + q) / w1[:, None]
+        self.weight[s, l] = w1
+
+    def voxels(self):
+        """(tsdf, weight, colour) in table order: [n,512], [n,512], [n,512,3]."""
+        return self.tsdf[self.slots], self.weight[self.slots], self.color[self.slots]
+
+    def extract(self):
+        return extract_mesh(self.keys, *self.voxels(), self.v)
+
+
+_TABLE = None
+
+
+def mc_table():
+    global _TABLE
+    if _TABLE is None:
+        _TABLE = gen_mc_table.table()
+    return _TABLE
+
+
+def _edge_owner(e):
+    """(offset of the owning voxel from the cube's lower corner, axis) of cube edge e."""
+    axis, n = divmod(e, 4)
+    o = [0, 0, 0]
+    others = [ax for ax in range(3) if ax != axis]
+    o[others[0]], o[others[1]] = n & 1, n >> 1
+    return tuple(o), axis
+
+
+def extract_mesh(keys, tsdf, weight, color, voxel_size):
+    """Marching cubes over blocks `keys` (sorted) with voxel arrays in the same order.
+    Returns (vertices [V,3] f32, colours [V,3] f32, triangles [F,3] i32)."""
+    v = f32(voxel_size)
+    if len(keys) == 0:
+        return np.zeros((0, 3), f32), np.zeros((0, 3), f32), np.zeros((0, 3), np.int32)
+    bc = unpack_keys(keys)
+    lane = np.arange(512)
+    loc = np.stack([lane & 7, (lane >> 3) & 7, lane >> 6], 1)
+    g = bc[:, None, :] * 8 + loc[None]  # [n,512,3] in output order
+    lo = g.reshape(-1, 3).min(0) - 1
+    dims = g.reshape(-1, 3).max(0) - lo + 2
+    F = np.full(dims, np.nan, f32)
+    Cg = np.zeros(tuple(dims) + (3,), f32)
+    gi = (g.reshape(-1, 3) - lo).T
+    F[tuple(gi)] = np.where(weight.reshape(-1) > 0, tsdf.reshape(-1), np.nan)
+    Cg[tuple(gi)] = color.reshape(-1, 3)
+    valid = ~np.isnan(F)
+    neg = F < 0
+    X, Y, Z = dims
+    # cube at lower corner (x, y, z): all corners valid; configuration bits
+    cv = np.zeros(dims, bool)
+    cfg = np.zeros(dims, np.int64)
+    sl = lambda c: (slice(c[0], X - 1 + c[0]), slice(c[1], Y - 1 + c[1]), slice(c[2], Z - 1 + c[2]))
+    inner = (slice(0, X - 1), slice(0, Y - 1), slice(0, Z - 1))
+    cv[inner] = True
+    for c in range(8):
+        off = (c & 1, (c >> 1) & 1, c >> 2)
+        cv[inner] &= valid[sl(off)]
+        cfg[inner] |= neg[sl(off)].astype(np.int64) << c
+    # edges owned by each voxel: crossing between two valid voxels used by a valid cube
+    owned = np.zeros(tuple(dims) + (3,), bool)
+    cvp = np.pad(cv, 1)  # index +1
+    for a in range(3):
+        e = [0, 0, 0]
+        e[a] = 1
+        f0 = F
+        f1 = np.full(dims, np.nan, f32)
+        f1[:X - e[0], :Y - e[1], :Z - e[2]] = F[e[0]:, e[1]:, e[2]:]
+        cross = ~np.isnan(f0) & ~np.isnan(f1) & ((f0 < 0) != (f1 < 0))
+        others = [ax for ax in range(3) if ax != a]
+        used = np.zeros(dims, bool)
+        for o in range(4):
+            d = [0, 0, 0]
+            d[others[0]], d[others[1]] = -(o & 1), -(o >> 1)
+            used |= cvp[1 + d[0]:1 + d[0] + X, 1 + d[1]:1 + d[1] + Y, 1 + d[2]:1 + d[2] + Z]
+        owned[..., a] = cross & used
+    # vertex ids in output order: blocks, voxels x fastest, edges +x +y +z
+    own_seq = owned[tuple(gi)]  # [n*512, 3]
+    flat = own_seq.reshape(-1)
+    vid = np.full(tuple(dims) + (3,), -1, np.int64)
+    ids = np.cumsum(flat) - 1
+    vid_seq = np.where(flat, ids, -1).reshape(-1, 3)
+    vid[tuple(gi)] = vid_seq
+    nz = np.nonzero(flat)[0]
+    vox, axis = nz // 3, nz % 3
+    gv = g.reshape(-1, 3)[vox]
+    p0 = gv - lo
+    p1 = p0 + np.eye(3, dtype=np.int64)[axis]
+    f0, f1 = F[tuple(p0.T)], F[tuple(p1.T)]
+    e = f0 / (f0 - f1)
+    cen = gv.astype(f32) + f32(0.5)
+    pos = cen.copy()
+    pos[np.arange(len(nz)), axis] = cen[np.arange(len(nz)), axis] + e
+    verts = (pos * v).astype(f32)
+    c0, c1 = Cg[tuple(p0.T)], Cg[tuple(p1.T)]
+    cols = ((c0 + e[:, None] * (c1 - c0)) / f32(255)).astype(f32)
+    # triangles: cubes in output order
+    tab = mc_table()
+    cube_ok = cv[tuple(gi)]
+    cube_cfg = cfg[tuple(gi)]
+    owners = [_edge_owner(k) for k in range(12)]
+    tris = []
+    for i in np.nonzero(cube_ok)[0]:
+        for tri in tab[cube_cfg[i]]:
+            row = []
+            for k in tri:
+                o, ax = owners[k]
+                q = gi[:, i] + np.array(o)
+                row.append(vid[q[0], q[1], q[2], ax])
+            tris.append(row)
+    tris = np.asarray(tris, np.int32).reshape(-1, 3)
+    assert (tris >= 0).all()
+    return verts, cols, tris
+
+
+def edge_use(tris):
+    """{(i, j): count of directed edge i->j} over the triangles."""
+    from collections import Counter
+    t = np.asarray(tris, np.int64).reshape(-1, 3)
+    return Counter(map(tuple, np.concatenate([t[:, [0, 1]], t[:, [1, 2]], t[:, [2, 0]]]).tolist()))
+
+
+def sphere_depth(cam_E, intr, W, H, center, radius):
+    """Analytic z-depth of a sphere seen by a camera (0 where the ray misses)."""
+    E = np.asarray(cam_E, np.float64).reshape(4, 4)
+    fx, fy, cx, cy = intr
+    u, v = np.meshgrid(np.arange(W), np.arange(H))
+    dirs = np.stack([(u - cx) / fx, (v - cy) / fy, np.ones_like(u, dtype=np.float64)], -1)
+    c = E[:3, :3] @ np.asarray(center, np.float64) + E[:3, 3]
+    # |z dir - c|^2 = r^2 -> z^2 |dir|^2 - 2 z dir.c + |c|^2 - r^2 = 0
+    A = (dirs ** 2).sum(-1)
+    B = -2 * (dirs @ c)
+    Cq = c @ c - radius ** 2
+    disc = B * B - 4 * A * Cq
+    z = np.where(disc >= 0, (-B - np.sqrt(np.maximum(disc, 0))) / (2 * A), 0.0)
+    return z.astype(f32)
