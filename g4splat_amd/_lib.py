@@ -96,6 +96,16 @@ SIGNATURES = {
                                  c_p]),
     "g4s_tsdf_extract_count": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_sz, c_p]),
     "g4s_tsdf_extract_emit": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_f, c_p, c_p, c_p, c_i, c_i, c_p, c_sz, c_p]),
+    "g4s_mesh_observed_vertices": (c_i, [c_i, c_p, c_i, c_p, c_p, c_f, c_p, c_p]),
+    "g4s_mesh_keep_unobserved": (c_i, [c_i, c_p, c_i, c_p, c_p, c_p]),
+    "g4s_mesh_keep_min_size": (c_i, [c_i, c_p, c_i, c_p, c_p]),
+    "g4s_mesh_keep_nondegenerate": (c_i, [c_i, c_p, c_p, c_p]),
+    "g4s_mesh_keep_short_edges": (c_i, [c_i, c_p, c_i, c_p, ctypes.c_double, c_p, c_p]),
+    "g4s_mesh_cluster_workspace": (c_sz, [c_i]),
+    "g4s_mesh_cluster_triangles": (c_i, [c_i, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_mesh_compact_workspace": (c_sz, [c_i, c_i]),
+    "g4s_mesh_compact_count": (c_i, [c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_sz, c_p]),
+    "g4s_mesh_compact_emit": (c_i, [c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_sz, c_p]),
 }
 
 _lib = None

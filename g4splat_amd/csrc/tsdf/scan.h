@@ -1,0 +1,13 @@
+// The generic exclusive scan of tsdf.hip, shared with mesh_ops.hip (both compact with it).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace g4s {
+
+// Exclusive scan of n u32 values in a fixed order (three launches): out must not alias in, *d_total = their sum,
+// `chunks` = scan_chunks(n) words of device scratch.
+int scan_chunks(long n);
+void scan_u32(const uint32_t* in, uint32_t* out, int n, uint32_t* chunks, uint32_t* d_total, hipStream_t s);
+
+}  // namespace g4s

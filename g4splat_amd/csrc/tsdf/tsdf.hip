@@ -15,6 +15,7 @@
 
 #include "../g4s_internal.h"
 #include "../g4s_device.h"
+#include "scan.h"
 #include "tsdf_mc_table.h"
 
 namespace g4s {
@@ -145,10 +146,11 @@ __global__ void __launch_bounds__(256) scan_apply_kernel(const uint32_t* __restr
     }
 }
 
-inline int scan_chunks(long n) { return (int)((n + SCAN_CHUNK - 1) / SCAN_CHUNK); }
+int scan_chunks(long n) { return (int)((n + SCAN_CHUNK - 1) / SCAN_CHUNK); }
 
 // out = exclusive scan of in (n values; out must not alias in), *d_total = sum; chunks: scan_chunks(n) words of scratch
-static void scan_u32(const uint32_t* in, uint32_t* out, int n, uint32_t* chunks, uint32_t* d_total, hipStream_t s) {
+// (declared in scan.h: mesh_ops.hip compacts with it too)
+void scan_u32(const uint32_t* in, uint32_t* out, int n, uint32_t* chunks, uint32_t* d_total, hipStream_t s) {
     const int nc = scan_chunks(n);
     if (nc == 0) {
         (void)hipMemsetAsync(d_total, 0, 4, s);

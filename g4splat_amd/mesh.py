@@ -8,6 +8,11 @@ host's decision (the library never overflows or reallocates anything).
     volume = TSDFVolume(voxel_size, sdf_trunc, depth_trunc, device)
     volume.integrate(depth, rgb, camera)           # per view
     mesh = volume.extract_triangle_mesh()          # TriangleMesh(vertices, vertex_colors, triangles), numpy
+
+The rest of the reference's export (render_multires.py:139-206, utils/mesh_utils.py:22-43, utils/mesh_filter.py) runs on
+the device too, over the "mesh operations" of the same header: cull_observed_faces, join_meshes,
+cluster_connected_triangles, post_process_mesh, filter_mesh, and GaussianExtractor.extract_mesh_multires that chains
+them.  Each takes a TriangleMesh (numpy; uploaded) or a DeviceMesh (tensors) and returns the kind it was given.
 """
 import ctypes
 from typing import NamedTuple
@@ -24,6 +29,12 @@ class TriangleMesh(NamedTuple):
     vertices: np.ndarray       # [V,3] float32
     vertex_colors: np.ndarray  # [V,3] float32, 0..1
     triangles: np.ndarray      # [F,3] int32, indices into vertices
+
+
+class DeviceMesh(NamedTuple):
+    vertices: torch.Tensor       # [V,3] float32, on the HIP device
+    vertex_colors: torch.Tensor  # [V,3] float32, 0..1
+    triangles: torch.Tensor      # [F,3] int32, indices into vertices
 
 
 def _to_np(x):
@@ -159,12 +170,14 @@ class TSDFVolume:
         return (self.tsdf.view(-1, VOXELS_PER_BLOCK)[s].cpu().numpy(), self.weight.view(-1, VOXELS_PER_BLOCK)[s].cpu().numpy(),
                 self.color.view(-1, VOXELS_PER_BLOCK, 3)[s].cpu().numpy())
 
-    def extract_triangle_mesh(self):
+    def extract_triangle_mesh(self, to_host=True):
         """Marching cubes over the volume (include/g4s_render_maps.h: indexed, oriented towards the cameras, in a
-        defined order; bit-identical between runs)."""
+        defined order; bit-identical between runs).  to_host=False: the same arrays as a DeviceMesh."""
         lib = _lib.load()
         n = self.num_blocks
         if n == 0:
+            if not to_host:
+                return _empty_device_mesh(self.device)
             return TriangleMesh(np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32))
         with torch.cuda.device(self.device):
             nws = lib.g4s_tsdf_workspace(0, 0, 0, n)
@@ -180,7 +193,190 @@ class TSDFVolume:
             _lib.call("g4s_tsdf_extract_emit", _lib.ptr(self.keys), _lib.ptr(self.slots), n, _lib.ptr(self.tsdf),
                       _lib.ptr(self.weight), _lib.ptr(self.color), self.pool_blocks, self.voxel_size, _lib.ptr(verts),
                       _lib.ptr(cols), _lib.ptr(tris), V, F, _lib.ptr(ws), ws.numel(), st)
+            if not to_host:
+                return DeviceMesh(verts[:V], cols[:V], tris[:F])
             return TriangleMesh(verts[:V].cpu().numpy(), cols[:V].cpu().numpy(), tris[:F].cpu().numpy())
+
+
+# ---- mesh operations (include/g4s_render_maps.h, "mesh operations"; csrc/tsdf/mesh_ops.hip) ---------------------------
+def _empty_device_mesh(device):
+    z = torch.zeros((0, 3), dtype=torch.float32, device=device)
+    return DeviceMesh(z, z.clone(), torch.zeros((0, 3), dtype=torch.int32, device=device))
+
+
+def _default_device():
+    if not torch.cuda.is_available():
+        raise RuntimeError("mesh operations need a HIP device (there is no CPU path)")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _as_device_mesh(mesh, device=None):
+    """(DeviceMesh, was_host): a TriangleMesh is uploaded (to `device` or the current HIP device)."""
+    if isinstance(mesh, DeviceMesh):
+        dev = mesh.vertices.device
+        if dev.type != "cuda" or mesh.vertex_colors.device != dev or mesh.triangles.device != dev:
+            raise RuntimeError("a DeviceMesh lives on one HIP device")
+        host = False
+    else:
+        dev = torch.device(device) if device is not None else _default_device()
+        host = True
+    v = torch.as_tensor(np.ascontiguousarray(mesh.vertices, np.float32) if host else mesh.vertices, device=dev)
+    c = torch.as_tensor(np.ascontiguousarray(mesh.vertex_colors, np.float32) if host else mesh.vertex_colors, device=dev)
+    t = torch.as_tensor(np.ascontiguousarray(mesh.triangles, np.int32) if host else mesh.triangles, device=dev)
+    v, c, t = v.float().reshape(-1, 3).contiguous(), c.float().reshape(-1, 3).contiguous(), t.reshape(-1, 3).contiguous()
+    if t.dtype != torch.int32:
+        t = t.to(torch.int32)
+    if c.shape != v.shape:
+        raise RuntimeError(f"vertex_colors {tuple(c.shape)} must match vertices {tuple(v.shape)}")
+    return DeviceMesh(v, c, t), host
+
+
+def _returned(mesh, host):
+    if not host:
+        return mesh
+    return TriangleMesh(mesh.vertices.cpu().numpy(), mesh.vertex_colors.cpu().numpy(), mesh.triangles.cpu().numpy())
+
+
+def _keep_mask(n, device):
+    return torch.empty(max(n, 1), dtype=torch.uint8, device=device)
+
+
+def compact_mesh(mesh, keep=None, compact_vertices=True):
+    """Stable compaction of a DeviceMesh: the triangles with keep != 0 (all when None) and -- compact_vertices -- only the
+    vertices they name, indices rewritten; otherwise the vertex arrays are passed through."""
+    lib = _lib.load()
+    v, c, t = mesh
+    dev = v.device
+    V, F = v.size(0), t.size(0)
+    with torch.cuda.device(dev):
+        ws = torch.empty(lib.g4s_mesh_compact_workspace(V, F), dtype=torch.uint8, device=dev)
+        st = _lib.stream(dev)
+        totals = (ctypes.c_int * 2)()
+        _lib.call("g4s_mesh_compact_count", V, F, _lib.ptr(t), _lib.ptr(keep), int(compact_vertices), totals, _lib.ptr(ws),
+                  ws.numel(), st)
+        Vo, Fo = totals[0], totals[1]
+        to = torch.empty((max(Fo, 1), 3), dtype=torch.int32, device=dev)
+        vo = co = None
+        if compact_vertices:
+            vo = torch.empty((max(Vo, 1), 3), dtype=torch.float32, device=dev)
+            co = torch.empty_like(vo)
+        _lib.call("g4s_mesh_compact_emit", V, F, _lib.ptr(v), _lib.ptr(c), _lib.ptr(t), int(compact_vertices), _lib.ptr(vo),
+                  _lib.ptr(co), _lib.ptr(to), Vo, Fo, _lib.ptr(ws), ws.numel(), st)
+    if compact_vertices:
+        return DeviceMesh(vo[:Vo], co[:Vo], to[:Fo])
+    return DeviceMesh(v, c, to[:Fo])
+
+
+def _camera_matrices(cameras, device):
+    """([C,16] world_view_transform, [C,16] full_proj_transform) float32 on `device`, row-vector convention."""
+    def stack(name):
+        rows = [torch.as_tensor(getattr(cam, name)).detach().to(device=device, dtype=torch.float32).reshape(16)
+                for cam in cameras]
+        return torch.stack(rows).contiguous() if rows else torch.zeros((0, 16), dtype=torch.float32, device=device)
+    return stack("world_view_transform"), stack("full_proj_transform")
+
+
+def observed_face_mask(mesh, cameras, near_trunc):
+    """Keep mask (uint8 [F], 1 = keep) of a DeviceMesh: 0 where all three vertices lie inside some camera's image and
+    nearer to it than near_trunc (render_multires.py:164-177)."""
+    v, _c, t = mesh
+    dev = v.device
+    V, F = v.size(0), t.size(0)
+    wv, fp = _camera_matrices(cameras, dev)
+    observed = _keep_mask(V, dev)
+    keep = _keep_mask(F, dev)
+    with torch.cuda.device(dev):
+        st = _lib.stream(dev)
+        _lib.call("g4s_mesh_observed_vertices", V, _lib.ptr(v), wv.size(0), _lib.ptr(wv), _lib.ptr(fp), float(near_trunc),
+                  _lib.ptr(observed), st)
+        _lib.call("g4s_mesh_keep_unobserved", F, _lib.ptr(t), V, _lib.ptr(observed), _lib.ptr(keep), st)
+    return keep[:F]
+
+
+def cull_observed_faces(mesh, cameras, near_trunc):
+    """Drop the faces a finer level already covers (observed_face_mask), then the vertices nothing names any more."""
+    dm, host = _as_device_mesh(mesh)
+    return _returned(compact_mesh(dm, observed_face_mask(dm, cameras, near_trunc)), host)
+
+
+def join_meshes(meshes):
+    """One mesh of all (join_meshes_as_scene): arrays concatenated, indices offset by the vertices before them."""
+    meshes = list(meshes)
+    if not meshes:
+        raise ValueError("join_meshes needs at least one mesh")
+    host = not isinstance(meshes[0], DeviceMesh)
+    if any(isinstance(m, DeviceMesh) == host for m in meshes):
+        raise TypeError("join_meshes takes meshes of one kind")
+    if host:
+        offs = np.cumsum([0] + [len(m.vertices) for m in meshes[:-1]])
+        return TriangleMesh(np.concatenate([np.asarray(m.vertices, np.float32).reshape(-1, 3) for m in meshes]),
+                            np.concatenate([np.asarray(m.vertex_colors, np.float32).reshape(-1, 3) for m in meshes]),
+                            np.concatenate([np.asarray(m.triangles, np.int32).reshape(-1, 3) + np.int32(o)
+                                            for m, o in zip(meshes, offs)]))
+    if sum(m.vertices.size(0) for m in meshes) > (2 ** 31 - 1) // 3:
+        raise RuntimeError("joined mesh exceeds 2^31 / 3 vertices")
+    tris, off = [], 0
+    for m in meshes:
+        tris.append(m.triangles + off)
+        off += m.vertices.size(0)
+    return DeviceMesh(torch.cat([m.vertices for m in meshes]), torch.cat([m.vertex_colors for m in meshes]), torch.cat(tris))
+
+
+def _cluster(dm):
+    lib = _lib.load()
+    t = dm.triangles
+    dev, F = t.device, t.size(0)
+    labels = torch.empty(max(F, 1), dtype=torch.int32, device=dev)
+    sizes = torch.empty_like(labels)
+    with torch.cuda.device(dev):
+        ws = torch.empty(lib.g4s_mesh_cluster_workspace(F), dtype=torch.uint8, device=dev)
+        _lib.call("g4s_mesh_cluster_triangles", F, _lib.ptr(t), _lib.ptr(labels), _lib.ptr(sizes), _lib.ptr(ws), ws.numel(),
+                  _lib.stream(dev))
+    return labels[:F], sizes[:F]
+
+
+def cluster_connected_triangles(mesh):
+    """(labels [F], sizes [F]) int32: the smallest triangle index of each triangle's edge-connected cluster and that
+    cluster's triangle count (open3d returns dense cluster numbers and per-cluster counts: the same partition)."""
+    dm, host = _as_device_mesh(mesh)
+    labels, sizes = _cluster(dm)
+    return (labels.cpu().numpy(), sizes.cpu().numpy()) if host else (labels, sizes)
+
+
+def post_process_mesh(mesh, cluster_to_keep=1000):
+    """mesh_utils.py:22-43: keep the clusters at least as large as the cluster_to_keep-th largest (never smaller than 50
+    triangles; ties all kept), drop unreferenced vertices, then degenerate triangles.  With fewer clusters than
+    cluster_to_keep the reference raises IndexError; here the smallest cluster size stands in for the k-th largest."""
+    if cluster_to_keep < 1:
+        raise ValueError("cluster_to_keep must be at least 1")
+    dm, host = _as_device_mesh(mesh)
+    dev, F = dm.triangles.device, dm.triangles.size(0)
+    if F == 0:
+        return _returned(compact_mesh(dm), host)
+    labels, sizes = _cluster(dm)
+    # one entry per cluster (its root triangle); only this per-cluster array is sorted, only one number reaches the host
+    cluster_sizes = sizes[labels == torch.arange(F, dtype=torch.int32, device=dev)]
+    ordered = torch.sort(cluster_sizes, descending=True).values
+    kth = int(ordered[min(int(cluster_to_keep), ordered.numel()) - 1])
+    keep = _keep_mask(F, dev)
+    with torch.cuda.device(dev):
+        _lib.call("g4s_mesh_keep_min_size", F, _lib.ptr(sizes), max(kth, 50), _lib.ptr(keep), _lib.stream(dev))
+    dm = compact_mesh(dm, keep)
+    F = dm.triangles.size(0)
+    with torch.cuda.device(dev):
+        _lib.call("g4s_mesh_keep_nondegenerate", F, _lib.ptr(dm.triangles), _lib.ptr(keep), _lib.stream(dev))
+    return _returned(compact_mesh(dm, keep, compact_vertices=False), host)
+
+
+def filter_mesh(mesh, length_threshold=0.05):
+    """utils/mesh_filter.py:6-32: drop the faces with an edge longer than length_threshold, then unreferenced vertices."""
+    dm, host = _as_device_mesh(mesh)
+    dev, F = dm.triangles.device, dm.triangles.size(0)
+    keep = _keep_mask(F, dev)
+    with torch.cuda.device(dev):
+        _lib.call("g4s_mesh_keep_short_edges", F, _lib.ptr(dm.triangles), dm.vertices.size(0), _lib.ptr(dm.vertices),
+                  float(length_threshold), _lib.ptr(keep), _lib.stream(dev))
+    return _returned(compact_mesh(dm, keep), host)
 
 
 def focus_point(c2ws):
@@ -238,14 +434,40 @@ class GaussianExtractor:
         return m
 
     @torch.no_grad()
-    def extract_mesh_bounded(self, voxel_size=0.004, sdf_trunc=0.02, depth_trunc=3, mask_backgrond=True):
+    def extract_mesh_bounded(self, voxel_size=0.004, sdf_trunc=0.02, depth_trunc=3, mask_backgrond=True, to_host=True):
         """TSDF fusion of the maps of reconstruction() and marching cubes (the reference's spelling of the keyword)."""
         volume = TSDFVolume(voxel_size, sdf_trunc, depth_trunc, self.device)
         for cam, depth, rgb in zip(self.viewpoint_stack, self.depthmaps, self.rgbmaps):
             m = self._mask(cam, mask_backgrond)
             volume.integrate(depth, rgb, cam, None if m is None else m.to(self.device))
         self.volume = volume
-        return volume.extract_triangle_mesh()
+        return volume.extract_triangle_mesh(to_host=to_host)
+
+    @torch.no_grad()
+    def extract_mesh_multires(self, multires_factors=(2, 8, 16), mesh_res=1024, mask_backgrond=True, to_host=True):
+        """render_multires.py:129-190 over the maps of reconstruction(): one bounded extraction per factor with
+        depth_trunc = radius * factor, voxel_size = depth_trunc / mesh_res, sdf_trunc = 5 voxel_size; every level after
+        the first loses the faces the cameras see nearer than the previous level's depth_trunc; the levels are joined in
+        order.  Meshes stay on the device between the steps and one volume is alive at a time.  Levels that end up
+        without faces are skipped.  `self.level_meshes` keeps the (depth_trunc, voxel_size, faces before the cull,
+        faces after) of every level."""
+        levels, self.level_meshes, previous_trunc = [], [], None
+        for factor in multires_factors:
+            depth_trunc = self.radius * factor
+            voxel_size = depth_trunc / mesh_res
+            self.volume = None  # the previous level's pool is released before the next one is allocated
+            mesh = self.extract_mesh_bounded(voxel_size=voxel_size, sdf_trunc=5.0 * voxel_size, depth_trunc=depth_trunc,
+                                             mask_backgrond=mask_backgrond, to_host=False)
+            before = mesh.triangles.size(0)
+            if previous_trunc is not None and before > 0:
+                mesh = compact_mesh(mesh, observed_face_mask(mesh, self.viewpoint_stack, previous_trunc))
+            previous_trunc = depth_trunc
+            self.level_meshes.append((depth_trunc, voxel_size, before, mesh.triangles.size(0)))
+            if mesh.triangles.size(0) > 0:
+                levels.append(mesh)
+        self.volume = None
+        joined = join_meshes(levels) if levels else _empty_device_mesh(self.device)
+        return _returned(joined, to_host)
 
     @torch.no_grad()
     def extract_mesh_bounded_streaming(self, viewpoint_stack, voxel_size=0.004, sdf_trunc=0.02, depth_trunc=3,

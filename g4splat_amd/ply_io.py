@@ -116,7 +116,10 @@ def read_gaussian_ply(path, max_sh_degree=3):
 def write_triangle_mesh(path, mesh):
     """Binary little-endian PLY of a triangle mesh (what open3d's write_triangle_mesh produces for the reference's
     TSDF meshes): `vertex` with x y z float and red green blue uchar, `face` with a uchar-counted int list
-    `vertex_indices`.  Colours in [0,1] are stored as round(255 c) after clamping."""
+    `vertex_indices`.  Colours in [0,1] are stored as round(255 c) after clamping.  A mesh of device tensors
+    (mesh.DeviceMesh) is copied to the host here."""
+    if hasattr(mesh.vertices, "detach"):
+        mesh = type(mesh)(*(a.detach().cpu().numpy() for a in mesh))
     v = np.ascontiguousarray(mesh.vertices, np.float32).reshape(-1, 3)
     c = np.asarray(mesh.vertex_colors, np.float32).reshape(-1, 3)
     t = np.ascontiguousarray(mesh.triangles, np.int32).reshape(-1, 3)

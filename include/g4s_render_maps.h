@@ -150,6 +150,79 @@ int g4s_tsdf_extract_emit(const long long* keys, const int* slots, int n_blocks,
                           int* triangles, int n_vertices, int n_triangles, char* workspace, size_t workspace_bytes,
                           void* stream);
 
+/* =====================================================================================================================
+ * Mesh operations of the multi-resolution export (g4splat_amd/csrc/tsdf/mesh_ops.hip).
+ *
+ * What the reference does to its TSDF meshes before it evaluates them (2d-gaussian-splatting/render_multires.py:139-206,
+ * utils/mesh_utils.py:22-43 post_process_mesh, utils/mesh_filter.py:6-32 filter_mesh), there through pytorch3d and
+ * open3d on the host.  As with the TSDF, the semantics below are this library's own, stated exactly
+ * (tests/mesh_ops_ref.py restates them in numpy).
+ *
+ * A mesh is vertices [V,3] float32, vertex_colors [V,3] float32, triangles [F,3] int32, all device pointers;
+ * 3 * V and 3 * F are below 2^31.  Every output is a pure function of the input arrays -- independent of launch geometry
+ * and scheduling -- and stable: surviving triangles and surviving vertices keep their relative order.  Only integer
+ * atomics are used (compare-and-swap, min, add on 32- and 64-bit words).  Keep masks are unsigned char, 1 = keep.
+ * No index is ever used unchecked: a triangle with an index outside [0, V) counts as having an unobserved vertex (A),
+ * fails the edge-length test (D), and that index is written as -1 by a compaction (E).
+ *
+ * A. Observed vertices.  Cameras: world_view_transforms and full_proj_transforms [C,16], row-major 4x4 in the row-vector
+ *   convention the cameras carry them in (point' = [p,1] @ M), device pointers.  For vertex p = (x,y,z) and matrix M:
+ *   col_k(M) = ((x*M[0][k] + y*M[1][k]) + z*M[2][k]) + M[3][k] in float32, no contraction.  With P = full_proj and
+ *   W = world_view of camera c: hx = col_0(P), hy = col_1(P), hw = col_3(P), w' = hw > 1e-6f ? hw : 1e-6f,
+ *   inside = |hx / w'| < 1 and |hy / w'| < 1 (strict; one correctly rounded division each), zc = col_2(W),
+ *   close = zc < near_trunc (no zc > 0 test: the reference has none).  observed(p) = inside and close for some camera.
+ *   keep_unobserved: a triangle is kept unless all three of its vertices are observed.
+ * B. Clusters.  Two triangles are adjacent iff they share an undirected edge {a,b}, a != b, by vertex index (not
+ *   position); an edge used by three or more triangles joins all of them; a triangle with a repeated index still owns its
+ *   other edges; sharing only a vertex does not connect.  labels[t] = the smallest triangle index in t's cluster (the
+ *   transitive closure), sizes[t] = the number of triangles of that cluster.  Index values are only compared, never
+ *   used as addresses.
+ * C. keep_min_size: keep[t] = sizes[t] >= min_size.  keep_nondegenerate: keep[t] = the three indices are pairwise
+ *   different.  (post_process_mesh = clusters, min_size = max(k-th largest cluster size, 50), compaction with vertices,
+ *   keep_nondegenerate, compaction without vertices; g4splat_amd/mesh.py.)
+ * D. keep_short_edges: per edge (a,b), (b,c), (c,a), in float64 from the float32 coordinates: d = p_a - p_b per axis,
+ *   sqrt((dx*dx + dy*dy) + dz*dz) <= length_threshold; all three edges.
+ * E. Compaction, two-phase.  compact_count: triangle t survives iff keep == NULL or keep[t] != 0; with compact_vertices,
+ *   a vertex survives iff a surviving triangle names it; totals = {surviving vertices (n_vertices without
+ *   compact_vertices), surviving triangles} (host int[2]; one host synchronisation).  compact_emit, same sizes,
+ *   compact_vertices and workspace, the workspace untouched in between: the surviving triangles in order with their
+ *   indices rewritten to the surviving vertices' new positions, and (with compact_vertices) the surviving vertices and
+ *   colours in order; without compact_vertices only triangles_out is written.  Nothing is written beyond
+ *   n_vertices_out / n_triangles_out.  Outputs must not alias inputs.
+ * Every argument is checked on the host before anything is launched.
+ */
+
+/* observed [n_vertices]: 1 iff some camera sees the vertex inside its image and nearer than near_trunc. */
+int g4s_mesh_observed_vertices(int n_vertices, const float* vertices, int n_cameras, const float* world_view_transforms,
+                               const float* full_proj_transforms, float near_trunc, unsigned char* observed, void* stream);
+
+int g4s_mesh_keep_unobserved(int n_triangles, const int* triangles, int n_vertices, const unsigned char* observed,
+                             unsigned char* keep, void* stream);
+
+int g4s_mesh_keep_min_size(int n_triangles, const int* sizes, int min_size, unsigned char* keep, void* stream);
+
+int g4s_mesh_keep_nondegenerate(int n_triangles, const int* triangles, unsigned char* keep, void* stream);
+
+int g4s_mesh_keep_short_edges(int n_triangles, const int* triangles, int n_vertices, const float* vertices,
+                              double length_threshold, unsigned char* keep, void* stream);
+
+/* Bytes of device workspace of g4s_mesh_cluster_triangles (edge table of at least 6 n_triangles slots, union-find). */
+size_t g4s_mesh_cluster_workspace(int n_triangles);
+
+/* labels, sizes [n_triangles] int32. */
+int g4s_mesh_cluster_triangles(int n_triangles, const int* triangles, int* labels, int* sizes, char* workspace,
+                               size_t workspace_bytes, void* stream);
+
+size_t g4s_mesh_compact_workspace(int n_vertices, int n_triangles);
+
+int g4s_mesh_compact_count(int n_vertices, int n_triangles, const int* triangles, const unsigned char* keep,
+                           int compact_vertices, int* totals, char* workspace, size_t workspace_bytes, void* stream);
+
+int g4s_mesh_compact_emit(int n_vertices, int n_triangles, const float* vertices, const float* vertex_colors,
+                          const int* triangles, int compact_vertices, float* vertices_out, float* vertex_colors_out,
+                          int* triangles_out, int n_vertices_out, int n_triangles_out, char* workspace,
+                          size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
