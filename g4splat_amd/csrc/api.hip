@@ -141,6 +141,60 @@ int tile_sort_bits(int tiles) {
     return b < 32 ? b : 32;
 }
 
+// What a frame size fixes, derived in this one place for g4s_rasterizer_layout, the forward and the backward: the tile
+// partition ping-pongs between the two halves of the binning chunk, and its (data-independent) pass count says which
+// half the backward finds the sorted entries in.
+struct FrameGeom { int tiles_x, tiles_y, tiles, tile_bits, passes; bool entries_in_b; };
+FrameGeom frame_geom(int width, int height) {
+    FrameGeom f{};
+    f.tiles_x = (width + TILE - 1) / TILE; f.tiles_y = (height + TILE - 1) / TILE;
+    f.tiles = (int)((uint32_t)f.tiles_x * (uint32_t)f.tiles_y);  // (the forward refuses frames where this wraps)
+    f.tile_bits = tile_sort_bits(f.tiles); f.passes = (f.tile_bits + 7) / 8;  // rasterizer_impl.cu:301
+    f.entries_in_b = (f.passes & 1) != 0;
+    return f;
+}
+
+// The arguments of the rasterizer's entry points as named fields: each extern "C" function below fills one by name
+// (`c.scales = scales`), so that two of its many float pointers cannot change places unseen on the way to the kernels.
+struct ForwardCall {
+    // capacity >= 0: the presized, host-synchronisation-free form -- the binning chunk holds `capacity` instances, the
+    // instance counts stay on the device (status_dev), nothing is read back.
+    int capacity = -1; uint32_t* status_dev;
+    struct Chunk { g4s_resize_fn resize; void* ctx; } geometry, binning, image;  // the three scratch callbacks
+    int P, D, M, width, height, prefiltered, debug; float scale_modifier, tan_fovx, tan_fovy;
+    // shs_rest == NULL: shs is the packed [P,M,3] tensor; otherwise shs = [P,1,3] and shs_rest = [P,M-1,3].
+    const float *background, *means3D, *shs, *shs_rest, *colors_precomp, *opacities, *scales, *rotations,
+        *transMat_precomp, *viewmatrix, *projmatrix, *cam_pos;
+    float *out_color, *out_others; int* radii; void* stream;
+};
+struct BackwardCall {
+    int P, D, M, R, width, height, debug; float scale_modifier, tan_fovx, tan_fovy;
+    const float *background, *means3D, *shs, *shs_rest, *colors_precomp, *scales, *rotations, *transMat_precomp,
+        *viewmatrix, *projmatrix, *campos, *dL_dpix, *dL_depths;
+    const int* radii; char *geom_buffer, *binning_buffer, *image_buffer, *workspace; size_t workspace_bytes;
+    float *dL_dmean2D, *dL_dnormal, *dL_dopacity, *dL_dcolor, *dL_dmean3D, *dL_dtransMat, *dL_dsh, *dL_dsh_rest,
+        *dL_dscale, *dL_drot;
+    // gradient accumulation over views (g4s_rasterizer_backward_accumulate_packed); unset in the other two backwards
+    bool accumulate; void* after_event; float* view_stats; const g4s_packed_rows* packed; void* stream;
+};
+// Declare `c` and fill it with the parameters that the forward / the backward entry points have in common, by the names
+// they carry in include/g4s_rasterizer.h; what differs (the SH arguments, the scratch, the extensions) is set beside it.
+#define DECLARE_FORWARD_CALL(c)                                                                                       \
+    ForwardCall c{}; c.P = P; c.D = D; c.M = M; c.background = background; c.width = width; c.height = height; c.means3D = means3D;    \
+    c.opacities = opacities; c.scales = scales; c.scale_modifier = scale_modifier; c.rotations = rotations;           \
+    c.transMat_precomp = transMat_precomp; c.viewmatrix = viewmatrix; c.projmatrix = projmatrix; c.cam_pos = cam_pos;  \
+    c.tan_fovx = tan_fovx; c.tan_fovy = tan_fovy; c.out_color = out_color; c.out_others = out_others;                 \
+    c.radii = radii; c.debug = debug; c.stream = stream
+#define DECLARE_BACKWARD_CALL(c)                                                                                      \
+    BackwardCall c{}; c.P = P; c.D = D; c.M = M; c.R = R; c.background = background; c.width = width; c.height = height;                \
+    c.means3D = means3D; c.scales = scales; c.scale_modifier = scale_modifier; c.rotations = rotations;               \
+    c.transMat_precomp = transMat_precomp; c.viewmatrix = viewmatrix; c.projmatrix = projmatrix; c.campos = campos;   \
+    c.tan_fovx = tan_fovx; c.tan_fovy = tan_fovy; c.radii = radii; c.geom_buffer = geom_buffer;                       \
+    c.binning_buffer = binning_buffer; c.image_buffer = image_buffer; c.dL_dpix = dL_dpix; c.dL_depths = dL_depths;   \
+    c.dL_dmean2D = dL_dmean2D; c.dL_dnormal = dL_dnormal; c.dL_dopacity = dL_dopacity; c.dL_dcolor = dL_dcolor;       \
+    c.dL_dmean3D = dL_dmean3D; c.dL_dtransMat = dL_dtransMat; c.dL_dscale = dL_dscale; c.dL_drot = dL_drot;           \
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.debug = debug; c.stream = stream
+
 }  // namespace
 
 extern "C" const char* g4s_last_error(void) { return t_err; }
@@ -198,19 +252,16 @@ extern "C" const char* g4s_version(void) { return "g4s-hip 0.1.0 gfx950 build " 
 
 extern "C" int g4s_rasterizer_layout(int P, int R, int width, int height, g4s_layout* out) {
     if (!out || P < 0 || R < 0 || width <= 0 || height <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "bad layout query");
-    const int tiles = ((width + TILE - 1) / TILE) * ((height + TILE - 1) / TILE);
+    const FrameGeom f = frame_geom(width, height);
     const GeomLayout g = geom_layout((size_t)P);
     const BinLayout b = bin_layout((size_t)R);
-    const ImgLayout im = img_layout((size_t)width * height, (size_t)tiles);
-    // which ping-pong half holds the results is fixed by the (even / data-independent) pass counts
-    const int tile_bits = tile_sort_bits(tiles);
-    const int passes = (tile_bits + 7) / 8;
+    const ImgLayout im = img_layout((size_t)width * height, (size_t)f.tiles);
     out->rec = g.rec;
     out->clamped = g.clamped;
     out->depth_sorted = g.vals_b;  // wherever the sort starts and however many passes it takes (g4s_rasterizer_forward)
     out->tiles_touched = g.tiles_touched;
     out->geom_bytes = g.bytes;
-    out->entries = (passes & 1) ? b.ent_b : b.ent_a;
+    out->entries = f.entries_in_b ? b.ent_b : b.ent_a;
     out->qhit = b.qhit;
     out->binning_bytes = b.bytes;
     out->ranges = im.ranges;
@@ -230,63 +281,51 @@ char* fixed_chunk_cb(void* ctx, size_t n) {
     return n <= c->bytes ? c->ptr : nullptr;
 }
 
-// shs_rest == NULL: shs is the packed [P,M,3] tensor; otherwise shs = [P,1,3] and shs_rest = [P,M-1,3].
-// capacity >= 0: the presized, host-synchronisation-free form -- the binning chunk holds `capacity` instances, the
-// instance counts stay on the device (status_dev), nothing is read back.
-static int rasterizer_forward_impl(
-    int capacity, uint32_t* status_dev,
-    g4s_resize_fn geometry_buffer, void* geometry_ctx, g4s_resize_fn binning_buffer, void* binning_ctx,
-    g4s_resize_fn image_buffer, void* image_ctx, int P, int D, int M, const float* background, int width, int height,
-    const float* means3D, const float* shs, const float* shs_rest, const float* colors_precomp, const float* opacities,
-    const float* scales,
-    float scale_modifier, const float* rotations, const float* transMat_precomp, const float* viewmatrix,
-    const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
-    float* out_others, int* radii, int debug, void* stream_) {
-    (void)tan_fovx; (void)tan_fovy; (void)prefiltered;
-    hipStream_t stream = (hipStream_t)stream_;
+static int rasterizer_forward_impl(const ForwardCall& c) {
+    hipStream_t stream = (hipStream_t)c.stream;
+    const int P = c.P, debug = c.debug;
     t_err[0] = 0;
-    if (P < 0 || width <= 0 || height <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "P, width, height must be positive");
-    if (!geometry_buffer || !binning_buffer || !image_buffer)
+    if (P < 0 || c.width <= 0 || c.height <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "P, width, height must be positive");
+    if (!c.geometry.resize || !c.binning.resize || !c.image.resize)
         return fail(G4S_ERR_INVALID_ARGUMENT, "resize callbacks must not be NULL");
-    if (!background || !viewmatrix || !projmatrix || !cam_pos || !out_color || !out_others)
+    if (!c.background || !c.viewmatrix || !c.projmatrix || !c.cam_pos || !c.out_color || !c.out_others)
         return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    const int tiles_x = (width + TILE - 1) / TILE, tiles_y = (height + TILE - 1) / TILE;
+    const FrameGeom FG = frame_geom(c.width, c.height);
+    const int tiles_x = FG.tiles_x, tiles_y = FG.tiles_y, tiles = FG.tiles;
     // (tile coordinates travel in 16 bits each -- the binned rect of a Gaussian -- and the tile id in 32)
     if (tiles_x > 65535 || tiles_y > 32767 || (long long)tiles_x * tiles_y > 0x7FFFFFFFll)
         return fail(G4S_ERR_INVALID_ARGUMENT, "image too large: %d x %d tiles (at most 65535 across, 32767 down)", tiles_x, tiles_y);
-    const int tiles = tiles_x * tiles_y;
-    const size_t N = (size_t)width * height;
 
     // image chunk first: with P == 0 the frame is still background (rasterize_points.cu:85-99
     // returns zero-filled outputs in that case; the binding handles P == 0 itself)
-    const ImgLayout IL = img_layout(N, (size_t)tiles);
-    char* img = image_buffer(image_ctx, IL.bytes);
+    const ImgLayout IL = img_layout((size_t)c.width * c.height, (size_t)tiles);
+    char* img = c.image.resize(c.image.ctx, IL.bytes);
     if (!img) return fail(G4S_ERR_ALLOC, "image buffer callback returned NULL");
     img = align_ptr(img);
     uint32_t* ranges = (uint32_t*)(img + IL.ranges);
     float* final_T = (float*)(img + IL.final_T);
     uint32_t* n_contrib = (uint32_t*)(img + IL.n_contrib);
     if (P <= 0) HIP_TRY(hipMemsetAsync(ranges, 0, (size_t)tiles * 8, stream));  // rasterizer_impl.cu:311 (P > 0: cleared by the totals scan)
-    const bool presized = capacity >= 0;
-    if (presized && status_dev && P <= 0) HIP_TRY(hipMemsetAsync(status_dev, 0, 16, stream));
+    const bool presized = c.capacity >= 0;
+    if (presized && c.status_dev && P <= 0) HIP_TRY(hipMemsetAsync(c.status_dev, 0, 16, stream));
 
     int R = 0;
     const float* rec_ptr = nullptr;
     const uint64_t* entries_ptr = nullptr;
     uint8_t* qhit_ptr = nullptr;
     if (P > 0) {
-        if (!means3D || !opacities) return fail(G4S_ERR_INVALID_ARGUMENT, "means3D / opacities must not be NULL");
-        if (!shs && !colors_precomp)  // NUM_CHANNELS == 3 here; mirrors rasterizer_impl.cu:243-246
+        if (!c.means3D || !c.opacities) return fail(G4S_ERR_INVALID_ARGUMENT, "means3D / opacities must not be NULL");
+        if (!c.shs && !c.colors_precomp)  // NUM_CHANNELS == 3 here; mirrors rasterizer_impl.cu:243-246
             return fail(G4S_ERR_UNSUPPORTED, "provide SHs or precomputed colours");
-        if (!transMat_precomp && (!scales || !rotations))
+        if (!c.transMat_precomp && (!c.scales || !c.rotations))
             return fail(G4S_ERR_INVALID_ARGUMENT, "provide scales+rotations or transMat_precomp");
-        if (misaligned(rotations, 16) || misaligned(scales, 8))
+        if (misaligned(c.rotations, 16) || misaligned(c.scales, 8))
             return fail(G4S_ERR_INVALID_ARGUMENT, "rotations must be 16-byte and scales 8-byte aligned");
-        if (shs && (D < 0 || D > 3 || (D + 1) * (D + 1) > M))
-            return fail(G4S_ERR_INVALID_ARGUMENT, "SH degree %d does not fit M = %d coefficients", D, M);
+        if (c.shs && (c.D < 0 || c.D > 3 || (c.D + 1) * (c.D + 1) > c.M))
+            return fail(G4S_ERR_INVALID_ARGUMENT, "SH degree %d does not fit M = %d coefficients", c.D, c.M);
 
         const GeomLayout GL = geom_layout((size_t)P);
-        char* geom = geometry_buffer(geometry_ctx, GL.bytes);
+        char* geom = c.geometry.resize(c.geometry.ctx, GL.bytes);
         if (!geom) return fail(G4S_ERR_ALLOC, "geometry buffer callback returned NULL");
         geom = align_ptr(geom);
         float* rec = (float*)(geom + GL.rec);
@@ -298,16 +337,16 @@ static int rasterizer_forward_impl(
         uint32_t* block_sums = (uint32_t*)(geom + GL.block_sums);
         uint32_t* block_offs = (uint32_t*)(geom + GL.block_offs);
         uint32_t* d_total = (uint32_t*)(geom + GL.total);
-        if (radii == nullptr) radii = (int*)(geom + GL.internal_radii);  // rasterizer_impl.cu:230-233
+        int* const radii = c.radii ? c.radii : (int*)(geom + GL.internal_radii);  // rasterizer_impl.cu:230-233
 
         PreprocessArgs pa{};
-        pa.P = P; pa.D = D; pa.M = M; pa.W = width; pa.H = height; pa.tiles_x = tiles_x; pa.tiles_y = tiles_y;
-        pa.means3D = means3D; pa.scales = scales; pa.rotations = rotations; pa.opacities = opacities; pa.shs = shs;
-        pa.transMat_precomp = transMat_precomp; pa.colors_precomp = colors_precomp;
-        pa.viewmatrix = viewmatrix; pa.projmatrix = projmatrix; pa.cam_pos = cam_pos;
-        pa.scale_modifier = scale_modifier;
-        pa.shs_rest = shs_rest;
-        pa.sh_vec16 = (shs != nullptr && shs_rest == nullptr && M == 16 && !misaligned(shs, 16));
+        pa.P = P; pa.D = c.D; pa.M = c.M; pa.W = c.width; pa.H = c.height; pa.tiles_x = tiles_x; pa.tiles_y = tiles_y;
+        pa.means3D = c.means3D; pa.scales = c.scales; pa.rotations = c.rotations; pa.opacities = c.opacities; pa.shs = c.shs;
+        pa.transMat_precomp = c.transMat_precomp; pa.colors_precomp = c.colors_precomp;
+        pa.viewmatrix = c.viewmatrix; pa.projmatrix = c.projmatrix; pa.cam_pos = c.cam_pos;
+        pa.scale_modifier = c.scale_modifier;
+        pa.shs_rest = c.shs_rest;
+        pa.sh_vec16 = (c.shs != nullptr && c.shs_rest == nullptr && c.M == 16 && !misaligned(c.shs, 16));
         pa.no_fastpath = opt(OPT_NO_FASTPATH) != 0;
         pa.rec = rec; pa.clamped = (uint8_t*)(geom + GL.clamped); pa.tiles_touched = tiles_touched; pa.radii = radii;
         pa.tight_rect = (uint2*)(geom + GL.tight_rect);
@@ -344,8 +383,8 @@ static int rasterizer_forward_impl(
         }
         { ProfScope ps(PF_COUNT_SCAN, stream);
           launch_scan_totals(pa.idx_block_sums, idx_block_offs, pa.ref_block_sums, pa.vis_block_sums, vis_block_offs,
-                             d_total, GL.nblocks, ranges, tiles * 2, stream, presized ? (uint32_t)capacity : 0xFFFFFFFFu,
-                             h_total_dev, presized ? status_dev : nullptr, pa.key_min_blocks, pa.key_max_blocks); }
+                             d_total, GL.nblocks, ranges, tiles * 2, stream, presized ? (uint32_t)c.capacity : 0xFFFFFFFFu,
+                             h_total_dev, presized ? c.status_dev : nullptr, pa.key_min_blocks, pa.key_max_blocks); }
         CHECK_LAUNCH("scan totals");
         if (!presized) {
             HIP_TRY(hipEventRecord(totals_ready, stream));  // (the kernel above stored the three counts in host memory)
@@ -398,8 +437,8 @@ static int rasterizer_forward_impl(
             }
         } else {
             // no read-back: every launch below is sized for the capacity and reads the counts on the device
-            R = capacity;  // what the layouts (here and in the backward) are computed from
-            R_binned = capacity;
+            R = c.capacity;  // what the layouts (here and in the backward) are computed from
+            R_binned = c.capacity;
             V_emit = P;
             nblocks_v = GL.nblocks;
             d_counts = d_total + 2;
@@ -417,7 +456,7 @@ static int rasterizer_forward_impl(
         CHECK_LAUNCH("count scan");
 
         const BinLayout BL = bin_layout((size_t)R);
-        char* bin = binning_buffer(binning_ctx, BL.bytes);
+        char* bin = c.binning.resize(c.binning.ctx, BL.bytes);
         if (!bin) return fail(G4S_ERR_ALLOC, presized ? "binning buffer smaller than g4s_rasterizer_layout(P, capacity).binning_bytes"
                                                       : "binning buffer callback returned NULL");
         bin = align_ptr(bin);
@@ -431,31 +470,31 @@ static int rasterizer_forward_impl(
                           (const uint2*)(geom + GL.tight_rect), ent_a, qhit_ptr, (uint8_t*)(bin + BL.rec_flag), stream,
                           d_counts); }
             CHECK_LAUNCH("emit");
-            const int tile_bits = tile_sort_bits(tiles);  // rasterizer_impl.cu:301
-            int c2;
+            int half;
             { ProfScope ps(PF_TILE_SORT, stream);
-              c2 = radix_sort_u64_keys(ent_a, ent_b, R_binned, ENTRY_TILE_SHIFT, ENTRY_TILE_SHIFT + tile_bits,
-                                       (uint32_t*)(bin + BL.hist), (uint32_t*)(bin + BL.bin_total), stream, d_nbinned); }
+              half = radix_sort_u64_keys(ent_a, ent_b, R_binned, ENTRY_TILE_SHIFT, ENTRY_TILE_SHIFT + FG.tile_bits,
+                                         (uint32_t*)(bin + BL.hist), (uint32_t*)(bin + BL.bin_total), stream, d_nbinned); }
             CHECK_LAUNCH("tile partition");
-            entries_ptr = c2 ? ent_b : ent_a;
+            if ((half != 0) != FG.entries_in_b) return fail(G4S_ERR_HIP, "tile partition ended in the other half than frame_geom says");
+            entries_ptr = FG.entries_in_b ? ent_b : ent_a;
             { ProfScope ps(PF_TILE_RANGES, stream); launch_tile_ranges(R_binned, entries_ptr, ranges, stream, d_nbinned); }
             CHECK_LAUNCH("tile ranges");
         }
         rec_ptr = rec;
     } else {
         // keep the callback protocol: zero-sized chunks are still requested
-        (void)geometry_buffer(geometry_ctx, 0);
-        (void)binning_buffer(binning_ctx, 0);
+        (void)c.geometry.resize(c.geometry.ctx, 0);
+        (void)c.binning.resize(c.binning.ctx, 0);
     }
 
     uint32_t* tile_order = (uint32_t*)(img + IL.tile_order);
     launch_tile_order(tiles, ranges, tile_order, stream);
     CHECK_LAUNCH("tile order");
     BlendFwdArgs ba{};
-    ba.W = width; ba.H = height; ba.tiles_x = tiles_x; ba.tiles_y = tiles_y;
+    ba.W = c.width; ba.H = c.height; ba.tiles_x = tiles_x; ba.tiles_y = tiles_y;
     ba.tile_depth = (uint32_t*)(img + IL.tile_depth);
-    ba.ranges = ranges; ba.tile_order = tile_order; ba.entries = entries_ptr; ba.rec = rec_ptr; ba.bg = background;
-    ba.final_T = final_T; ba.n_contrib = n_contrib; ba.out_color = out_color; ba.out_others = out_others;
+    ba.ranges = ranges; ba.tile_order = tile_order; ba.entries = entries_ptr; ba.rec = rec_ptr; ba.bg = c.background;
+    ba.final_T = final_T; ba.n_contrib = n_contrib; ba.out_color = c.out_color; ba.out_others = c.out_others;
     ba.qhit = qhit_ptr;
     ba.box_only = opt(OPT_BOX_ONLY) != 0;
     { ProfScope ps(PF_BLEND_FWD, stream); launch_blend_fwd(ba, stream); }
@@ -470,10 +509,11 @@ extern "C" int g4s_rasterizer_forward(
     float scale_modifier, const float* rotations, const float* transMat_precomp, const float* viewmatrix,
     const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
     float* out_others, int* radii, int debug, void* stream) {
-    return rasterizer_forward_impl(-1, nullptr, geometry_buffer, geometry_ctx, binning_buffer, binning_ctx, image_buffer, image_ctx, P, D,
-                                   M, background, width, height, means3D, shs, nullptr, colors_precomp, opacities, scales,
-                                   scale_modifier, rotations, transMat_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx,
-                                   tan_fovy, prefiltered, out_color, out_others, radii, debug, stream);
+    DECLARE_FORWARD_CALL(c);
+    c.geometry = {geometry_buffer, geometry_ctx}; c.binning = {binning_buffer, binning_ctx}; c.image = {image_buffer, image_ctx};
+    c.prefiltered = prefiltered;
+    c.shs = shs; c.colors_precomp = colors_precomp;
+    return rasterizer_forward_impl(c);
 }
 
 extern "C" int g4s_rasterizer_forward_split_sh(
@@ -486,11 +526,12 @@ extern "C" int g4s_rasterizer_forward_split_sh(
     t_err[0] = 0;
     if (P > 0 && (!sh_dc || M < 1 || (M > 1 && !sh_rest)))
         return fail(G4S_ERR_INVALID_ARGUMENT, "split SH needs sh_dc [P,1,3] and, for M > 1, sh_rest [P,M-1,3]");
+    DECLARE_FORWARD_CALL(c);
+    c.geometry = {geometry_buffer, geometry_ctx}; c.binning = {binning_buffer, binning_ctx}; c.image = {image_buffer, image_ctx};
+    c.prefiltered = prefiltered;
     // M == 1: there is no rest tensor; the packed layout [P,1,3] is the same memory
-    return rasterizer_forward_impl(-1, nullptr, geometry_buffer, geometry_ctx, binning_buffer, binning_ctx, image_buffer, image_ctx, P, D,
-                                   M, background, width, height, means3D, sh_dc, M > 1 ? sh_rest : nullptr, nullptr, opacities,
-                                   scales, scale_modifier, rotations, transMat_precomp, viewmatrix, projmatrix, cam_pos,
-                                   tan_fovx, tan_fovy, prefiltered, out_color, out_others, radii, debug, stream);
+    c.shs = sh_dc; c.shs_rest = M > 1 ? sh_rest : nullptr;
+    return rasterizer_forward_impl(c);
 }
 
 // The forward without its host synchronisation (include/g4s_rasterizer.h).  sh_rest == NULL: packed SH.
@@ -505,11 +546,11 @@ extern "C" int g4s_rasterizer_forward_presized(
     if (instance_capacity < 0 || !status_dev) return fail(G4S_ERR_INVALID_ARGUMENT, "capacity must be >= 0 and status_dev non-NULL");
     if (!geom_buffer || !binning_buffer || !image_buffer) return fail(G4S_ERR_INVALID_ARGUMENT, "state buffers must not be NULL");
     FixedChunk g{geom_buffer, geom_bytes}, b{binning_buffer, binning_bytes}, im{image_buffer, image_bytes};
-    const int rc = rasterizer_forward_impl(instance_capacity, status_dev, fixed_chunk_cb, &g, fixed_chunk_cb, &b, fixed_chunk_cb,
-                                           &im, P, D, M, background, width, height, means3D, shs, (M > 1 ? sh_rest : nullptr),
-                                           colors_precomp, opacities, scales, scale_modifier, rotations, transMat_precomp,
-                                           viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, 0, out_color, out_others, radii,
-                                           debug, stream);
+    DECLARE_FORWARD_CALL(c);
+    c.capacity = instance_capacity; c.status_dev = status_dev;
+    c.geometry = {fixed_chunk_cb, &g}; c.binning = {fixed_chunk_cb, &b}; c.image = {fixed_chunk_cb, &im};
+    c.shs = shs; c.shs_rest = M > 1 ? sh_rest : nullptr; c.colors_precomp = colors_precomp;
+    const int rc = rasterizer_forward_impl(c);
     return rc < 0 ? rc : G4S_OK;  // (the impl returns the capacity as "R"; the real count is status_dev[0])
 }
 
@@ -519,40 +560,32 @@ extern "C" size_t g4s_rasterizer_backward_workspace(int P, int R) {
     return align_up((size_t)(R > 0 ? R : 1) * GRAD_STRIDE * 4) + 256;
 }
 
-static int rasterizer_backward_impl(
-    int P, int D, int M, int R, const float* background, int width, int height, const float* means3D,
-    const float* shs, const float* shs_rest, const float* colors_precomp, const float* scales, float scale_modifier,
-    const float* rotations,
-    const float* transMat_precomp, const float* viewmatrix, const float* projmatrix, const float* campos,
-    float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-    const float* dL_dpix, const float* dL_depths, float* dL_dmean2D, float* dL_dnormal, float* dL_dopacity,
-    float* dL_dcolor, float* dL_dmean3D, float* dL_dtransMat, float* dL_dsh, float* dL_dsh_rest, float* dL_dscale,
-    float* dL_drot, char* workspace, size_t workspace_bytes, int debug, void* stream_, bool accumulate = false,
-    void* after_event = nullptr, float* view_stats = nullptr, const g4s_packed_rows* packed = nullptr) {
-    hipStream_t stream = (hipStream_t)stream_;
+static int rasterizer_backward_impl(const BackwardCall& c) {
+    hipStream_t stream = (hipStream_t)c.stream;
+    const int P = c.P, M = c.M, R = c.R, debug = c.debug;
     t_err[0] = 0;
-    if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "bad sizes");
+    if (P < 0 || R < 0 || c.width <= 0 || c.height <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "bad sizes");
     if (P == 0) return G4S_OK;  // rasterize_points.cu:197: nothing to do, outputs are [0,*]
-    if (!geom_buffer || !image_buffer || (R > 0 && !binning_buffer))
+    if (!c.geom_buffer || !c.image_buffer || (R > 0 && !c.binning_buffer))
         return fail(G4S_ERR_INVALID_ARGUMENT, "state buffers must not be NULL");
-    if (!dL_dpix || !dL_depths || !dL_dmean2D || !dL_dopacity || !dL_dcolor || !dL_dmean3D ||
-        !dL_dscale || !dL_drot || (M > 0 && !dL_dsh) || (shs_rest && M > 1 && !dL_dsh_rest))
+    if (!c.dL_dpix || !c.dL_depths || !c.dL_dmean2D || !c.dL_dopacity || !c.dL_dcolor || !c.dL_dmean3D ||
+        !c.dL_dscale || !c.dL_drot || (M > 0 && !c.dL_dsh) || (c.shs_rest && M > 1 && !c.dL_dsh_rest))
         return fail(G4S_ERR_INVALID_ARGUMENT, "NULL gradient pointer");
-    if (workspace_bytes < g4s_rasterizer_backward_workspace(P, R) || !workspace)
+    if (c.workspace_bytes < g4s_rasterizer_backward_workspace(P, R) || !c.workspace)
         return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
-    if (misaligned(rotations, 16) || misaligned(scales, 8) || misaligned(dL_drot, 16) || misaligned(dL_dscale, 8))
+    if (misaligned(c.rotations, 16) || misaligned(c.scales, 8) || misaligned(c.dL_drot, 16) || misaligned(c.dL_dscale, 8))
         return fail(G4S_ERR_INVALID_ARGUMENT, "rotations/dL_drot must be 16-byte, scales/dL_dscale 8-byte aligned");
 
-    const int tiles_x = (width + TILE - 1) / TILE, tiles_y = (height + TILE - 1) / TILE;
-    const int tiles = tiles_x * tiles_y;
+    const FrameGeom FG = frame_geom(c.width, c.height);
+    const int tiles = FG.tiles;
     const GeomLayout GL = geom_layout((size_t)P);
     const BinLayout BL = bin_layout((size_t)R);
-    const ImgLayout IL = img_layout((size_t)width * height, (size_t)tiles);
-    char* geom = align_ptr(geom_buffer);
-    char* img = align_ptr(image_buffer);
+    const ImgLayout IL = img_layout((size_t)c.width * c.height, (size_t)tiles);
+    char* geom = align_ptr(c.geom_buffer);
+    char* img = align_ptr(c.image_buffer);
     const float* rec = (const float*)(geom + GL.rec);
-    if (radii == nullptr) radii = (const int*)(geom + GL.internal_radii);
-    float* grad_inst = (float*)align_ptr(workspace);
+    const int* const radii = c.radii ? c.radii : (const int*)(geom + GL.internal_radii);
+    float* grad_inst = (float*)align_ptr(c.workspace);
 
     // gradient records: only instances that receive a contribution are written by the blend backward; instead of
     // clearing 80 B per instance, one validity byte per instance is cleared and the fold selects on it
@@ -565,23 +598,21 @@ static int rasterizer_backward_impl(
     uint8_t* rec_flag = nullptr;
     bool sh_prezeroed = false;
     if (R > 0) {
-        char* bin = align_ptr(binning_buffer);
+        char* bin = align_ptr(c.binning_buffer);
         rec_flag = (uint8_t*)(bin + BL.rec_flag);
-        const int tile_bits = tile_sort_bits(tiles);
-        const int passes = (tile_bits + 7) / 8;
         BlendBwdArgs bb{};
-        bb.W = width; bb.H = height; bb.tiles_x = tiles_x; bb.tiles_y = tiles_y;
+        bb.W = c.width; bb.H = c.height; bb.tiles_x = FG.tiles_x; bb.tiles_y = FG.tiles_y;
         bb.ranges = (const uint32_t*)(img + IL.ranges);
         // backward order: most blended (entry, quadrant) pairs first -- the forward counted them per tile
         uint32_t* tile_order_bwd = (uint32_t*)(img + IL.tile_order_bwd);
         launch_tile_order(tiles, (const uint32_t*)(img + IL.tile_depth), tile_order_bwd, stream, hot_count);
         bb.tile_order = opt(OPT_BWD_FWD_ORDER) ? (const uint32_t*)(img + IL.tile_order) : tile_order_bwd;
-        bb.entries = (const uint64_t*)(bin + ((passes & 1) ? BL.ent_b : BL.ent_a));
-        bb.rec = rec; bb.bg = background;
+        bb.entries = (const uint64_t*)(bin + (FG.entries_in_b ? BL.ent_b : BL.ent_a));
+        bb.rec = rec; bb.bg = c.background;
         bb.final_T = (const float*)(img + IL.final_T);
         bb.n_contrib = (const uint32_t*)(img + IL.n_contrib);
         bb.qhit = (const uint8_t*)(bin + BL.qhit);
-        bb.dL_dpix = dL_dpix; bb.dL_depths = dL_depths; bb.grad_inst = grad_inst; bb.rec_flag = rec_flag;
+        bb.dL_dpix = c.dL_dpix; bb.dL_depths = c.dL_depths; bb.grad_inst = grad_inst; bb.rec_flag = rec_flag;
         bb.n_slots = (uint32_t)R;
         // One wave per tile is the efficient form when there are enough tiles to fill the GPU (1 024 SIMDs x 3
         // waves); a small frame (<= 768 tiles, e.g. 256 x 256) runs about twice as fast with four waves per tile,
@@ -598,9 +629,9 @@ static int rasterizer_backward_impl(
         // dL_dsh is mostly zero rows (invisible Gaussians).  When the one-wave kernel runs, its workgroups clear the
         // tensor on the side (blend.hip) and K8 writes the visible rows only; otherwise K8 clears the rows it skips.
         // (accumulating: dL_dsh holds the sum over the previous views -- nothing is cleared anywhere)
-        if (bb.hot_threshold >= 0 && M > 0 && !opt(OPT_NO_SIDE_ZERO) && !accumulate) {
-            float* zb[2] = {dL_dsh, dL_dsh_rest};
-            const size_t zn[2] = {(size_t)P * (dL_dsh_rest ? 1 : M) * 3, dL_dsh_rest ? (size_t)P * (M - 1) * 3 : 0};
+        if (bb.hot_threshold >= 0 && M > 0 && !opt(OPT_NO_SIDE_ZERO) && !c.accumulate) {
+            float* zb[2] = {c.dL_dsh, c.dL_dsh_rest};
+            const size_t zn[2] = {(size_t)P * (c.dL_dsh_rest ? 1 : M) * 3, c.dL_dsh_rest ? (size_t)P * (M - 1) * 3 : 0};
             bool ok = true;
             for (int z = 0; z < 2; z++) ok = ok && (zn[z] == 0 || (!misaligned(zb[z], 16) && (zn[z] >> 2) < 0x80000000ull));  // (the kernel's u32 loop index must not wrap)
             if (ok) {
@@ -616,36 +647,37 @@ static int rasterizer_backward_impl(
     }
 
     // backward.cu:618-619: W,H re-derived through float truncation (may be W-1 / H-1)
-    const float focal_y = height / (2.0f * tan_fovy);
-    const float focal_x = width / (2.0f * tan_fovx);
+    const float focal_y = c.height / (2.0f * c.tan_fovy);
+    const float focal_x = c.width / (2.0f * c.tan_fovx);
     PreprocessBwdArgs pb{};
-    pb.P = P; pb.D = D; pb.M = M;
-    pb.W = (int)(focal_x * tan_fovx * 2);
-    pb.H = (int)(focal_y * tan_fovy * 2);
-    pb.means3D = means3D; pb.scales = scales; pb.rotations = rotations; pb.shs = shs;
-    pb.transMat_precomp = transMat_precomp; pb.colors_precomp = colors_precomp;
-    pb.viewmatrix = viewmatrix; pb.projmatrix = projmatrix; pb.campos = campos;
+    pb.P = P; pb.D = c.D; pb.M = M;
+    pb.W = (int)(focal_x * c.tan_fovx * 2);
+    pb.H = (int)(focal_y * c.tan_fovy * 2);
+    pb.means3D = c.means3D; pb.scales = c.scales; pb.rotations = c.rotations; pb.shs = c.shs;
+    pb.transMat_precomp = c.transMat_precomp; pb.colors_precomp = c.colors_precomp;
+    pb.viewmatrix = c.viewmatrix; pb.projmatrix = c.projmatrix; pb.campos = c.campos;
     pb.radii = radii; pb.rec = rec; pb.clamped = (const uint8_t*)(geom + GL.clamped); pb.grad_inst = grad_inst;
     pb.rec_flag = rec_flag; pb.n_slots = (uint32_t)R;
     // the forward's own T (scale_modifier applied, exact W / H) is what the blend kernels' moments refer to
-    pb.frame_W = width; pb.frame_H = height; pb.scale_modifier = scale_modifier;
-    pb.shs_rest = shs_rest; pb.dL_dsh_rest = dL_dsh_rest; pb.sh_prezeroed = sh_prezeroed;
-    pb.accumulate = accumulate;
-    pb.view_stats = view_stats;
+    pb.frame_W = c.width; pb.frame_H = c.height; pb.scale_modifier = c.scale_modifier;
+    pb.shs_rest = c.shs_rest; pb.dL_dsh_rest = c.dL_dsh_rest; pb.sh_prezeroed = sh_prezeroed;
+    pb.accumulate = c.accumulate;
+    pb.view_stats = c.view_stats;
+    const g4s_packed_rows* const packed = c.packed;
     if (packed != nullptr && packed->rows != nullptr) {
-        if (accumulate) return fail(G4S_ERR_INVALID_ARGUMENT, "packed rows: only the first view of a batch (first_view != 0) can write them");
-        if (!packed->block_offs || packed->capacity < 0 || shs == nullptr)
+        if (c.accumulate) return fail(G4S_ERR_INVALID_ARGUMENT, "packed rows: only the first view of a batch (first_view != 0) can write them");
+        if (!packed->block_offs || packed->capacity < 0 || c.shs == nullptr)
             return fail(G4S_ERR_INVALID_ARGUMENT, "packed rows: block_offs must not be NULL, capacity >= 0, colours from SH");
         pb.packed_rows = packed->rows; pb.packed_block_offs = packed->block_offs;
         pb.packed_capacity = (uint32_t)(packed->capacity < 0xFFFFFFFFll ? packed->capacity : 0xFFFFFFFFll);
     }
     // The blend backward above touches only this call's own state; the per-Gaussian kernel below adds into tensors that
     // the previous view's backward -- on another stream -- may still be adding into: it waits for the caller's event.
-    if (after_event) HIP_TRY(hipStreamWaitEvent(stream, (hipEvent_t)after_event, 0));
-    pb.sh_vec16 = (shs != nullptr && shs_rest == nullptr && M == 16 && !misaligned(shs, 16) && !misaligned(dL_dsh, 16));
-    pb.dL_dmean2D = dL_dmean2D; pb.dL_dnormal = dL_dnormal; pb.dL_dopacity = dL_dopacity; pb.dL_dcolor = dL_dcolor;
-    pb.dL_dmean3D = dL_dmean3D; pb.dL_dtransMat = dL_dtransMat; pb.dL_dsh = dL_dsh; pb.dL_dscale = dL_dscale;
-    pb.dL_drot = dL_drot;
+    if (c.after_event) HIP_TRY(hipStreamWaitEvent(stream, (hipEvent_t)c.after_event, 0));
+    pb.sh_vec16 = (c.shs != nullptr && c.shs_rest == nullptr && M == 16 && !misaligned(c.shs, 16) && !misaligned(c.dL_dsh, 16));
+    pb.dL_dmean2D = c.dL_dmean2D; pb.dL_dnormal = c.dL_dnormal; pb.dL_dopacity = c.dL_dopacity; pb.dL_dcolor = c.dL_dcolor;
+    pb.dL_dmean3D = c.dL_dmean3D; pb.dL_dtransMat = c.dL_dtransMat; pb.dL_dsh = c.dL_dsh; pb.dL_dscale = c.dL_dscale;
+    pb.dL_drot = c.dL_drot;
     { ProfScope ps(PF_PREPROCESS_BWD, stream); launch_preprocess_bwd(pb, stream); }
     CHECK_LAUNCH("preprocess_bwd");
     return G4S_OK;
@@ -659,11 +691,9 @@ extern "C" int g4s_rasterizer_backward(
     const float* dL_dpix, const float* dL_depths, float* dL_dmean2D, float* dL_dnormal, float* dL_dopacity,
     float* dL_dcolor, float* dL_dmean3D, float* dL_dtransMat, float* dL_dsh, float* dL_dscale, float* dL_drot,
     char* workspace, size_t workspace_bytes, int debug, void* stream) {
-    return rasterizer_backward_impl(P, D, M, R, background, width, height, means3D, shs, nullptr, colors_precomp, scales,
-                                    scale_modifier, rotations, transMat_precomp, viewmatrix, projmatrix, campos, tan_fovx,
-                                    tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_depths,
-                                    dL_dmean2D, dL_dnormal, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dtransMat, dL_dsh, nullptr,
-                                    dL_dscale, dL_drot, workspace, workspace_bytes, debug, stream);
+    DECLARE_BACKWARD_CALL(c);
+    c.shs = shs; c.colors_precomp = colors_precomp; c.dL_dsh = dL_dsh;
+    return rasterizer_backward_impl(c);
 }
 
 extern "C" int g4s_rasterizer_backward_split_sh(
@@ -677,12 +707,10 @@ extern "C" int g4s_rasterizer_backward_split_sh(
     t_err[0] = 0;
     if (P > 0 && (!sh_dc || M < 1 || (M > 1 && (!sh_rest || !dL_dsh_rest))))
         return fail(G4S_ERR_INVALID_ARGUMENT, "split SH needs sh_dc / dL_dsh_dc and, for M > 1, sh_rest / dL_dsh_rest");
-    return rasterizer_backward_impl(P, D, M, R, background, width, height, means3D, sh_dc, M > 1 ? sh_rest : nullptr, nullptr,
-                                    scales, scale_modifier, rotations, transMat_precomp, viewmatrix, projmatrix, campos,
-                                    tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_depths,
-                                    dL_dmean2D, dL_dnormal, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dtransMat, dL_dsh_dc,
-                                    M > 1 ? dL_dsh_rest : nullptr, dL_dscale, dL_drot, workspace, workspace_bytes, debug,
-                                    stream);
+    DECLARE_BACKWARD_CALL(c);
+    c.shs = sh_dc; c.shs_rest = M > 1 ? sh_rest : nullptr;
+    c.dL_dsh = dL_dsh_dc; c.dL_dsh_rest = M > 1 ? dL_dsh_rest : nullptr;
+    return rasterizer_backward_impl(c);
 }
 
 // Gradient accumulation over views (include/g4s_rasterizer.h).  sh_rest == NULL: sh_dc is the packed [P,M,3] tensor.
@@ -698,14 +726,15 @@ extern "C" int g4s_rasterizer_backward_accumulate_packed(
     t_err[0] = 0;
     if (P > 0 && (!sh_dc || M < 1 || (sh_rest && M > 1 && !dL_dsh_rest)))
         return fail(G4S_ERR_INVALID_ARGUMENT, "accumulating backward needs SH coefficients (packed, or sh_dc + sh_rest / dL_dsh_rest)");
-    return rasterizer_backward_impl(P, D, M, R, background, width, height, means3D, sh_dc, (sh_rest && M > 1) ? sh_rest : nullptr,
-                                    nullptr, scales, scale_modifier, rotations, transMat_precomp, viewmatrix, projmatrix, campos,
-                                    tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_depths,
-                                    dL_dmean2D, dL_dnormal, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dtransMat, dL_dsh_dc,
-                                    (sh_rest && M > 1) ? dL_dsh_rest : nullptr, dL_dscale, dL_drot, workspace, workspace_bytes,
-                                    debug, stream, first_view == 0, after_event, view_stats, packed);
+    DECLARE_BACKWARD_CALL(c);
+    const bool split = sh_rest && M > 1;
+    c.shs = sh_dc; c.shs_rest = split ? sh_rest : nullptr;
+    c.dL_dsh = dL_dsh_dc; c.dL_dsh_rest = split ? dL_dsh_rest : nullptr;
+    c.accumulate = first_view == 0; c.after_event = after_event; c.view_stats = view_stats; c.packed = packed;
+    return rasterizer_backward_impl(c);
 }
 
+// (the one ABI-sized call left in this file: the same entry point without the packed rows)
 extern "C" int g4s_rasterizer_backward_accumulate(
     int P, int D, int M, int R, const float* background, int width, int height, const float* means3D,
     const float* sh_dc, const float* sh_rest, const float* scales, float scale_modifier, const float* rotations,
@@ -715,15 +744,11 @@ extern "C" int g4s_rasterizer_backward_accumulate(
     float* dL_dcolor, float* dL_dmean3D, float* dL_dtransMat, float* dL_dsh_dc, float* dL_dsh_rest, float* dL_dscale,
     float* dL_drot, float* view_stats, int first_view, char* workspace, size_t workspace_bytes, void* after_event, int debug,
     void* stream) {
-    t_err[0] = 0;
-    if (P > 0 && (!sh_dc || M < 1 || (sh_rest && M > 1 && !dL_dsh_rest)))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "accumulating backward needs SH coefficients (packed, or sh_dc + sh_rest / dL_dsh_rest)");
-    return rasterizer_backward_impl(P, D, M, R, background, width, height, means3D, sh_dc, (sh_rest && M > 1) ? sh_rest : nullptr,
-                                    nullptr, scales, scale_modifier, rotations, transMat_precomp, viewmatrix, projmatrix, campos,
-                                    tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_depths,
-                                    dL_dmean2D, dL_dnormal, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dtransMat, dL_dsh_dc,
-                                    (sh_rest && M > 1) ? dL_dsh_rest : nullptr, dL_dscale, dL_drot, workspace, workspace_bytes,
-                                    debug, stream, first_view == 0, after_event, view_stats);
+    return g4s_rasterizer_backward_accumulate_packed(
+        P, D, M, R, background, width, height, means3D, sh_dc, sh_rest, scales, scale_modifier, rotations, transMat_precomp,
+        viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix,
+        dL_depths, dL_dmean2D, dL_dnormal, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dtransMat, dL_dsh_dc, dL_dsh_rest, dL_dscale,
+        dL_drot, view_stats, first_view, /*packed=*/nullptr, workspace, workspace_bytes, after_event, debug, stream);
 }
 
 extern "C" int g4s_rasterizer_mark_visible(int P, const float* means3D, const float* viewmatrix,

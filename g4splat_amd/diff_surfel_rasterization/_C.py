@@ -16,6 +16,7 @@ torch is plumbing here (device memory, current stream); all compute is in the HI
 There is no CPU path: tensors must live on a HIP device ("cuda" in torch-ROCm).
 """
 import ctypes
+import types
 
 import torch
 
@@ -132,9 +133,12 @@ def _raise(code, what):
     raise RuntimeError(f"{what} failed ({code}): {_lib.last_error()}")
 
 
-def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, transMat_precomp,
-                        viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
-                        prefiltered, debug):
+def _prepare_forward(background, means3D, colors, opacity, scales, rotations, scale_modifier, transMat_precomp,
+                     viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
+                     prefiltered, debug, state=None):
+    """What the two forwards share: the checks, the output tensors and the argument runs of the native forwards, which
+    take `*f.head`, their own SH / colour pointers (f.rest, f.col), `*f.tail`, prefiltered where they have it, `*f.end`.
+    `f.keep` holds the converted inputs: the pointers into them must stay valid until the native call has returned."""
     if means3D.ndim != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     split = isinstance(sh, (tuple, list))  # extension: (features_dc [P,1,3], features_rest [P,M-1,3]), never concatenated
@@ -146,46 +150,55 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
         _check_cuda(t, name)
     if split:
         _check_split_sh(sh_dc, sh_rest, means3D, colors)
-    lib = _lib.load()
-    P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
+    f = types.SimpleNamespace(lib=_lib.load(), split=split, dev=means3D.device)
+    f.P, f.H, f.W = P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
+    if state is not None and (P, W, H) != (state.P, state.width, state.height):
+        raise RuntimeError(f"PresizedState was built for P={state.P}, {state.width}x{state.height}")
     _check_shapes(P, background, colors, opacity, scales, rotations, transMat_precomp, viewmatrix, projmatrix, sh, campos)
-    dev = means3D.device
-    with torch.cuda.device(dev):
-        fopt = dict(dtype=torch.float32, device=dev)
-        key = (dev.index, P, W, H)
-        geom, binning, img = _Scratch(dev, key + ("geom",)), _Scratch(dev, key + ("binning",)), _Scratch(dev, key + ("img",))
-        if P == 0:  # rasterize_points.cu:85-99: zero-filled outputs, nothing launched
-            return (0, torch.zeros((NUM_CHANNELS, H, W), **fopt), torch.zeros((7, H, W), **fopt),
-                    torch.zeros((0,), dtype=torch.int32, device=dev), geom.tensor, binning.tensor, img.tensor)
-        out_color = torch.empty((NUM_CHANNELS, H, W), **fopt)
-        out_others = torch.empty((7, H, W), **fopt)
-        radii = torch.empty((P,), dtype=torch.int32, device=dev)
-        bg, m3, col, opa = _f32c(background), _f32c(means3D), _f32c(colors), _f32c(opacity)
-        sc, rot, tm = _f32c(scales, 8), _f32c(rotations, 16), _f32c(transMat_precomp)
-        vm, pm, cp = _f32c(viewmatrix), _f32c(projmatrix), _f32c(campos)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        if split:
-            M = 1 + int(sh_rest.size(1))
-            dc, rest = _f32c(sh_dc), _f32c(sh_rest)
-            rendered = lib.g4s_rasterizer_forward_split_sh(
-                geom.cb, None, binning.cb, None, img.cb, None, P, int(degree), M, _ptr(bg), W, H, _ptr(m3), _ptr(dc),
-                _ptr(rest), _ptr(opa), _ptr(sc), float(scale_modifier), _ptr(rot), _ptr(tm), _ptr(vm), _ptr(pm),
-                _ptr(cp), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), _ptr(out_color), _ptr(out_others),
-                _ptr(radii), int(bool(debug)), stream)
-        else:
-            M = int(sh.size(1)) if sh.size(0) != 0 else 0
-            shc = _f32c(sh, 16)
-            rendered = lib.g4s_rasterizer_forward(
-                geom.cb, None, binning.cb, None, img.cb, None, P, int(degree), M, _ptr(bg), W, H, _ptr(m3), _ptr(shc),
-                _ptr(col), _ptr(opa), _ptr(sc), float(scale_modifier), _ptr(rot), _ptr(tm), _ptr(vm), _ptr(pm),
-                _ptr(cp), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), _ptr(out_color), _ptr(out_others),
-                _ptr(radii), int(bool(debug)), stream)
+    fopt = dict(dtype=torch.float32, device=f.dev)
+    f.out_color = torch.empty((NUM_CHANNELS, H, W), **fopt)
+    f.out_others = torch.empty((7, H, W), **fopt)
+    f.radii = torch.empty((P,), dtype=torch.int32, device=f.dev)
+    bg, m3, col, opa = _f32c(background), _f32c(means3D), _f32c(colors), _f32c(opacity)
+    sc, rot, tm = _f32c(scales, 8), _f32c(rotations, 16), _f32c(transMat_precomp)
+    vm, pm, cp = _f32c(viewmatrix), _f32c(projmatrix), _f32c(campos)
+    if split:
+        M = 1 + int(sh_rest.size(1))
+        shc, rest = _f32c(sh_dc), _f32c(sh_rest)
+    else:
+        M = int(sh.size(1)) if sh.size(0) != 0 else 0
+        shc, rest = _f32c(sh, 16), None
+    f.keep = (bg, m3, col, opa, sc, rot, tm, vm, pm, cp, shc, rest)
+    f.head = (P, int(degree), M, _ptr(bg), W, H, _ptr(m3), _ptr(shc))
+    f.rest, f.col, f.prefiltered = _ptr(rest), _ptr(col), int(bool(prefiltered))
+    f.tail = (_ptr(opa), _ptr(sc), float(scale_modifier), _ptr(rot), _ptr(tm), _ptr(vm), _ptr(pm), _ptr(cp),
+              float(tan_fovx), float(tan_fovy))
+    f.end = (_ptr(f.out_color), _ptr(f.out_others), _ptr(f.radii), int(bool(debug)),
+             ctypes.c_void_p(torch.cuda.current_stream(f.dev).cuda_stream))
+    return f
+
+
+def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, transMat_precomp,
+                        viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
+                        prefiltered, debug):
+    f = _prepare_forward(background, means3D, colors, opacity, scales, rotations, scale_modifier, transMat_precomp,
+                         viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
+                         prefiltered, debug)
+    with torch.cuda.device(f.dev):
+        key = (f.dev.index, f.P, f.W, f.H)
+        geom, binning, img = _Scratch(f.dev, key + ("geom",)), _Scratch(f.dev, key + ("binning",)), _Scratch(f.dev, key + ("img",))
+        if f.P == 0:  # rasterize_points.cu:85-99: zero-filled outputs, nothing launched
+            return 0, f.out_color.zero_(), f.out_others.zero_(), f.radii, geom.tensor, binning.tensor, img.tensor
+        native, sh_or_colors = ((f.lib.g4s_rasterizer_forward_split_sh, f.rest) if f.split
+                                else (f.lib.g4s_rasterizer_forward, f.col))
+        rendered = native(geom.cb, None, binning.cb, None, img.cb, None, *f.head, sh_or_colors, *f.tail, f.prefiltered,
+                          *f.end)
         for s in (geom, binning, img):
             if s.error is not None:
                 raise s.error
         if rendered < 0:
             _raise(rendered, "rasterize_gaussians")
-    return rendered, out_color, out_others, radii, geom.tensor, binning.tensor, img.tensor
+    return rendered, f.out_color, f.out_others, f.radii, geom.tensor, binning.tensor, img.tensor
 
 
 class PresizedState:
@@ -211,47 +224,16 @@ def rasterize_gaussians_presized(state, background, means3D, colors, opacity, sc
     """`rasterize_gaussians` without the read-back of num_rendered: same arguments after `state` (a PresizedState), same
     outputs -- except that the first element of the returned tuple is the CAPACITY (pass it as `R` to
     rasterize_gaussians_backward); the real counts are in `state.status` on the device.  The host never waits."""
-    if means3D.ndim != 2 or means3D.size(1) != 3:
-        raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    split = isinstance(sh, (tuple, list))
-    sh_dc, sh_rest = sh if split else (sh, None)
-    for name, t in (("background", background), ("means3D", means3D), ("colors", colors), ("opacity", opacity),
-                    ("scales", scales), ("rotations", rotations), ("transMat_precomp", transMat_precomp),
-                    ("viewmatrix", viewmatrix), ("projmatrix", projmatrix), ("sh", sh_dc), ("campos", campos)) + (
-                        (("sh_rest", sh_rest),) if split else ()):
-        _check_cuda(t, name)
-    if split:
-        _check_split_sh(sh_dc, sh_rest, means3D, colors)
-    lib = _lib.load()
-    P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
-    if (P, W, H) != (state.P, state.width, state.height):
-        raise RuntimeError(f"PresizedState was built for P={state.P}, {state.width}x{state.height}")
-    _check_shapes(P, background, colors, opacity, scales, rotations, transMat_precomp, viewmatrix, projmatrix, sh, campos)
-    dev = means3D.device
-    with torch.cuda.device(dev):
-        fopt = dict(dtype=torch.float32, device=dev)
-        out_color = torch.empty((NUM_CHANNELS, H, W), **fopt)
-        out_others = torch.empty((7, H, W), **fopt)
-        radii = torch.empty((P,), dtype=torch.int32, device=dev)
-        bg, m3, col, opa = _f32c(background), _f32c(means3D), _f32c(colors), _f32c(opacity)
-        sc, rot, tm = _f32c(scales, 8), _f32c(rotations, 16), _f32c(transMat_precomp)
-        vm, pm, cp = _f32c(viewmatrix), _f32c(projmatrix), _f32c(campos)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        if split:
-            M = 1 + int(sh_rest.size(1))
-            shc, rest = _f32c(sh_dc), _f32c(sh_rest)
-        else:
-            M = int(sh.size(1)) if sh.size(0) != 0 else 0
-            shc, rest = _f32c(sh, 16), None
-        rc = lib.g4s_rasterizer_forward_presized(
+    f = _prepare_forward(background, means3D, colors, opacity, scales, rotations, scale_modifier, transMat_precomp,
+                         viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
+                         prefiltered, debug, state=state)
+    with torch.cuda.device(f.dev):
+        rc = f.lib.g4s_rasterizer_forward_presized(
             _ptr(state.geom), state.geom.numel(), _ptr(state.binning), state.binning.numel(), _ptr(state.img),
-            state.img.numel(), state.capacity, _ptr(state.status), P, int(degree), M, _ptr(bg), W, H, _ptr(m3), _ptr(shc),
-            _ptr(rest), _ptr(col), _ptr(opa), _ptr(sc), float(scale_modifier), _ptr(rot), _ptr(tm), _ptr(vm), _ptr(pm),
-            _ptr(cp), float(tan_fovx), float(tan_fovy), _ptr(out_color), _ptr(out_others), _ptr(radii), int(bool(debug)),
-            stream)
+            state.img.numel(), state.capacity, _ptr(state.status), *f.head, f.rest, f.col, *f.tail, *f.end)
         if rc < 0:
             _raise(rc, "rasterize_gaussians_presized")
-    return state.capacity, out_color, out_others, radii, state.geom, state.binning, state.img
+    return state.capacity, f.out_color, f.out_others, f.radii, state.geom, state.binning, state.img
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier,
@@ -386,40 +368,28 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
             gc, go = _f32c(dL_dout_color), _f32c(dL_dout_others)
             rad = radii.contiguous()
             stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            sh0, sh1 = (_f32c(sh_dc), _f32c(sh_rest)) if split else (_f32c(sh, 16), None)
+            g0, g1 = dL_dsh if split else (dL_dsh, None)
+            # the argument runs that the three native backwards share; between them go their own SH arguments
+            lead = (P, int(degree), M, int(R), _ptr(bg), W, H, _ptr(m3))
+            mid = (_ptr(sc), float(scale_modifier), _ptr(rot), _ptr(tm), _ptr(vm), _ptr(pm), _ptr(cp), float(tan_fovx),
+                   float(tan_fovy), _ptr(rad), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(gc),
+                   _ptr(go), _ptr(dL_dmeans2D), _ptr(dL_dnormal), _ptr(dL_dopacity), _ptr(dL_dcolors),
+                   _ptr(dL_dmeans3D), _ptr(dL_dtransMat))
+            scale_rot, ws, end = (_ptr(dL_dscales), _ptr(dL_drotations)), (_ptr(workspace), ws_bytes), (int(bool(debug)), stream)
             if accumulate:
-                dc, rest = (_f32c(sh_dc), _f32c(sh_rest)) if split else (_f32c(sh, 16), None)
-                gdc, grest = (dL_dsh[0], dL_dsh[1]) if split else (dL_dsh, None)
                 ev = ctypes.c_void_p(after.cuda_event if after is not None else 0)
                 pk = None
                 if packed is not None:
                     pk = _lib.G4sPackedRows(packed[0].data_ptr(), packed[1].data_ptr(), int(packed[0].size(0)))
                 rc = lib.g4s_rasterizer_backward_accumulate_packed(
-                    P, int(degree), M, int(R), _ptr(bg), W, H, _ptr(m3), _ptr(dc), _ptr(rest), _ptr(sc),
-                    float(scale_modifier), _ptr(rot), _ptr(tm), _ptr(vm), _ptr(pm), _ptr(cp), float(tan_fovx),
-                    float(tan_fovy), _ptr(rad), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(gc),
-                    _ptr(go), _ptr(dL_dmeans2D), _ptr(dL_dnormal), _ptr(dL_dopacity), _ptr(dL_dcolors),
-                    _ptr(dL_dmeans3D), _ptr(dL_dtransMat), _ptr(gdc), _ptr(grest), _ptr(dL_dscales),
-                    _ptr(dL_drotations), _ptr(view_stats), int(first_view),
-                    ctypes.byref(pk) if pk is not None else None, _ptr(workspace), ws_bytes, ev,
-                    int(bool(debug)), stream)
+                    *lead, _ptr(sh0), _ptr(sh1), *mid, _ptr(g0), _ptr(g1), *scale_rot, _ptr(view_stats), int(first_view),
+                    ctypes.byref(pk) if pk is not None else None, *ws, ev, *end)
             elif split:
-                dc, rest = _f32c(sh_dc), _f32c(sh_rest)
                 rc = lib.g4s_rasterizer_backward_split_sh(
-                    P, int(degree), M, int(R), _ptr(bg), W, H, _ptr(m3), _ptr(dc), _ptr(rest), _ptr(sc),
-                    float(scale_modifier), _ptr(rot), _ptr(tm), _ptr(vm), _ptr(pm), _ptr(cp), float(tan_fovx),
-                    float(tan_fovy), _ptr(rad), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(gc),
-                    _ptr(go), _ptr(dL_dmeans2D), _ptr(dL_dnormal), _ptr(dL_dopacity), _ptr(dL_dcolors),
-                    _ptr(dL_dmeans3D), _ptr(dL_dtransMat), _ptr(dL_dsh[0]), _ptr(dL_dsh[1]), _ptr(dL_dscales),
-                    _ptr(dL_drotations), _ptr(workspace), ws_bytes, int(bool(debug)), stream)
+                    *lead, _ptr(sh0), _ptr(sh1), *mid, _ptr(g0), _ptr(g1), *scale_rot, *ws, *end)
             else:
-                shc = _f32c(sh, 16)
-                rc = lib.g4s_rasterizer_backward(
-                    P, int(degree), M, int(R), _ptr(bg), W, H, _ptr(m3), _ptr(shc), _ptr(col), _ptr(sc),
-                    float(scale_modifier), _ptr(rot), _ptr(tm), _ptr(vm), _ptr(pm), _ptr(cp), float(tan_fovx),
-                    float(tan_fovy), _ptr(rad), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(gc),
-                    _ptr(go), _ptr(dL_dmeans2D), _ptr(dL_dnormal), _ptr(dL_dopacity), _ptr(dL_dcolors),
-                    _ptr(dL_dmeans3D), _ptr(dL_dtransMat), _ptr(dL_dsh), _ptr(dL_dscales), _ptr(dL_drotations),
-                    _ptr(workspace), ws_bytes, int(bool(debug)), stream)
+                rc = lib.g4s_rasterizer_backward(*lead, _ptr(sh0), _ptr(col), *mid, _ptr(g0), *scale_rot, *ws, *end)
             if rc != 0:
                 _raise(rc, "rasterize_gaussians_backward")
     return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dtransMat, dL_dsh, dL_dscales, dL_drotations

@@ -129,37 +129,47 @@ def _present(grad_color, grad_depth, rs, device):
     return grad_color, grad_depth
 
 
+def _run_forward(ctx, rs, means3D, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, sh):
+    """The guarded native forward of both nodes (`sh`: the packed tensor or the split pair).  Leaves what the backward
+    needs besides the saved tensors on `ctx`; returns (color, depth, radii, geomBuffer, binningBuffer, imgBuffer)."""
+    fwd_args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
+                rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
+                rs.sh_degree, rs.campos, rs.prefiltered, rs.debug)
+    (ctx.num_rendered, color, depth, radii, *buffers), ctx.workspace = _call_guarded(
+        _forward, fwd_args, rs.debug, "snapshot_fw.dump",
+        "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
+    ctx.raster_settings = rs
+    ctx.mark_non_differentiable(radii)
+    return (color, depth, radii, *buffers)
+
+
+def _run_backward(ctx, grad_out_color, grad_depth, means3D, radii, colors_precomp, scales, rotations, cov3Ds_precomp, sh,
+                  geomBuffer, binningBuffer, imgBuffer):
+    """The guarded native backward of both nodes: the gradient tuple of _C.rasterize_gaussians_backward."""
+    rs = ctx.raster_settings
+    grad_out_color, grad_depth = _present(grad_out_color, grad_depth, rs, means3D.device)
+    bwd_args = (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
+                rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, grad_depth, sh,
+                rs.sh_degree, rs.campos, geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, rs.debug)
+    return _call_guarded(_backward(ctx.workspace), bwd_args, rs.debug, "snapshot_bw.dump",
+                         "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings):
-        rs = raster_settings
-        fwd_args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
-                    rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
-                    rs.sh_degree, rs.campos, rs.prefiltered, rs.debug)
-        (num_rendered, color, depth, radii, geomBuffer, binningBuffer, imgBuffer), ctx.workspace = _call_guarded(
-            _forward, fwd_args, rs.debug, "snapshot_fw.dump",
-            "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
-        ctx.raster_settings = rs
-        ctx.num_rendered = num_rendered
-        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
-                              binningBuffer, imgBuffer)
-        ctx.mark_non_differentiable(radii)
+        color, depth, radii, *buffers = _run_forward(ctx, raster_settings, means3D, colors_precomp, opacities, scales,
+                                                     rotations, cov3Ds_precomp, sh)
+        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, *buffers)
         return color, radii, depth
 
     @staticmethod
     def backward(ctx, grad_out_color, grad_radii, grad_depth):
-        rs = ctx.raster_settings
-        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
-         imgBuffer) = ctx.saved_tensors
-        grad_out_color, grad_depth = _present(grad_out_color, grad_depth, rs, means3D.device)
-        bwd_args = (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
-                    rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, grad_depth, sh,
-                    rs.sh_degree, rs.campos, geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, rs.debug)
+        colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, *buffers = ctx.saved_tensors
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_rotations) = _call_guarded(
-            _backward(ctx.workspace), bwd_args, rs.debug, "snapshot_bw.dump",
-            "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+         grad_rotations) = _run_backward(ctx, grad_out_color, grad_depth, means3D, radii, colors_precomp, scales,
+                                         rotations, cov3Ds_precomp, sh, *buffers)
         # one gradient per forward input, in input order; raster_settings gets None
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales,
                 grad_rotations, grad_cov3Ds_precomp, None)
@@ -172,35 +182,19 @@ class _RasterizeGaussiansSplitSH(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh_dc, sh_rest, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
-        rs = raster_settings
         empty = torch.empty(0, dtype=torch.float32, device=means3D.device)
-        fwd_args = (rs.bg, means3D, empty, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
-                    rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width,
-                    (sh_dc, sh_rest), rs.sh_degree, rs.campos, rs.prefiltered, rs.debug)
-        (num_rendered, color, depth, radii, geomBuffer, binningBuffer, imgBuffer), ctx.workspace = _call_guarded(
-            _forward, fwd_args, rs.debug, "snapshot_fw.dump",
-            "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
-        ctx.raster_settings = rs
-        ctx.num_rendered = num_rendered
-        ctx.save_for_backward(means3D, scales, rotations, cov3Ds_precomp, radii, sh_dc, sh_rest, geomBuffer,
-                              binningBuffer, imgBuffer)
-        ctx.mark_non_differentiable(radii)
+        color, depth, radii, *buffers = _run_forward(ctx, raster_settings, means3D, empty, opacities, scales, rotations,
+                                                     cov3Ds_precomp, (sh_dc, sh_rest))
+        ctx.save_for_backward(means3D, scales, rotations, cov3Ds_precomp, radii, sh_dc, sh_rest, *buffers)
         return color, radii, depth
 
     @staticmethod
     def backward(ctx, grad_out_color, grad_radii, grad_depth):
-        rs = ctx.raster_settings
-        (means3D, scales, rotations, cov3Ds_precomp, radii, sh_dc, sh_rest, geomBuffer, binningBuffer,
-         imgBuffer) = ctx.saved_tensors
-        grad_out_color, grad_depth = _present(grad_out_color, grad_depth, rs, means3D.device)
+        means3D, scales, rotations, cov3Ds_precomp, radii, sh_dc, sh_rest, *buffers = ctx.saved_tensors
         empty = torch.empty(0, dtype=torch.float32, device=means3D.device)
-        bwd_args = (rs.bg, means3D, radii, empty, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
-                    rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, grad_depth, (sh_dc, sh_rest), rs.sh_degree,
-                    rs.campos, geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, rs.debug)
         (grad_means2D, _grad_colors, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_rotations) = _call_guarded(
-            _backward(ctx.workspace), bwd_args, rs.debug, "snapshot_bw.dump",
-            "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+         grad_rotations) = _run_backward(ctx, grad_out_color, grad_depth, means3D, radii, empty, scales, rotations,
+                                         cov3Ds_precomp, (sh_dc, sh_rest), *buffers)
         return (grad_means3D, grad_means2D, grad_sh[0], grad_sh[1], grad_opacities, grad_scales, grad_rotations,
                 grad_cov3Ds_precomp, None)
 
