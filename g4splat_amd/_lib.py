@@ -96,6 +96,12 @@ SIGNATURES = {
                                  c_p]),
     "g4s_tsdf_extract_count": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_sz, c_p]),
     "g4s_tsdf_extract_emit": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_f, c_p, c_p, c_p, c_i, c_i, c_p, c_sz, c_p]),
+    "g4s_utsdf_workspace": (c_sz, [c_i]),
+    "g4s_utsdf_grid": (c_i, [c_i, c_f, c_p, c_f, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_utsdf_sample": (c_i, [c_i, c_p, c_i, c_p, c_f, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_dense_mc_workspace": (c_sz, [c_i]),
+    "g4s_dense_mc_count": (c_i, [c_i, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_dense_mc_emit": (c_i, [c_i, c_p, c_f, c_p, c_f, c_f, c_p, c_p, c_i, c_i, c_p, c_sz, c_p]),
     "g4s_mesh_observed_vertices": (c_i, [c_i, c_p, c_i, c_p, c_p, c_f, c_p, c_p]),
     "g4s_mesh_keep_unobserved": (c_i, [c_i, c_p, c_i, c_p, c_p, c_p]),
     "g4s_mesh_keep_min_size": (c_i, [c_i, c_p, c_i, c_p, c_p]),

@@ -13,8 +13,14 @@ The rest of the reference's export (render_multires.py:139-206, utils/mesh_utils
 the device too, over the "mesh operations" of the same header: cull_observed_faces, join_meshes,
 cluster_connected_triangles, post_process_mesh, filter_mesh, and GaussianExtractor.extract_mesh_multires that chains
 them.  Each takes a TriangleMesh (numpy; uploaded) or a DeviceMesh (tensors) and returns the kind it was given.
+
+Unbounded scenes (mesh_utils.py:184-279 extract_mesh_unbounded, utils/mcube_utils.py) go through the "unbounded TSDF and
+dense marching cubes" of the same header: GaussianExtractor.extract_mesh_unbounded fuses every view into a lattice of the
+contracted space in one kernel (unbounded_tsdf_grid), extracts it (dense_marching_cubes) and colours the vertices
+(unbounded_tsdf); nothing leaves the device before the mesh is complete.
 """
 import ctypes
+import math
 from typing import NamedTuple
 
 import numpy as np
@@ -379,6 +385,135 @@ def filter_mesh(mesh, length_threshold=0.05):
     return _returned(compact_mesh(dm, keep), host)
 
 
+# ---- unbounded extraction (include/g4s_render_maps.h, "Unbounded TSDF and dense marching cubes"; csrc/tsdf/unbounded.hip)
+class _ViewStack:
+    """The host arrays the utsdf entry points take, and the device tensors they point into (kept alive here).
+    views: (camera or 4x4 full_proj_transform, depth [H,W] / [1,H,W], rgb [3,H,W] or None) per view, maps on `device`."""
+
+    def __init__(self, views, device, need_rgb):
+        self.maps, proj, sizes, dptr, cptr = [], [], [], [], []
+        for cam, depth, rgb in views:
+            M = _to_np(getattr(cam, "full_proj_transform", cam)).astype(np.float32).reshape(16)
+            depth = self._map(depth, device, "depth")
+            if depth.dim() == 3 and depth.size(0) == 1:
+                depth = depth[0]
+            if depth.dim() != 2:
+                raise RuntimeError(f"depth must be [H,W] or [1,H,W] (got {tuple(depth.shape)})")
+            H, W = depth.shape
+            depth = depth.contiguous()
+            self.maps.append(depth)
+            dptr.append(depth.data_ptr())
+            if need_rgb:
+                if rgb is None:
+                    raise RuntimeError("colours need the rgb map of every view")
+                rgb = self._map(rgb, device, "rgb").contiguous()
+                if tuple(rgb.shape) != (3, H, W):
+                    raise RuntimeError(f"rgb must have shape {(3, H, W)} (got {tuple(rgb.shape)})")
+                self.maps.append(rgb)
+                cptr.append(rgb.data_ptr())
+            proj.extend(M.tolist())
+            sizes.extend([W, H])
+        self.n = len(dptr)
+        self.proj = (ctypes.c_float * max(len(proj), 1))(*proj)
+        self.sizes = (ctypes.c_int * max(len(sizes), 1))(*sizes)
+        self.depth = (ctypes.c_void_p * max(self.n, 1))(*dptr)
+        self.rgb = (ctypes.c_void_p * max(self.n, 1))(*cptr) if need_rgb else None
+        nws = _lib.load().g4s_utsdf_workspace(self.n)
+        self.ws = torch.empty(nws, dtype=torch.uint8, device=device)
+
+    @staticmethod
+    def _map(t, device, name):
+        if not isinstance(t, torch.Tensor) or t.device != device:
+            raise RuntimeError(f"{name} must be a tensor on {device}")
+        return t.detach().float()
+
+
+def _hip_device(device):
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("the unbounded extraction needs a HIP device (there is no CPU path)")
+    return torch.device("cuda", torch.cuda.current_device() if device.index is None else device.index)
+
+
+def unbounded_tsdf(points, views, center, radius, voxel_size, contracted=True, return_rgb=False):
+    """g4s_utsdf_sample: the running-mean TSDF of `views` (see _ViewStack) at explicit points [n,3] (a device tensor) --
+    points of the contracted, normalised space (contracted=True; center, radius map them to the world) or world points
+    (contracted=False).  Returns tsdf [n], and with return_rgb (tsdf, colour [n,3])."""
+    if not isinstance(points, torch.Tensor):
+        raise RuntimeError("points must be a tensor on a HIP device")
+    dev = _hip_device(points.device)
+    pts = points.detach().float().reshape(-1, 3).contiguous()
+    n = pts.size(0)
+    stack = _ViewStack(views, dev, return_rgb)
+    tsdf = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
+    col = torch.empty((max(n, 1), 3), dtype=torch.float32, device=dev) if return_rgb else None
+    with torch.cuda.device(dev):
+        _lib.call("g4s_utsdf_sample", n, _lib.ptr(pts), int(bool(contracted)), _host_f32(_to_np(center)), float(radius),
+                  float(voxel_size), stack.n, stack.proj, stack.sizes, stack.depth, stack.rgb, _lib.ptr(tsdf), _lib.ptr(col),
+                  _lib.ptr(stack.ws), stack.ws.numel(), _lib.stream(dev))
+        torch.cuda.current_stream(dev).synchronize()  # the stack's tensors may go once the kernel has run
+    return (tsdf[:n], col[:n]) if return_rgb else tsdf[:n]
+
+
+def unbounded_tsdf_grid(resolution, R, views, center, radius, voxel_size, device=None):
+    """g4s_utsdf_grid: the same evaluation at the resolution^3 lattice over [-R, R]^3 of the contracted space, generated in
+    the kernel; returns tsdf [resolution^3] (x fastest) on the device."""
+    dev = _hip_device(device if device is not None else _default_device())
+    N = int(resolution)
+    if N < 2 or N ** 3 >= 2 ** 31:
+        raise ValueError("resolution must be at least 2 and resolution^3 below 2^31")
+    stack = _ViewStack(views, dev, False)
+    tsdf = torch.empty(N ** 3, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call("g4s_utsdf_grid", N, float(R), _host_f32(_to_np(center)), float(radius), float(voxel_size), stack.n,
+                  stack.proj, stack.sizes, stack.depth, _lib.ptr(tsdf), _lib.ptr(stack.ws), stack.ws.numel(), _lib.stream(dev))
+        torch.cuda.current_stream(dev).synchronize()
+    return tsdf
+
+
+def dense_marching_cubes(tsdf, R, center, radius, max_range=32.0, to_host=True):
+    """Marching cubes over a dense lattice tsdf [N,N,N] (stored x fastest: tsdf[k,j,i]) or [N^3] of the contracted space
+    over [-R, R]^3: (vertices [V,3] world, clamped to +-max_range; triangles [F,3] int32), numpy or -- to_host=False --
+    device tensors.  A field without a sign change gives (0,3) arrays."""
+    if not isinstance(tsdf, torch.Tensor):
+        tsdf = torch.as_tensor(np.ascontiguousarray(tsdf, np.float32), device=_default_device())
+    dev = _hip_device(tsdf.device)
+    f = tsdf.detach().float().contiguous().reshape(-1)
+    N = round(f.numel() ** (1.0 / 3.0))
+    if N ** 3 != f.numel() or N < 2 or N ** 3 >= 2 ** 31:
+        raise ValueError("tsdf must hold N^3 values, N at least 2 and N^3 below 2^31")
+    lib = _lib.load()
+    c = _host_f32(_to_np(center))
+    with torch.cuda.device(dev):
+        ws = torch.empty(lib.g4s_dense_mc_workspace(N), dtype=torch.uint8, device=dev)
+        st = _lib.stream(dev)
+        totals = (ctypes.c_int * 2)()
+        _lib.call("g4s_dense_mc_count", N, _lib.ptr(f), totals, _lib.ptr(ws), ws.numel(), st)
+        V, F = totals[0], totals[1]
+        verts = torch.empty((max(V, 1), 3), dtype=torch.float32, device=dev)
+        tris = torch.empty((max(F, 1), 3), dtype=torch.int32, device=dev)
+        _lib.call("g4s_dense_mc_emit", N, _lib.ptr(f), float(R), c, float(radius), float(max_range), _lib.ptr(verts),
+                  _lib.ptr(tris), V, F, _lib.ptr(ws), ws.numel(), st)
+        torch.cuda.current_stream(dev).synchronize()  # `ws` is released on return
+    if to_host:
+        return verts[:V].cpu().numpy(), tris[:F].cpu().numpy()
+    return verts[:V], tris[:F]
+
+
+def quantile_linear(values, q):
+    """numpy's default (linear-interpolation) quantile of a device tensor: sorted on the device, the two order statistics
+    interpolated on the host in float64 (torch.quantile refuses large inputs)."""
+    v = torch.sort(values.detach().reshape(-1)).values
+    n = v.numel()
+    if n == 0:
+        raise ValueError("quantile of an empty tensor")
+    pos = float(q) * (n - 1)
+    lo = min(max(int(math.floor(pos)), 0), n - 1)
+    hi = min(lo + 1, n - 1)
+    a, b = float(v[lo]), float(v[hi])
+    return a + (b - a) * (pos - lo)
+
+
 def focus_point(c2ws):
     """The point nearest (least squares) to every camera's optical axis: argmin_p sum_i |(I - d_i d_i^T)(p - o_i)|^2,
     d_i the viewing direction (+z of the camera), o_i its centre."""
@@ -468,6 +603,35 @@ class GaussianExtractor:
         self.volume = None
         joined = join_meshes(levels) if levels else _empty_device_mesh(self.device)
         return _returned(joined, to_host)
+
+    def _unbounded_views(self):
+        return list(zip(self.viewpoint_stack, self.depthmaps, self.rgbmaps))
+
+    @torch.no_grad()
+    def extract_mesh_unbounded(self, resolution=1024, to_host=True, max_range=32.0, keep_grid=False):
+        """mesh_utils.py:184-279 over the maps of reconstruction(): a TSDF over a resolution^3 lattice of the contracted,
+        normalised space (voxel_size = 2 radius / resolution, half extent R = min(q + 0.01, 1.9) with q the 0.95 quantile
+        of the Gaussians' contracted norms), dense marching cubes, vertices back in the world and clamped to
+        +-max_range, colours from a world-mode evaluation at the vertices.  Stated differences (include/g4s_render_maps.h):
+        one lattice of any resolution instead of 512^3 crops, triangles face positive tsdf, no vertex merge (vertices are
+        shared by construction).  keep_grid=True leaves the lattice in self.unbounded_tsdf."""
+        N = int(resolution)
+        voxel_size = self.radius * 2 / N
+        x = (self.gaussians.get_xyz.detach().float() - self.center) / self.radius
+        mag = torch.linalg.norm(x, ord=2, dim=-1)[..., None]
+        contracted = torch.where(mag < 1, x, (2 - (1 / mag)) * (x / mag))
+        R = min(quantile_linear(contracted.norm(dim=-1), 0.95) + 0.01, 1.9)
+        self.unbounded_R, self.unbounded_voxel_size = R, voxel_size
+        views = self._unbounded_views()
+        self.unbounded_tsdf = unbounded_tsdf_grid(N, R, views, self.center, self.radius, voxel_size, self.device)
+        verts, tris = dense_marching_cubes(self.unbounded_tsdf, R, self.center, self.radius, max_range, to_host=False)
+        if not keep_grid:
+            self.unbounded_tsdf = None
+        if verts.size(0) > 0:
+            _t, cols = unbounded_tsdf(verts, views, self.center, self.radius, voxel_size, contracted=False, return_rgb=True)
+        else:
+            cols = torch.zeros((0, 3), dtype=torch.float32, device=verts.device)
+        return _returned(DeviceMesh(verts, cols, tris), to_host)
 
     @torch.no_grad()
     def extract_mesh_bounded_streaming(self, viewpoint_stack, voxel_size=0.004, sdf_trunc=0.02, depth_trunc=3,

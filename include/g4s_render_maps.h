@@ -151,6 +151,87 @@ int g4s_tsdf_extract_emit(const long long* keys, const int* slots, int n_blocks,
                           void* stream);
 
 /* =====================================================================================================================
+ * Unbounded TSDF and dense marching cubes (g4splat_amd/csrc/tsdf/unbounded.hip).
+ *
+ * The reference's mesh extraction for unbounded scenes (2d-gaussian-splatting/utils/mesh_utils.py:184-279
+ * extract_mesh_unbounded, utils/mcube_utils.py; render.py --unbounded): a TSDF over a lattice of the contracted,
+ * normalised space, every view fused into every lattice point, marching cubes over the lattice, the vertices mapped back
+ * to the world.  As above, the semantics are this library's own, stated exactly (tests/unbounded_ref.py restates them in
+ * numpy): float32, round-to-nearest-even, correctly rounded / and sqrt, no fused multiply-add, evaluated left to right
+ * as written.  min / max are IEEE minNum / maxNum (a NaN operand yields the other one).
+ *
+ * Views.  V views, fused in stack order.  View v has full_proj_transform M (16 floats, row-major, used as
+ *   row-vector @ M: M[r][c] = M[4r + c]), a depth map [H,W] and -- for colours -- an rgb map [3,H,W], float32 device
+ *   pointers.  W and H may differ between views (sizes = {W0, H0, W1, H1, ...}).
+ * Lattice.  n points per axis over [-R, R]^3 of the contracted, normalised space (R = half_extent):
+ *   c(i) = -R + float(i) * h, h = (2 * R) / float(n - 1); storage x fastest, idx = i + n * (j + n * k).  2 <= n and
+ *   n^3 < 2^31.  Stated difference: the reference demands n % 512 == 0 and evaluates overlapping 512^3 crops, each with
+ *   its own linspace and spacing; here it is one lattice and any n.
+ * Point in contracted mode (lattice points, explicit points with contracted != 0, marching-cubes vertices):
+ *   m = sqrt((y0*y0 + y1*y1) + y2*y2); if m < 1, u = y; otherwise s = 1 / (2 - m) and u_c = s * (y_c / m).  World point
+ *   p_c = u_c * radius + center_c.  Truncation T = 5 * voxel_size, and if m > 1, T = T * (1 / (2 - min(m, 1.9))).  The
+ *   expressions are evaluated as written also for m >= 2 (lattice corners reach 1.9 * sqrt(3)), where they give a
+ *   mirrored or non-finite point -- the reference's arithmetic does the same; every comparison with NaN is false, so a
+ *   NaN point is seen by no view.
+ * Point in world mode (explicit points with contracted == 0; the vertex colours): p is given, T = 5 * voxel_size;
+ *   center and radius are not read.
+ * State per point: tsdf = 1, w = 1, colour = 0 -- the reference's prior observation of +1, which also darkens a colour
+ *   seen n times by n / (n + 1); both quirks are reproduced.
+ * Per view, in order:  h_c = ((p0*M[0][c] + p1*M[1][c]) + p2*M[2][c]) + M[3][c] for c = 0, 1, 3; z = h_3, px = h_0 / z,
+ *   py = h_1 / z; inside = px > -1 && px < 1 && py > -1 && py < 1 && z > 0.  If inside, a bilinear sample with
+ *   align_corners: ix = ((px + 1) / 2) * float(W - 1), x0 = floor(ix), x1 = min(x0 + 1, W - 1), fx = ix - x0, the same
+ *   in y with H; w00 = (1-fx)*(1-fy), w10 = fx*(1-fy), w01 = (1-fx)*fy, w11 = fx*fy (first index x);
+ *   d = ((d00*w00 + d10*w10) + d01*w01) + d11*w11, each rgb channel s_c likewise.  sdf = d - z.  The view is skipped
+ *   unless inside && sdf > -T.  t = min(1, max(-1, sdf / T)); tsdf <- (tsdf*w + t) / (w + 1);
+ *   colour_c <- (colour_c*w + s_c) / (w + 1); w <- w + 1.
+ * Dense marching cubes over a lattice of tsdf values (any device array of n^3 floats).  Every point is valid.  A cube has
+ *   its lower corner at (i,j,k), i,j,k < n-1; configuration bit c is set iff tsdf(corner c) < 0, corners numbered as in
+ *   the TSDF section.  An edge is owned by its lower point and carries a vertex iff the signs (tsdf < 0) of its two points
+ *   differ.  e = f0 / (f0 - f1) (f0 at the owner); contracted position: c(.) on the other two axes and c(g_a) + e * h
+ *   along the edge's axis; then un-contracted and un-normalised as a point in contracted mode; then each world
+ *   coordinate q becomes min(max(q, -max_range), max_range) (the reference's default is 32; it clamps world units, the
+ *   reference's own quirk; a NaN coordinate becomes -max_range).  Triangles come from
+ *   g4splat_amd/csrc/tsdf/tsdf_mc_table.h and face positive tsdf (the reference's skimage orientation is not modelled).
+ *   Order: vertices by owner point in storage order (x fastest), edges +x, +y, +z; triangles by cube in storage order,
+ *   the table's order.  No atomics: two runs are bit-identical.  Vertices are shared by construction, so the reference's
+ *   merge_vertices(digits_vertex=6) has no counterpart.
+ * Vertex colours: the world-mode evaluation at the clamped vertices, its colour as it stands -- not divided by 255 (the
+ *   rgb maps are used as floats here, unlike the bounded path).
+ *
+ * center = 3 host floats; full_proj [V,16], sizes [V,2] and the arrays of V map pointers are HOST arrays, read during the
+ * call (the library packs them into a table in the workspace).  Every argument is checked on the host before anything is
+ * launched; capacities are the caller's.  Sequence: utsdf_grid -> dense_mc_count (reads back two totals) -> the caller
+ * allocates -> dense_mc_emit (same n, tsdf and workspace, untouched in between) -> utsdf_sample (world mode, colours).
+ */
+
+/* Bytes of device workspace of g4s_utsdf_grid / g4s_utsdf_sample for a stack of n_views views. */
+size_t g4s_utsdf_workspace(int n_views);
+
+/* tsdf [n^3]: the fused lattice, written once.  n_views = 0: every value is exactly 1. */
+int g4s_utsdf_grid(int n, float half_extent, const float* center, float radius, float voxel_size, int n_views,
+                   const float* full_proj, const int* sizes, const float* const* depth, float* tsdf, char* workspace,
+                   size_t workspace_bytes, void* stream);
+
+/* The same evaluation at explicit points [n_points,3] (device), contracted != 0: contracted mode, else world mode.
+ * tsdf [n_points] and colour [n_points,3] are optional (at least one); colour needs the rgb maps. */
+int g4s_utsdf_sample(int n_points, const float* points, int contracted, const float* center, float radius,
+                     float voxel_size, int n_views, const float* full_proj, const int* sizes, const float* const* depth,
+                     const float* const* rgb, float* tsdf, float* colour, char* workspace, size_t workspace_bytes,
+                     void* stream);
+
+/* Bytes of device workspace of the dense marching cubes over n^3 points (0 for an n outside the lattice's range). */
+size_t g4s_dense_mc_workspace(int n);
+
+/* totals[0] = vertices, totals[1] = triangles (host int[2]; one host synchronisation). */
+int g4s_dense_mc_count(int n, const float* tsdf, int* totals, char* workspace, size_t workspace_bytes, void* stream);
+
+/* vertices [n_vertices,3] (world, clamped), triangles [n_triangles,3]: the totals of dense_mc_count (nothing is written
+ * beyond them; with n_vertices = 0 nothing is written at all). */
+int g4s_dense_mc_emit(int n, const float* tsdf, float half_extent, const float* center, float radius, float max_range,
+                      float* vertices, int* triangles, int n_vertices, int n_triangles, char* workspace,
+                      size_t workspace_bytes, void* stream);
+
+/* =====================================================================================================================
  * Mesh operations of the multi-resolution export (g4splat_amd/csrc/tsdf/mesh_ops.hip).
  *
  * What the reference does to its TSDF meshes before it evaluates them (2d-gaussian-splatting/render_multires.py:139-206,
