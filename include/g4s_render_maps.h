@@ -104,7 +104,9 @@ int g4s_render_maps_backward(int width, int height, const float* allmap, const f
  *   (c0 + e*(c1 - c0)) / 255 per channel.  Triangles come from g4splat_amd/csrc/tsdf/tsdf_mc_table.h (generated by
  *   tools/gen_mc_table.py: crossing polygons walked over the cube faces, ambiguous faces separate the negative corners,
  *   fan triangulation from a vertex whose diagonals cross the cube's interior) and face towards positive tsdf, i.e.
- *   towards the cameras.
+ *   towards the cameras.  Comparisons and the division are IEEE float32 without flush-to-zero: a subnormal tsdf counts
+ *   as its sign (-1e-40 is negative; +1e-40, 0.0 and -0.0 are not) and f0 / (f0 - f1) of subnormals is the correctly
+ *   rounded quotient.  The library is built with the compiler's default denormal mode, which keeps them.
  * Order.  Vertices: blocks in ascending key, voxels x fastest, edges +x, +y, +z.  Triangles: blocks in ascending key,
  *   cubes (by lower corner) x fastest, the table's order.  No atomics anywhere: two runs are bit-identical.
  *
@@ -187,8 +189,8 @@ int g4s_tsdf_extract_emit(const long long* keys, const int* slots, int n_blocks,
  * Dense marching cubes over a lattice of tsdf values (any device array of n^3 floats).  Every point is valid.  A cube has
  *   its lower corner at (i,j,k), i,j,k < n-1; configuration bit c is set iff tsdf(corner c) < 0, corners numbered as in
  *   the TSDF section.  An edge is owned by its lower point and carries a vertex iff the signs (tsdf < 0) of its two points
- *   differ.  e = f0 / (f0 - f1) (f0 at the owner); contracted position: c(.) on the other two axes and c(g_a) + e * h
- *   along the edge's axis; then un-contracted and un-normalised as a point in contracted mode; then each world
+ *   differ (subnormals count as their sign, as in the TSDF section).  e = f0 / (f0 - f1) (f0 at the owner); contracted
+ *   position: c(.) on the other two axes and c(g_a) + e * h along the edge's axis; then un-contracted and un-normalised as a point in contracted mode; then each world
  *   coordinate q becomes min(max(q, -max_range), max_range) (the reference's default is 32; it clamps world units, the
  *   reference's own quirk; a NaN coordinate becomes -max_range).  Triangles come from
  *   g4splat_amd/csrc/tsdf/tsdf_mc_table.h and face positive tsdf (the reference's skimage orientation is not modelled).

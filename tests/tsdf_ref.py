@@ -1,7 +1,8 @@
 """numpy restatement of the TSDF fusion and marching-cubes contract (include/g4s_render_maps.h, TSDF section).
 
 Every float operation is float32 in the header's order, so the allocation, the slot order, the voxel values and the
-extracted mesh can be compared with the HIP library exactly.  Slow and simple: for tests only.
+extracted mesh can be compared with the HIP library exactly.  Subnormals are kept (numpy never flushes them): a subnormal
+tsdf counts as its sign and divides exactly, which is the header's contract too.  Slow and simple: for tests only.
 """
 import os
 import sys
@@ -182,55 +183,103 @@ def _edge_owner(e):
     return tuple(o), axis
 
 
+def _compress(bc):
+    """Block coordinates [n,3] -> small non-negative ones with the same 27-neighbourhoods: per axis consecutive values stay
+    consecutive and every larger step becomes 2 (one empty block in between), so blocks that do not touch still do not
+    touch and a dense array over the result stays small wherever the keys lie."""
+    out = np.empty_like(bc)
+    for a in range(3):
+        u, inv = np.unique(bc[:, a], return_inverse=True)
+        out[:, a] = np.concatenate([[0], np.cumsum(np.where(np.diff(u) == 1, 1, 2))]).astype(np.int64)[inv.reshape(-1)]
+    return out
+
+
+class _Lattice:
+    """The voxels of blocks `keys` (sorted) on a dense array over compressed block coordinates, one voxel of padding:
+    F (tsdf, NaN where not allocated or weight 0), cv / cfg (validity and configuration of the cube at each lower
+    corner), cross / owned ([..., 3]: sign change between two valid voxels on the +axis edge / one that a valid cube
+    uses), g ([n,512,3] true voxel coordinates in output order) and gi ([3, n*512] their indices into the arrays)."""
+
+    def __init__(self, keys, tsdf, weight):
+        bc = unpack_keys(keys)
+        lane = np.arange(512)
+        loc = np.stack([lane & 7, (lane >> 3) & 7, lane >> 6], 1)
+        self.g = bc[:, None, :] * 8 + loc[None]  # [n,512,3] in output order
+        gc = (_compress(bc)[:, None, :] * 8 + loc[None]).reshape(-1, 3)
+        self.lo = lo = gc.min(0) - 1
+        self.dims = dims = gc.max(0) - lo + 2
+        self.F = F = np.full(dims, np.nan, f32)
+        self.gi = gi = (gc - lo).T
+        F[tuple(gi)] = np.where(np.asarray(weight).reshape(-1) > 0, np.asarray(tsdf, f32).reshape(-1), np.nan)
+        valid = ~np.isnan(F)
+        neg = F < 0
+        X, Y, Z = dims
+        # cube at lower corner (x, y, z): all corners valid; configuration bits
+        self.cv = cv = np.zeros(dims, bool)
+        self.cfg = cfg = np.zeros(dims, np.int64)
+        sl = lambda c: (slice(c[0], X - 1 + c[0]), slice(c[1], Y - 1 + c[1]), slice(c[2], Z - 1 + c[2]))
+        inner = (slice(0, X - 1), slice(0, Y - 1), slice(0, Z - 1))
+        cv[inner] = True
+        for c in range(8):
+            off = (c & 1, (c >> 1) & 1, c >> 2)
+            cv[inner] &= valid[sl(off)]
+            cfg[inner] |= neg[sl(off)].astype(np.int64) << c
+        # edges owned by each voxel: crossing between two valid voxels used by a valid cube
+        self.cross = np.zeros(tuple(dims) + (3,), bool)
+        self.owned = np.zeros(tuple(dims) + (3,), bool)
+        cvp = np.pad(cv, 1)  # index +1
+        for a in range(3):
+            e = [0, 0, 0]
+            e[a] = 1
+            f0 = F
+            f1 = np.full(dims, np.nan, f32)
+            f1[:X - e[0], :Y - e[1], :Z - e[2]] = F[e[0]:, e[1]:, e[2]:]
+            cross = ~np.isnan(f0) & ~np.isnan(f1) & ((f0 < 0) != (f1 < 0))
+            others = [ax for ax in range(3) if ax != a]
+            used = np.zeros(dims, bool)
+            for o in range(4):
+                d = [0, 0, 0]
+                d[others[0]], d[others[1]] = -(o & 1), -(o >> 1)
+                used |= cvp[1 + d[0]:1 + d[0] + X, 1 + d[1]:1 + d[1] + Y, 1 + d[2]:1 + d[2] + Z]
+            self.cross[..., a] = cross
+            self.owned[..., a] = cross & used
+
+
+def cube_cases(keys, tsdf, weight):
+    """Per cube, by lower-corner voxel in output order ([n,512] each): valid (all eight corners valid), cfg (the
+    configuration; meaningful where valid) and mixed (among the valid corners some are negative and some are not: the
+    cube has a sign change whether or not it is valid)."""
+    L = _Lattice(keys, tsdf, weight)
+    n = len(keys)
+    X, Y, Z = L.dims
+    Fp = np.pad(L.F, ((0, 1), (0, 1), (0, 1)), constant_values=np.nan)
+    some_neg, some_pos = np.zeros(L.dims, bool), np.zeros(L.dims, bool)
+    for c in range(8):
+        f = Fp[(c & 1):(c & 1) + X, ((c >> 1) & 1):((c >> 1) & 1) + Y, (c >> 2):(c >> 2) + Z]
+        some_neg |= f < 0
+        some_pos |= f >= 0
+    pick = lambda a: a[tuple(L.gi)].reshape(n, 512)
+    return pick(L.cv), pick(L.cfg), pick(some_neg & some_pos)
+
+
+def unused_crossings(keys, tsdf, weight):
+    """Number of edges with a sign change between two valid voxels that no valid cube uses (they carry no vertex)."""
+    L = _Lattice(keys, tsdf, weight)
+    return int((L.cross & ~L.owned)[tuple(L.gi)].sum())
+
+
 def extract_mesh(keys, tsdf, weight, color, voxel_size):
     """Marching cubes over blocks `keys` (sorted) with voxel arrays in the same order.
     Returns (vertices [V,3] f32, colours [V,3] f32, triangles [F,3] i32)."""
     v = f32(voxel_size)
     if len(keys) == 0:
         return np.zeros((0, 3), f32), np.zeros((0, 3), f32), np.zeros((0, 3), np.int32)
-    bc = unpack_keys(keys)
-    lane = np.arange(512)
-    loc = np.stack([lane & 7, (lane >> 3) & 7, lane >> 6], 1)
-    g = bc[:, None, :] * 8 + loc[None]  # [n,512,3] in output order
-    lo = g.reshape(-1, 3).min(0) - 1
-    dims = g.reshape(-1, 3).max(0) - lo + 2
-    F = np.full(dims, np.nan, f32)
+    L = _Lattice(keys, tsdf, weight)
+    g, gi, dims, F = L.g, L.gi, L.dims, L.F
     Cg = np.zeros(tuple(dims) + (3,), f32)
-    gi = (g.reshape(-1, 3) - lo).T
-    F[tuple(gi)] = np.where(weight.reshape(-1) > 0, tsdf.reshape(-1), np.nan)
-    Cg[tuple(gi)] = color.reshape(-1, 3)
-    valid = ~np.isnan(F)
-    neg = F < 0
-    X, Y, Z = dims
-    # cube at lower corner (x, y, z): all corners valid; configuration bits
-    cv = np.zeros(dims, bool)
-    cfg = np.zeros(dims, np.int64)
-    sl = lambda c: (slice(c[0], X - 1 + c[0]), slice(c[1], Y - 1 + c[1]), slice(c[2], Z - 1 + c[2]))
-    inner = (slice(0, X - 1), slice(0, Y - 1), slice(0, Z - 1))
-    cv[inner] = True
-    for c in range(8):
-        off = (c & 1, (c >> 1) & 1, c >> 2)
-        cv[inner] &= valid[sl(off)]
-        cfg[inner] |= neg[sl(off)].astype(np.int64) << c
-    # edges owned by each voxel: crossing between two valid voxels used by a valid cube
-    owned = np.zeros(tuple(dims) + (3,), bool)
-    cvp = np.pad(cv, 1)  # index +1
-    for a in range(3):
-        e = [0, 0, 0]
-        e[a] = 1
-        f0 = F
-        f1 = np.full(dims, np.nan, f32)
-        f1[:X - e[0], :Y - e[1], :Z - e[2]] = F[e[0]:, e[1]:, e[2]:]
-        cross = ~np.isnan(f0) & ~np.isnan(f1) & ((f0 < 0) != (f1 < 0))
-        others = [ax for ax in range(3) if ax != a]
-        used = np.zeros(dims, bool)
-        for o in range(4):
-            d = [0, 0, 0]
-            d[others[0]], d[others[1]] = -(o & 1), -(o >> 1)
-            used |= cvp[1 + d[0]:1 + d[0] + X, 1 + d[1]:1 + d[1] + Y, 1 + d[2]:1 + d[2] + Z]
-        owned[..., a] = cross & used
+    Cg[tuple(gi)] = np.asarray(color, f32).reshape(-1, 3)
     # vertex ids in output order: blocks, voxels x fastest, edges +x +y +z
-    own_seq = owned[tuple(gi)]  # [n*512, 3]
+    own_seq = L.owned[tuple(gi)]  # [n*512, 3]
     flat = own_seq.reshape(-1)
     vid = np.full(tuple(dims) + (3,), -1, np.int64)
     ids = np.cumsum(flat) - 1
@@ -239,7 +288,7 @@ def extract_mesh(keys, tsdf, weight, color, voxel_size):
     nz = np.nonzero(flat)[0]
     vox, axis = nz // 3, nz % 3
     gv = g.reshape(-1, 3)[vox]
-    p0 = gv - lo
+    p0 = gi.T[vox]
     p1 = p0 + np.eye(3, dtype=np.int64)[axis]
     f0, f1 = F[tuple(p0.T)], F[tuple(p1.T)]
     e = f0 / (f0 - f1)
@@ -249,13 +298,13 @@ def extract_mesh(keys, tsdf, weight, color, voxel_size):
     verts = (pos * v).astype(f32)
     c0, c1 = Cg[tuple(p0.T)], Cg[tuple(p1.T)]
     cols = ((c0 + e[:, None] * (c1 - c0)) / f32(255)).astype(f32)
-    # triangles: cubes in output order
+    # triangles: cubes in output order (configurations 0 and 255 have none)
     tab = mc_table()
-    cube_ok = cv[tuple(gi)]
-    cube_cfg = cfg[tuple(gi)]
+    cube_ok = L.cv[tuple(gi)]
+    cube_cfg = L.cfg[tuple(gi)]
     owners = [_edge_owner(k) for k in range(12)]
     tris = []
-    for i in np.nonzero(cube_ok)[0]:
+    for i in np.nonzero(cube_ok & (cube_cfg != 0) & (cube_cfg != 255))[0]:
         for tri in tab[cube_cfg[i]]:
             row = []
             for k in tri:
