@@ -21,9 +21,12 @@ extern "C" void g4s_maps_launch_internal(int fwd, int W, int H, float depth_rati
                                          const float* const* grads, float* g_allmap, hipStream_t s);
 
 namespace {
+thread_local char t_err[512] = "";  // behind g4s_last_error(); written here only
+}
 
-thread_local char t_err[512] = "";
-
+// the library's error path (declared in g4s_internal.h)
+namespace g4s {
+void clear_error() { t_err[0] = 0; }
 int fail(int code, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -31,6 +34,13 @@ int fail(int code, const char* fmt, ...) {
     va_end(ap);
     return code;
 }
+int finish(hipError_t e, const char* what) {
+    if (e == hipSuccess) e = hipGetLastError();
+    return e == hipSuccess ? G4S_OK : fail(G4S_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+}
+}  // namespace g4s
+
+namespace {
 
 // One pinned, device-mapped word block per host thread for the read-back of the instance counts: the totals kernel
 // stores them straight into host memory (no copy launch between it and the event the host waits on).

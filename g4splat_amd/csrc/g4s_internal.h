@@ -81,6 +81,11 @@ __host__ __device__ inline uint32_t instance_number(uint32_t extent_word, uint32
 }
 
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
+// Carves 256-byte aligned ranges out of a workspace: take() returns the current offset and advances past `bytes`.
+struct WorkspaceCursor {
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t r = off; off = align_up(off + bytes); return r; }
+};
 
 // Sub-allocation of the three caller-owned chunks.  Private between forward and backward
 // (the reference's GeometryState/BinningState/ImageState, rasterizer_impl.h:21-73).
@@ -98,65 +103,67 @@ struct ImgLayout {
 
 inline GeomLayout geom_layout(size_t P) {
     GeomLayout L{};
-    size_t o = 0;
-    auto take = [&](size_t n) { size_t r = o; o = align_up(o + n); return r; };
+    WorkspaceCursor c;
     L.nblocks = (int)((P + 255) / 256);
-    L.rec = take(P * REC_FLOATS * 4);
-    L.clamped = take(P);
-    L.tiles_touched = take(P * 4);
-    L.tight_rect = take(P * 8);  // (x0 | y0 << 16, width) of the tile rect the Gaussian is binned into; written where tiles_touched > 0
-    L.internal_radii = take(P * 4);
-    L.keys_a = take(P * 4);
-    L.keys_b = take(P * 4);
-    L.vals_a = take(P * 4);
-    L.vals_b = take(P * 4);
+    L.rec = c.take(P * REC_FLOATS * 4);
+    L.clamped = c.take(P);
+    L.tiles_touched = c.take(P * 4);
+    L.tight_rect = c.take(P * 8);  // (x0 | y0 << 16, width) of the tile rect the Gaussian is binned into; written where tiles_touched > 0
+    L.internal_radii = c.take(P * 4);
+    L.keys_a = c.take(P * 4);
+    L.keys_b = c.take(P * 4);
+    L.vals_a = c.take(P * 4);
+    L.vals_b = c.take(P * 4);
     // the depth sort runs over the emitting Gaussians only (n <= P): capacity for n = P
-    L.hist = take((size_t)512 * (sort_blocks(P, SORT_ITEMS_U32) + 1) * 4);  // (9-bit digits: 512 rows)
-    L.bin_total = take(512 * 4);
-    L.key_min_blocks = take((size_t)(L.nblocks ? L.nblocks : 1) * 4);
-    L.key_max_blocks = take((size_t)(L.nblocks ? L.nblocks : 1) * 4);
-    L.block_sums = take((size_t)(L.nblocks ? L.nblocks : 1) * 4);
-    L.block_offs = take((size_t)(L.nblocks ? L.nblocks : 1) * 4);
-    L.ref_block_sums = take((size_t)(L.nblocks ? L.nblocks : 1) * 4);
-    L.idx_block_sums = take((size_t)(L.nblocks ? L.nblocks : 1) * 4);
-    L.idx_block_offs = take((size_t)(L.nblocks ? L.nblocks : 1) * 4);
-    L.vis_block_sums = take((size_t)(L.nblocks ? L.nblocks : 1) * 4);
-    L.vis_block_offs = take((size_t)(L.nblocks ? L.nblocks : 1) * 4);
-    L.total = take(256);
-    L.bytes = o + 256;  // slack for aligning the chunk base
+    L.hist = c.take((size_t)512 * (sort_blocks(P, SORT_ITEMS_U32) + 1) * 4);  // (9-bit digits: 512 rows)
+    L.bin_total = c.take(512 * 4);
+    L.key_min_blocks = c.take((size_t)(L.nblocks ? L.nblocks : 1) * 4);
+    L.key_max_blocks = c.take((size_t)(L.nblocks ? L.nblocks : 1) * 4);
+    L.block_sums = c.take((size_t)(L.nblocks ? L.nblocks : 1) * 4);
+    L.block_offs = c.take((size_t)(L.nblocks ? L.nblocks : 1) * 4);
+    L.ref_block_sums = c.take((size_t)(L.nblocks ? L.nblocks : 1) * 4);
+    L.idx_block_sums = c.take((size_t)(L.nblocks ? L.nblocks : 1) * 4);
+    L.idx_block_offs = c.take((size_t)(L.nblocks ? L.nblocks : 1) * 4);
+    L.vis_block_sums = c.take((size_t)(L.nblocks ? L.nblocks : 1) * 4);
+    L.vis_block_offs = c.take((size_t)(L.nblocks ? L.nblocks : 1) * 4);
+    L.total = c.take(256);
+    L.bytes = c.off + 256;  // slack for aligning the chunk base
     return L;
 }
 inline BinLayout bin_layout(size_t R) {
     BinLayout L{};
-    size_t o = 0;
-    auto take = [&](size_t n) { size_t r = o; o = align_up(o + n); return r; };
-    L.ent_a = take((R ? R : 1) * 8);
-    L.ent_b = take((R ? R : 1) * 8);
-    L.hist = take((size_t)256 * (sort_blocks(R, SORT_ITEMS_U64) + 1) * 4);
-    L.bin_total = take(256 * 4);
-    L.qhit = take((R ? R : 1));
+    WorkspaceCursor c;
+    L.ent_a = c.take((R ? R : 1) * 8);
+    L.ent_b = c.take((R ? R : 1) * 8);
+    L.hist = c.take((size_t)256 * (sort_blocks(R, SORT_ITEMS_U64) + 1) * 4);
+    L.bin_total = c.take(256 * 4);
+    L.qhit = c.take((R ? R : 1));
     // one validity byte per gradient-record slot of the backward (cleared by emit together with qhit): bit 0 = terms
     // 0..15 written, bit 1 = the low-pass terms 16..17 written
-    L.rec_flag = take((R ? R : 1));
-    L.bytes = o + 256;
+    L.rec_flag = c.take((R ? R : 1));
+    L.bytes = c.off + 256;
     return L;
 }
 inline ImgLayout img_layout(size_t N, size_t tiles) {
     ImgLayout L{};
-    size_t o = 0;
-    auto take = [&](size_t n) { size_t r = o; o = align_up(o + n); return r; };
-    L.ranges = take(tiles * 8);
-    L.final_T = take(N * 3 * 4);
-    L.n_contrib = take(N * 2 * 4);
-    L.tile_order = take(tiles * 4);
-    L.tile_depth = take(tiles * 8);      // (0, deepest last contributor) per tile, written by the blend forward
-    L.tile_order_bwd = take(tiles * 4);  // processing order of the backward: deepest live list first
-    L.hot_count = take(256);             // the backward's deep-tile counter ...
-    L.hot_list = take(tiles * 4);        // ... and list (blend_bwd_hot_kernel)
-    L.bytes = o + 256;
+    WorkspaceCursor c;
+    L.ranges = c.take(tiles * 8);
+    L.final_T = c.take(N * 3 * 4);
+    L.n_contrib = c.take(N * 2 * 4);
+    L.tile_order = c.take(tiles * 4);
+    L.tile_depth = c.take(tiles * 8);      // (0, deepest last contributor) per tile, written by the blend forward
+    L.tile_order_bwd = c.take(tiles * 4);  // processing order of the backward: deepest live list first
+    L.hot_count = c.take(256);             // the backward's deep-tile counter ...
+    L.hot_list = c.take(tiles * 4);        // ... and list (blend_bwd_hot_kernel)
+    L.bytes = c.off + 256;
     return L;
 }
 inline char* align_ptr(char* p) { return (char*)align_up((size_t)p); }
+
+// ---- the error path (api.hip owns the calling thread's message buffer behind g4s_last_error() and alone writes it) ----
+void clear_error();
+int fail(int code, const char* fmt, ...);    // formats the message, returns `code`
+int finish(hipError_t e, const char* what);  // e, or if that is hipSuccess the last launch error: G4S_OK or "what: <error>"
 
 // ---- launchers (each defined next to its kernels) --------------------------------------
 

@@ -45,20 +45,19 @@ struct KnnLayout {
 };
 static KnnLayout knn_layout(size_t P) {
     KnnLayout L{};
-    size_t o = 0;
-    auto take = [&](size_t n) { size_t r = o; o = align_up(o + n); return r; };
+    WorkspaceCursor c;
     L.n0 = (int)((P + KNN_LEAF - 1) / KNN_LEAF);
     L.n1 = (L.n0 + KNN_FAN - 1) / KNN_FAN;
     L.n2 = (L.n1 + KNN_FAN - 1) / KNN_FAN;
     L.nparts = (int)((P + 1023) / 1024);
-    L.keys_a = take(P * 4); L.keys_b = take(P * 4); L.vals_a = take(P * 4); L.vals_b = take(P * 4);
-    L.hist = take((size_t)256 * (sort_blocks(P, SORT_ITEMS_U32) + 1) * 4);
-    L.bin_total = take(256 * 4);
-    L.sorted = take((size_t)(L.n0 ? L.n0 : 1) * KNN_LEAF * 16);
-    L.nodes = take((size_t)(L.n0 + L.n1 + L.n2 + 1) * 32);
-    L.partial = take((size_t)(L.nparts ? L.nparts : 1) * 32);
-    L.extent = take(32);
-    L.bytes = o + 256;
+    L.keys_a = c.take(P * 4); L.keys_b = c.take(P * 4); L.vals_a = c.take(P * 4); L.vals_b = c.take(P * 4);
+    L.hist = c.take((size_t)256 * (sort_blocks(P, SORT_ITEMS_U32) + 1) * 4);
+    L.bin_total = c.take(256 * 4);
+    L.sorted = c.take((size_t)(L.n0 ? L.n0 : 1) * KNN_LEAF * 16);
+    L.nodes = c.take((size_t)(L.n0 + L.n1 + L.n2 + 1) * 32);
+    L.partial = c.take((size_t)(L.nparts ? L.nparts : 1) * 32);
+    L.extent = c.take(32);
+    L.bytes = c.off + 256;
     return L;
 }
 

@@ -1,0 +1,51 @@
+// What two or more of the mesh units (tsdf.hip, unbounded.hip, mesh_ops.hip) share: the argument checks of their entry
+// points, the read-back of the two scan totals, and the index arithmetic of the marching-cubes table (tsdf_mc_table.h).
+#pragma once
+#include <math.h>
+
+#include "../g4s_internal.h"
+
+namespace g4s {
+
+// ---- argument checks: each leaves its message behind and returns the entry point's status ----
+inline bool finite_pos(float x) { return x > 0.0f && x < 3.0e38f; }
+inline bool finite(float x) { return fabsf(x) < 3.0e38f; }
+inline int null_pointer() { return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer"); }
+inline int check_workspace(const char* workspace, size_t bytes, size_t need) {
+    return workspace && bytes >= need ? G4S_OK : fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
+}
+inline bool lattice_ok(int n) { return n >= 2 && (long long)n * n * n < (1ll << 31); }
+inline int check_lattice(int n) {
+    return lattice_ok(n) ? G4S_OK : fail(G4S_ERR_INVALID_ARGUMENT, "n must be at least 2 and n^3 below 2^31");
+}
+
+// out[0..1] = the two adjacent scan totals words[0..1]: pending launch errors first, then one copy and the one host
+// synchronisation of a count call.  `out` is written on success only.
+inline hipError_t read_totals(const uint32_t* words, int out[2], hipStream_t s) {
+    uint32_t host[2];
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(host, words, 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return e;
+    out[0] = (int)host[0];
+    out[1] = (int)host[1];
+    return hipSuccess;
+}
+
+// ---- the cube table's encoding (tsdf_mc_table.h): edge id = 4 * axis + n, n = the lower corner's other two coordinates ----
+struct McEdge {
+    int x, y, z, a;  // the lattice point that owns the edge's vertex (the edge's lower end), and the edge's axis
+};
+// edge e of the cube whose lower corner is (x, y, z)
+__device__ __forceinline__ McEdge mc_edge(int e, int x, int y, int z) {
+    const int a = e >> 2, n = e & 3;
+    const int o1 = n & 1, o2 = n >> 1;  // the lower corner's other two coordinates, in axis order
+    return McEdge{x + (a == 0 ? 0 : o1), y + (a == 1 ? 0 : (a == 0 ? o1 : o2)), z + (a == 2 ? 0 : o2), a};
+}
+// rank of the +a vertex among the vertices before and of its owner, whose word is w = exclusive vertex prefix << 3 |
+// owned-edge mask
+__device__ __forceinline__ uint32_t mc_vertex_rank(uint32_t w, int a) {
+    return (w >> 3) + (uint32_t)__builtin_popcount(w & 7u & ((1u << a) - 1u));
+}
+
+}  // namespace g4s

@@ -8,14 +8,12 @@
 //   triangle that finds an earlier one there unites with it in a lock-free union-find that always links the larger root
 //   under the smaller.  Whatever the interleaving, the root of a finished tree is the smallest triangle of its cluster:
 //   the labels are a function of the mesh alone.  Sizes are integer counts at the roots.
-// Compaction: keep flags -> fixed-order exclusive scans (scan_u32 of tsdf.hip) -> [host: sizes] -> gather.
+// Compaction: keep flags -> fixed-order exclusive scans (scan_u32 of scan.hip) -> [host: sizes] -> gather.
 // Only integer atomics (CAS / min / add); every output is bit-reproducible.
-#include <stdarg.h>
-#include <stdio.h>
-
 #include "../g4s_internal.h"
 #include "../g4s_device.h"
 #include "../../../include/g4s_render_maps.h"
+#include "mesh_common.h"
 #include "scan.h"
 
 namespace g4s {
@@ -232,16 +230,12 @@ ClusterLayout cluster_layout(int F) {
     size_t slots = 1024;
     while (slots < (size_t)6 * (size_t)F) slots <<= 1;  // at most 3 F edges: load <= 1/2
     L.slots = slots;
-    size_t off = 0;
-    auto take = [&](size_t& field, size_t bytes) {
-        field = off;
-        off += (bytes + 255) & ~(size_t)255;
-    };
-    take(L.keys, slots * 8);
-    take(L.owner, slots * 4);
-    take(L.parent, (size_t)F * 4);
-    take(L.count, (size_t)F * 4);
-    L.bytes = off;
+    WorkspaceCursor c;
+    L.keys = c.take(slots * 8);
+    L.owner = c.take(slots * 4);
+    L.parent = c.take((size_t)F * 4);
+    L.count = c.take((size_t)F * 4);
+    L.bytes = c.off;
     return L;
 }
 
@@ -320,18 +314,14 @@ struct CompactLayout {
 };
 CompactLayout compact_layout(int V, int F) {
     CompactLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t& field, size_t bytes) {
-        field = off;
-        off += (bytes + 255) & ~(size_t)255;
-    };
-    take(L.tflag, (size_t)F * 4);
-    take(L.tpos, (size_t)F * 4);
-    take(L.vflag, (size_t)V * 4);
-    take(L.vpos, (size_t)V * 4);
-    take(L.chunks, (size_t)scan_chunks((long)(V > F ? V : F)) * 4 + 4);
-    take(L.words, 64);
-    L.bytes = off;
+    WorkspaceCursor c;
+    L.tflag = c.take((size_t)F * 4);
+    L.tpos = c.take((size_t)F * 4);
+    L.vflag = c.take((size_t)V * 4);
+    L.vpos = c.take((size_t)V * 4);
+    L.chunks = c.take((size_t)scan_chunks((long)(V > F ? V : F)) * 4 + 4);
+    L.words = c.take(64);
+    L.bytes = c.off;
     return L;
 }
 
@@ -355,15 +345,11 @@ hipError_t mesh_compact_count(int V, int F, const int* tris, const uint8_t* keep
         if (F > 0 && V > 0) hipLaunchKernelGGL(mesh_mark_vertices_kernel, dim3(g), dim3(256), 0, s, F, tris, tflag, V, vflag);
         scan_u32(vflag, (uint32_t*)(ws + L.vpos), V, chunks, words + 1, s);
     }
-    e = hipGetLastError();
+    int t[2];  // (kept triangles, referenced vertices)
+    e = read_totals(words, t, s);
     if (e != hipSuccess) return e;
-    uint32_t host[2];
-    e = hipMemcpyAsync(host, words, 8, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return e;
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return e;
-    totals[0] = compact_vertices ? (int)host[1] : V;
-    totals[1] = (int)host[0];
+    totals[0] = compact_vertices ? t[1] : V;
+    totals[1] = t[0];
     return hipSuccess;
 }
 
@@ -390,21 +376,6 @@ using namespace g4s;
 // extern "C" entry points (include/g4s_render_maps.h, mesh operations); every argument is checked before any launch
 namespace {
 
-constexpr size_t ERR_BYTES = 512;  // the calling thread's message buffer (api.hip)
-char* err_buf() { return const_cast<char*>(g4s_last_error()); }
-void clear_error() { err_buf()[0] = 0; }
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(err_buf(), ERR_BYTES, fmt, ap);
-    va_end(ap);
-    return code;
-}
-int finish(hipError_t e, const char* what) {
-    if (e == hipSuccess) e = hipGetLastError();
-    return e == hipSuccess ? G4S_OK : fail(G4S_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-}
-
 constexpr int MAX_TRIANGLES = 2147483647 / 3;  // 3 * n_triangles < 2^31
 
 int check_triangles(int n_triangles) {
@@ -417,7 +388,6 @@ int check_vertices(int n_vertices) {
     if (n_vertices > MAX_TRIANGLES) return fail(G4S_ERR_INVALID_ARGUMENT, "3 * n_vertices exceeds 2^31 - 1");
     return G4S_OK;
 }
-int null_pointer() { return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer"); }
 
 }  // namespace
 
@@ -496,8 +466,7 @@ extern "C" int g4s_mesh_cluster_triangles(int n_triangles, const int* triangles,
     if (check_triangles(n_triangles) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     if (n_triangles > 0 && (!triangles || !labels || !sizes)) return null_pointer();
     if (n_triangles == 0) return G4S_OK;
-    if (!workspace || workspace_bytes < g4s_mesh_cluster_workspace(n_triangles))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
+    if (check_workspace(workspace, workspace_bytes, g4s_mesh_cluster_workspace(n_triangles)) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     return finish(mesh_cluster(n_triangles, triangles, labels, sizes, align_ptr(workspace), stream), "mesh cluster_triangles");
 }
 
@@ -514,8 +483,7 @@ extern "C" int g4s_mesh_compact_count(int n_vertices, int n_triangles, const int
     clear_error();
     if (check_vertices(n_vertices) != G4S_OK || check_triangles(n_triangles) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     if (!totals || (n_triangles > 0 && !triangles)) return null_pointer();
-    if (!workspace || workspace_bytes < g4s_mesh_compact_workspace(n_vertices, n_triangles))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
+    if (check_workspace(workspace, workspace_bytes, g4s_mesh_compact_workspace(n_vertices, n_triangles)) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     const hipError_t e = mesh_compact_count(n_vertices, n_triangles, triangles, keep, compact_vertices != 0,
                                             align_ptr(workspace), totals, stream);
     return finish(e, "mesh compact_count");
@@ -536,8 +504,7 @@ extern "C" int g4s_mesh_compact_emit(int n_vertices, int n_triangles, const floa
         return fail(G4S_ERR_INVALID_ARGUMENT, "vertex_colors and vertex_colors_out go together");
     if ((const void*)triangles == (const void*)triangles_out || (vertices && (const void*)vertices == (const void*)vertices_out))
         return fail(G4S_ERR_INVALID_ARGUMENT, "outputs must not alias the inputs");
-    if (!workspace || workspace_bytes < g4s_mesh_compact_workspace(n_vertices, n_triangles))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
+    if (check_workspace(workspace, workspace_bytes, g4s_mesh_compact_workspace(n_vertices, n_triangles)) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     const hipError_t e = mesh_compact_emit(n_vertices, n_triangles, vertices, vertex_colors, triangles, compact_vertices != 0,
                                            vertices_out, vertex_colors_out, triangles_out, n_vertices_out, n_triangles_out,
                                            align_ptr(workspace), stream);

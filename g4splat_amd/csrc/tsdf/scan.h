@@ -1,4 +1,4 @@
-// The generic exclusive scan of tsdf.hip, shared with mesh_ops.hip (both compact with it).
+// The generic exclusive scan of scan.hip, shared by tsdf.hip, unbounded.hip and mesh_ops.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -10,11 +10,10 @@
 // scans of the per-block vertex / triangle counts -> [host: sizes] -> emit.
 // Nothing is accumulated with atomics: every output position is a scan result, so every result is bit-reproducible.
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include "../g4s_internal.h"
 #include "../g4s_device.h"
+#include "mesh_common.h"
 #include "scan.h"
 #include "tsdf_mc_table.h"
 
@@ -36,23 +35,6 @@ struct TsdfViewLayout {  // byte offsets into the per-view workspace
 struct TsdfMcLayout {    // byte offsets into the extraction workspace
     size_t vpre, nv, nt, vbase, tbase, chunks, words, bytes;
 };
-TsdfViewLayout tsdf_view_layout(int W, int H, int cap);
-TsdfMcLayout tsdf_mc_layout(int n_blocks);
-// counts[0] = touched blocks, counts[1] = new blocks (one host synchronisation)
-hipError_t tsdf_alloc_count(const TsdfView& c, const float* depth, const float* mask, int cap, const uint64_t* table,
-                            int n_blocks, char* ws, int* counts, hipStream_t s);
-hipError_t tsdf_merge(const TsdfView& c, int cap, const uint64_t* keys_in, const int* slots_in, int n_blocks, int m,
-                      int n_new, uint64_t* keys_out, int* slots_out, float* tsdf, float* weight, float* color, char* ws,
-                      hipStream_t s);
-hipError_t tsdf_integrate(const TsdfView& c, int cap, const float* depth, const float* mask, const float* rgb, int m,
-                          float* tsdf, float* weight, float* color, char* ws, hipStream_t s);
-// totals[0] = vertices, totals[1] = triangles (one host synchronisation)
-hipError_t tsdf_extract_count(const uint64_t* keys, const int* slots, int n_blocks, const float* tsdf, const float* weight,
-                              char* ws, int* totals, hipStream_t s);
-hipError_t tsdf_extract_emit(const uint64_t* keys, const int* slots, int n_blocks, const float* tsdf, const float* weight,
-                             const float* color, float voxel_size, float* verts, float* vcols, int* tris, int n_vertices,
-                             int n_triangles, char* ws, hipStream_t s);
-
 
 constexpr int TSDF_VOX = TSDF_BLOCK * TSDF_BLOCK * TSDF_BLOCK;  // 512: voxels per block = lanes per workgroup
 constexpr uint64_t KEY_SENTINEL = ~0ull;                         // above every packed key (bit 63 of a key is 0)
@@ -91,74 +73,6 @@ __device__ inline uint32_t block512_excl_scan_u32(uint32_t v, uint32_t* smem8, u
     }
     *total = sum;
     return base + inc - v;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// generic exclusive scan of n u32 values (three launches, fixed order): chunk sums, one workgroup scanning them, apply
-
-constexpr int SCAN_CHUNK = 1024;  // values per 256-thread workgroup (4 per thread, contiguous)
-
-__global__ void __launch_bounds__(256) scan_chunk_sums_kernel(const uint32_t* __restrict__ in, int n,
-                                                              uint32_t* __restrict__ chunk_sums) {
-    __shared__ uint32_t sm4[4];
-    const long base = (long)blockIdx.x * SCAN_CHUNK + 4 * (long)threadIdx.x;
-    uint32_t s = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) s += base + j < n ? in[base + j] : 0u;
-    uint32_t total;
-    (void)block256_excl_scan_u32(s, sm4, &total);
-    if (threadIdx.x == 0) chunk_sums[blockIdx.x] = total;
-}
-
-// single workgroup: chunk_offs = exclusive scan of chunk_sums, in place, *total = their sum
-__global__ void __launch_bounds__(256) scan_chunk_offs_kernel(uint32_t* __restrict__ chunks, int nchunks,
-                                                              uint32_t* __restrict__ total) {
-    __shared__ uint32_t sm4[4];
-    uint32_t run = 0;
-    for (int b = 0; b < nchunks; b += 256) {
-        const int i = b + (int)threadIdx.x;
-        const uint32_t v = i < nchunks ? chunks[i] : 0u;
-        uint32_t t;
-        const uint32_t ex = block256_excl_scan_u32(v, sm4, &t);
-        if (i < nchunks) chunks[i] = run + ex;
-        run += t;
-    }
-    if (threadIdx.x == 0) *total = run;
-}
-
-__global__ void __launch_bounds__(256) scan_apply_kernel(const uint32_t* __restrict__ in, int n,
-                                                         const uint32_t* __restrict__ chunk_offs,
-                                                         uint32_t* __restrict__ out) {
-    __shared__ uint32_t sm4[4];
-    const long base = (long)blockIdx.x * SCAN_CHUNK + 4 * (long)threadIdx.x;
-    uint32_t v[4], s = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        v[j] = base + j < n ? in[base + j] : 0u;
-        s += v[j];
-    }
-    uint32_t total;
-    uint32_t run = chunk_offs[blockIdx.x] + block256_excl_scan_u32(s, sm4, &total);
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        if (base + j < n) out[base + j] = run;
-        run += v[j];
-    }
-}
-
-int scan_chunks(long n) { return (int)((n + SCAN_CHUNK - 1) / SCAN_CHUNK); }
-
-// out = exclusive scan of in (n values; out must not alias in), *d_total = sum; chunks: scan_chunks(n) words of scratch
-// (declared in scan.h: mesh_ops.hip compacts with it too)
-void scan_u32(const uint32_t* in, uint32_t* out, int n, uint32_t* chunks, uint32_t* d_total, hipStream_t s) {
-    const int nc = scan_chunks(n);
-    if (nc == 0) {
-        (void)hipMemsetAsync(d_total, 0, 4, s);
-        return;
-    }
-    hipLaunchKernelGGL(scan_chunk_sums_kernel, dim3(nc), dim3(256), 0, s, in, n, chunks);
-    hipLaunchKernelGGL(scan_chunk_offs_kernel, dim3(1), dim3(256), 0, s, chunks, nc, d_total);
-    hipLaunchKernelGGL(scan_apply_kernel, dim3(nc), dim3(256), 0, s, in, n, chunks, out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -262,12 +176,6 @@ __global__ void __launch_bounds__(256) tsdf_lookup_kernel(const uint64_t* __rest
     const int l = lower_bound_u64(table, n_blocks, k);
     lb[r] = l;
     newflag[r] = (l < n_blocks && table[l] == k) ? 0u : 1u;
-}
-
-__global__ void __launch_bounds__(256) tsdf_counts_kernel(const uint32_t* __restrict__ d_m, const uint32_t* __restrict__ d_new,
-                                                          uint32_t* __restrict__ out) {
-    out[0] = *d_m;
-    out[1] = *d_new;
 }
 
 // merge, old entries: position = own index + number of new keys below it
@@ -467,18 +375,12 @@ __global__ void __launch_bounds__(TSDF_VOX) tsdf_mc_count_kernel(const uint64_t*
     }
 }
 
-__global__ void __launch_bounds__(256) tsdf_totals_kernel(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
-                                                          uint32_t* __restrict__ out) {
-    out[0] = *a;
-    out[1] = *b;
-}
-
 // global index of the vertex on the +a edge of local voxel (x, y, z), x, y, z in 0..8 (8: the + neighbour block)
 __device__ inline uint32_t vertex_id(const McShared& s, const uint32_t* __restrict__ vpre, const uint32_t* __restrict__ vbase,
                                      int x, int y, int z, int a) {
     const int nb = s.nbr[nbr_idx(block_of(x), block_of(y), block_of(z))];
     const uint32_t w = vpre[(size_t)nb * TSDF_VOX + (size_t)((x & 7) + 8 * (y & 7) + 64 * (z & 7))];
-    return vbase[nb] + (w >> 3) + (uint32_t)__builtin_popcount(w & 7u & ((1u << a) - 1u));
+    return vbase[nb] + mc_vertex_rank(w, a);
 }
 
 __global__ void __launch_bounds__(TSDF_VOX) tsdf_mc_emit_kernel(const uint64_t* __restrict__ keys, const int* __restrict__ slots,
@@ -522,65 +424,50 @@ __global__ void __launch_bounds__(TSDF_VOX) tsdf_mc_emit_kernel(const uint64_t* 
     uint32_t ti = tbase[p] + block512_excl_scan_u32(ntri, s.scan, &tt);
     const signed char* row = g4s_mc_tris[cube & 0xFF];
     for (uint32_t k = 0; k < 3 * ntri && ti + k / 3 < tcap; k++) {
-        const int e = row[k], a = e >> 2, n = e & 3;
-        const int o1 = n & 1, o2 = n >> 1;  // the lower corner's other two coordinates, in axis order
-        const int ex = x + (a == 0 ? 0 : o1), ey = y + (a == 1 ? 0 : (a == 0 ? o1 : o2)), ez = z + (a == 2 ? 0 : o2);
-        tris[3 * (size_t)ti + k] = (int)vertex_id(s, vpre, vbase, ex, ey, ez, a);
+        const McEdge e = mc_edge(row[k], x, y, z);
+        tris[3 * (size_t)ti + k] = (int)vertex_id(s, vpre, vbase, e.x, e.y, e.z, e.a);
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// host sequencing (the entry points in api.hip validate every argument before calling these)
+// host sequencing (the entry points below validate every argument before calling these)
 
 TsdfViewLayout tsdf_view_layout(int W, int H, int cap) {
     TsdfViewLayout L{};
     const size_t n = (size_t)W * H * cap;
-    size_t off = 0;
-    auto take = [&](size_t& field, size_t bytes) {
-        field = off;
-        off += (bytes + 255) & ~(size_t)255;
-    };
+    WorkspaceCursor c;
     L.n = n;
-    take(L.keys_a, n * 8);
-    take(L.keys_b, n * 8);
-    take(L.hist, (size_t)256 * sort_blocks(n, SORT_ITEMS_U64) * 4);
-    take(L.bin_total, 512 * 4);
-    take(L.flag, n * 4);
-    take(L.pos, n * 4);
-    take(L.lb, n * 4);
-    take(L.new_keys, n * 8);
-    take(L.touched_slot, n * 4);
-    take(L.chunks, (size_t)scan_chunks((long)n) * 4 + 4);
-    take(L.words, 64);
-    L.bytes = off;
+    L.keys_a = c.take(n * 8);
+    L.keys_b = c.take(n * 8);
+    L.hist = c.take((size_t)256 * sort_blocks(n, SORT_ITEMS_U64) * 4);
+    L.bin_total = c.take(512 * 4);
+    L.flag = c.take(n * 4);
+    L.pos = c.take(n * 4);
+    L.lb = c.take(n * 4);
+    L.new_keys = c.take(n * 8);
+    L.touched_slot = c.take(n * 4);
+    L.chunks = c.take((size_t)scan_chunks((long)n) * 4 + 4);
+    L.words = c.take(64);
+    L.bytes = c.off;
     return L;
 }
 
 TsdfMcLayout tsdf_mc_layout(int n_blocks) {
     TsdfMcLayout L{};
     const size_t nb = (size_t)n_blocks;
-    size_t off = 0;
-    auto take = [&](size_t& field, size_t bytes) {
-        field = off;
-        off += (bytes + 255) & ~(size_t)255;
-    };
-    take(L.vpre, nb * TSDF_VOX * 4);
-    take(L.nv, nb * 4);
-    take(L.nt, nb * 4);
-    take(L.vbase, nb * 4);
-    take(L.tbase, nb * 4);
-    take(L.chunks, (size_t)scan_chunks((long)nb) * 4 + 4);
-    take(L.words, 64);
-    L.bytes = off;
+    WorkspaceCursor c;
+    L.vpre = c.take(nb * TSDF_VOX * 4);
+    L.nv = c.take(nb * 4);
+    L.nt = c.take(nb * 4);
+    L.vbase = c.take(nb * 4);
+    L.tbase = c.take(nb * 4);
+    L.chunks = c.take((size_t)scan_chunks((long)nb) * 4 + 4);
+    L.words = c.take(64);
+    L.bytes = c.off;
     return L;
 }
 
-#define TSDF_TRY(expr)                                  \
-    do {                                                \
-        hipError_t _e = (expr);                         \
-        if (_e != hipSuccess) return _e;                \
-    } while (0)
-
+// counts[0] = touched blocks, counts[1] = new blocks (one host synchronisation)
 hipError_t tsdf_alloc_count(const TsdfView& c, const float* depth, const float* mask, int cap, const uint64_t* table,
                             int n_blocks, char* ws, int* counts, hipStream_t s) {
     const TsdfViewLayout L = tsdf_view_layout(c.W, c.H, cap);
@@ -605,20 +492,11 @@ hipError_t tsdf_alloc_count(const TsdfView& c, const float* depth, const float* 
     hipLaunchKernelGGL(tsdf_lookup_kernel, dim3(g), dim3(256), 0, s, uniq, words + 0, n, table, n_blocks, (int*)(ws + L.lb), flag);
     scan_u32(flag, pos, n, chunks, words + 1, s);
     hipLaunchKernelGGL(compact_u64_kernel, dim3(g), dim3(256), 0, s, uniq, flag, pos, n, (uint64_t*)(ws + L.new_keys));
-    hipLaunchKernelGGL(tsdf_counts_kernel, dim3(1), dim3(1), 0, s, words + 0, words + 1, words + 2);
-    TSDF_TRY(hipGetLastError());
-    uint32_t host[2];
-    TSDF_TRY(hipMemcpyAsync(host, words + 2, 8, hipMemcpyDeviceToHost, s));
-    TSDF_TRY(hipStreamSynchronize(s));
-    counts[0] = (int)host[0];
-    counts[1] = (int)host[1];
-    return hipSuccess;
+    return read_totals(words, counts, s);
 }
 
-hipError_t tsdf_merge(const TsdfView& c, int cap, const uint64_t* keys_in, const int* slots_in, int n_blocks, int m,
-                      int n_new, uint64_t* keys_out, int* slots_out, float* tsdf, float* weight, float* color, char* ws,
-                      hipStream_t s) {
-    const TsdfViewLayout L = tsdf_view_layout(c.W, c.H, cap);
+hipError_t tsdf_merge(const TsdfViewLayout& L, const uint64_t* keys_in, const int* slots_in, int n_blocks, int m, int n_new,
+                      uint64_t* keys_out, int* slots_out, float* tsdf, float* weight, float* color, char* ws, hipStream_t s) {
     if (n_blocks > 0)
         hipLaunchKernelGGL(tsdf_merge_old_kernel, dim3((n_blocks + 255) / 256), dim3(256), 0, s, keys_in, slots_in, n_blocks,
                            (const uint64_t*)(ws + L.new_keys), n_new, keys_out, slots_out);
@@ -631,15 +509,15 @@ hipError_t tsdf_merge(const TsdfView& c, int cap, const uint64_t* keys_in, const
     return hipGetLastError();
 }
 
-hipError_t tsdf_integrate(const TsdfView& c, int cap, const float* depth, const float* mask, const float* rgb, int m,
-                          float* tsdf, float* weight, float* color, char* ws, hipStream_t s) {
-    const TsdfViewLayout L = tsdf_view_layout(c.W, c.H, cap);
+hipError_t tsdf_integrate(const TsdfView& c, const TsdfViewLayout& L, const float* depth, const float* mask, const float* rgb,
+                          int m, float* tsdf, float* weight, float* color, char* ws, hipStream_t s) {
     if (m > 0)
         hipLaunchKernelGGL(tsdf_integrate_kernel, dim3(m), dim3(TSDF_VOX), 0, s, c, depth, mask, rgb,
                            (const uint64_t*)(ws + L.keys_b), (const int*)(ws + L.touched_slot), tsdf, weight, color);
     return hipGetLastError();
 }
 
+// totals[0] = vertices, totals[1] = triangles (one host synchronisation)
 hipError_t tsdf_extract_count(const uint64_t* keys, const int* slots, int n_blocks, const float* tsdf, const float* weight,
                               char* ws, int* totals, hipStream_t s) {
     const TsdfMcLayout L = tsdf_mc_layout(n_blocks);
@@ -651,14 +529,7 @@ hipError_t tsdf_extract_count(const uint64_t* keys, const int* slots, int n_bloc
                        (uint32_t*)(ws + L.vpre), nv, nt);
     scan_u32(nv, (uint32_t*)(ws + L.vbase), n_blocks, chunks, words + 0, s);  // per-block vertex / triangle bases
     scan_u32(nt, (uint32_t*)(ws + L.tbase), n_blocks, chunks, words + 1, s);
-    hipLaunchKernelGGL(tsdf_totals_kernel, dim3(1), dim3(1), 0, s, words + 0, words + 1, words + 2);
-    TSDF_TRY(hipGetLastError());
-    uint32_t host[2];
-    TSDF_TRY(hipMemcpyAsync(host, words + 2, 8, hipMemcpyDeviceToHost, s));
-    TSDF_TRY(hipStreamSynchronize(s));
-    totals[0] = (int)host[0];
-    totals[1] = (int)host[1];
-    return hipSuccess;
+    return read_totals(words, totals, s);
 }
 
 hipError_t tsdf_extract_emit(const uint64_t* keys, const int* slots, int n_blocks, const float* tsdf, const float* weight,
@@ -680,30 +551,9 @@ using namespace g4s;
 // extern "C" entry points (include/g4s_render_maps.h, TSDF section); every argument is checked before any launch
 namespace {
 
-// The library's error message lives in the calling thread's buffer that g4s_last_error() returns (api.hip: 512 bytes,
-// thread_local); these entry points write their messages there as every other entry point does.
-constexpr size_t ERR_BYTES = 512;
-char* err_buf() { return const_cast<char*>(g4s_last_error()); }
-void clear_error() { err_buf()[0] = 0; }
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(err_buf(), ERR_BYTES, fmt, ap);
-    va_end(ap);
-    return code;
-}
-// launch errors (the stream is not synchronised: a fault inside a kernel surfaces at the next synchronising call)
-int check_launch(const char* what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? G4S_OK : fail(G4S_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-}
-
-bool finite_pos(float x) { return x > 0.0f && x < 3.0e38f; }
-
 int tsdf_check_intrinsic(const float* intrinsic) {
-    if (!intrinsic) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    if (!finite_pos(intrinsic[0]) || !finite_pos(intrinsic[1]) || !(fabsf(intrinsic[2]) < 3.0e38f) ||
-        !(fabsf(intrinsic[3]) < 3.0e38f))
+    if (!intrinsic) return null_pointer();
+    if (!finite_pos(intrinsic[0]) || !finite_pos(intrinsic[1]) || !finite(intrinsic[2]) || !finite(intrinsic[3]))
         return fail(G4S_ERR_INVALID_ARGUMENT, "intrinsic fx, fy must be positive and cx, cy finite");
     return G4S_OK;
 }
@@ -714,7 +564,7 @@ int tsdf_view(int W, int H, const float* intrinsic, const float* extrinsic, floa
     if (!finite_pos(voxel_size) || !finite_pos(sdf_trunc) || !finite_pos(depth_trunc))
         return fail(G4S_ERR_INVALID_ARGUMENT, "voxel_size, sdf_trunc, depth_trunc must be positive");
     if (tsdf_check_intrinsic(intrinsic) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
-    if (!extrinsic) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (!extrinsic) return null_pointer();
     *c = TsdfView{};
     c->W = W;
     c->H = H;
@@ -770,7 +620,7 @@ extern "C" int g4s_tsdf_alloc_count(int width, int height, const float* depth, c
     TsdfView c;
     if (tsdf_view(width, height, intrinsic, extrinsic, voxel_size, sdf_trunc, depth_trunc, &c) != G4S_OK)
         return G4S_ERR_INVALID_ARGUMENT;
-    if (!depth || !counts || (n_blocks > 0 && !keys)) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (!depth || !counts || (n_blocks > 0 && !keys)) return null_pointer();
     if (n_blocks < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "n_blocks must not be negative");
     const int need = g4s_tsdf_blocks_per_pixel(width, height, intrinsic, voxel_size, sdf_trunc);
     if (need < 0) return need;
@@ -778,12 +628,10 @@ extern "C" int g4s_tsdf_alloc_count(int width, int height, const float* depth, c
         return fail(G4S_ERR_INVALID_ARGUMENT, "blocks_per_pixel %d below the %d this camera needs", blocks_per_pixel, need);
     if ((double)width * height * blocks_per_pixel >= 2147483647.0)
         return fail(G4S_ERR_INVALID_ARGUMENT, "width * height * blocks_per_pixel exceeds 2^31 - 1 keys");
-    if (!workspace || workspace_bytes < g4s_tsdf_workspace(width, height, blocks_per_pixel, 0))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
-    hipError_t e = tsdf_alloc_count(c, depth, mask, blocks_per_pixel, (const uint64_t*)keys, n_blocks,
-                                    (char*)align_ptr(workspace), counts, stream);
-    if (e != hipSuccess) return fail(G4S_ERR_HIP, "tsdf alloc_count: %s", hipGetErrorString(e));
-    return check_launch("tsdf alloc_count");
+    if (check_workspace(workspace, workspace_bytes, g4s_tsdf_workspace(width, height, blocks_per_pixel, 0)) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
+    return finish(tsdf_alloc_count(c, depth, mask, blocks_per_pixel, (const uint64_t*)keys, n_blocks, align_ptr(workspace),
+                                   counts, stream),
+                  "tsdf alloc_count");
 }
 
 extern "C" int g4s_tsdf_merge(int width, int height, int blocks_per_pixel, const long long* keys_in, const int* slots_in,
@@ -797,22 +645,18 @@ extern "C" int g4s_tsdf_merge(int width, int height, int blocks_per_pixel, const
     if (n_blocks < 0 || n_touched < 0 || n_new < 0 || n_new > n_touched)
         return fail(G4S_ERR_INVALID_ARGUMENT, "counts must not be negative (and n_new <= n_touched)");
     if ((n_blocks > 0 && (!keys_in || !slots_in)) || !keys_out || !slots_out || !tsdf || !weight || !color)
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+        return null_pointer();
     if ((const void*)keys_in == (const void*)keys_out || (const void*)slots_in == (const void*)slots_out)
         return fail(G4S_ERR_INVALID_ARGUMENT, "the new table must not alias the old one");
     if ((long long)n_blocks + n_new > (long long)pool_blocks)
         return fail(G4S_ERR_INVALID_ARGUMENT, "pool of %d blocks cannot hold %d + %d", pool_blocks, n_blocks, n_new);
     if ((double)n_touched > (double)width * height * blocks_per_pixel)
         return fail(G4S_ERR_INVALID_ARGUMENT, "n_touched exceeds the view's key slots");
-    if (!workspace || workspace_bytes < g4s_tsdf_workspace(width, height, blocks_per_pixel, 0))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
-    TsdfView c{};
-    c.W = width;
-    c.H = height;
-    hipError_t e = tsdf_merge(c, blocks_per_pixel, (const uint64_t*)keys_in, slots_in, n_blocks, n_touched, n_new,
-                              (uint64_t*)keys_out, slots_out, tsdf, weight, color, (char*)align_ptr(workspace), stream);
-    if (e != hipSuccess) return fail(G4S_ERR_HIP, "tsdf merge: %s", hipGetErrorString(e));
-    return check_launch("tsdf merge");
+    if (check_workspace(workspace, workspace_bytes, g4s_tsdf_workspace(width, height, blocks_per_pixel, 0)) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
+    return finish(tsdf_merge(tsdf_view_layout(width, height, blocks_per_pixel), (const uint64_t*)keys_in, slots_in, n_blocks,
+                             n_touched, n_new, (uint64_t*)keys_out, slots_out, tsdf, weight, color, align_ptr(workspace),
+                             stream),
+                  "tsdf merge");
 }
 
 extern "C" int g4s_tsdf_integrate(int width, int height, const float* depth, const float* mask, const float* rgb,
@@ -824,17 +668,15 @@ extern "C" int g4s_tsdf_integrate(int width, int height, const float* depth, con
     TsdfView c;
     if (tsdf_view(width, height, intrinsic, extrinsic, voxel_size, sdf_trunc, depth_trunc, &c) != G4S_OK)
         return G4S_ERR_INVALID_ARGUMENT;
-    if (!depth || !rgb || !tsdf || !weight || !color) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (!depth || !rgb || !tsdf || !weight || !color) return null_pointer();
     if (blocks_per_pixel <= 0 || n_touched < 0 || pool_blocks < 0)
         return fail(G4S_ERR_INVALID_ARGUMENT, "blocks_per_pixel must be positive, counts not negative");
     if ((double)n_touched > (double)width * height * blocks_per_pixel || n_touched > pool_blocks)
         return fail(G4S_ERR_INVALID_ARGUMENT, "n_touched exceeds the view's key slots or the pool");
-    if (!workspace || workspace_bytes < g4s_tsdf_workspace(width, height, blocks_per_pixel, 0))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
-    hipError_t e = tsdf_integrate(c, blocks_per_pixel, depth, mask, rgb, n_touched, tsdf, weight, color,
-                                  (char*)align_ptr(workspace), stream);
-    if (e != hipSuccess) return fail(G4S_ERR_HIP, "tsdf integrate: %s", hipGetErrorString(e));
-    return check_launch("tsdf integrate");
+    if (check_workspace(workspace, workspace_bytes, g4s_tsdf_workspace(width, height, blocks_per_pixel, 0)) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
+    return finish(tsdf_integrate(c, tsdf_view_layout(width, height, blocks_per_pixel), depth, mask, rgb, n_touched, tsdf,
+                                 weight, color, align_ptr(workspace), stream),
+                  "tsdf integrate");
 }
 
 extern "C" int g4s_tsdf_extract_count(const long long* keys, const int* slots, int n_blocks, const float* tsdf,
@@ -845,17 +687,14 @@ extern "C" int g4s_tsdf_extract_count(const long long* keys, const int* slots, i
     if (n_blocks < 0 || pool_blocks < n_blocks)
         return fail(G4S_ERR_INVALID_ARGUMENT, "n_blocks must not be negative nor exceed pool_blocks");
     if (!totals || (n_blocks > 0 && (!keys || !slots || !tsdf || !weight)))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+        return null_pointer();
     if (n_blocks == 0) {
         totals[0] = totals[1] = 0;
         return G4S_OK;
     }
-    if (!workspace || workspace_bytes < g4s_tsdf_workspace(0, 0, 0, n_blocks))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
-    hipError_t e = tsdf_extract_count((const uint64_t*)keys, slots, n_blocks, tsdf, weight, (char*)align_ptr(workspace),
-                                      totals, stream);
-    if (e != hipSuccess) return fail(G4S_ERR_HIP, "tsdf extract_count: %s", hipGetErrorString(e));
-    return check_launch("tsdf extract_count");
+    if (check_workspace(workspace, workspace_bytes, g4s_tsdf_workspace(0, 0, 0, n_blocks)) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
+    return finish(tsdf_extract_count((const uint64_t*)keys, slots, n_blocks, tsdf, weight, align_ptr(workspace), totals, stream),
+                  "tsdf extract_count");
 }
 
 extern "C" int g4s_tsdf_extract_emit(const long long* keys, const int* slots, int n_blocks, const float* tsdf,
@@ -869,12 +708,10 @@ extern "C" int g4s_tsdf_extract_emit(const long long* keys, const int* slots, in
     if (!finite_pos(voxel_size)) return fail(G4S_ERR_INVALID_ARGUMENT, "voxel_size must be positive");
     if ((n_blocks > 0 && (!keys || !slots || !tsdf || !weight || !color)) || (n_vertices > 0 && (!vertices || !vertex_colors)) ||
         (n_triangles > 0 && !triangles))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+        return null_pointer();
     if (n_blocks == 0 || n_vertices == 0) return G4S_OK;
-    if (!workspace || workspace_bytes < g4s_tsdf_workspace(0, 0, 0, n_blocks))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
-    hipError_t e = tsdf_extract_emit((const uint64_t*)keys, slots, n_blocks, tsdf, weight, color, voxel_size, vertices,
-                                     vertex_colors, triangles, n_vertices, n_triangles, (char*)align_ptr(workspace), stream);
-    if (e != hipSuccess) return fail(G4S_ERR_HIP, "tsdf extract_emit: %s", hipGetErrorString(e));
-    return check_launch("tsdf extract_emit");
+    if (check_workspace(workspace, workspace_bytes, g4s_tsdf_workspace(0, 0, 0, n_blocks)) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
+    return finish(tsdf_extract_emit((const uint64_t*)keys, slots, n_blocks, tsdf, weight, color, voxel_size, vertices,
+                                    vertex_colors, triangles, n_vertices, n_triangles, align_ptr(workspace), stream),
+                  "tsdf extract_emit");
 }

@@ -11,14 +11,13 @@
 // exclusive scans of the per-workgroup totals (scan.h) -> [host: sizes] -> emit.  No atomics: every output position is a
 // scan result, so two runs are bit-identical.
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include <vector>
 
 #include "../g4s_internal.h"
 #include "../g4s_device.h"
 #include "../../../include/g4s_render_maps.h"
+#include "mesh_common.h"
 #include "scan.h"
 #include "tsdf_mc_table.h"
 
@@ -158,19 +157,15 @@ DmcLayout dmc_layout(int N) {
     const size_t total = (size_t)N * N * N;
     L.groups = (int)((total + DMC_GROUP - 1) / DMC_GROUP);
     const size_t g = (size_t)L.groups;
-    size_t off = 0;
-    auto take = [&](size_t& field, size_t bytes) {
-        field = off;
-        off += (bytes + 255) & ~(size_t)255;
-    };
-    take(L.vpre, g * DMC_GROUP * 2);  // per point: in-workgroup exclusive vertex prefix << 3 | owned-edge mask (<= 765 << 3 | 7)
-    take(L.nv, g * 4);
-    take(L.nt, g * 4);
-    take(L.vbase, g * 4);
-    take(L.tbase, g * 4);
-    take(L.chunks, (size_t)scan_chunks((long)g) * 4 + 4);
-    take(L.words, 64);
-    L.bytes = off;
+    WorkspaceCursor c;
+    L.vpre = c.take(g * DMC_GROUP * 2);  // per point: in-workgroup exclusive vertex prefix << 3 | owned-edge mask (<= 765 << 3 | 7)
+    L.nv = c.take(g * 4);
+    L.nt = c.take(g * 4);
+    L.vbase = c.take(g * 4);
+    L.tbase = c.take(g * 4);
+    L.chunks = c.take((size_t)scan_chunks((long)g) * 4 + 4);
+    L.words = c.take(64);
+    L.bytes = c.off;
     return L;
 }
 
@@ -229,16 +224,11 @@ __global__ void __launch_bounds__(DMC_GROUP) dmc_count_kernel(const float* __res
     }
 }
 
-__global__ void dmc_totals_kernel(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t* __restrict__ out) {
-    out[0] = *a;
-    out[1] = *b;
-}
-
 // index of the vertex on the +a edge of lattice point idx
 __device__ __forceinline__ uint32_t dmc_vertex_id(const uint16_t* __restrict__ vpre, const uint32_t* __restrict__ vbase,
                                                   size_t idx, int a) {
     const uint32_t w = vpre[idx];
-    return vbase[idx / DMC_GROUP] + (w >> 3) + (uint32_t)__builtin_popcount(w & 7u & ((1u << a) - 1u));
+    return vbase[idx / DMC_GROUP] + mc_vertex_rank(w, a);
 }
 
 __global__ void __launch_bounds__(DMC_GROUP) dmc_emit_kernel(const float* __restrict__ tsdf, int N, size_t total, float R,
@@ -280,10 +270,8 @@ __global__ void __launch_bounds__(DMC_GROUP) dmc_emit_kernel(const float* __rest
     uint32_t ti = tbase[blockIdx.x] + block256_excl_scan_u32(ntri, sm4, &tt);
     const signed char* row = g4s_mc_tris[cfg];
     for (uint32_t q = 0; q < 3 * ntri && ti + q / 3 < tcap; q++) {
-        const int e = row[q], a = e >> 2, n = e & 3;
-        const int o1 = n & 1, o2 = n >> 1;  // the lower corner's other two coordinates, in axis order
-        const int ex = i + (a == 0 ? 0 : o1), ey = j + (a == 1 ? 0 : (a == 0 ? o1 : o2)), ez = k + (a == 2 ? 0 : o2);
-        tris[3 * (size_t)ti + q] = (int)dmc_vertex_id(vpre, vbase, (size_t)ex + (size_t)N * ((size_t)ey + (size_t)N * (size_t)ez), a);
+        const McEdge e = mc_edge(row[q], i, j, k);
+        tris[3 * (size_t)ti + q] = (int)dmc_vertex_id(vpre, vbase, (size_t)e.x + (size_t)N * ((size_t)e.y + (size_t)N * (size_t)e.z), e.a);
     }
 }
 
@@ -295,30 +283,11 @@ using namespace g4s;
 // extern "C" entry points; every argument is checked before any launch
 namespace {
 
-constexpr size_t ERR_BYTES = 512;  // the calling thread's buffer behind g4s_last_error() (api.hip)
-char* err_buf() { return const_cast<char*>(g4s_last_error()); }
-void clear_error() { err_buf()[0] = 0; }
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(err_buf(), ERR_BYTES, fmt, ap);
-    va_end(ap);
-    return code;
-}
-int check_launch(const char* what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? G4S_OK : fail(G4S_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-}
-bool finite_pos(float x) { return x > 0.0f && x < 3.0e38f; }
-bool finite(float x) { return fabsf(x) < 3.0e38f; }
-
-bool lattice_ok(int n) { return n >= 2 && (long long)n * n * n < (1ll << 31); }
-
 int check_frame(const float* center, float radius, float voxel_size, bool need_frame, UtsdfFrame* f) {
     if (!finite_pos(voxel_size)) return fail(G4S_ERR_INVALID_ARGUMENT, "voxel_size must be positive");
     *f = UtsdfFrame{0.0f, 0.0f, 0.0f, 1.0f, voxel_size};
     if (!need_frame) return G4S_OK;
-    if (!center) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (!center) return null_pointer();
     if (!finite_pos(radius) || !finite(center[0]) || !finite(center[1]) || !finite(center[2]))
         return fail(G4S_ERR_INVALID_ARGUMENT, "radius must be positive and center finite");
     f->cx = center[0];
@@ -334,8 +303,8 @@ int stage_views(int n_views, const float* full_proj, const int* sizes, const flo
     if (n_views < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "n_views must not be negative");
     *table = nullptr;
     if (n_views == 0) return G4S_OK;
-    if (!full_proj || !sizes || !depth || (need_rgb && !rgb)) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    if (!workspace || workspace_bytes < g4s_utsdf_workspace(n_views)) return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
+    if (!full_proj || !sizes || !depth || (need_rgb && !rgb)) return null_pointer();
+    if (check_workspace(workspace, workspace_bytes, g4s_utsdf_workspace(n_views)) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     std::vector<UtsdfView> host((size_t)n_views);
     for (int v = 0; v < n_views; v++) {
         UtsdfView& u = host[(size_t)v];
@@ -366,18 +335,18 @@ extern "C" int g4s_utsdf_grid(int n, float half_extent, const float* center, flo
                               char* workspace, size_t workspace_bytes, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     clear_error();
-    if (!lattice_ok(n)) return fail(G4S_ERR_INVALID_ARGUMENT, "n must be at least 2 and n^3 below 2^31");
+    if (check_lattice(n) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     if (!finite_pos(half_extent)) return fail(G4S_ERR_INVALID_ARGUMENT, "half_extent must be positive");
     UtsdfFrame f;
     if (check_frame(center, radius, voxel_size, true, &f) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
-    if (!tsdf) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (!tsdf) return null_pointer();
     const UtsdfView* table;
     const int rc = stage_views(n_views, full_proj, sizes, depth, nullptr, false, workspace, workspace_bytes, stream, &table);
     if (rc != G4S_OK) return rc;
     const float h = (2.0f * half_extent) / (float)(n - 1);
     hipLaunchKernelGGL(utsdf_grid_kernel, dim3((n + 15) / 16, (n + 3) / 4, (n + 3) / 4), dim3(256), 0, stream, n, half_extent, h,
                        f, table, n_views, tsdf);
-    return check_launch("utsdf grid");
+    return finish(hipSuccess, "utsdf grid");
 }
 
 extern "C" int g4s_utsdf_sample(int n_points, const float* points, int contracted, const float* center, float radius,
@@ -389,7 +358,7 @@ extern "C" int g4s_utsdf_sample(int n_points, const float* points, int contracte
     if (n_points < 0 || n_points > (1 << 30)) return fail(G4S_ERR_INVALID_ARGUMENT, "n_points must be in 0 .. 2^30");
     UtsdfFrame f;
     if (check_frame(center, radius, voxel_size, contracted != 0, &f) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
-    if (n_points > 0 && (!points || (!tsdf && !colour))) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (n_points > 0 && (!points || (!tsdf && !colour))) return null_pointer();
     const UtsdfView* table;
     const int rc = stage_views(n_views, full_proj, sizes, depth, rgb, colour != nullptr, workspace, workspace_bytes, stream,
                                &table);
@@ -402,7 +371,7 @@ extern "C" int g4s_utsdf_sample(int n_points, const float* points, int contracte
     else
         hipLaunchKernelGGL(utsdf_sample_kernel<false>, grid, dim3(256), 0, stream, n_points, points, contracted, f, table,
                            n_views, tsdf, colour);
-    return check_launch("utsdf sample");
+    return finish(hipSuccess, "utsdf sample");
 }
 
 extern "C" size_t g4s_dense_mc_workspace(int n) { return lattice_ok(n) ? dmc_layout(n).bytes + 256 : 0; }
@@ -411,9 +380,9 @@ extern "C" int g4s_dense_mc_count(int n, const float* tsdf, int* totals, char* w
                                   void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     clear_error();
-    if (!lattice_ok(n)) return fail(G4S_ERR_INVALID_ARGUMENT, "n must be at least 2 and n^3 below 2^31");
-    if (!tsdf || !totals) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    if (!workspace || workspace_bytes < g4s_dense_mc_workspace(n)) return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
+    if (check_lattice(n) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
+    if (!tsdf || !totals) return null_pointer();
+    if (check_workspace(workspace, workspace_bytes, g4s_dense_mc_workspace(n)) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     const DmcLayout L = dmc_layout(n);
     char* ws = align_ptr(workspace);
     uint32_t* nv = (uint32_t*)(ws + L.nv);
@@ -424,16 +393,13 @@ extern "C" int g4s_dense_mc_count(int n, const float* tsdf, int* totals, char* w
                        (uint16_t*)(ws + L.vpre), nv, nt);
     scan_u32(nv, (uint32_t*)(ws + L.vbase), L.groups, chunks, words + 0, stream);
     scan_u32(nt, (uint32_t*)(ws + L.tbase), L.groups, chunks, words + 1, stream);
-    hipLaunchKernelGGL(dmc_totals_kernel, dim3(1), dim3(1), 0, stream, words + 0, words + 1, words + 2);
-    if (check_launch("dense_mc count") != G4S_OK) return G4S_ERR_HIP;
-    uint32_t host[2];
-    hipError_t e = hipMemcpyAsync(host, words + 2, 8, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return fail(G4S_ERR_HIP, "dense_mc count: %s", hipGetErrorString(e));
-    if (host[0] > 0x7FFFFFFFu / 3 || host[1] > 0x7FFFFFFFu / 3)
+    int t[2];
+    const hipError_t e = read_totals(words, t, stream);
+    if (e != hipSuccess) return finish(e, "dense_mc count");
+    if ((uint32_t)t[0] > 0x7FFFFFFFu / 3 || (uint32_t)t[1] > 0x7FFFFFFFu / 3)
         return fail(G4S_ERR_INVALID_ARGUMENT, "mesh exceeds 2^31 / 3 vertices or triangles");
-    totals[0] = (int)host[0];
-    totals[1] = (int)host[1];
+    totals[0] = t[0];
+    totals[1] = t[1];
     return G4S_OK;
 }
 
@@ -442,21 +408,21 @@ extern "C" int g4s_dense_mc_emit(int n, const float* tsdf, float half_extent, co
                                  char* workspace, size_t workspace_bytes, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     clear_error();
-    if (!lattice_ok(n)) return fail(G4S_ERR_INVALID_ARGUMENT, "n must be at least 2 and n^3 below 2^31");
+    if (check_lattice(n) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     if (n_vertices < 0 || n_triangles < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "counts must not be negative");
     if (!finite_pos(half_extent) || !finite_pos(max_range))
         return fail(G4S_ERR_INVALID_ARGUMENT, "half_extent, max_range must be positive");
     UtsdfFrame f;
     if (check_frame(center, radius, 1.0f, true, &f) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     if (!tsdf || (n_vertices > 0 && !vertices) || (n_triangles > 0 && !triangles))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+        return null_pointer();
     if (n_vertices == 0) return G4S_OK;  // no crossing: nothing to write
-    if (!workspace || workspace_bytes < g4s_dense_mc_workspace(n)) return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
+    if (check_workspace(workspace, workspace_bytes, g4s_dense_mc_workspace(n)) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     const DmcLayout L = dmc_layout(n);
     char* ws = align_ptr(workspace);
     const float h = (2.0f * half_extent) / (float)(n - 1);
     hipLaunchKernelGGL(dmc_emit_kernel, dim3(L.groups), dim3(DMC_GROUP), 0, stream, tsdf, n, (size_t)n * n * n, half_extent, h,
                        f, max_range, (const uint16_t*)(ws + L.vpre), (const uint32_t*)(ws + L.vbase),
                        (const uint32_t*)(ws + L.tbase), vertices, triangles, (uint32_t)n_vertices, (uint32_t)n_triangles);
-    return check_launch("dense_mc emit");
+    return finish(hipSuccess, "dense_mc emit");
 }
