@@ -102,6 +102,12 @@ SIGNATURES = {
     "g4s_dense_mc_workspace": (c_sz, [c_i]),
     "g4s_dense_mc_count": (c_i, [c_i, c_p, c_p, c_p, c_sz, c_p]),
     "g4s_dense_mc_emit": (c_i, [c_i, c_p, c_f, c_p, c_f, c_f, c_p, c_p, c_i, c_i, c_p, c_sz, c_p]),
+    "g4s_atsdf_workspace": (c_sz, [c_i]),
+    "g4s_atsdf_sample": (c_i, [c_i, c_p, c_f, c_f, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_atsdf_bisect": (c_i, [c_i, c_p, c_i, c_p, c_p, c_i, c_f, c_f, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_mtet_workspace": (c_sz, [c_i]),
+    "g4s_mtet_count": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_mtet_emit": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_sz, c_p]),
     "g4s_mesh_observed_vertices": (c_i, [c_i, c_p, c_i, c_p, c_p, c_f, c_p, c_p]),
     "g4s_mesh_keep_unobserved": (c_i, [c_i, c_p, c_i, c_p, c_p, c_p]),
     "g4s_mesh_keep_min_size": (c_i, [c_i, c_p, c_i, c_p, c_p]),

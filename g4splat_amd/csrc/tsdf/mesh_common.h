@@ -1,4 +1,4 @@
-// What two or more of the mesh units (tsdf.hip, unbounded.hip, mesh_ops.hip) share: the argument checks of their entry
+// What two or more of the mesh units (tsdf.hip, unbounded.hip, tetra.hip, mesh_ops.hip) share: the argument checks of their entry
 // points, the read-back of the two scan totals, and the index arithmetic of the marching-cubes table (tsdf_mc_table.h).
 #pragma once
 #include <math.h>

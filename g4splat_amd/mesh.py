@@ -18,6 +18,12 @@ Unbounded scenes (mesh_utils.py:184-279 extract_mesh_unbounded, utils/mcube_util
 dense marching cubes" of the same header: GaussianExtractor.extract_mesh_unbounded fuses every view into a lattice of the
 contracted space in one kernel (unbounded_tsdf_grid), extracts it (dense_marching_cubes) and colours the vertices
 (unbounded_tsdf); nothing leaves the device before the mesh is complete.
+
+The reference's default mesh (scripts/extract_tetra_mesh.py -> extract_mesh_adaptive_tsdf.py:259-377) goes through the
+"adaptive TSDF at points and marching tetrahedra" of the same header (csrc/tsdf/tetra.hip):
+GaussianExtractor.extract_mesh_tetra takes the tetra points of the Gaussians (tetra_points), triangulates them on the host
+(triangulate) unless the cells are given, evaluates the field at the points (adaptive_tsdf), marches the tetrahedra
+(marching_tetrahedra) and bisects every crossing edge against the field in one launch (bisect_surface).
 """
 import ctypes
 import math
@@ -431,7 +437,7 @@ class _ViewStack:
 def _hip_device(device):
     device = torch.device(device)
     if device.type != "cuda":
-        raise RuntimeError("the unbounded extraction needs a HIP device (there is no CPU path)")
+        raise RuntimeError("the mesh kernels need tensors on a HIP device (there is no CPU path)")
     return torch.device("cuda", torch.cuda.current_device() if device.index is None else device.index)
 
 
@@ -500,6 +506,190 @@ def dense_marching_cubes(tsdf, R, center, radius, max_range=32.0, to_host=True):
     return verts[:V], tris[:F]
 
 
+# ---- tetrahedral extraction (include/g4s_render_maps.h, "Adaptive TSDF at points and marching tetrahedra"; csrc/tsdf/tetra.hip)
+class _PointViewStack:
+    """The host arrays the atsdf entry points take, and the device tensors they point into (kept alive here).
+    views: (camera or (world_view_transform, projection_matrix) pair of 4x4, depth [H,W] / [1,H,W], rgb [3,H,W] or None)
+    per view, maps on `device`."""
+
+    def __init__(self, views, device, need_rgb):
+        self.maps, wv, pm, sizes, dptr, cptr = [], [], [], [], [], []
+        for cam, depth, rgb in views:
+            if hasattr(cam, "world_view_transform"):
+                Wv, Pm = _to_np(cam.world_view_transform), _projection_matrix(cam)
+            else:
+                Wv, Pm = (_to_np(m) for m in cam)
+            depth = _ViewStack._map(depth, device, "depth")
+            if depth.dim() == 3 and depth.size(0) == 1:
+                depth = depth[0]
+            if depth.dim() != 2:
+                raise RuntimeError(f"depth must be [H,W] or [1,H,W] (got {tuple(depth.shape)})")
+            H, W = depth.shape
+            depth = depth.contiguous()
+            self.maps.append(depth)
+            dptr.append(depth.data_ptr())
+            if need_rgb:
+                if rgb is None:
+                    raise RuntimeError("colours need the rgb map of every view")
+                rgb = _ViewStack._map(rgb, device, "rgb").contiguous()
+                if tuple(rgb.shape) != (3, H, W):
+                    raise RuntimeError(f"rgb must have shape {(3, H, W)} (got {tuple(rgb.shape)})")
+                self.maps.append(rgb)
+                cptr.append(rgb.data_ptr())
+            wv.extend(np.asarray(Wv, np.float32).reshape(16).tolist())
+            pm.extend(np.asarray(Pm, np.float32).reshape(16).tolist())
+            sizes.extend([W, H])
+        self.n = len(dptr)
+        self.wv = (ctypes.c_float * max(len(wv), 1))(*wv)
+        self.pm = (ctypes.c_float * max(len(pm), 1))(*pm)
+        self.sizes = (ctypes.c_int * max(len(sizes), 1))(*sizes)
+        self.depth = (ctypes.c_void_p * max(self.n, 1))(*dptr)
+        self.rgb = (ctypes.c_void_p * max(self.n, 1))(*cptr) if need_rgb else None
+        self.ws = torch.empty(_lib.load().g4s_atsdf_workspace(self.n), dtype=torch.uint8, device=device)
+
+
+def _device_points(points, what="points"):
+    if not isinstance(points, torch.Tensor):
+        raise RuntimeError(f"{what} must be a tensor on a HIP device")
+    return _hip_device(points.device), points.detach().float().reshape(-1, 3).contiguous()
+
+
+def adaptive_tsdf(points, views, trunc_margin, return_rgb=False, znear=1e-6, zfar=1e6):
+    """g4s_atsdf_sample: the running-mean TSDF of `views` (see _PointViewStack) at points [n,3] (a device tensor), with the
+    default flags of the reference's AdaptiveTSDF.integrate (matcha/dm_extractors/adaptive_tsdf.py:162-339): a point no
+    view accepts keeps -1.  Returns tsdf [n], and with return_rgb (tsdf, colour [n,3])."""
+    dev, pts = _device_points(points)
+    n = pts.size(0)
+    stack = _PointViewStack(views, dev, return_rgb)
+    tsdf = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
+    col = torch.empty((max(n, 1), 3), dtype=torch.float32, device=dev) if return_rgb else None
+    with torch.cuda.device(dev):
+        _lib.call("g4s_atsdf_sample", n, _lib.ptr(pts), float(trunc_margin), float(znear), float(zfar), stack.n, stack.wv,
+                  stack.pm, stack.sizes, stack.depth, stack.rgb, _lib.ptr(tsdf), _lib.ptr(col), _lib.ptr(stack.ws),
+                  stack.ws.numel(), _lib.stream(dev))
+        torch.cuda.current_stream(dev).synchronize()  # the stack's tensors may go once the kernel has run
+    return (tsdf[:n], col[:n]) if return_rgb else tsdf[:n]
+
+
+def marching_tetrahedra(points, tets, sdf):
+    """g4s_mtet_count / g4s_mtet_emit (utils/tetmesh.py:97-138): tets [T,4] over points [n,3] with the field sdf [n]
+    (occupied: sdf > 0), all device tensors.  Returns (edges [E,2] int32: the crossing edges (lo, hi) in ascending order --
+    vertex i of the mesh lies on edge i --, faces [F,3] int32 in tet order).  No crossing: (0,2) and (0,3) tensors."""
+    dev, pts = _device_points(points)
+    n = pts.size(0)
+    if not isinstance(tets, torch.Tensor) or not isinstance(sdf, torch.Tensor) or tets.device != dev or sdf.device != dev:
+        raise RuntimeError(f"tets and sdf must be tensors on {dev}")
+    if tets.dtype.is_floating_point or tets.numel() % 4:
+        raise RuntimeError("tets must be an integer tensor [T,4]")
+    tets = tets.detach().reshape(-1, 4)
+    f = sdf.detach().float().reshape(-1).contiguous()
+    if f.numel() != n:
+        raise RuntimeError(f"sdf must hold one value per point ({f.numel()} for {n} points)")
+    T = tets.size(0)
+    if n >= 2 ** 31 or T > (2 ** 31 - 1) // 4:
+        raise RuntimeError("marching tetrahedra takes fewer than 2^31 points and 2^29 tets")
+    if T > 0 and (int(tets.min()) < 0 or int(tets.max()) >= n):
+        raise RuntimeError(f"tets name a point outside [0, {n})")
+    tets = tets.to(torch.int32).contiguous()
+    if tets.data_ptr() % 16:  # a view at an odd offset: the kernels read a tet as one 16-byte row
+        tets = tets.clone()
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        ws = torch.empty(lib.g4s_mtet_workspace(T), dtype=torch.uint8, device=dev)
+        st = _lib.stream(dev)
+        totals = (ctypes.c_int * 2)()
+        _lib.call("g4s_mtet_count", n, T, _lib.ptr(tets), _lib.ptr(f), totals, _lib.ptr(ws), ws.numel(), st)
+        E, F = totals[0], totals[1]
+        edges = torch.empty((max(E, 1), 2), dtype=torch.int32, device=dev)
+        faces = torch.empty((max(F, 1), 3), dtype=torch.int32, device=dev)
+        _lib.call("g4s_mtet_emit", n, T, _lib.ptr(tets), _lib.ptr(f), _lib.ptr(edges), _lib.ptr(faces), E, F, _lib.ptr(ws),
+                  ws.numel(), st)
+        torch.cuda.current_stream(dev).synchronize()  # `ws` is released on return
+    return edges[:E], faces[:F]
+
+
+def bisect_surface(points, edges, sdf, views, trunc_margin, steps=8, znear=1e-6, zfar=1e6):
+    """g4s_atsdf_bisect (extract_mesh_adaptive_tsdf.py:319-349): every crossing edge of marching_tetrahedra bisected `steps`
+    times against the field of `views`, all steps in one launch.  Returns vertices [E,3] on the device."""
+    dev, pts = _device_points(points)
+    n = pts.size(0)
+    if not isinstance(edges, torch.Tensor) or not isinstance(sdf, torch.Tensor) or edges.device != dev or sdf.device != dev:
+        raise RuntimeError(f"edges and sdf must be tensors on {dev}")
+    if edges.dtype.is_floating_point or edges.numel() % 2:
+        raise RuntimeError("edges must be an integer tensor [E,2]")
+    e = edges.detach().reshape(-1, 2)
+    E = e.size(0)
+    if E > 0 and (int(e.min()) < 0 or int(e.max()) >= n):
+        raise RuntimeError(f"edges name a point outside [0, {n})")
+    e = e.to(torch.int32).contiguous()
+    f = sdf.detach().float().reshape(-1).contiguous()
+    if f.numel() != n:
+        raise RuntimeError(f"sdf must hold one value per point ({f.numel()} for {n} points)")
+    if not 0 <= int(steps) <= 64:
+        raise ValueError("steps must be in 0 .. 64")
+    stack = _PointViewStack(views, dev, False)
+    verts = torch.empty((max(E, 1), 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call("g4s_atsdf_bisect", E, _lib.ptr(e), n, _lib.ptr(pts), _lib.ptr(f), int(steps), float(trunc_margin),
+                  float(znear), float(zfar), stack.n, stack.wv, stack.pm, stack.sizes, stack.depth, _lib.ptr(verts),
+                  _lib.ptr(stack.ws), stack.ws.numel(), _lib.stream(dev))
+        torch.cuda.current_stream(dev).synchronize()
+    return verts[:E]
+
+
+# corners of the box [-1, 1]^3 in the order of trimesh.creation.box, which the reference takes them from (x slowest)
+_BOX_CORNERS = [(x, y, z) for x in (-1.0, 1.0) for y in (-1.0, 1.0) for z in (-1.0, 1.0)]
+
+
+@torch.no_grad()
+def tetra_points(gaussians, downsample_ratio=None, gaussian_flatness=1e-3, points_idx=None, generator=None):
+    """scene/gaussian_model.py:318-375 (get_tetra_points), plain torch: per Gaussian the 8 corners of its +-3 sigma box --
+    the two scales padded with gaussian_flatness as the third --, then all the centres.  With downsample_ratio a random
+    subset (torch.randperm, `generator`) of int(n * ratio) Gaussians is taken, with points_idx the named ones; their boxes
+    grow by ratio^(-1/3).  Returns (points [9 m, 3], scale [9 m, 1]: the largest box half-extent of the point's Gaussian)."""
+    from .densify import build_rotation
+    xyz_all = gaussians.get_xyz.detach().float()
+    rot = getattr(gaussians, "_rotation", None)
+    rots = build_rotation((rot if rot is not None else gaussians.get_rotation).detach().float())
+    scales = torch.nn.functional.pad(gaussians.get_scaling.detach().float()[:, :2], (0, 1), mode="constant",
+                                     value=float(gaussian_flatness))
+    if downsample_ratio is None and points_idx is None:
+        xyz, scale = xyz_all, scales * 3.0
+    else:
+        if points_idx is None:
+            n = xyz_all.size(0)
+            idx = torch.randperm(n, generator=generator)[:int(n * downsample_ratio)].to(xyz_all.device)
+        else:
+            idx = torch.as_tensor(points_idx, device=xyz_all.device).long()
+            downsample_ratio = idx.numel() / xyz_all.size(0)
+        xyz, rots = xyz_all[idx], rots[idx]
+        scale = scales[idx] * 3.0 / (downsample_ratio ** (1 / 3))
+    box = torch.tensor(_BOX_CORNERS, dtype=torch.float32, device=xyz.device).T  # [3,8]
+    corners = torch.bmm(rots, box[None] * scale[:, :, None]) + xyz[:, :, None]  # [m,3,8]
+    points = torch.cat([corners.permute(0, 2, 1).reshape(-1, 3), xyz], 0).contiguous()
+    smax = scale.max(dim=-1, keepdim=True)[0]
+    return points, torch.cat([smax.repeat(1, 8).reshape(-1, 1), smax], 0)
+
+
+def cameras_spatial_extent(cameras):
+    """matcha/dm_scene/cameras.py:854-869 (get_spatial_extent): 1.1 x the largest distance of a camera centre from the
+    mean of the centres."""
+    centres = np.stack([np.linalg.inv(camera_extrinsic(cam).astype(np.float64))[:3, 3] for cam in cameras]).astype(np.float32)
+    return 1.1 * float(np.linalg.norm(centres - centres.mean(0, keepdims=True), axis=-1).max())
+
+
+def triangulate(points):
+    """Delaunay tetrahedralisation of points [n,3] on the HOST (scipy.spatial.Delaunay; the reference's step is CGAL on
+    the CPU too): int32 [T,4] on the points' device."""
+    try:
+        from scipy.spatial import Delaunay
+    except ImportError as e:
+        raise RuntimeError("triangulate needs scipy (scipy.spatial.Delaunay); install it or pass the cells") from e
+    dev = points.device if isinstance(points, torch.Tensor) else None
+    cells = Delaunay(_to_np(points).astype(np.float64).reshape(-1, 3)).simplices
+    return torch.as_tensor(np.ascontiguousarray(cells, np.int32), device=dev)
+
+
 def quantile_linear(values, q):
     """numpy's default (linear-interpolation) quantile of a device tensor: sorted on the device, the two order statistics
     interpolated on the host in float64 (torch.quantile refuses large inputs)."""
@@ -543,6 +733,7 @@ class GaussianExtractor:
     @torch.no_grad()
     def clean(self):
         self.depthmaps, self.rgbmaps, self.viewpoint_stack = [], [], []
+        self.tetra = None  # (points, point scales, cells, sdf, edges) of the last extract_mesh_tetra over these maps
 
     @torch.no_grad()
     def reconstruction(self, viewpoint_stack):
@@ -632,6 +823,40 @@ class GaussianExtractor:
         else:
             cols = torch.zeros((0, 3), dtype=torch.float32, device=verts.device)
         return _returned(DeviceMesh(verts, cols, tris), to_host)
+
+    @torch.no_grad()
+    def extract_mesh_tetra(self, downsample_ratio=0.5, gaussian_flatness=2e-4, truncation_margin=5e-3, texture_mesh=True,
+                           cells=None, n_binary_steps=8, to_host=True, generator=None):
+        """extract_mesh_adaptive_tsdf.py:259-377 over the maps of reconstruction() (rendered with pipe.depth_ratio = 1.0, as
+        the reference's configuration does): tetra points of the Gaussians, their tetrahedralisation (`cells` [T,4] as the
+        reference's cells.pt holds them, or triangulate()), the adaptive TSDF at the points with trunc = truncation_margin
+        x the cameras' spatial extent, marching tetrahedra, n_binary_steps bisections of every crossing edge in one launch,
+        and -- texture_mesh -- vertex colours from a second render pass at SH degree 0 evaluated at the final vertices.
+        Stated differences (include/g4s_render_maps.h): triangles in tet order, only the default flags of
+        AdaptiveTSDF.integrate, colours from the maps rendered here.  Without texture_mesh the colours are zero.
+        Two additions to the reference's signature: `generator` seeds the random subset of tetra_points, and
+        `self.tetra` keeps (points, point scales, cells, sdf, edges) of the run until the next reconstruction()."""
+        extent = cameras_spatial_extent(self.viewpoint_stack)
+        trunc = float(truncation_margin) * extent
+        points, scale = tetra_points(self.gaussians, downsample_ratio, float(gaussian_flatness) * extent, generator=generator)
+        if cells is None:
+            cells = triangulate(points)
+        cells = torch.as_tensor(cells).to(points.device)
+        views = [(cam, d, None) for cam, d in zip(self.viewpoint_stack, self.depthmaps)]
+        sdf = adaptive_tsdf(points, views, trunc)
+        edges, faces = marching_tetrahedra(points, cells, sdf)
+        self.tetra = (points, scale, cells, sdf, edges)
+        verts = bisect_surface(points, edges, sdf, views, trunc, steps=n_binary_steps)
+        cols = torch.zeros_like(verts)
+        if texture_mesh and verts.size(0) > 0:
+            degree = self.gaussians.active_sh_degree
+            self.gaussians.active_sh_degree = 0
+            try:
+                rgbs = [self.render(cam)["render"].detach() for cam in self.viewpoint_stack]
+            finally:
+                self.gaussians.active_sh_degree = degree
+            _t, cols = adaptive_tsdf(verts, [(cam, d, c) for (cam, d, _n), c in zip(views, rgbs)], trunc, return_rgb=True)
+        return _returned(DeviceMesh(verts, cols, faces), to_host)
 
     @torch.no_grad()
     def extract_mesh_bounded_streaming(self, viewpoint_stack, voxel_size=0.004, sdf_trunc=0.02, depth_trunc=3,

@@ -234,6 +234,89 @@ int g4s_dense_mc_emit(int n, const float* tsdf, float half_extent, const float* 
                       size_t workspace_bytes, void* stream);
 
 /* =====================================================================================================================
+ * Adaptive TSDF at points and marching tetrahedra (g4splat_amd/csrc/tsdf/tetra.hip).
+ *
+ * The reference's default mesh (scripts/extract_tetra_mesh.py -> 2d-gaussian-splatting/extract_mesh_adaptive_tsdf.py:259-377
+ * marching_tetrahedra_with_binary_search; matcha/dm_extractors/adaptive_tsdf.py AdaptiveTSDF.integrate with the flags of
+ * configs/adaptive_tetrahedralization/default.yaml; utils/tetmesh.py): a TSDF evaluated at the points of a tetrahedralisation,
+ * marching tetrahedra over its cells, every crossing edge bisected against the same field.  As above, the semantics are
+ * this library's own, stated exactly (tests/tetra_ref.py restates them in numpy): float32, round-to-nearest-even,
+ * correctly rounded /, no fused multiply-add, evaluated left to right as written; min / max are IEEE minNum / maxNum.
+ *
+ * Views.  V views, fused in stack order.  View v has world_view_transform Wv and projection_matrix Pm (16 floats each,
+ *   row-major, used as row-vector @ M: M[r][c] = M[4r + c]), a depth map [H,W] and -- for colours -- an rgb map [3,H,W],
+ *   float32 device pointers.  W and H may differ between views (sizes = {W0, H0, W1, H1, ...}).
+ * State per point p before the first view: tsdf = -1, w = 0, colour = 0.
+ * Per view, in order:
+ *   v_c = ((p0*Wv[0][c] + p1*Wv[1][c]) + p2*Wv[2][c]) + Wv[3][c] for c = 0, 1, 2;  z = v_2.
+ *   q_c = ((v_0*Pm[0][c] + v_1*Pm[1][c]) + v_2*Pm[2][c]) + Pm[3][c] for c = 0, 1, 3;  qw = q_3 > znear ? q_3 : znear.
+ *   ix = ((1 + q_0 / qw) * float(W)) / 2, iy = ((1 + q_1 / qw) * float(H)) / 2 -- W and H, not W - 1 and H - 1: the
+ *   reference's pixel convention, kept.
+ *   used = ix >= 0 && ix <= W-1 && iy >= 0 && iy <= H-1 && z > znear && z < zfar (every comparison with NaN is false).
+ *   If used, a bilinear sample at (ix, iy) taken as pixel-index coordinates: x0 = floor(ix), x1 = min(x0 + 1, W - 1),
+ *   fx = ix - x0, the same in y with H; w00 = (1-fx)*(1-fy), w10 = fx*(1-fy), w01 = (1-fx)*fy, w11 = fx*fy (first index x);
+ *   d = ((d00*w00 + d10*w10) + d01*w01) + d11*w11, each rgb channel s_c likewise.  (The reference normalises (ix, iy) to
+ *   [-1, 1] and grid_sample maps them back: a float32 round trip this contract does not make.)
+ *   The view is skipped unless used && d > 0 && d - z >= -trunc_margin.
+ *   dist = min((d - z) / trunc_margin, 1) -- no lower clamp --; tsdf <- (tsdf*w + dist) / (w + 1);
+ *   colour_c <- min(max((colour_c*w + s_c) / (w + 1), 0), 1); w <- w + 1.
+ *   A point no view accepts keeps tsdf = -1: unseen counts as inside, the reference's quirk.  Only this default flag set
+ *   of AdaptiveTSDF.integrate exists (bilinear depth, obs_weight 1, every filter and weighting flag off).
+ * Marching tetrahedra.  points are named by index < n_points < 2^31; tets [T,4] int32 (16-byte aligned), T < 2^29.  A point
+ *   is occupied iff sdf > 0 (exactly 0, and NaN, are not).  Case bit c of a tet is set iff its corner c is occupied; a tet
+ *   that names an index outside [0, n_points) is skipped (case 0) and none of its indices is used as an address.  A tet
+ *   with one to three occupied corners has its crossing edges (exactly one end occupied) among the corner pairs
+ *   (01, 02, 03, 12, 13, 23) = edge ids 0..5; an edge between points a, b has the key min(a,b) << 32 | max(a,b).
+ *   Vertices: the distinct keys of all crossing edges in ascending key order; edges[i] = (lo, hi) of key i -- the
+ *   reference's unique, occupied-on-one-end edges in torch.unique's order.  Triangles: tets in input order, each one's
+ *   triangles in the order of g4splat_amd/csrc/tsdf/tsdf_mtet_table.h (tools/gen_mtet_table.py: one triangle for one or
+ *   three occupied corners, a quad split along the crossings of opposite tet edges (02, 13), else (03, 12), for two; in a
+ *   tet of positive orientation the normals point to the occupied corners -- the reference's table up to a rotation of each
+ *   triple), each index the position of that edge's key among the vertices (binary search).  Stated difference: the
+ *   reference emits all one-triangle tets before all two-triangle tets; here triangles stay in tet order.
+ *   No atomics: two runs are bit-identical.
+ * Bisection.  Per crossing edge (lo, hi): l = points[lo], r = points[hi], ls = sdf[lo].  `steps` times: m_c = (l_c + r_c) / 2;
+ *   ms = the tsdf of the whole stack at m (as above, no colour); low = (ms < 0 && ls < 0) || (ms > 0 && ls > 0); if low,
+ *   l <- m and ls <- ms; otherwise r <- m (so ms == 0 moves the right end).  vertices[i] = (l + r) / 2 per coordinate
+ *   (steps = 0: the edge's midpoint).  An edge that names an index outside [0, n_points) gets three NaNs.
+ *
+ * world_view, projection [V,16], sizes [V,2] and the arrays of V map pointers are HOST arrays, read during the call (the
+ * library packs them into a table in the workspace).  Every argument is checked on the host before anything is launched;
+ * capacities are the caller's.  Sequence: atsdf_sample at the points -> mtet_count (reads back its totals) -> the caller
+ * allocates -> mtet_emit (same tets, sdf and workspace, untouched in between) -> atsdf_bisect -> atsdf_sample (colours).
+ */
+
+/* Bytes of device workspace of g4s_atsdf_sample / g4s_atsdf_bisect for a stack of n_views views. */
+size_t g4s_atsdf_workspace(int n_views);
+
+/* The fused field at points [n_points,3] (device).  tsdf [n_points] and colour [n_points,3] are optional (at least one);
+ * colour needs the rgb maps.  n_views = 0: every tsdf is exactly -1. */
+int g4s_atsdf_sample(int n_points, const float* points, float trunc_margin, float znear, float zfar, int n_views,
+                     const float* world_view, const float* projection, const int* sizes, const float* const* depth,
+                     const float* const* rgb, float* tsdf, float* colour, char* workspace, size_t workspace_bytes,
+                     void* stream);
+
+/* vertices [n_edges,3]: every crossing edge (edges [n_edges,2], as g4s_mtet_emit writes them) bisected `steps` times
+ * (0 .. 64) against the fused field; sdf [n_points] is that field at the points. */
+int g4s_atsdf_bisect(int n_edges, const int* edges, int n_points, const float* points, const float* sdf, int steps,
+                     float trunc_margin, float znear, float zfar, int n_views, const float* world_view,
+                     const float* projection, const int* sizes, const float* const* depth, float* vertices,
+                     char* workspace, size_t workspace_bytes, void* stream);
+
+/* Bytes of device workspace of the marching tetrahedra over n_tets tets (0 for an n_tets outside 0 .. 2^29 - 1). */
+size_t g4s_mtet_workspace(int n_tets);
+
+/* totals[0] = vertices (crossing edges), totals[1] = triangles (host int[2]; two host synchronisations).  n_tets = 0 or
+ * no crossing tet: both 0, nothing else is done. */
+int g4s_mtet_count(int n_points, int n_tets, const int* tets, const float* sdf, int* totals, char* workspace,
+                   size_t workspace_bytes, void* stream);
+
+/* edges [n_edges,2], faces [n_faces,3]: the totals of mtet_count (nothing is written beyond them; with n_edges = 0
+ * nothing is written at all). */
+int g4s_mtet_emit(int n_points, int n_tets, const int* tets, const float* sdf, int* edges, int* faces, int n_edges,
+                  int n_faces, char* workspace, size_t workspace_bytes, void* stream);
+
+/* =====================================================================================================================
  * Mesh operations of the multi-resolution export (g4splat_amd/csrc/tsdf/mesh_ops.hip).
  *
  * What the reference does to its TSDF meshes before it evaluates them (2d-gaussian-splatting/render_multires.py:139-206,
