@@ -118,6 +118,12 @@ SIGNATURES = {
     "g4s_mesh_compact_workspace": (c_sz, [c_i, c_i]),
     "g4s_mesh_compact_count": (c_i, [c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_sz, c_p]),
     "g4s_mesh_compact_emit": (c_i, [c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_sz, c_p]),
+    "g4s_nn_workspace": (c_sz, [c_i, c_i]),
+    "g4s_nn_search": (c_i, [c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_voxel_downsample_workspace": (c_sz, [c_i]),
+    "g4s_voxel_downsample_count": (c_i, [c_i, c_p, c_f, c_p, c_p, c_sz, c_p]),
+    "g4s_voxel_downsample_emit": (c_i, [c_i, c_p, c_i, c_p, c_p, c_sz, c_p]),
+    "g4s_mesh_sample_surface": (c_i, [c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p]),
 }
 
 _lib = None

@@ -389,6 +389,64 @@ int g4s_mesh_compact_emit(int n_vertices, int n_triangles, const float* vertices
                           int* triangles_out, int n_vertices_out, int n_triangles_out, char* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* =====================================================================================================================
+ * Mesh evaluation (g4splat_amd/csrc/tsdf/mesh_eval.hip).
+ *
+ * What the reference's eval/mesh_eval.py asks of scikit-learn's KDTree, open3d's VoxelDownSample and trimesh's
+ * sample_surface before it forms accuracy, completeness, Chamfer-L1, precision, recall, F-score and normal consistency
+ * (g4splat_amd/mesh_eval.py forms them).  The semantics below are this library's own, stated exactly
+ * (tests/mesh_eval_ref.py restates them in numpy).  Clouds are [n,3] float32 device pointers with 3 n below 2^31.
+ * Every output is a pure function of the input arrays; no atomics are used.
+ *
+ * A. Nearest neighbour.  For query q and reference index j: d(j) = ((x_j - q_x)^2 + (y_j - q_y)^2) + (z_j - q_z)^2 in
+ *   float32, separate multiplies and adds in this association (g4s_knn_mean_dist's distance).  A candidate whose d is NaN
+ *   or +inf never wins.  dist2_out[q] = the smallest d, index_out[q] = the smallest j that attains it; if no candidate
+ *   is finite -- which includes a query with a non-finite coordinate -- FLT_MAX and -1.  The minimum and the tie rule are
+ *   properties of the two clouds, so every exact search returns these bits.  n_query == 0 succeeds without a launch;
+ *   n_ref <= 0 is an error (there is nothing to be nearest to).
+ * B. Voxel down-sample (open3d's VoxelDownSample, with a defined order), two-phase.  lo = the per-axis minimum of the
+ *   cloud minus voxel_size / 2, in float32.  Cell of a coordinate p: floor(((double)p - (double)lo) / (double)voxel_size),
+ *   all in float64.  An output point is the sum of its voxel's points in float64 in ascending input index, divided by
+ *   their count, rounded once to float32.  Voxels come out in ascending (cz, cy, cx).  count: *n_voxels (host int; one
+ *   host synchronisation); emit, same n, points and workspace, the workspace untouched in between: points_out
+ *   [n_voxels,3]; nothing is written beyond n_voxels.  Limit: with cells_a = the cell of the axis maximum + 1, the product
+ *   cells_x cells_y cells_z - 1 and n - 1 must together fit 64 bits (cell bits + index bits <= 64), otherwise count
+ *   returns G4S_ERR_INVALID_ARGUMENT and says so; so does a non-finite point (checked on the device, reported by count)
+ *   and a voxel_size that is not finite and positive.  One thread sums a voxel: a cloud inside one voxel is summed
+ *   serially.
+ * C. Surface sampling (trimesh's sample_surface and face_normals, the random numbers passed in).  u [n_samples,3] float32
+ *   in [0,1), cum_area [n_triangles] float64 = the inclusive running sum of the face areas (the caller's; non-decreasing).
+ *   face = min(#{i : cum_area[i] <= (double)u0 * cum_area[n_triangles - 1]}, n_triangles - 1), i.e. searchsorted with
+ *   side = 'right': a face of zero area is never chosen.  a = u1, b = u2; if a + b > 1 (float32): a = 1 - a, b = 1 - b.
+ *   point = v0 + (a * (v1 - v0) + b * (v2 - v0)) in float32, this association, no contraction.  normal = c / len with
+ *   c = (v1 - v0) x (v2 - v0) (each component one product minus the other) and len = sqrtf((cx^2 + cy^2) + cz^2); len == 0
+ *   gives a zero normal.  A face that names a vertex outside [0, n_vertices) gives a NaN point and a zero normal.
+ * Differences from the reference's libraries: points are float32 (open3d and trimesh work in float64); the down-sample
+ * has an order (open3d's is a hash map's); the random numbers are the caller's, not numpy's global state; the sampler
+ * uses side = 'right'; an empty reference cloud is an error (the reference returns NaN figures).
+ * Every argument is checked on the host before anything is launched.
+ */
+
+/* Bytes of device workspace of g4s_nn_search: the reference cloud's tree and the queries' curve order. */
+size_t g4s_nn_workspace(int n_ref, int n_query);
+
+/* dist2_out [n_query] float32, index_out [n_query] int32. */
+int g4s_nn_search(int n_ref, const float* ref, int n_query, const float* query, float* dist2_out, int* index_out,
+                  char* workspace, size_t workspace_bytes, void* stream);
+
+size_t g4s_voxel_downsample_workspace(int n);
+
+int g4s_voxel_downsample_count(int n, const float* points, float voxel_size, int* n_voxels, char* workspace,
+                               size_t workspace_bytes, void* stream);
+
+int g4s_voxel_downsample_emit(int n, const float* points, int n_voxels, float* points_out, char* workspace,
+                              size_t workspace_bytes, void* stream);
+
+/* points_out, normals_out [n_samples,3] float32, face_out [n_samples] int32. */
+int g4s_mesh_sample_surface(int n_samples, const float* u, const double* cum_area, int n_triangles, const int* triangles,
+                            int n_vertices, const float* vertices, float* points_out, float* normals_out, int* face_out,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif
