@@ -1,5 +1,6 @@
-// What two or more of the mesh units (tsdf.hip, unbounded.hip, tetra.hip, mesh_ops.hip) share: the argument checks of their entry
-// points, the read-back of the two scan totals, and the index arithmetic of the marching-cubes table (tsdf_mc_table.h).
+// What two or more of the mesh units (tsdf.hip, unbounded.hip, tetra.hip, mesh_ops.hip, mesh_eval.hip) share: the argument
+// checks of their entry points, the read-back of the two scan totals, and the index arithmetic of the marching-cubes table
+// (tsdf_mc_table.h).  What only the two view-stack fields share is in view_stack.h.
 #pragma once
 #include <math.h>
 

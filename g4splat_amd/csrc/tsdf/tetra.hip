@@ -3,7 +3,8 @@
 //
 // Point TSDF:  one thread per point, the whole view stack in one loop with the running mean (tsdf, w, colour) in
 // registers; the view records (two matrices, size, map pointers) sit in a device table indexed by the loop counter alone,
-// which makes every read of them wave-uniform -- the design of unbounded.hip with the reference's AdaptiveTSDF update.
+// which makes every read of them wave-uniform.  The record's tail, the bilinear tap, the staging of the table and the
+// point kernel are view_stack.h's, shared with unbounded.hip; the update is the reference's AdaptiveTSDF.
 // Bisection:  one thread per crossing edge runs all steps; every step is the same __device__ view loop at the midpoint, so
 // one launch stands for the reference's eight render-and-integrate passes over the view stack.
 // Marching tetrahedra:  per tet the numbers of crossing edges and triangles -> fixed-order exclusive scans (scan.h) ->
@@ -13,25 +14,23 @@
 // runs are bit-identical.
 #include <math.h>
 
-#include <vector>
-
 #include "../g4s_internal.h"
 #include "../g4s_device.h"
 #include "../../../include/g4s_render_maps.h"
 #include "mesh_common.h"
 #include "scan.h"
 #include "tsdf_mtet_table.h"
+#include "view_stack.h"
 
 namespace g4s {
 
 // One view of the stack as the kernels read it (152 bytes; the table is an array of these in the workspace).
 struct AtsdfView {
-    float wv[16];        // world_view_transform, row-major, used as row-vector @ M
-    float pm[16];        // projection_matrix, likewise
-    int W, H;
-    const float* depth;  // [H,W]
-    const float* rgb;    // [3,H,W] or NULL (no colour output)
+    float wv[16];  // world_view_transform, row-major, used as row-vector @ M
+    float pm[16];  // projection_matrix, likewise
+    ViewMaps maps;
 };
+static_assert(sizeof(AtsdfView) == 152, "g4s_atsdf_workspace is stated in records of 152 bytes");
 
 struct AtsdfParams {
     float trunc, znear, zfar;
@@ -64,18 +63,11 @@ __device__ __forceinline__ void atsdf_view(AtsdfPoint& s, const AtsdfView& v, co
     const float q1 = ((v0 * P[1] + v1 * P[5]) + z * P[9]) + P[13];
     const float q3 = ((v0 * P[3] + v1 * P[7]) + z * P[11]) + P[15];
     const float qw = q3 > a.znear ? q3 : a.znear;  // clamp_min; a NaN q3 becomes znear, and the view is still rejected: ix, iy or z is NaN then
-    const int W = v.W, H = v.H;
+    const int W = v.maps.W, H = v.maps.H;
     const float ix = ((1.0f + q0 / qw) * (float)W) / 2.0f, iy = ((1.0f + q1 / qw) * (float)H) / 2.0f;
     if (!(ix >= 0.0f && ix <= (float)(W - 1) && iy >= 0.0f && iy <= (float)(H - 1) && z > a.znear && z < a.zfar)) return;
-    const float fx0 = floorf(ix), fy0 = floorf(iy);
-    // 0 <= ix <= W-1 was tested; the clamps never change a value and keep every tap inside the map
-    const int x0 = imin_(imax_((int)fx0, 0), W - 1), y0 = imin_(imax_((int)fy0, 0), H - 1);
-    const int x1 = imin_(x0 + 1, W - 1), y1 = imin_(y0 + 1, H - 1);
-    const float fx = ix - fx0, fy = iy - fy0;
-    const float w00 = (1.0f - fx) * (1.0f - fy), w10 = fx * (1.0f - fy), w01 = (1.0f - fx) * fy, w11 = fx * fy;
-    const size_t i00 = (size_t)y0 * W + x0, i10 = (size_t)y0 * W + x1, i01 = (size_t)y1 * W + x0, i11 = (size_t)y1 * W + x1;
-    const float* D = v.depth;
-    const float d = ((D[i00] * w00 + D[i10] * w10) + D[i01] * w01) + D[i11] * w11;
+    const ViewTap tap(ix, iy, W, H);
+    const float d = tap.blend(v.maps.depth);
     const float diff = d - z;
     if (!(d > 0.0f && diff >= -a.trunc)) return;
     const float dist = fminf(diff / a.trunc, 1.0f);
@@ -85,8 +77,7 @@ __device__ __forceinline__ void atsdf_view(AtsdfPoint& s, const AtsdfView& v, co
         const size_t plane = (size_t)W * H;
 #pragma unroll
         for (int c = 0; c < 3; c++) {
-            const float* C = v.rgb + c * plane;
-            const float sc = ((C[i00] * w00 + C[i10] * w10) + C[i01] * w01) + C[i11] * w11;
+            const float sc = tap.blend(v.maps.rgb + c * plane);
             s.col[c] = fminf(fmaxf((s.col[c] * s.w + sc) / w1, 0.0f), 1.0f);
         }
     }
@@ -102,21 +93,15 @@ __device__ __forceinline__ float atsdf_at(float x, float y, float z, const Atsdf
     return s.tsdf;
 }
 
-template <bool RGB>
-__global__ void __launch_bounds__(256) atsdf_sample_kernel(int n, const float* __restrict__ points,
-                                                           const AtsdfView* __restrict__ views, int n_views, AtsdfParams a,
-                                                           float* __restrict__ tsdf, float* __restrict__ colour) {
-    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (i >= n) return;
-    AtsdfPoint s;
-    atsdf_init(s, points[3 * (size_t)i], points[3 * (size_t)i + 1], points[3 * (size_t)i + 2]);
-    for (int v = 0; v < n_views; v++) atsdf_view<RGB>(s, views[v], a);
-    if (tsdf != nullptr) tsdf[i] = s.tsdf;
-    if (RGB) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) colour[3 * (size_t)i + c] = s.col[c];
-    }
-}
+// the field as view_stack.h's point kernel takes it
+struct AtsdfField {
+    using View = AtsdfView;
+    using Point = AtsdfPoint;
+    using Params = AtsdfParams;
+    static __device__ __forceinline__ void init(Point& s, float x, float y, float z, const Params&) { atsdf_init(s, x, y, z); }
+    template <bool RGB>
+    static __device__ __forceinline__ void view(Point& s, const View& v, const Params& a) { atsdf_view<RGB>(s, v, a); }
+};
 
 __global__ void __launch_bounds__(256) atsdf_bisect_kernel(int n_edges, const int* __restrict__ edges, int n_points,
                                                            const float* __restrict__ points, const float* __restrict__ sdf,
@@ -297,35 +282,17 @@ int check_params(float trunc, float znear, float zfar, AtsdfParams* a) {
     return G4S_OK;
 }
 
-// checks the view stack, builds the table on the host and copies it into the workspace
-int stage_views(int n_views, const float* world_view, const float* projection, const int* sizes, const float* const* depth,
+// the view table of this field in the workspace (view_stack.h)
+int atsdf_table(int n_views, const float* world_view, const float* projection, const int* sizes, const float* const* depth,
                 const float* const* rgb, bool need_rgb, char* workspace, size_t workspace_bytes, hipStream_t stream,
                 const AtsdfView** table) {
-    if (n_views < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "n_views must not be negative");
-    *table = nullptr;
-    if (n_views == 0) return G4S_OK;
-    if (!world_view || !projection || !sizes || !depth || (need_rgb && !rgb)) return null_pointer();
-    if (check_workspace(workspace, workspace_bytes, g4s_atsdf_workspace(n_views)) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
-    std::vector<AtsdfView> host((size_t)n_views);
-    for (int v = 0; v < n_views; v++) {
-        AtsdfView& u = host[(size_t)v];
-        u.W = sizes[2 * v];
-        u.H = sizes[2 * v + 1];
-        if (u.W <= 0 || u.H <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "view %d: width, height must be positive", v);
-        if (!depth[v] || (need_rgb && !rgb[v])) return fail(G4S_ERR_INVALID_ARGUMENT, "view %d: NULL map pointer", v);
-        for (int i = 0; i < 16; i++) {
-            u.wv[i] = world_view[16 * (size_t)v + i];
-            u.pm[i] = projection[16 * (size_t)v + i];
-        }
-        u.depth = depth[v];
-        u.rgb = need_rgb ? rgb[v] : nullptr;
-    }
-    AtsdfView* dev = (AtsdfView*)align_ptr(workspace);
-    hipError_t e = hipMemcpyAsync(dev, host.data(), host.size() * sizeof(AtsdfView), hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);  // `host` dies with this frame
-    if (e != hipSuccess) return fail(G4S_ERR_HIP, "atsdf view table: %s", hipGetErrorString(e));
-    *table = dev;
-    return G4S_OK;
+    return stage_views("atsdf", n_views, world_view && projection, sizes, depth, rgb, need_rgb, workspace, workspace_bytes,
+                       stream, table, [=](AtsdfView& u, int v) {
+                           for (int i = 0; i < 16; i++) {
+                               u.wv[i] = world_view[16 * (size_t)v + i];
+                               u.pm[i] = projection[16 * (size_t)v + i];
+                           }
+                       });
 }
 
 int check_mtet(int n_points, int n_tets, const int* tets) {
@@ -344,7 +311,7 @@ int key_bits(int n_points) {  // bits of the largest point index
 }  // namespace
 
 extern "C" size_t g4s_atsdf_workspace(int n_views) {
-    return (n_views > 0 ? (size_t)n_views * sizeof(AtsdfView) : 0) + 256;  // + alignment of the base pointer
+    return view_table_bytes<AtsdfView>(n_views);
 }
 
 extern "C" int g4s_atsdf_sample(int n_points, const float* points, float trunc_margin, float znear, float zfar, int n_views,
@@ -358,17 +325,11 @@ extern "C" int g4s_atsdf_sample(int n_points, const float* points, float trunc_m
     if (check_params(trunc_margin, znear, zfar, &a) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     if (n_points > 0 && (!points || (!tsdf && !colour))) return null_pointer();
     const AtsdfView* table;
-    const int rc = stage_views(n_views, world_view, projection, sizes, depth, rgb, colour != nullptr, workspace,
+    const int rc = atsdf_table(n_views, world_view, projection, sizes, depth, rgb, colour != nullptr, workspace,
                                workspace_bytes, stream, &table);
     if (rc != G4S_OK) return rc;
     if (n_points == 0) return G4S_OK;
-    const dim3 grid(((unsigned)n_points + 255u) / 256u);
-    if (colour)
-        hipLaunchKernelGGL(atsdf_sample_kernel<true>, grid, dim3(256), 0, stream, n_points, points, table, n_views, a, tsdf,
-                           colour);
-    else
-        hipLaunchKernelGGL(atsdf_sample_kernel<false>, grid, dim3(256), 0, stream, n_points, points, table, n_views, a, tsdf,
-                           colour);
+    launch_point_sample<AtsdfField>(n_points, points, table, n_views, a, tsdf, colour, stream);
     return finish(hipSuccess, "atsdf sample");
 }
 
@@ -384,7 +345,7 @@ extern "C" int g4s_atsdf_bisect(int n_edges, const int* edges, int n_points, con
     if (check_params(trunc_margin, znear, zfar, &a) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     if (n_edges > 0 && (!edges || !vertices || (n_points > 0 && (!points || !sdf)))) return null_pointer();
     const AtsdfView* table;
-    const int rc = stage_views(n_views, world_view, projection, sizes, depth, nullptr, false, workspace, workspace_bytes,
+    const int rc = atsdf_table(n_views, world_view, projection, sizes, depth, nullptr, false, workspace, workspace_bytes,
                                stream, &table);
     if (rc != G4S_OK) return rc;
     if (n_edges == 0) return G4S_OK;

@@ -5,14 +5,13 @@
 // lattice is generated in the kernel and written exactly once.  A wave64 owns a 4x4x4 micro-brick of lattice points, so
 // its 256 bilinear taps per view fall into a footprint of a few pixels; the view records (matrix, size, map pointers)
 // sit in a device table indexed by the loop counter alone, which makes every read of them wave-uniform.  The explicit
-// point kernel (vertex colours, probes) runs the same __device__ functions on points read from memory.
+// point kernel (vertex colours, probes) runs the same __device__ functions on points read from memory.  The record's
+// tail, the bilinear tap, the staging of the table and the point kernel are view_stack.h's, shared with tetra.hip.
 // Dense cubes:  one thread per lattice point in storage order (x fastest), 256 consecutive points per workgroup: count
 // (owned-edge mask and in-workgroup vertex prefix per point, vertex / triangle totals per workgroup) -> fixed-order
 // exclusive scans of the per-workgroup totals (scan.h) -> [host: sizes] -> emit.  No atomics: every output position is a
 // scan result, so two runs are bit-identical.
 #include <math.h>
-
-#include <vector>
 
 #include "../g4s_internal.h"
 #include "../g4s_device.h"
@@ -20,16 +19,16 @@
 #include "mesh_common.h"
 #include "scan.h"
 #include "tsdf_mc_table.h"
+#include "view_stack.h"
 
 namespace g4s {
 
 // One view of the stack as the kernels read it (88 bytes; the table is an array of these in the workspace).
 struct UtsdfView {
-    float m[16];         // full_proj_transform, row-major, used as row-vector @ M
-    int W, H;
-    const float* depth;  // [H,W]
-    const float* rgb;    // [3,H,W] or NULL (no colour output)
+    float m[16];  // full_proj_transform, row-major, used as row-vector @ M
+    ViewMaps maps;
 };
+static_assert(sizeof(UtsdfView) == 88, "g4s_utsdf_workspace is stated in records of 88 bytes");
 
 struct UtsdfFrame {      // contracted space -> world
     float cx, cy, cz, radius, voxel_size;
@@ -79,17 +78,10 @@ __device__ __forceinline__ void utsdf_view(UtsdfPoint& s, const UtsdfView& v) {
     const float z = ((s.p[0] * M[3] + s.p[1] * M[7]) + s.p[2] * M[11]) + M[15];
     const float px = h0 / z, py = h1 / z;
     if (!(px > -1.0f && px < 1.0f && py > -1.0f && py < 1.0f && z > 0.0f)) return;
-    const int W = v.W, H = v.H;
-    const float ix = ((px + 1.0f) / 2.0f) * (float)(W - 1), iy = ((py + 1.0f) / 2.0f) * (float)(H - 1);
-    const float fx0 = floorf(ix), fy0 = floorf(iy);
-    // 0 <= ix <= W-1 follows from -1 < px < 1; the clamps never change a value and keep every tap inside the map
-    const int x0 = imin_(imax_((int)fx0, 0), W - 1), y0 = imin_(imax_((int)fy0, 0), H - 1);
-    const int x1 = imin_(x0 + 1, W - 1), y1 = imin_(y0 + 1, H - 1);
-    const float fx = ix - fx0, fy = iy - fy0;
-    const float w00 = (1.0f - fx) * (1.0f - fy), w10 = fx * (1.0f - fy), w01 = (1.0f - fx) * fy, w11 = fx * fy;
-    const size_t i00 = (size_t)y0 * W + x0, i10 = (size_t)y0 * W + x1, i01 = (size_t)y1 * W + x0, i11 = (size_t)y1 * W + x1;
-    const float* D = v.depth;
-    const float d = ((D[i00] * w00 + D[i10] * w10) + D[i01] * w01) + D[i11] * w11;
+    const int W = v.maps.W, H = v.maps.H;
+    // 0 <= ix <= W-1 follows from -1 < px < 1
+    const ViewTap tap(((px + 1.0f) / 2.0f) * (float)(W - 1), ((py + 1.0f) / 2.0f) * (float)(H - 1), W, H);
+    const float d = tap.blend(v.maps.depth);
     const float sdf = d - z;
     if (!(sdf > -s.T)) return;
     const float t = fminf(1.0f, fmaxf(-1.0f, sdf / s.T));
@@ -99,8 +91,7 @@ __device__ __forceinline__ void utsdf_view(UtsdfPoint& s, const UtsdfView& v) {
         const size_t plane = (size_t)W * H;
 #pragma unroll
         for (int c = 0; c < 3; c++) {
-            const float* C = v.rgb + c * plane;
-            const float sc = ((C[i00] * w00 + C[i10] * w10) + C[i01] * w01) + C[i11] * w11;
+            const float sc = tap.blend(v.maps.rgb + c * plane);
             s.col[c] = (s.col[c] * s.w + sc) / w1;
         }
     }
@@ -126,21 +117,17 @@ __global__ void __launch_bounds__(256) utsdf_grid_kernel(int N, float R, float h
     tsdf[(size_t)i + (size_t)N * ((size_t)j + (size_t)N * (size_t)k)] = s.tsdf;
 }
 
-template <bool RGB>
-__global__ void __launch_bounds__(256) utsdf_sample_kernel(int n, const float* __restrict__ points, int contracted,
-                                                           UtsdfFrame f, const UtsdfView* __restrict__ views, int n_views,
-                                                           float* __restrict__ tsdf, float* __restrict__ colour) {
-    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (i >= n) return;
-    UtsdfPoint s;
-    utsdf_init(s, contracted != 0, points[3 * (size_t)i], points[3 * (size_t)i + 1], points[3 * (size_t)i + 2], f);
-    for (int v = 0; v < n_views; v++) utsdf_view<RGB>(s, views[v]);
-    if (tsdf != nullptr) tsdf[i] = s.tsdf;
-    if (RGB) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) colour[3 * (size_t)i + c] = s.col[c];
+// the field as view_stack.h's point kernel takes it
+struct UtsdfField {
+    using View = UtsdfView;
+    using Point = UtsdfPoint;
+    struct Params { UtsdfFrame f; int contracted; };
+    static __device__ __forceinline__ void init(Point& s, float y0, float y1, float y2, const Params& a) {
+        utsdf_init(s, a.contracted != 0, y0, y1, y2, a.f);
     }
-}
+    template <bool RGB>
+    static __device__ __forceinline__ void view(Point& s, const View& v, const Params&) { utsdf_view<RGB>(s, v); }
+};
 
 // ---------------------------------------------------------------------------------------------------------------------
 // dense marching cubes
@@ -297,37 +284,19 @@ int check_frame(const float* center, float radius, float voxel_size, bool need_f
     return G4S_OK;
 }
 
-// checks the view stack, builds the table on the host and copies it into the workspace
-int stage_views(int n_views, const float* full_proj, const int* sizes, const float* const* depth, const float* const* rgb,
+// the view table of this field in the workspace (view_stack.h)
+int utsdf_table(int n_views, const float* full_proj, const int* sizes, const float* const* depth, const float* const* rgb,
                 bool need_rgb, char* workspace, size_t workspace_bytes, hipStream_t stream, const UtsdfView** table) {
-    if (n_views < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "n_views must not be negative");
-    *table = nullptr;
-    if (n_views == 0) return G4S_OK;
-    if (!full_proj || !sizes || !depth || (need_rgb && !rgb)) return null_pointer();
-    if (check_workspace(workspace, workspace_bytes, g4s_utsdf_workspace(n_views)) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
-    std::vector<UtsdfView> host((size_t)n_views);
-    for (int v = 0; v < n_views; v++) {
-        UtsdfView& u = host[(size_t)v];
-        u.W = sizes[2 * v];
-        u.H = sizes[2 * v + 1];
-        if (u.W <= 0 || u.H <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "view %d: width, height must be positive", v);
-        if (!depth[v] || (need_rgb && !rgb[v])) return fail(G4S_ERR_INVALID_ARGUMENT, "view %d: NULL map pointer", v);
-        for (int i = 0; i < 16; i++) u.m[i] = full_proj[16 * (size_t)v + i];
-        u.depth = depth[v];
-        u.rgb = need_rgb ? rgb[v] : nullptr;
-    }
-    UtsdfView* dev = (UtsdfView*)align_ptr(workspace);
-    hipError_t e = hipMemcpyAsync(dev, host.data(), host.size() * sizeof(UtsdfView), hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);  // `host` dies with this frame
-    if (e != hipSuccess) return fail(G4S_ERR_HIP, "utsdf view table: %s", hipGetErrorString(e));
-    *table = dev;
-    return G4S_OK;
+    return stage_views("utsdf", n_views, full_proj != nullptr, sizes, depth, rgb, need_rgb, workspace, workspace_bytes, stream,
+                       table, [=](UtsdfView& u, int v) {
+                           for (int i = 0; i < 16; i++) u.m[i] = full_proj[16 * (size_t)v + i];
+                       });
 }
 
 }  // namespace
 
 extern "C" size_t g4s_utsdf_workspace(int n_views) {
-    return (n_views > 0 ? (size_t)n_views * sizeof(UtsdfView) : 0) + 256;  // + alignment of the base pointer
+    return view_table_bytes<UtsdfView>(n_views);
 }
 
 extern "C" int g4s_utsdf_grid(int n, float half_extent, const float* center, float radius, float voxel_size, int n_views,
@@ -341,7 +310,7 @@ extern "C" int g4s_utsdf_grid(int n, float half_extent, const float* center, flo
     if (check_frame(center, radius, voxel_size, true, &f) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     if (!tsdf) return null_pointer();
     const UtsdfView* table;
-    const int rc = stage_views(n_views, full_proj, sizes, depth, nullptr, false, workspace, workspace_bytes, stream, &table);
+    const int rc = utsdf_table(n_views, full_proj, sizes, depth, nullptr, false, workspace, workspace_bytes, stream, &table);
     if (rc != G4S_OK) return rc;
     const float h = (2.0f * half_extent) / (float)(n - 1);
     hipLaunchKernelGGL(utsdf_grid_kernel, dim3((n + 15) / 16, (n + 3) / 4, (n + 3) / 4), dim3(256), 0, stream, n, half_extent, h,
@@ -360,17 +329,11 @@ extern "C" int g4s_utsdf_sample(int n_points, const float* points, int contracte
     if (check_frame(center, radius, voxel_size, contracted != 0, &f) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     if (n_points > 0 && (!points || (!tsdf && !colour))) return null_pointer();
     const UtsdfView* table;
-    const int rc = stage_views(n_views, full_proj, sizes, depth, rgb, colour != nullptr, workspace, workspace_bytes, stream,
+    const int rc = utsdf_table(n_views, full_proj, sizes, depth, rgb, colour != nullptr, workspace, workspace_bytes, stream,
                                &table);
     if (rc != G4S_OK) return rc;
     if (n_points == 0) return G4S_OK;
-    const dim3 grid((n_points + 255) / 256);
-    if (colour)
-        hipLaunchKernelGGL(utsdf_sample_kernel<true>, grid, dim3(256), 0, stream, n_points, points, contracted, f, table,
-                           n_views, tsdf, colour);
-    else
-        hipLaunchKernelGGL(utsdf_sample_kernel<false>, grid, dim3(256), 0, stream, n_points, points, contracted, f, table,
-                           n_views, tsdf, colour);
+    launch_point_sample<UtsdfField>(n_points, points, table, n_views, UtsdfField::Params{f, contracted}, tsdf, colour, stream);
     return finish(hipSuccess, "utsdf sample");
 }
 

@@ -391,15 +391,18 @@ def filter_mesh(mesh, length_threshold=0.05):
     return _returned(compact_mesh(dm, keep), host)
 
 
-# ---- unbounded extraction (include/g4s_render_maps.h, "Unbounded TSDF and dense marching cubes"; csrc/tsdf/unbounded.hip)
+# ---- the view stack of the unbounded and the tetrahedral extraction (csrc/tsdf/view_stack.h)
 class _ViewStack:
-    """The host arrays the utsdf entry points take, and the device tensors they point into (kept alive here).
-    views: (camera or 4x4 full_proj_transform, depth [H,W] / [1,H,W], rgb [3,H,W] or None) per view, maps on `device`."""
+    """The host arrays the utsdf / atsdf entry points take, and the device tensors they point into (kept alive here).
+    views: (camera, depth [H,W] / [1,H,W], rgb [3,H,W] or None) per view, maps on `device`.  matrices(camera) gives the
+    n_matrices 4x4 the field reads per view; workspace names the entry point that sizes the view table."""
 
-    def __init__(self, views, device, need_rgb):
-        self.maps, proj, sizes, dptr, cptr = [], [], [], [], []
+    def __init__(self, views, device, need_rgb, n_matrices, matrices, workspace):
+        self.maps, sizes, dptr, cptr = [], [], [], []
+        mats = [[] for _ in range(n_matrices)]
         for cam, depth, rgb in views:
-            M = _to_np(getattr(cam, "full_proj_transform", cam)).astype(np.float32).reshape(16)
+            for m, M in zip(mats, matrices(cam)):
+                m.extend(np.asarray(_to_np(M), np.float32).reshape(16).tolist())
             depth = self._map(depth, device, "depth")
             if depth.dim() == 3 and depth.size(0) == 1:
                 depth = depth[0]
@@ -417,21 +420,31 @@ class _ViewStack:
                     raise RuntimeError(f"rgb must have shape {(3, H, W)} (got {tuple(rgb.shape)})")
                 self.maps.append(rgb)
                 cptr.append(rgb.data_ptr())
-            proj.extend(M.tolist())
             sizes.extend([W, H])
         self.n = len(dptr)
-        self.proj = (ctypes.c_float * max(len(proj), 1))(*proj)
         self.sizes = (ctypes.c_int * max(len(sizes), 1))(*sizes)
         self.depth = (ctypes.c_void_p * max(self.n, 1))(*dptr)
         self.rgb = (ctypes.c_void_p * max(self.n, 1))(*cptr) if need_rgb else None
-        nws = _lib.load().g4s_utsdf_workspace(self.n)
-        self.ws = torch.empty(nws, dtype=torch.uint8, device=device)
+        # the run of arguments every entry point has: n_views, the matrices, sizes, depth
+        self.head = [self.n] + [(ctypes.c_float * max(len(m), 1))(*m) for m in mats] + [self.sizes, self.depth]
+        self.ws = torch.empty(getattr(_lib.load(), workspace)(self.n), dtype=torch.uint8, device=device)
 
     @staticmethod
     def _map(t, device, name):
         if not isinstance(t, torch.Tensor) or t.device != device:
             raise RuntimeError(f"{name} must be a tensor on {device}")
         return t.detach().float()
+
+
+def _view_and_projection(cam):
+    Wv, Pm = (cam.world_view_transform, _projection_matrix(cam)) if hasattr(cam, "world_view_transform") else cam
+    return Wv, Pm
+
+
+# The two fields' (n_matrices, matrices, workspace) of _ViewStack.  In place of a camera the unbounded field takes the bare
+# 4x4 full_proj_transform and the adaptive one the pair (world_view_transform, projection_matrix) of 4x4.
+_UTSDF_VIEWS = (1, lambda cam: [getattr(cam, "full_proj_transform", cam)], "g4s_utsdf_workspace")
+_ATSDF_VIEWS = (2, _view_and_projection, "g4s_atsdf_workspace")
 
 
 def _hip_device(device):
@@ -441,24 +454,33 @@ def _hip_device(device):
     return torch.device("cuda", torch.cuda.current_device() if device.index is None else device.index)
 
 
-def unbounded_tsdf(points, views, center, radius, voxel_size, contracted=True, return_rgb=False):
-    """g4s_utsdf_sample: the running-mean TSDF of `views` (see _ViewStack) at explicit points [n,3] (a device tensor) --
-    points of the contracted, normalised space (contracted=True; center, radius map them to the world) or world points
-    (contracted=False).  Returns tsdf [n], and with return_rgb (tsdf, colour [n,3])."""
+def _device_points(points, what="points"):
     if not isinstance(points, torch.Tensor):
-        raise RuntimeError("points must be a tensor on a HIP device")
-    dev = _hip_device(points.device)
-    pts = points.detach().float().reshape(-1, 3).contiguous()
+        raise RuntimeError(f"{what} must be a tensor on a HIP device")
+    return _hip_device(points.device), points.detach().float().reshape(-1, 3).contiguous()
+
+
+def _sample_views(entry, field, points, views, return_rgb, *field_args):
+    """One g4s_*tsdf_sample call: tsdf [n] of `views` at points [n,3], and with return_rgb (tsdf, colour [n,3])."""
+    dev, pts = _device_points(points)
     n = pts.size(0)
-    stack = _ViewStack(views, dev, return_rgb)
+    stack = _ViewStack(views, dev, return_rgb, *field)
     tsdf = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
     col = torch.empty((max(n, 1), 3), dtype=torch.float32, device=dev) if return_rgb else None
     with torch.cuda.device(dev):
-        _lib.call("g4s_utsdf_sample", n, _lib.ptr(pts), int(bool(contracted)), _host_f32(_to_np(center)), float(radius),
-                  float(voxel_size), stack.n, stack.proj, stack.sizes, stack.depth, stack.rgb, _lib.ptr(tsdf), _lib.ptr(col),
+        _lib.call(entry, n, _lib.ptr(pts), *field_args, *stack.head, stack.rgb, _lib.ptr(tsdf), _lib.ptr(col),
                   _lib.ptr(stack.ws), stack.ws.numel(), _lib.stream(dev))
         torch.cuda.current_stream(dev).synchronize()  # the stack's tensors may go once the kernel has run
     return (tsdf[:n], col[:n]) if return_rgb else tsdf[:n]
+
+
+# ---- unbounded extraction (include/g4s_render_maps.h, "Unbounded TSDF and dense marching cubes"; csrc/tsdf/unbounded.hip)
+def unbounded_tsdf(points, views, center, radius, voxel_size, contracted=True, return_rgb=False):
+    """g4s_utsdf_sample: the running-mean TSDF of `views` (see _UTSDF_VIEWS) at explicit points [n,3] (a device tensor) --
+    points of the contracted, normalised space (contracted=True; center, radius map them to the world) or world points
+    (contracted=False).  Returns tsdf [n], and with return_rgb (tsdf, colour [n,3])."""
+    return _sample_views("g4s_utsdf_sample", _UTSDF_VIEWS, points, views, return_rgb, int(bool(contracted)),
+                         _host_f32(_to_np(center)), float(radius), float(voxel_size))
 
 
 def unbounded_tsdf_grid(resolution, R, views, center, radius, voxel_size, device=None):
@@ -468,11 +490,11 @@ def unbounded_tsdf_grid(resolution, R, views, center, radius, voxel_size, device
     N = int(resolution)
     if N < 2 or N ** 3 >= 2 ** 31:
         raise ValueError("resolution must be at least 2 and resolution^3 below 2^31")
-    stack = _ViewStack(views, dev, False)
+    stack = _ViewStack(views, dev, False, *_UTSDF_VIEWS)
     tsdf = torch.empty(N ** 3, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        _lib.call("g4s_utsdf_grid", N, float(R), _host_f32(_to_np(center)), float(radius), float(voxel_size), stack.n,
-                  stack.proj, stack.sizes, stack.depth, _lib.ptr(tsdf), _lib.ptr(stack.ws), stack.ws.numel(), _lib.stream(dev))
+        _lib.call("g4s_utsdf_grid", N, float(R), _host_f32(_to_np(center)), float(radius), float(voxel_size), *stack.head,
+                  _lib.ptr(tsdf), _lib.ptr(stack.ws), stack.ws.numel(), _lib.stream(dev))
         torch.cuda.current_stream(dev).synchronize()
     return tsdf
 
@@ -507,68 +529,35 @@ def dense_marching_cubes(tsdf, R, center, radius, max_range=32.0, to_host=True):
 
 
 # ---- tetrahedral extraction (include/g4s_render_maps.h, "Adaptive TSDF at points and marching tetrahedra"; csrc/tsdf/tetra.hip)
-class _PointViewStack:
-    """The host arrays the atsdf entry points take, and the device tensors they point into (kept alive here).
-    views: (camera or (world_view_transform, projection_matrix) pair of 4x4, depth [H,W] / [1,H,W], rgb [3,H,W] or None)
-    per view, maps on `device`."""
-
-    def __init__(self, views, device, need_rgb):
-        self.maps, wv, pm, sizes, dptr, cptr = [], [], [], [], [], []
-        for cam, depth, rgb in views:
-            if hasattr(cam, "world_view_transform"):
-                Wv, Pm = _to_np(cam.world_view_transform), _projection_matrix(cam)
-            else:
-                Wv, Pm = (_to_np(m) for m in cam)
-            depth = _ViewStack._map(depth, device, "depth")
-            if depth.dim() == 3 and depth.size(0) == 1:
-                depth = depth[0]
-            if depth.dim() != 2:
-                raise RuntimeError(f"depth must be [H,W] or [1,H,W] (got {tuple(depth.shape)})")
-            H, W = depth.shape
-            depth = depth.contiguous()
-            self.maps.append(depth)
-            dptr.append(depth.data_ptr())
-            if need_rgb:
-                if rgb is None:
-                    raise RuntimeError("colours need the rgb map of every view")
-                rgb = _ViewStack._map(rgb, device, "rgb").contiguous()
-                if tuple(rgb.shape) != (3, H, W):
-                    raise RuntimeError(f"rgb must have shape {(3, H, W)} (got {tuple(rgb.shape)})")
-                self.maps.append(rgb)
-                cptr.append(rgb.data_ptr())
-            wv.extend(np.asarray(Wv, np.float32).reshape(16).tolist())
-            pm.extend(np.asarray(Pm, np.float32).reshape(16).tolist())
-            sizes.extend([W, H])
-        self.n = len(dptr)
-        self.wv = (ctypes.c_float * max(len(wv), 1))(*wv)
-        self.pm = (ctypes.c_float * max(len(pm), 1))(*pm)
-        self.sizes = (ctypes.c_int * max(len(sizes), 1))(*sizes)
-        self.depth = (ctypes.c_void_p * max(self.n, 1))(*dptr)
-        self.rgb = (ctypes.c_void_p * max(self.n, 1))(*cptr) if need_rgb else None
-        self.ws = torch.empty(_lib.load().g4s_atsdf_workspace(self.n), dtype=torch.uint8, device=device)
-
-
-def _device_points(points, what="points"):
-    if not isinstance(points, torch.Tensor):
-        raise RuntimeError(f"{what} must be a tensor on a HIP device")
-    return _hip_device(points.device), points.detach().float().reshape(-1, 3).contiguous()
-
-
 def adaptive_tsdf(points, views, trunc_margin, return_rgb=False, znear=1e-6, zfar=1e6):
-    """g4s_atsdf_sample: the running-mean TSDF of `views` (see _PointViewStack) at points [n,3] (a device tensor), with the
+    """g4s_atsdf_sample: the running-mean TSDF of `views` (see _ATSDF_VIEWS) at points [n,3] (a device tensor), with the
     default flags of the reference's AdaptiveTSDF.integrate (matcha/dm_extractors/adaptive_tsdf.py:162-339): a point no
     view accepts keeps -1.  Returns tsdf [n], and with return_rgb (tsdf, colour [n,3])."""
-    dev, pts = _device_points(points)
-    n = pts.size(0)
-    stack = _PointViewStack(views, dev, return_rgb)
-    tsdf = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
-    col = torch.empty((max(n, 1), 3), dtype=torch.float32, device=dev) if return_rgb else None
-    with torch.cuda.device(dev):
-        _lib.call("g4s_atsdf_sample", n, _lib.ptr(pts), float(trunc_margin), float(znear), float(zfar), stack.n, stack.wv,
-                  stack.pm, stack.sizes, stack.depth, stack.rgb, _lib.ptr(tsdf), _lib.ptr(col), _lib.ptr(stack.ws),
-                  stack.ws.numel(), _lib.stream(dev))
-        torch.cuda.current_stream(dev).synchronize()  # the stack's tensors may go once the kernel has run
-    return (tsdf[:n], col[:n]) if return_rgb else tsdf[:n]
+    return _sample_views("g4s_atsdf_sample", _ATSDF_VIEWS, points, views, return_rgb, float(trunc_margin), float(znear),
+                         float(zfar))
+
+
+def _index_rows(rows, width, name, shape, sdf, dev):
+    """With _point_sdf and _rows_in_range the checks of marching_tetrahedra and bisect_surface: rows as [m,width]."""
+    if not isinstance(rows, torch.Tensor) or not isinstance(sdf, torch.Tensor) or rows.device != dev or sdf.device != dev:
+        raise RuntimeError(f"{name} and sdf must be tensors on {dev}")
+    if rows.dtype.is_floating_point or rows.numel() % width:
+        raise RuntimeError(f"{name} must be an integer tensor {shape}")
+    return rows.detach().reshape(-1, width)
+
+
+def _point_sdf(sdf, n):
+    f = sdf.detach().float().reshape(-1).contiguous()
+    if f.numel() != n:
+        raise RuntimeError(f"sdf must hold one value per point ({f.numel()} for {n} points)")
+    return f
+
+
+def _rows_in_range(rows, name, n):
+    """rows as int32, every entry a point of [0, n)."""
+    if rows.size(0) > 0 and (int(rows.min()) < 0 or int(rows.max()) >= n):
+        raise RuntimeError(f"{name} name a point outside [0, {n})")
+    return rows.to(torch.int32).contiguous()
 
 
 def marching_tetrahedra(points, tets, sdf):
@@ -577,20 +566,12 @@ def marching_tetrahedra(points, tets, sdf):
     vertex i of the mesh lies on edge i --, faces [F,3] int32 in tet order).  No crossing: (0,2) and (0,3) tensors."""
     dev, pts = _device_points(points)
     n = pts.size(0)
-    if not isinstance(tets, torch.Tensor) or not isinstance(sdf, torch.Tensor) or tets.device != dev or sdf.device != dev:
-        raise RuntimeError(f"tets and sdf must be tensors on {dev}")
-    if tets.dtype.is_floating_point or tets.numel() % 4:
-        raise RuntimeError("tets must be an integer tensor [T,4]")
-    tets = tets.detach().reshape(-1, 4)
-    f = sdf.detach().float().reshape(-1).contiguous()
-    if f.numel() != n:
-        raise RuntimeError(f"sdf must hold one value per point ({f.numel()} for {n} points)")
+    tets = _index_rows(tets, 4, "tets", "[T,4]", sdf, dev)
+    f = _point_sdf(sdf, n)
     T = tets.size(0)
     if n >= 2 ** 31 or T > (2 ** 31 - 1) // 4:
         raise RuntimeError("marching tetrahedra takes fewer than 2^31 points and 2^29 tets")
-    if T > 0 and (int(tets.min()) < 0 or int(tets.max()) >= n):
-        raise RuntimeError(f"tets name a point outside [0, {n})")
-    tets = tets.to(torch.int32).contiguous()
+    tets = _rows_in_range(tets, "tets", n)
     if tets.data_ptr() % 16:  # a view at an odd offset: the kernels read a tet as one 16-byte row
         tets = tets.clone()
     lib = _lib.load()
@@ -613,26 +594,17 @@ def bisect_surface(points, edges, sdf, views, trunc_margin, steps=8, znear=1e-6,
     times against the field of `views`, all steps in one launch.  Returns vertices [E,3] on the device."""
     dev, pts = _device_points(points)
     n = pts.size(0)
-    if not isinstance(edges, torch.Tensor) or not isinstance(sdf, torch.Tensor) or edges.device != dev or sdf.device != dev:
-        raise RuntimeError(f"edges and sdf must be tensors on {dev}")
-    if edges.dtype.is_floating_point or edges.numel() % 2:
-        raise RuntimeError("edges must be an integer tensor [E,2]")
-    e = edges.detach().reshape(-1, 2)
+    e = _rows_in_range(_index_rows(edges, 2, "edges", "[E,2]", sdf, dev), "edges", n)
     E = e.size(0)
-    if E > 0 and (int(e.min()) < 0 or int(e.max()) >= n):
-        raise RuntimeError(f"edges name a point outside [0, {n})")
-    e = e.to(torch.int32).contiguous()
-    f = sdf.detach().float().reshape(-1).contiguous()
-    if f.numel() != n:
-        raise RuntimeError(f"sdf must hold one value per point ({f.numel()} for {n} points)")
+    f = _point_sdf(sdf, n)
     if not 0 <= int(steps) <= 64:
         raise ValueError("steps must be in 0 .. 64")
-    stack = _PointViewStack(views, dev, False)
+    stack = _ViewStack(views, dev, False, *_ATSDF_VIEWS)
     verts = torch.empty((max(E, 1), 3), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         _lib.call("g4s_atsdf_bisect", E, _lib.ptr(e), n, _lib.ptr(pts), _lib.ptr(f), int(steps), float(trunc_margin),
-                  float(znear), float(zfar), stack.n, stack.wv, stack.pm, stack.sizes, stack.depth, _lib.ptr(verts),
-                  _lib.ptr(stack.ws), stack.ws.numel(), _lib.stream(dev))
+                  float(znear), float(zfar), *stack.head, _lib.ptr(verts), _lib.ptr(stack.ws), stack.ws.numel(),
+                  _lib.stream(dev))
         torch.cuda.current_stream(dev).synchronize()
     return verts[:E]
 

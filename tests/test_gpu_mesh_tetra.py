@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import tetra_ref as tr
+import view_tap_ref
 from g4splat_amd import mesh as mesh_mod
 from g4splat_amd import ply_io, synthetic
 
@@ -30,13 +31,7 @@ def scene():
     """5 analytic views of the unit sphere, 64x48, and the same maps at half resolution; sample points around it."""
     full = [v[1:] for v in tr.sphere_views(64, 48, background=0.0, seed=7)]
     half = [(Wv, Pm, np.ascontiguousarray(d[::2, ::2]), np.ascontiguousarray(c[:, ::2, ::2])) for Wv, Pm, d, c in full]
-    rng = np.random.default_rng(31)
-    n = 257
-    pts = rng.uniform(-1.8, 1.8, (n, 3))
-    s = rng.normal(size=(n // 2, 3))
-    pts[: n // 2] = s / np.linalg.norm(s, axis=1, keepdims=True) * rng.uniform(0.9, 1.2, (n // 2, 1))
-    pts[-4:] = [(30.0, 0, 0), (0, -40.0, 3.0), (5.0, 5.0, 5.0), (0, 0, 9.0)]  # behind the cameras / outside every frustum
-    return SimpleNamespace(full=full, half=half, points=pts.astype(np.float32))
+    return SimpleNamespace(full=full, half=half, points=view_tap_ref.probe_points(257, 31))
 
 
 def _gpu_views(views, rgb=True):
@@ -68,6 +63,30 @@ def test_adaptive_tsdf_equals_the_restatement_bit_for_bit(hip_lib, scene, stack,
         # only where its ray meets the sphere and the point is at most trunc behind it, a small share of the points, so
         # the floors count per view -- every view accepts some points, and accepted-outside and unseen points both occur.
         assert (used.sum(0) >= 8).all() and (want_t > 0).sum() >= 8 and (want_t == -1).sum() >= 8
+
+
+def _cropped(view, rows, cols):
+    Wv, Pm, d, c = view
+    return Wv, Pm, np.ascontiguousarray(d[rows, cols]), np.ascontiguousarray(c[:, rows, cols])
+
+
+@pytest.mark.parametrize("crop,floor", [("two_columns", 7), ("two_rows", 7), ("two_by_two", 2), ("mixed", 7)])
+def test_adaptive_tsdf_on_maps_two_pixels_wide(hip_lib, scene, crop, floor):
+    """The tap at the border: in a map two pixels wide or high every accepted point has its lower corner on the first
+    pixel or exactly on the last, where the upper corner clamps.  (A map one pixel wide accepts nothing under
+    0 <= ix <= W-1.)  "mixed" puts a two-column view between two full ones: each view's own size is read."""
+    rows, cols = {"two_columns": (slice(None), slice(31, 33)), "two_rows": (slice(23, 25), slice(None)),
+                  "two_by_two": (slice(23, 25), slice(31, 33)), "mixed": (slice(None), slice(31, 33))}[crop]
+    views = [_cropped(v, rows, cols) for v in scene.full]
+    if crop == "mixed":
+        views = [scene.full[0], views[1], scene.full[2]]
+    want_t, want_c, used = tr.adaptive_tsdf(scene.points, views, TRUNC)
+    print(crop, "accepted per view:", used.sum(0))
+    assert (used.sum(0) >= floor).all()  # from the restatement alone
+    got = mesh_mod.adaptive_tsdf(_dev(scene.points), _gpu_views(views), TRUNC, return_rgb=True)
+    got_t, got_c = (o.cpu().numpy() for o in got)
+    assert np.array_equal(_bits(got_t), _bits(want_t)), np.abs(got_t - want_t).max()
+    assert np.array_equal(_bits(got_c), _bits(want_c)), np.abs(got_c - want_c).max()
 
 
 def _sphere_field(p, centre, radius):

@@ -11,6 +11,7 @@ import torch
 
 import tsdf_ref
 import unbounded_ref as ur
+import view_tap_ref
 from g4splat_amd import mesh as mesh_mod
 from g4splat_amd import ply_io, synthetic
 
@@ -59,6 +60,26 @@ def test_sample_equals_the_restatement_bit_for_bit(hip_lib, scene, contracted):
     assert np.array_equal(_bits(got_c), _bits(want_c)), np.abs(got_c - want_c).max()
     only_t = _gpu_sample(pts, scene.full, f, contracted, False)  # the kernel without colours: the same tsdf
     assert np.array_equal(_bits(only_t), _bits(want_t))
+
+
+@pytest.mark.parametrize("crop", ["one_column", "one_row", "one_pixel", "mixed"])
+def test_sample_on_maps_one_pixel_wide(hip_lib, scene, crop):
+    """The tap at the border: in a map of one column, one row or one pixel the upper corner always clamps onto the lower
+    one.  World mode with colours, 257 points about the scene.  "mixed" puts a one-column view between two full ones:
+    each view's own size is read."""
+    rows, cols = {"one_column": (slice(None), slice(32, 33)), "one_row": (slice(24, 25), slice(None)),
+                  "one_pixel": (slice(24, 25), slice(32, 33)), "mixed": (slice(None), slice(32, 33))}[crop]
+    views = [(M, np.ascontiguousarray(d[rows, cols]), np.ascontiguousarray(c[:, rows, cols]))
+             for M, d, c in scene.full]
+    if crop == "mixed":
+        views = [scene.full[0], views[1], scene.full[2]]
+    pts, f = view_tap_ref.probe_points(257, 31), scene.frame
+    want_t, want_c, _m, used = ur.sample(pts, views, f["center"], f["radius"], f["voxel_size"], False)
+    print(crop, "accepted per view:", used.sum(0))
+    assert (used.sum(0) >= 8).all()  # from the restatement alone
+    got_t, got_c = _gpu_sample(pts, views, f, False, True)
+    assert np.array_equal(_bits(got_t), _bits(want_t)), np.abs(got_t - want_t).max()
+    assert np.array_equal(_bits(got_c), _bits(want_c)), np.abs(got_c - want_c).max()
 
 
 def _stacks(scene):

@@ -14,6 +14,7 @@ SIZES = {
                            ((0, 0, 0, 1025), 2117376)],
     "g4s_dense_mc_workspace": [((1,), 0), ((2,), 2304), ((33,), 76032), ((257,), 35012608), ((1024,), 2214609664)],
     "g4s_utsdf_workspace": [((0,), 256), ((5,), 696)],
+    "g4s_atsdf_workspace": [((0,), 256), ((5,), 1016)],  # newer than that commit: 5 records of 152 bytes + 256
     "g4s_mesh_cluster_workspace": [((0,), 256), ((1,), 13056), ((171,), 26368), ((1000,), 106752), ((334000,), 27838208)],
     "g4s_mesh_compact_workspace": [((0, 0), 768), ((1, 1), 1792), ((500, 1000), 13056)],
     "g4s_knn_workspace": [((0,), 4096), ((1,), 6144), ((257,), 14336), ((100000,), 3308032)],

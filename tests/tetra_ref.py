@@ -13,6 +13,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import gen_mtet_table  # noqa: E402
+from view_tap_ref import bilinear, tap  # noqa: E402
 
 f32 = np.float32
 TET_EDGES = np.asarray(gen_mtet_table.EDGES)  # corner pairs of edge ids 0..5
@@ -24,10 +25,6 @@ def mtet_table():
     if _TABLE is None:
         _TABLE = gen_mtet_table.table()
     return _TABLE
-
-
-def _bilinear(img, x0, x1, y0, y1, w00, w10, w01, w11):
-    return ((img[y0, x0] * w00 + img[y0, x1] * w10) + img[y1, x0] * w01) + img[y1, x1] * w11
 
 
 def pixel_coordinates(points, view, znear=1e-6):
@@ -59,13 +56,8 @@ def adaptive_tsdf(points, views, trunc, znear=1e-6, zfar=1e6):
         with np.errstate(invalid="ignore"):
             ok = (ix >= 0) & (ix <= f32(W - 1)) & (iy >= 0) & (iy <= f32(H - 1)) & (z > zn) & (z < zf)
         idx = np.nonzero(ok)[0]
-        ixk, iyk = ix[idx], iy[idx]
-        fx0, fy0 = np.floor(ixk), np.floor(iyk)
-        x0, y0 = fx0.astype(np.int64), fy0.astype(np.int64)
-        x1, y1 = np.minimum(x0 + 1, W - 1), np.minimum(y0 + 1, H - 1)
-        fx, fy = ixk - fx0, iyk - fy0
-        w00, w10, w01, w11 = (f32(1) - fx) * (f32(1) - fy), fx * (f32(1) - fy), (f32(1) - fx) * fy, fx * fy
-        d = _bilinear(depth, x0, x1, y0, y1, w00, w10, w01, w11)
+        t4 = tap(ix[idx], iy[idx], W, H)
+        d = bilinear(depth, t4)
         diff = d - z[idx]
         with np.errstate(invalid="ignore"):
             keep = (d > 0) & (diff >= -T)
@@ -77,9 +69,8 @@ def adaptive_tsdf(points, views, trunc, znear=1e-6, zfar=1e6):
         tsdf[k] = (tsdf[k] * wk + dist) / w1
         if rgb is not None:
             rgb = np.asarray(rgb, f32)
-            sel = lambda a: a[keep]
             for c in range(3):
-                sc = _bilinear(rgb[c], sel(x0), sel(x1), sel(y0), sel(y1), sel(w00), sel(w10), sel(w01), sel(w11))
+                sc = bilinear(rgb[c], t4, keep)
                 col[k, c] = np.fmin(np.fmax((col[k, c] * wk + sc) / w1, f32(0)), f32(1))
         w[k] = w1
     return tsdf, col, used

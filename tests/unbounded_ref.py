@@ -10,6 +10,7 @@ A view is (M [4,4] full_proj_transform, depth [H,W], rgb [3,H,W] or None).
 import numpy as np
 
 import tsdf_ref
+from view_tap_ref import bilinear, tap
 
 f32 = np.float32
 
@@ -30,10 +31,6 @@ def point_state(y, contracted, center, radius, voxel_size, dtype=f32):
         p = u * r + c[None]
         T = np.where(m > 1, T * (ft(1) / (ft(2) - np.minimum(m, ft(1.9)))), T)
     return p.astype(ft), T.astype(ft)
-
-
-def _bilinear(img, x0, x1, y0, y1, w00, w10, w01, w11):
-    return ((img[y0, x0] * w00 + img[y0, x1] * w10) + img[y1, x0] * w01) + img[y1, x1] * w11
 
 
 def sample(points, views, center, radius, voxel_size, contracted, dtype=f32):
@@ -63,13 +60,10 @@ def sample(points, views, center, radius, voxel_size, contracted, dtype=f32):
         idx = np.nonzero(inside)[0]
         ix = ((px[idx] + ft(1)) / ft(2)) * ft(W - 1)
         iy = ((py[idx] + ft(1)) / ft(2)) * ft(H - 1)
-        fx0, fy0 = np.floor(ix), np.floor(iy)
-        x0, y0 = fx0.astype(np.int64), fy0.astype(np.int64)
+        t4 = tap(ix, iy, W, H)
+        x0, y0 = t4[0], t4[2]
         assert ((x0 >= 0) & (x0 <= W - 1) & (y0 >= 0) & (y0 <= H - 1)).all()
-        x1, y1 = np.minimum(x0 + 1, W - 1), np.minimum(y0 + 1, H - 1)
-        fx, fy = ix - fx0, iy - fy0
-        w00, w10, w01, w11 = (ft(1) - fx) * (ft(1) - fy), fx * (ft(1) - fy), (ft(1) - fx) * fy, fx * fy
-        d = _bilinear(depth, x0, x1, y0, y1, w00, w10, w01, w11)
+        d = bilinear(depth, t4)
         sdf = d - z[idx]
         Ti = T[idx]
         with np.errstate(invalid="ignore"):
@@ -85,9 +79,8 @@ def sample(points, views, center, radius, voxel_size, contracted, dtype=f32):
         tsdf[k] = (tsdf[k] * wk + t) / w1
         if rgb is not None:
             rgb = np.asarray(rgb, ft)
-            sel = lambda a: a[keep]
             for c in range(3):
-                sc = _bilinear(rgb[c], sel(x0), sel(x1), sel(y0), sel(y1), sel(w00), sel(w10), sel(w01), sel(w11))
+                sc = bilinear(rgb[c], t4, keep)
                 col[k, c] = (col[k, c] * wk + sc) / w1
         w[k] = w1
     return tsdf, col, margins, used
