@@ -1,7 +1,7 @@
-// extern "C" entry points of libg4s_hip.so (see include/g4s_rasterizer.h) and the host-side
-// sequencing of the kernels.  Mirrors Rasterizer::forward / ::backward / ::markVisible
-// (dsr/cuda_rasterizer/rasterizer_impl.cu:141-153,198-448) and SimpleKNN::knn
-// (knn/simple_knn.cu:185-221).
+// The rasterizer's extern "C" entry points (include/g4s_rasterizer.h) with the host-side sequencing of its kernels --
+// mirrors Rasterizer::forward / ::backward (dsr/cuda_rasterizer/rasterizer_impl.cu:198-448) -- and what every unit of
+// libg4s_hip.so shares (g4s_internal.h): the error path, the options, the per-kernel profiling, g4s_version.  Every
+// other entry point sits beside its kernels.
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -14,11 +14,6 @@
 #include "g4s_internal.h"
 
 using namespace g4s;
-
-extern "C" int g4s_knn_launch_internal(int P, const float* points, float* meanDists, char* workspace, hipStream_t s);
-extern "C" void g4s_maps_launch_internal(int fwd, int W, int H, float depth_ratio, const float* allmap, const float* wvt,
-                                         const float* fpt, float* cam, float* const* outs, const float* surf_depth_in,
-                                         const float* const* grads, float* g_allmap, hipStream_t s);
 
 namespace {
 thread_local char t_err[512] = "";  // behind g4s_last_error(); written here only
@@ -84,7 +79,6 @@ inline bool trace_on() {
     static const bool on = getenv("G4S_TRACE") != nullptr;
     return on;
 }
-inline bool misaligned(const void* p, size_t a) { return p != nullptr && ((size_t)p % a) != 0; }
 
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
@@ -92,19 +86,9 @@ inline bool misaligned(const void* p, size_t a) { return p != nullptr && ((size_
         if (_e != hipSuccess) return fail(G4S_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
     } while (0)
 
-// CHECK_CUDA of the reference (auxiliary.h:295-302): launch errors always, sync + check in debug.
-// G4S_TRACE=1 in the environment: synchronise after every stage and log it to stderr.
-#define CHECK_LAUNCH(what)                                                                          \
-    do {                                                                                            \
-        hipError_t _e = hipGetLastError();                                                          \
-        if (_e == hipSuccess && (debug || trace_on())) _e = hipStreamSynchronize(stream);           \
-        if (trace_on()) { fprintf(stderr, "[g4s] %s: %s\n", what, hipGetErrorString(_e)); fflush(stderr); } \
-        if (_e != hipSuccess) return fail(G4S_ERR_HIP, "%s: %s", what, hipGetErrorString(_e));      \
-    } while (0)
+#define CHECK_LAUNCH(what) do { if (int _rc = stage_done(what, stream, debug)) return _rc; } while (0)
 
 // ---- optional per-kernel timing with HIP events on the launch stream (bench.py roofline) ----
-enum ProfId { PF_PREPROCESS_FWD, PF_DEPTH_SORT, PF_COUNT_SCAN, PF_EMIT, PF_TILE_SORT, PF_TILE_RANGES, PF_BLEND_FWD,
-              PF_BLEND_BWD, PF_PREPROCESS_BWD, PF_MAPS_FWD, PF_MAPS_BWD, PF_PHOTO_LOSS, PF_ADAM, PF_GEO_REG, PF_COUNT };
 const char* const kProfNames[PF_COUNT] = {"preprocess_fwd", "depth_sort", "count_scan", "emit", "tile_sort",
                                           "tile_ranges",    "blend_fwd",  "blend_bwd",  "preprocess_bwd",
                                           "maps_fwd",       "maps_bwd",   "photometric_loss",
@@ -116,24 +100,6 @@ std::vector<ProfRec> g_prof;          // recorded (kernel group, start, stop)
 std::vector<hipEvent_t> g_prof_pool;  // events are created up front, never inside a timed region
 size_t g_prof_next = 0;
 constexpr size_t PROF_POOL = 16384;
-
-struct ProfScope {
-    int id; hipStream_t s; hipEvent_t a = nullptr, b = nullptr; bool on = false;
-    ProfScope(int id_, hipStream_t s_) : id(id_), s(s_) {
-        if (!g_prof_on) return;
-        std::lock_guard<std::mutex> lk(g_prof_mu);
-        if (g_prof_next + 2 > g_prof_pool.size()) return;  // pool exhausted: stop recording
-        a = g_prof_pool[g_prof_next++];
-        b = g_prof_pool[g_prof_next++];
-        on = hipEventRecord(a, s) == hipSuccess;
-    }
-    ~ProfScope() {
-        if (!on) return;
-        (void)hipEventRecord(b, s);
-        std::lock_guard<std::mutex> lk(g_prof_mu);
-        g_prof.push_back(ProfRec{id, a, b});
-    }
-};
 
 // Bits of the tile field the partition sorts on: the reference's getHigherMsb(tiles) (rasterizer_impl.cu:301), capped
 // at the 32 bits the field has.
@@ -206,6 +172,31 @@ struct BackwardCall {
     c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.debug = debug; c.stream = stream
 
 }  // namespace
+
+namespace g4s {
+// CHECK_CUDA of the reference (auxiliary.h:295-302): launch errors always, sync + check in debug.
+// G4S_TRACE=1 in the environment: synchronise after every stage and log it to stderr.
+int stage_done(const char* what, hipStream_t s, bool debug) {
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && (debug || trace_on())) e = hipStreamSynchronize(s);
+    if (trace_on()) { fprintf(stderr, "[g4s] %s: %s\n", what, hipGetErrorString(e)); fflush(stderr); }
+    return e == hipSuccess ? G4S_OK : fail(G4S_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+}
+ProfScope::ProfScope(int id_, hipStream_t s_) : id(id_), s(s_) {
+    if (!g_prof_on) return;
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    if (g_prof_next + 2 > g_prof_pool.size()) return;  // pool exhausted: stop recording
+    a = g_prof_pool[g_prof_next++];
+    b = g_prof_pool[g_prof_next++];
+    on = hipEventRecord(a, s) == hipSuccess;
+}
+ProfScope::~ProfScope() {
+    if (!on) return;
+    (void)hipEventRecord(b, s);
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    g_prof.push_back(ProfRec{id, a, b});
+}
+}  // namespace g4s
 
 extern "C" const char* g4s_last_error(void) { return t_err; }
 
@@ -759,351 +750,4 @@ extern "C" int g4s_rasterizer_backward_accumulate(
         viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix,
         dL_depths, dL_dmean2D, dL_dnormal, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dtransMat, dL_dsh_dc, dL_dsh_rest, dL_dscale,
         dL_drot, view_stats, first_view, /*packed=*/nullptr, workspace, workspace_bytes, after_event, debug, stream);
-}
-
-extern "C" int g4s_rasterizer_mark_visible(int P, const float* means3D, const float* viewmatrix,
-                                           const float* projmatrix, uint8_t* present, void* stream_) {
-    (void)projmatrix;
-    hipStream_t stream = (hipStream_t)stream_;
-    const int debug = 0;
-    t_err[0] = 0;
-    if (P < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "P < 0");
-    if (P == 0) return G4S_OK;
-    if (!means3D || !viewmatrix || !present) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL pointer");
-    launch_mark_visible(P, means3D, viewmatrix, present, stream);
-    CHECK_LAUNCH("mark_visible");
-    return G4S_OK;
-}
-
-extern "C" int g4s_knn_mean_dist(int P, const float* points, float* meanDists, char* workspace,
-                                 size_t workspace_bytes, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    const int debug = 0;
-    t_err[0] = 0;
-    if (P < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "P < 0");
-    if (P == 0) return G4S_OK;
-    if (!points || !meanDists || !workspace) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL pointer");
-    if (workspace_bytes < g4s_knn_workspace(P)) return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
-    g4s_knn_launch_internal(P, points, meanDists, workspace, stream);
-    CHECK_LAUNCH("knn");
-    return G4S_OK;
-}
-
-// ---- fused photometric loss (include/g4s_losses.h) ------------------------------------------------
-#include "../../include/g4s_losses.h"
-extern "C" void g4s_photometric_launch_internal(int W, int H, const float* image, const float* gt, float lambda, float* out3,
-                                                float* dL_dimage, char* workspace, hipStream_t s);
-
-extern "C" int g4s_photometric_loss(int width, int height, const float* image, const float* gt, float lambda_dssim,
-                                    float* out3, float* dL_dimage, char* workspace, size_t workspace_bytes, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    const int debug = 0;
-    t_err[0] = 0;
-    if (width <= 0 || height <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "width, height must be positive");
-    if (!image || !gt || !out3) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    if (!workspace || workspace_bytes < g4s_photometric_workspace(width, height))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
-    { ProfScope ps(PF_PHOTO_LOSS, stream);
-      g4s_photometric_launch_internal(width, height, image, gt, lambda_dssim, out3, dL_dimage, workspace, stream); }
-    CHECK_LAUNCH("photometric_loss");
-    return G4S_OK;
-}
-
-extern "C" void g4s_georeg_launch_internal(int fwd, int W, int H, const float* rn, const float* sn, const float* dist, float* out2,
-                                           const float* g2, float* d_rn, float* d_sn, float* d_dist, char* workspace,
-                                           hipStream_t s);
-
-extern "C" int g4s_geometry_regularizers_forward(int width, int height, const float* rend_normal, const float* surf_normal,
-                                                 const float* rend_dist, float* out2, char* workspace, size_t workspace_bytes,
-                                                 void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    const int debug = 0;
-    t_err[0] = 0;
-    if (width <= 0 || height <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "width, height must be positive");
-    if (!rend_normal || !surf_normal || !rend_dist || !out2) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    if (!workspace || workspace_bytes < g4s_geometry_regularizers_workspace(width, height))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
-    { ProfScope ps(PF_GEO_REG, stream);
-      g4s_georeg_launch_internal(1, width, height, rend_normal, surf_normal, rend_dist, out2, nullptr, nullptr, nullptr, nullptr,
-                                 workspace, stream); }
-    CHECK_LAUNCH("geometry_regularizers_forward");
-    return G4S_OK;
-}
-
-extern "C" int g4s_geometry_regularizers_backward(int width, int height, const float* rend_normal, const float* surf_normal,
-                                                  const float* grad_out2, float* dL_drend_normal, float* dL_dsurf_normal,
-                                                  float* dL_drend_dist, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    const int debug = 0;
-    t_err[0] = 0;
-    if (width <= 0 || height <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "width, height must be positive");
-    if (!rend_normal || !surf_normal || !grad_out2 || !dL_drend_normal || !dL_dsurf_normal || !dL_drend_dist)
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    { ProfScope ps(PF_GEO_REG, stream);
-      g4s_georeg_launch_internal(0, width, height, rend_normal, surf_normal, nullptr, nullptr, grad_out2, dL_drend_normal,
-                                 dL_dsurf_normal, dL_drend_dist, nullptr, stream); }
-    CHECK_LAUNCH("geometry_regularizers_backward");
-    return G4S_OK;
-}
-
-// ---- fused Adam (include/g4s_optim.h) ---------------------------------------------------------------
-#include "../../include/g4s_optim.h"
-extern "C" void g4s_adam_launch_internal(int nseg, float* const* params, const float* const* grads, float* const* exp_avg,
-                                         float* const* exp_avg_sq, const long long* numel, const double* lr, const int* step,
-                                         double beta1, double beta2, double eps, hipStream_t s);
-
-extern "C" int g4s_adam_step(int nseg, float* const* params, const float* const* grads, float* const* exp_avg,
-                             float* const* exp_avg_sq, const long long* numel, const double* lr, const int* step, double beta1,
-                             double beta2, double eps, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    const int debug = 0;
-    t_err[0] = 0;
-    if (nseg < 1 || nseg > 8) return fail(G4S_ERR_INVALID_ARGUMENT, "1..8 segments");
-    if (!params || !grads || !exp_avg || !exp_avg_sq || !numel || !lr || !step) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL array");
-    for (int i = 0; i < nseg; i++) {
-        if (numel[i] < 0 || step[i] < 1) return fail(G4S_ERR_INVALID_ARGUMENT, "segment %d: numel < 0 or step < 1", i);
-        if (numel[i] > 0 && (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i]))
-            return fail(G4S_ERR_INVALID_ARGUMENT, "segment %d: NULL pointer", i);
-    }
-    { ProfScope ps(PF_ADAM, stream);
-      g4s_adam_launch_internal(nseg, params, grads, exp_avg, exp_avg_sq, numel, lr, step, beta1, beta2, eps, stream); }
-    CHECK_LAUNCH("adam_step");
-    return G4S_OK;
-}
-
-extern "C" void g4s_adam_device_launch_internal(int nseg, float* const* params, const float* const* grads,
-                                                float* const* exp_avg, float* const* exp_avg_sq, const long long* numel,
-                                                const double* lr_dev, float* const* step_dev, float* coef_dev, double beta1,
-                                                double beta2, double eps, hipStream_t s);
-
-extern "C" int g4s_adam_step_device(int nseg, float* const* params, const float* const* grads, float* const* exp_avg,
-                                    float* const* exp_avg_sq, const long long* numel, const double* lr_dev,
-                                    float* const* step_dev, float* coef_dev, double beta1, double beta2, double eps,
-                                    void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    const int debug = 0;
-    t_err[0] = 0;
-    if (nseg < 1 || nseg > 8) return fail(G4S_ERR_INVALID_ARGUMENT, "1..8 segments");
-    if (!params || !grads || !exp_avg || !exp_avg_sq || !numel || !lr_dev || !step_dev || !coef_dev)
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL array");
-    for (int i = 0; i < nseg; i++) {
-        if (numel[i] < 0 || !step_dev[i]) return fail(G4S_ERR_INVALID_ARGUMENT, "segment %d: numel < 0 or NULL step", i);
-        if (numel[i] > 0 && (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i]))
-            return fail(G4S_ERR_INVALID_ARGUMENT, "segment %d: NULL pointer", i);
-    }
-    { ProfScope ps(PF_ADAM, stream);
-      g4s_adam_device_launch_internal(nseg, params, grads, exp_avg, exp_avg_sq, numel, lr_dev, step_dev, coef_dev, beta1, beta2,
-                                      eps, stream); }
-    CHECK_LAUNCH("adam_step_device");
-    return G4S_OK;
-}
-
-// ---- stream compaction of Gaussian rows (include/g4s_optim.h) ------------------------------------
-extern "C" int g4s_compact_scan_launch_internal(int P, const uint8_t* keep, int* out_count, char* workspace, hipStream_t s);
-extern "C" int g4s_compact_gather_launch_internal(int P, const uint8_t* keep, const char* workspace, int nseg,
-                                                  const float* const* src, float* const* dst, const int* widths,
-                                                  long long dst_row0, hipStream_t s);
-
-extern "C" int g4s_compact_scan(int P, const unsigned char* keep, int* out_count, char* workspace, size_t workspace_bytes,
-                                void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    t_err[0] = 0;
-    if (P < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "P must not be negative");
-    if (!out_count || !workspace || (P > 0 && !keep)) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    if (workspace_bytes < g4s_compact_workspace(P)) return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
-    if (P == 0) {
-        if (hipMemsetAsync(out_count, 0, sizeof(int), stream) != hipSuccess) return fail(G4S_ERR_HIP, "memset failed");
-        return G4S_OK;
-    }
-    g4s_compact_scan_launch_internal(P, keep, out_count, workspace, stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(G4S_ERR_HIP, "compact_scan launch: %s", hipGetErrorString(e));
-    return G4S_OK;
-}
-
-extern "C" int g4s_compact_gather(int P, const unsigned char* keep, const char* workspace, int nseg, const float* const* src,
-                                  float* const* dst, const int* widths, long long dst_row0, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    t_err[0] = 0;
-    if (P < 0 || nseg < 0 || dst_row0 < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "P, nseg, dst_row0 must not be negative");
-    if (P == 0 || nseg == 0) return G4S_OK;
-    if (!keep || !workspace || !src || !dst || !widths) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    for (int i = 0; i < nseg; i++)
-        if (!src[i] || !dst[i] || widths[i] <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "tensor %d: NULL pointer or width <= 0", i);
-    g4s_compact_gather_launch_internal(P, keep, workspace, nseg, src, dst, widths, dst_row0, stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(G4S_ERR_HIP, "compact_gather launch: %s", hipGetErrorString(e));
-    return G4S_OK;
-}
-
-// ---- packed rows for the visible-rows gradient exchange ------------------------------------------
-extern "C" void g4s_densify_stats_launch_internal(int P, const float* grad, const unsigned char* filter, const int* radii,
-                                                  float* accum, float* denom, float* max_radii, hipStream_t s);
-
-extern "C" int g4s_densify_stats(int P, const float* grad_mean2D, const unsigned char* update_filter, const int* radii,
-                                 float* xyz_gradient_accum, float* denom, float* max_radii2D, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    t_err[0] = 0;
-    if (P < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "P must not be negative");
-    if (P == 0) return G4S_OK;
-    if (!grad_mean2D || !update_filter || !xyz_gradient_accum || !denom || (max_radii2D && !radii))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    g4s_densify_stats_launch_internal(P, grad_mean2D, update_filter, radii, xyz_gradient_accum, denom, max_radii2D, stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(G4S_ERR_HIP, "densify_stats launch: %s", hipGetErrorString(e));
-    return G4S_OK;
-}
-
-extern "C" void g4s_activations_launch_internal(int fwd, int P, const float* scaling_or_scales, const float* rotation,
-                                                const float* opacity_or_opac, const float* g_scales, const float* g_rots,
-                                                const float* g_opac, float* out_s, float* out_r, float* out_o, hipStream_t s);
-
-extern "C" int g4s_activations_forward(int P, const float* scaling_raw, const float* rotation_raw, const float* opacity_raw,
-                                       float* scales, float* rotations, float* opacities, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    t_err[0] = 0;
-    if (P < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "P must not be negative");
-    if (P == 0) return G4S_OK;
-    if (!scaling_raw || !rotation_raw || !opacity_raw || !scales || !rotations || !opacities)
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    if (misaligned(scaling_raw, 8) || misaligned(scales, 8) || misaligned(rotation_raw, 16) || misaligned(rotations, 16))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "scaling / scales must be 8-byte, rotations 16-byte aligned");
-    g4s_activations_launch_internal(1, P, scaling_raw, rotation_raw, opacity_raw, nullptr, nullptr, nullptr, scales, rotations,
-                                    opacities, stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(G4S_ERR_HIP, "activations launch: %s", hipGetErrorString(e));
-    return G4S_OK;
-}
-
-extern "C" int g4s_activations_backward(int P, const float* scales, const float* rotation_raw, const float* opacities,
-                                        const float* dL_dscales, const float* dL_drotations, const float* dL_dopacities,
-                                        float* dL_dscaling_raw, float* dL_drotation_raw, float* dL_dopacity_raw, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    t_err[0] = 0;
-    if (P < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "P must not be negative");
-    if (P == 0) return G4S_OK;
-    if (!scales || !rotation_raw || !opacities || !dL_dscales || !dL_drotations || !dL_dopacities || !dL_dscaling_raw ||
-        !dL_drotation_raw || !dL_dopacity_raw)
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    if (misaligned(scales, 8) || misaligned(dL_dscales, 8) || misaligned(dL_dscaling_raw, 8) || misaligned(rotation_raw, 16) ||
-        misaligned(dL_drotations, 16) || misaligned(dL_drotation_raw, 16))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "scale tensors must be 8-byte, rotation tensors 16-byte aligned");
-    g4s_activations_launch_internal(0, P, scales, rotation_raw, opacities, dL_dscales, dL_drotations, dL_dopacities,
-                                    dL_dscaling_raw, dL_drotation_raw, dL_dopacity_raw, stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(G4S_ERR_HIP, "activations backward launch: %s", hipGetErrorString(e));
-    return G4S_OK;
-}
-
-extern "C" void g4s_pack_rows_launch_internal(int nseg, float* const* ptrs, const int* widths, const long long* idx, int n,
-                                              float* packed, int unpack, hipStream_t s);
-
-extern "C" int g4s_pack_rows(int nseg, float* const* segments, const int* widths, const long long* row_index, int n,
-                             float* packed, int unpack, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    const int debug = 0;
-    t_err[0] = 0;
-    if (nseg < 1 || nseg > 8 || n < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "1..8 segments, n >= 0");
-    if (unpack < 0 || unpack > 15 || ((unpack & 4) && !(unpack & 1)) || ((unpack & 8) && !(unpack & 2)))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "mode: bit 0 unpack, bit 1 row-major buffer, bit 2 add (unpack only), "
-                                              "bit 3 index column (row-major only)");
-    const bool idx_from_buffer = (unpack & 9) == 9;
-    if (!segments || !widths || (n > 0 && ((!row_index && !idx_from_buffer) || !packed)))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL pointer");
-    for (int i = 0; i < nseg; i++)
-        if (!segments[i] || widths[i] <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "segment %d: NULL pointer or width <= 0", i);
-    g4s_pack_rows_launch_internal(nseg, segments, widths, row_index, n, packed, unpack, stream);
-    CHECK_LAUNCH("pack_rows");
-    return G4S_OK;
-}
-
-extern "C" int g4s_accumulate_rows_launch_internal(int nseg, float* const* ptrs, const int* widths, int nsrc, const int* src_off,
-                                                   const int* src_cnt, const float* packed, int row_lo, int row_hi,
-                                                   hipStream_t s, int own_pos);
-
-static int accumulate_rows_impl(int nseg, float* const* segments, const int* widths, int nsrc, const int* src_offsets,
-                                const int* src_counts, const float* packed, int row_lo, int row_hi, int own_position, void* stream_);
-
-extern "C" int g4s_accumulate_rows(int nseg, float* const* segments, const int* widths, int nsrc, const int* src_offsets,
-                                   const int* src_counts, const float* packed, int row_lo, int row_hi, void* stream_) {
-    return accumulate_rows_impl(nseg, segments, widths, nsrc, src_offsets, src_counts, packed, row_lo, row_hi, 0, stream_);
-}
-
-extern "C" int g4s_accumulate_rows_ordered(int nseg, float* const* segments, const int* widths, int nsrc, const int* src_offsets,
-                                           const int* src_counts, const float* packed, int row_lo, int row_hi, int own_position,
-                                           void* stream_) {
-    t_err[0] = 0;
-    if (own_position < 0 || own_position > nsrc) return fail(G4S_ERR_INVALID_ARGUMENT, "0 <= own_position <= nsrc");
-    if (own_position != 0 && nsrc > 8) return fail(G4S_ERR_UNSUPPORTED, "the ordered accumulation takes at most 8 sources");
-    return accumulate_rows_impl(nseg, segments, widths, nsrc, src_offsets, src_counts, packed, row_lo, row_hi, own_position, stream_);
-}
-
-static int accumulate_rows_impl(int nseg, float* const* segments, const int* widths, int nsrc, const int* src_offsets,
-                                const int* src_counts, const float* packed, int row_lo, int row_hi, int own_position, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    const int debug = 0;
-    t_err[0] = 0;
-    if (nseg < 1 || nseg > 8 || nsrc < 0 || row_lo < 0 || row_hi < row_lo)
-        return fail(G4S_ERR_INVALID_ARGUMENT, "1..8 segments, nsrc >= 0, 0 <= row_lo <= row_hi");
-    if (!segments || !widths || (nsrc > 0 && (!src_offsets || !src_counts || !packed)))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL pointer");
-    for (int i = 0; i < nseg; i++)
-        if (!segments[i] || widths[i] <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "segment %d: NULL pointer or width <= 0", i);
-    for (int i = 0; i < nsrc; i++)
-        if (src_offsets[i] < 0 || src_counts[i] < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "source %d: negative offset / count", i);
-    if (nsrc == 0 || row_hi == row_lo) return G4S_OK;
-    if (g4s_accumulate_rows_launch_internal(nseg, segments, widths, nsrc, src_offsets, src_counts, packed, row_lo, row_hi, stream,
-                                            own_position) != 0)
-        return fail(G4S_ERR_UNSUPPORTED, "rows wider than 240 floats");
-    CHECK_LAUNCH("accumulate_rows");
-    return G4S_OK;
-}
-
-// ---- fused render() map post-processing (include/g4s_render_maps.h) -------------------------------
-#include "../../include/g4s_render_maps.h"
-
-extern "C" size_t g4s_render_maps_workspace(void) { return 512; }
-
-extern "C" int g4s_render_maps_forward(int width, int height, const float* allmap, const float* world_view_transform,
-                                       const float* full_proj_transform, float depth_ratio, float* rend_alpha,
-                                       float* rend_normal, float* rend_normal_cam, float* rend_depth, float* rend_dist,
-                                       float* surf_depth, float* surf_normal, float* surf_normal_cam, char* workspace,
-                                       size_t workspace_bytes, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    const int debug = 0;
-    t_err[0] = 0;
-    if (width <= 0 || height <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "width, height must be positive");
-    if (!allmap || !world_view_transform || !full_proj_transform || !rend_alpha || !rend_normal || !rend_normal_cam ||
-        !rend_depth || !rend_dist || !surf_depth || !surf_normal || !surf_normal_cam)
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    if (!workspace || workspace_bytes < g4s_render_maps_workspace()) return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
-    float* outs[8] = {rend_alpha, rend_normal, rend_normal_cam, rend_depth, rend_dist, surf_depth, surf_normal, surf_normal_cam};
-    { ProfScope ps(PF_MAPS_FWD, stream);
-      g4s_maps_launch_internal(1, width, height, depth_ratio, allmap, world_view_transform, full_proj_transform,
-                               (float*)align_ptr(workspace), outs, nullptr, nullptr, nullptr, stream); }
-    CHECK_LAUNCH("render_maps_forward");
-    return G4S_OK;
-}
-
-extern "C" int g4s_render_maps_backward(int width, int height, const float* allmap, const float* surf_depth,
-                                        const float* world_view_transform, const float* full_proj_transform,
-                                        float depth_ratio, const float* dL_rend_alpha, const float* dL_rend_normal,
-                                        const float* dL_rend_normal_cam, const float* dL_rend_depth,
-                                        const float* dL_rend_dist, const float* dL_surf_depth, const float* dL_surf_normal,
-                                        const float* dL_surf_normal_cam, float* dL_dallmap, char* workspace,
-                                        size_t workspace_bytes, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    const int debug = 0;
-    t_err[0] = 0;
-    if (width <= 0 || height <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "width, height must be positive");
-    if (!allmap || !surf_depth || !world_view_transform || !full_proj_transform || !dL_dallmap)
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    if (!workspace || workspace_bytes < g4s_render_maps_workspace()) return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
-    const float* grads[8] = {dL_rend_alpha, dL_rend_normal, dL_rend_normal_cam, dL_rend_depth, dL_rend_dist,
-                             dL_surf_depth, dL_surf_normal, dL_surf_normal_cam};
-    { ProfScope ps(PF_MAPS_BWD, stream);
-      g4s_maps_launch_internal(0, width, height, depth_ratio, allmap, world_view_transform, full_proj_transform,
-                               (float*)align_ptr(workspace), nullptr, surf_depth, grads, dL_dallmap, stream); }
-    CHECK_LAUNCH("render_maps_backward");
-    return G4S_OK;
 }

@@ -164,6 +164,20 @@ inline char* align_ptr(char* p) { return (char*)align_up((size_t)p); }
 void clear_error();
 int fail(int code, const char* fmt, ...);    // formats the message, returns `code`
 int finish(hipError_t e, const char* what);  // e, or if that is hipSuccess the last launch error: G4S_OK or "what: <error>"
+// What a stage ends with: the last launch error -- after synchronising on `s` if `debug` is set or G4S_TRACE is in the
+// environment, which also logs "[g4s] what: <error>" to stderr -- as G4S_OK or "what: <error>".
+int stage_done(const char* what, hipStream_t s, bool debug = false);
+inline bool misaligned(const void* p, size_t a) { return p != nullptr && ((size_t)p % a) != 0; }
+
+// ---- optional per-kernel timing with HIP events on the launch stream (api.hip; bench.py reads the groups by name) ----
+enum ProfId { PF_PREPROCESS_FWD, PF_DEPTH_SORT, PF_COUNT_SCAN, PF_EMIT, PF_TILE_SORT, PF_TILE_RANGES, PF_BLEND_FWD,
+              PF_BLEND_BWD, PF_PREPROCESS_BWD, PF_MAPS_FWD, PF_MAPS_BWD, PF_PHOTO_LOSS, PF_ADAM, PF_GEO_REG, PF_COUNT };
+// Times what is launched on `s` during its lifetime as one recording of group `id`; does nothing unless profiling is on.
+struct ProfScope {
+    int id; hipStream_t s; hipEvent_t a = nullptr, b = nullptr; bool on = false;
+    ProfScope(int id_, hipStream_t s_);
+    ~ProfScope();
+};
 
 // ---- launchers (each defined next to its kernels) --------------------------------------
 
@@ -188,7 +202,6 @@ struct PreprocessArgs {
     uint32_t* depth_keys;
 };
 void launch_preprocess_fwd(const PreprocessArgs& a, hipStream_t s);
-void launch_mark_visible(int P, const float* means3D, const float* viewmatrix, uint8_t* present, hipStream_t s);
 
 // Stable LSD radix sort.  32-bit keys with 32-bit payload (ping-pong a<->b, result index
 // returned: 0 = in *_a, 1 = in *_b) over bits [0,32).

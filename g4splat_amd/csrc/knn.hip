@@ -123,13 +123,20 @@ using namespace g4s;
 
 extern "C" size_t g4s_knn_workspace(int P) { return knn_layout(P > 0 ? (size_t)P : 0).bytes; }
 
-extern "C" int g4s_knn_launch_internal(int P, const float* points, float* meanDists, char* workspace,
-                                       hipStream_t s) {
+// SimpleKNN::knn (knn/simple_knn.cu:185-221)
+extern "C" int g4s_knn_mean_dist(int P, const float* points, float* meanDists, char* workspace,
+                                 size_t workspace_bytes, void* stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    clear_error();
+    if (P < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "P < 0");
+    if (P == 0) return G4S_OK;
+    if (!points || !meanDists || !workspace) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL pointer");
+    if (workspace_bytes < g4s_knn_workspace(P)) return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
     const KnnLayout L = knn_layout((size_t)P);
     char* w = align_ptr(workspace);
     knn_build_tree(L, P, points, w, s);
     const Box* leaves = (const Box*)(w + L.nodes);
     hipLaunchKernelGGL(knn_search_kernel, dim3((L.n0 + 3) / 4), dim3(256), 0, s, P, (const float4*)(w + L.sorted), leaves,
                        leaves + L.n0, leaves + L.n0 + L.n1, L.n0, L.n1, L.n2, meanDists);
-    return 0;
+    return stage_done("knn", s);
 }

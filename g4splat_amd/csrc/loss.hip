@@ -1,4 +1,5 @@
-// Fused L1 + SSIM photometric loss with its gradient (include/g4s_losses.h).
+// The losses of include/g4s_losses.h, kernels and entry points: the fused L1 + SSIM photometric loss with its gradient
+//  and, further down, the geometry regularisers of the training step.
 //
 // Reference semantics: 2dgs/utils/loss_utils.py:17-18 (l1_loss), :31-33 (gaussian), :46-79 (ssim / _ssim:
 // five depthwise 11x11 convolutions with zero padding), combined as train_with_refine_depth.py:382-383.
@@ -12,6 +13,7 @@
 // per channel-pixel against ~25 full-image passes of the eager formulation.
 #include "g4s_internal.h"
 #include "g4s_device.h"
+#include "../../include/g4s_losses.h"
 
 namespace g4s {
 
@@ -190,19 +192,29 @@ extern "C" size_t g4s_photometric_workspace(int width, int height) {
     return align_up(9 * N * 4) + align_up(blocks * 8) + 256;
 }
 
-extern "C" void g4s_photometric_launch_internal(int W, int H, const float* image, const float* gt, float lambda, float* out3,
-                                                float* dL_dimage, char* workspace, hipStream_t s) {
+extern "C" int g4s_photometric_loss(int width, int height, const float* image, const float* gt, float lambda_dssim,
+                                    float* out3, float* dL_dimage, char* workspace, size_t workspace_bytes, void* stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    clear_error();
+    if (width <= 0 || height <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "width, height must be positive");
+    if (!image || !gt || !out3) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (!workspace || workspace_bytes < g4s_photometric_workspace(width, height))
+        return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
     PhotoArgs a{};
-    a.W = W; a.H = H; a.lambda = lambda; a.image = image; a.gt = gt; a.out3 = out3; a.dL_dimage = dL_dimage;
-    const size_t N = (size_t)W * H;
+    a.W = width; a.H = height; a.lambda = lambda_dssim; a.image = image; a.gt = gt; a.out3 = out3; a.dL_dimage = dL_dimage;
+    const size_t N = (size_t)width * height;
     char* w = align_ptr(workspace);
     a.maps = (float*)w;
     a.partials = (float*)(w + align_up(9 * N * 4));
-    const dim3 grid((W + SS_T - 1) / SS_T, (H + SS_T - 1) / SS_T, 3);
+    const dim3 grid((width + SS_T - 1) / SS_T, (height + SS_T - 1) / SS_T, 3);
     a.nblocks = (int)(grid.x * grid.y * grid.z);
-    hipLaunchKernelGGL(ssim_fwd_kernel, grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL(photo_reduce_kernel, dim3(1), dim3(1024), 0, s, a);
-    if (dL_dimage) hipLaunchKernelGGL(ssim_bwd_kernel, grid, dim3(256), 0, s, a);
+    {
+        ProfScope ps(PF_PHOTO_LOSS, s);
+        hipLaunchKernelGGL(ssim_fwd_kernel, grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(photo_reduce_kernel, dim3(1), dim3(1024), 0, s, a);
+        if (dL_dimage) hipLaunchKernelGGL(ssim_bwd_kernel, grid, dim3(256), 0, s, a);
+    }
+    return stage_done("photometric_loss", s);
 }
 
 // ---- geometry regularisers of the training step (include/g4s_losses.h) ------------------------------
@@ -314,224 +326,52 @@ extern "C" size_t g4s_geometry_regularizers_workspace(int width, int height) {
     return g4s::align_up(blocks * 8) + 256;
 }
 
+// what both directions share; vec = float4 accesses: N % 4 == 0 and every plane of the direction on a 16-byte aligned base
 static inline bool georeg_al16(const void* p) { return ((size_t)p & 15) == 0; }
-
-extern "C" void g4s_georeg_launch_internal(int fwd, int W, int H, const float* rn, const float* sn, const float* dist, float* out2,
-                                           const float* g2, float* d_rn, float* d_sn, float* d_dist, char* workspace,
-                                           hipStream_t s) {
-    using namespace g4s;
+static GeoRegArgs georeg_args(int width, int height, const float* rn, const float* sn) {
     GeoRegArgs a{};
-    a.N = (long long)W * H;
-    a.rn = rn; a.sn = sn; a.dist = dist; a.out2 = out2; a.g2 = g2; a.d_rn = d_rn; a.d_sn = d_sn; a.d_dist = d_dist;
+    a.N = (long long)width * height;
+    a.rn = rn; a.sn = sn;
     a.nblocks = (int)((a.N + 1023) / 1024);
-    a.vec = (a.N % 4 == 0) && georeg_al16(rn) && georeg_al16(sn) && (fwd ? georeg_al16(dist) : (georeg_al16(d_rn) && georeg_al16(d_sn) && georeg_al16(d_dist)));
-    if (fwd) {
-        a.partials = (float*)align_ptr(workspace);
+    a.vec = (a.N % 4 == 0) && georeg_al16(rn) && georeg_al16(sn);
+    return a;
+}
+
+extern "C" int g4s_geometry_regularizers_forward(int width, int height, const float* rend_normal, const float* surf_normal,
+                                                 const float* rend_dist, float* out2, char* workspace, size_t workspace_bytes,
+                                                 void* stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    clear_error();
+    if (width <= 0 || height <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "width, height must be positive");
+    if (!rend_normal || !surf_normal || !rend_dist || !out2) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (!workspace || workspace_bytes < g4s_geometry_regularizers_workspace(width, height))
+        return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
+    GeoRegArgs a = georeg_args(width, height, rend_normal, surf_normal);
+    a.dist = rend_dist; a.out2 = out2;
+    a.vec = a.vec && georeg_al16(rend_dist);
+    a.partials = (float*)align_ptr(workspace);
+    {
+        ProfScope ps(PF_GEO_REG, s);
         hipLaunchKernelGGL(georeg_fwd_kernel, dim3(a.nblocks), dim3(256), 0, s, a);
         hipLaunchKernelGGL(georeg_reduce_kernel, dim3(1), dim3(1024), 0, s, a);
-    } else {
+    }
+    return stage_done("geometry_regularizers_forward", s);
+}
+
+extern "C" int g4s_geometry_regularizers_backward(int width, int height, const float* rend_normal, const float* surf_normal,
+                                                  const float* grad_out2, float* dL_drend_normal, float* dL_dsurf_normal,
+                                                  float* dL_drend_dist, void* stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    clear_error();
+    if (width <= 0 || height <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "width, height must be positive");
+    if (!rend_normal || !surf_normal || !grad_out2 || !dL_drend_normal || !dL_dsurf_normal || !dL_drend_dist)
+        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    GeoRegArgs a = georeg_args(width, height, rend_normal, surf_normal);
+    a.g2 = grad_out2; a.d_rn = dL_drend_normal; a.d_sn = dL_dsurf_normal; a.d_dist = dL_drend_dist;
+    a.vec = a.vec && georeg_al16(dL_drend_normal) && georeg_al16(dL_dsurf_normal) && georeg_al16(dL_drend_dist);
+    {
+        ProfScope ps(PF_GEO_REG, s);
         hipLaunchKernelGGL(georeg_bwd_kernel, dim3(a.nblocks), dim3(256), 0, s, a);
     }
-}
-
-// ---- fused Adam over up to eight parameter segments (include/g4s_optim.h) ------------------------------
-namespace g4s {
-struct AdamSegs {
-    float* p[8];
-    const float* g[8];
-    float* m[8];
-    float* v[8];
-    long long n[8];        // elements
-    long long first[9];    // first float4-block of each segment in the launch's block space (prefix sums)
-    float step_size[8];    // lr / (1 - beta1^t)
-    float inv_sqrt_bc2[8]; // 1 / sqrt(1 - beta2^t)
-    int nseg;
-    float w1, w2, beta2, eps;  // 1 - beta1, 1 - beta2 (formed in double on the host), beta2, eps
-    const float* coef;     // g4s_adam_step_device: step_size[s] = coef[s], inv_sqrt_bc2[s] = coef[8 + s] (device memory,
-                           // written by adam_prep_kernel in front of this launch); NULL: the two arrays above
-};
-
-// g4s_adam_step_device: the step counts and learning rates live on the device, so that a captured launch (hipGraph) does
-// the right update at every replay.  One thread per segment: t <- t + 1, then the two bias-correction factors in double,
-// exactly as the host does for g4s_adam_step.
-struct AdamPrep {
-    float* step[8];   // per segment: torch's capturable state["step"] (a float32 scalar on the device), incremented here
-    const double* lr; // [nseg] on the device (double, like the Python floats the host path divides)
-    float* coef;      // [16] scratch on the device
-    int nseg;
-    double beta1, beta2;
-};
-__global__ void adam_prep_kernel(AdamPrep a) {
-    const int i = (int)threadIdx.x;
-    if (i >= a.nseg) return;
-    const float t = *a.step[i] + 1.0f;
-    *a.step[i] = t;
-    const double bc1 = 1.0 - pow(a.beta1, (double)t), bc2 = 1.0 - pow(a.beta2, (double)t);
-    a.coef[i] = (float)(a.lr[i] / bc1);
-    a.coef[8 + i] = (float)(1.0 / sqrt(bc2));
-}
-
-// One thread per 4 consecutive floats (16-byte accesses when the segment base is 16-byte aligned, which torch
-// allocations are; the tail and misaligned bases fall back to scalar accesses).
-__global__ void __launch_bounds__(256) adam_kernel(AdamSegs a) {
-    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;  // float4-block index over all segments
-    int s = 0;
-#pragma unroll
-    for (int i = 1; i < 8; i++) s += (i < a.nseg && q >= a.first[i]) ? 1 : 0;
-    const long long e0 = (q - a.first[s]) * 4;
-    if (q >= a.first[a.nseg] || e0 >= a.n[s]) return;
-    float* p = a.p[s] + e0;
-    const float* g = a.g[s] + e0;
-    float* m = a.m[s] + e0;
-    float* v = a.v[s] + e0;
-    const float w1 = a.w1, w2 = a.w2;
-    const float ss = a.coef ? a.coef[s] : a.step_size[s], ib = a.coef ? a.coef[8 + s] : a.inv_sqrt_bc2[s];
-    const bool vec = e0 + 4 <= a.n[s] && (((size_t)p | (size_t)g | (size_t)m | (size_t)v) & 15) == 0;
-    float pv[4], gv[4], mv[4], vv[4];
-    const int cnt = vec ? 4 : (int)((a.n[s] - e0) < 4 ? (a.n[s] - e0) : 4);
-    if (vec) {
-        *reinterpret_cast<float4*>(pv) = *reinterpret_cast<const float4*>(p);
-        *reinterpret_cast<float4*>(gv) = *reinterpret_cast<const float4*>(g);
-        *reinterpret_cast<float4*>(mv) = *reinterpret_cast<const float4*>(m);
-        *reinterpret_cast<float4*>(vv) = *reinterpret_cast<const float4*>(v);
-    } else {
-        for (int i = 0; i < cnt; i++) { pv[i] = p[i]; gv[i] = g[i]; mv[i] = m[i]; vv[i] = v[i]; }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        if (i >= cnt) break;
-        mv[i] = mv[i] + w1 * (gv[i] - mv[i]);              // exp_avg.lerp_(grad, 1 - beta1)
-        vv[i] = a.beta2 * vv[i] + w2 * gv[i] * gv[i];      // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-        const float denom = sqrtf(vv[i]) * ib + a.eps;     // (exp_avg_sq.sqrt() / sqrt(bias_correction2)).add_(eps)
-        pv[i] = pv[i] - ss * (mv[i] / denom);              // param.addcdiv_(exp_avg, denom, value=-step_size)
-    }
-    if (vec) {
-        *reinterpret_cast<float4*>(p) = *reinterpret_cast<const float4*>(pv);
-        *reinterpret_cast<float4*>(m) = *reinterpret_cast<const float4*>(mv);
-        *reinterpret_cast<float4*>(v) = *reinterpret_cast<const float4*>(vv);
-    } else {
-        for (int i = 0; i < cnt; i++) { p[i] = pv[i]; m[i] = mv[i]; v[i] = vv[i]; }
-    }
-}
-
-// Densification statistics of one view (2dgs/scene/gaussian_model.py:649-651 and the max_radii2D update of the
-// training loop, train_with_refine_depth.py): for the Gaussians selected by `filter`
-//   xyz_gradient_accum += |dL/dmean2D|_2,  denom += 1,  max_radii2D = max(max_radii2D, radii)
-// in one pass (28 B per Gaussian) instead of boolean-mask gathers, a norm and scatters (about twenty launches).
-__global__ void __launch_bounds__(256) densify_stats_kernel(int P, const float* __restrict__ grad, const uint8_t* __restrict__ filter,
-                                                            const int* __restrict__ radii, float* __restrict__ accum,
-                                                            float* __restrict__ denom, float* __restrict__ max_radii) {
-    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (i >= P || !filter[i]) return;
-    const float gx = grad[3 * i], gy = grad[3 * i + 1], gz = grad[3 * i + 2];
-    accum[i] += sqrtf((gx * gx + gy * gy) + gz * gz);
-    denom[i] += 1.0f;
-    if (max_radii != nullptr) max_radii[i] = fmaxf(max_radii[i], (float)radii[i]);
-}
-}  // namespace g4s
-
-// Activations of the Gaussian parameters as render() reads them (2dgs/scene/gaussian_model.py:157-192, without the
-// optional mip filter): scales = exp(_scaling), rotations = _rotation / max(|_rotation|, 1e-12), opacity =
-// sigmoid(_opacity) -- one pass instead of ~5 element-wise / reduction launches, and one pass for their backward
-// instead of ~9.
-namespace g4s {
-__global__ void __launch_bounds__(256) activations_fwd_kernel(int P, const float2* __restrict__ scaling,
-                                                              const float4* __restrict__ rotation,
-                                                              const float* __restrict__ opacity, float2* __restrict__ scales,
-                                                              float4* __restrict__ rots, float* __restrict__ opac) {
-    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (i >= P) return;
-    const float2 s = scaling[i];
-    scales[i] = make_float2(expf(s.x), expf(s.y));
-    const float4 q = rotation[i];
-    const float n = fmaxf(sqrtf(((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w), 1e-12f);
-    rots[i] = make_float4(q.x / n, q.y / n, q.z / n, q.w / n);
-    opac[i] = 1.0f / (1.0f + expf(-opacity[i]));
-}
-
-__global__ void __launch_bounds__(256) activations_bwd_kernel(int P, const float2* __restrict__ scales,
-                                                              const float4* __restrict__ rotation,
-                                                              const float* __restrict__ opac, const float2* __restrict__ g_scales,
-                                                              const float4* __restrict__ g_rots, const float* __restrict__ g_opac,
-                                                              float2* __restrict__ d_scaling, float4* __restrict__ d_rotation,
-                                                              float* __restrict__ d_opacity) {
-    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (i >= P) return;
-    const float2 y = scales[i], gs = g_scales[i];
-    d_scaling[i] = make_float2(gs.x * y.x, gs.y * y.y);  // exp' = exp
-    const float4 q = rotation[i], g = g_rots[i];
-    const float norm = sqrtf(((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w);
-    if (norm > 1e-12f) {  // y = q / |q|:  dq = (g - y <y, g>) / |q|
-        const float inv = 1.0f / norm;
-        const float4 u = make_float4(q.x * inv, q.y * inv, q.z * inv, q.w * inv);
-        const float d = ((u.x * g.x + u.y * g.y) + u.z * g.z) + u.w * g.w;
-        d_rotation[i] = make_float4((g.x - u.x * d) * inv, (g.y - u.y * d) * inv, (g.z - u.z * d) * inv, (g.w - u.w * d) * inv);
-    } else {              // clamped denominator: y = q / 1e-12
-        d_rotation[i] = make_float4(g.x * 1e12f, g.y * 1e12f, g.z * 1e12f, g.w * 1e12f);
-    }
-    const float o = opac[i];
-    d_opacity[i] = g_opac[i] * o * (1.0f - o);  // sigmoid' = y (1 - y)
-}
-}  // namespace g4s
-
-extern "C" void g4s_activations_launch_internal(int fwd, int P, const float* scaling_or_scales, const float* rotation,
-                                                const float* opacity_or_opac, const float* g_scales, const float* g_rots,
-                                                const float* g_opac, float* out_s, float* out_r, float* out_o, hipStream_t s) {
-    if (P <= 0) return;
-    const dim3 grid((unsigned)((P + 255) / 256)), block(256);
-    if (fwd)
-        hipLaunchKernelGGL(g4s::activations_fwd_kernel, grid, block, 0, s, P, (const float2*)scaling_or_scales, (const float4*)rotation,
-                           opacity_or_opac, (float2*)out_s, (float4*)out_r, out_o);
-    else
-        hipLaunchKernelGGL(g4s::activations_bwd_kernel, grid, block, 0, s, P, (const float2*)scaling_or_scales, (const float4*)rotation,
-                           opacity_or_opac, (const float2*)g_scales, (const float4*)g_rots, g_opac, (float2*)out_s, (float4*)out_r,
-                           out_o);
-}
-
-extern "C" void g4s_densify_stats_launch_internal(int P, const float* grad, const unsigned char* filter, const int* radii,
-                                                  float* accum, float* denom, float* max_radii, hipStream_t s) {
-    if (P <= 0) return;
-    hipLaunchKernelGGL(g4s::densify_stats_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, P, grad, filter, radii,
-                       accum, denom, max_radii);
-}
-
-extern "C" void g4s_adam_device_launch_internal(int nseg, float* const* params, const float* const* grads,
-                                                float* const* exp_avg, float* const* exp_avg_sq, const long long* numel,
-                                                const double* lr_dev, float* const* step_dev, float* coef_dev, double beta1,
-                                                double beta2, double eps, hipStream_t s) {
-    g4s::AdamPrep pr{};
-    pr.nseg = nseg; pr.lr = lr_dev; pr.coef = coef_dev; pr.beta1 = beta1; pr.beta2 = beta2;
-    g4s::AdamSegs a{};
-    a.nseg = nseg; a.w1 = (float)(1.0 - beta1); a.w2 = (float)(1.0 - beta2); a.beta2 = (float)beta2; a.eps = (float)eps;
-    a.coef = coef_dev;
-    long long blocks4 = 0;
-    for (int i = 0; i < nseg; i++) {
-        pr.step[i] = step_dev[i];
-        a.p[i] = params[i]; a.g[i] = grads[i]; a.m[i] = exp_avg[i]; a.v[i] = exp_avg_sq[i]; a.n[i] = numel[i];
-        a.first[i] = blocks4;
-        blocks4 += (numel[i] + 3) / 4;
-    }
-    for (int i = nseg; i <= 8; i++) a.first[i] = blocks4;
-    hipLaunchKernelGGL(g4s::adam_prep_kernel, dim3(1), dim3(8), 0, s, pr);  // (the counts advance even when all segments are empty)
-    if (blocks4 == 0) return;
-    hipLaunchKernelGGL(g4s::adam_kernel, dim3((unsigned)((blocks4 + 255) / 256)), dim3(256), 0, s, a);
-}
-
-extern "C" void g4s_adam_launch_internal(int nseg, float* const* params, const float* const* grads, float* const* exp_avg,
-                                         float* const* exp_avg_sq, const long long* numel, const double* lr, const int* step,
-                                         double beta1, double beta2, double eps, hipStream_t s) {
-    AdamSegs a{};
-    a.nseg = nseg; a.w1 = (float)(1.0 - beta1); a.w2 = (float)(1.0 - beta2); a.beta2 = (float)beta2; a.eps = (float)eps;
-    long long blocks4 = 0;
-    for (int i = 0; i < nseg; i++) {
-        a.p[i] = params[i]; a.g[i] = grads[i]; a.m[i] = exp_avg[i]; a.v[i] = exp_avg_sq[i]; a.n[i] = numel[i];
-        a.first[i] = blocks4;
-        blocks4 += (numel[i] + 3) / 4;
-        const double bc1 = 1.0 - pow(beta1, (double)step[i]), bc2 = 1.0 - pow(beta2, (double)step[i]);
-        a.step_size[i] = (float)(lr[i] / bc1);
-        a.inv_sqrt_bc2[i] = (float)(1.0 / sqrt(bc2));
-    }
-    for (int i = nseg; i <= 8; i++) a.first[i] = blocks4;
-    if (blocks4 == 0) return;
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((blocks4 + 255) / 256)), dim3(256), 0, s, a);
+    return stage_done("geometry_regularizers_backward", s);
 }

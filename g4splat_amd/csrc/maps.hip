@@ -1,4 +1,4 @@
-// Fused map post-processing of render() (include/g4s_render_maps.h).
+// Fused map post-processing of render(), kernels and entry points (include/g4s_render_maps.h).
 //
 // Reference semantics: 2dgs/gaussian_renderer/__init__.py:117-164 and 2dgs/utils/point_utils.py:9-37
 // (about fifteen element-wise torch kernels + two 3x3 matmuls over [H,W,3] + a cross product).
@@ -12,6 +12,7 @@
 // runs once per call in one thread, in double, into a 160-byte device scratch.
 #include "g4s_internal.h"
 #include "g4s_device.h"
+#include "../../include/g4s_render_maps.h"
 
 namespace g4s {
 
@@ -269,274 +270,64 @@ __global__ void __launch_bounds__(MAPS_BX * MAPS_BY) maps_bwd_kernel(MapsArgs a)
 
 using namespace g4s;
 
-extern "C" void g4s_maps_launch_internal(int fwd, int W, int H, float depth_ratio, const float* allmap, const float* wvt,
-                                         const float* fpt, float* cam, float* const* outs, const float* surf_depth_in,
-                                         const float* const* grads, float* g_allmap, hipStream_t s) {
-    hipLaunchKernelGGL(maps_camera_kernel, dim3(1), dim3(64), 0, s, wvt, fpt, W, H, cam);
+extern "C" size_t g4s_render_maps_workspace(void) { return 512; }
+
+// the camera algebra into the workspace, and what the forward and the backward kernel both read
+static MapsArgs maps_prepare(int width, int height, float depth_ratio, const float* allmap, const float* wvt, const float* fpt,
+                             char* workspace, hipStream_t s) {
+    float* cam = (float*)align_ptr(workspace);
+    hipLaunchKernelGGL(maps_camera_kernel, dim3(1), dim3(64), 0, s, wvt, fpt, width, height, cam);
     MapsArgs a{};
-    a.W = W; a.H = H; a.r = depth_ratio; a.omr = (float)(1.0 - (double)depth_ratio);
+    a.W = width; a.H = height; a.r = depth_ratio; a.omr = (float)(1.0 - (double)depth_ratio);
     a.allmap = allmap; a.cam = cam;
-    const dim3 grid((W + MAPS_BX - 1) / MAPS_BX, (H + MAPS_BY - 1) / MAPS_BY), block(MAPS_BX * MAPS_BY);
-    if (fwd) {
-        a.rend_alpha = outs[0]; a.rend_normal = outs[1]; a.rend_normal_cam = outs[2]; a.rend_depth = outs[3];
-        a.rend_dist = outs[4]; a.surf_depth = outs[5]; a.surf_normal = outs[6]; a.surf_normal_cam = outs[7];
-        hipLaunchKernelGGL(maps_fwd_kernel, grid, block, 0, s, a);
-    } else {
-        a.surf_depth_in = surf_depth_in;
-        a.g_alpha = grads[0]; a.g_normal = grads[1]; a.g_normal_cam = grads[2]; a.g_depth = grads[3]; a.g_dist = grads[4];
-        a.g_surf_depth = grads[5]; a.g_surf_normal = grads[6]; a.g_surf_normal_cam = grads[7];
-        a.g_allmap = g_allmap;
-        hipLaunchKernelGGL(maps_bwd_kernel, grid, block, 0, s, a);
-    }
+    return a;
 }
+static dim3 maps_grid(int width, int height) { return dim3((width + MAPS_BX - 1) / MAPS_BX, (height + MAPS_BY - 1) / MAPS_BY); }
 
-// ---- packed rows for the visible-rows gradient exchange (g4splat_amd/parallel.py) -----------------
-// mode bit 0: direction (0 = pack: rows -> buffer, 1 = unpack: buffer -> rows)
-// mode bit 1: buffer layout (0 = segment after segment, packed[seg_off(s) * n + j * w_s + c]; 1 = row-major [n, sum w],
-//             packed[j * sum_w + seg_off(s) + c] -- what an all_to_all with per-destination row ranges needs)
-// mode bit 2: unpack ADDS to the rows instead of overwriting them (the owner's accumulation of one source's rows; a
-//             source holds a row at most once, so there are no duplicate indices inside one launch)
-// mode bit 3: (row-major only) buffer rows are sum w + 1 floats: the last one is the row's index as int32 bits --
-//             pack writes it, unpack reads it instead of idx[] (idx may be NULL then)
-// A row's floats over all segments (58 + 2 for the gradient bucket) are spread over the lanes of a wave --
-// lane -> (segment, column) is fixed for the whole kernel, so there is no per-element division -- and each wave
-// walks rows j, j + #waves, ...: both sides move contiguous w_s-float runs.  Rows wider than 64 floats take
-// several lane passes.
-namespace g4s {
-struct RowSegs {
-    float* ptr[8];
-    int width[8];
-    int nseg;
-};
-__global__ void __launch_bounds__(256) pack_rows_kernel(RowSegs segs, const long long* __restrict__ idx, int n,
-                                                        float* __restrict__ packed, int mode) {
-    const int lane = (int)(threadIdx.x & 63);
-    const int wave = (int)(blockIdx.x * 4 + (threadIdx.x >> 6)), nwaves = (int)(gridDim.x * 4);
-    const bool unpack = (mode & 1) != 0, row_major = (mode & 2) != 0, add = (mode & 4) != 0, carry = (mode & 8) != 0;
-    int row_floats = 0;
-    for (int s = 0; s < segs.nseg; s++) row_floats += segs.width[s];
-    // carry (row-major only): every buffer row ends with its row index as an int32 column -- written by pack, and
-    // read by unpack INSTEAD of idx[] (the rows and their indices then travel in one all_to_all)
-    const int buf_floats = row_floats + (carry ? 1 : 0);
-    for (int f0 = 0; f0 < buf_floats; f0 += 64) {
-        // this lane's (segment, column) for float f0 + lane of a row
-        const int f = f0 + lane;
-        int seg = -1, col = 0, w = 1;
-        size_t seg_off = 0;  // floats of a row before this segment
-        {
-            int base = 0;
-            size_t off = 0;
-            for (int s = 0; s < segs.nseg; s++) {
-                if (f >= base && f < base + segs.width[s]) { seg = s; col = f - base; w = segs.width[s]; seg_off = off; }
-                base += segs.width[s];
-                off += (size_t)segs.width[s];
-            }
-        }
-        const bool index_lane = carry && f == row_floats;
-        if (seg < 0 && !index_lane) continue;
-        if (index_lane) {
-            if (!unpack)
-                for (int j = wave; j < n; j += nwaves) packed[(size_t)j * buf_floats + row_floats] = __int_as_float((int)idx[j]);
-            continue;
-        }
-        float* sp = segs.ptr[seg];
-        float* pp = row_major ? packed + f : packed + seg_off * (size_t)n + col;
-        const size_t pstride = row_major ? (size_t)buf_floats : (size_t)w;
-        for (int j = wave; j < n; j += nwaves) {
-            const long long row = (carry && unpack) ? (long long)__float_as_int(packed[(size_t)j * buf_floats + row_floats]) : idx[j];
-            float* src = sp + (size_t)row * w + col;
-            float* dst = pp + (size_t)j * pstride;
-            if (!unpack) *dst = *src;
-            else if (add) *src += *dst;
-            else *src = *dst;
-        }
-    }
-}
-
-// The owner's accumulation of ALL sources in one launch (g4s_accumulate_rows, include/g4s_rasterizer.h).  The per-source
-// form -- one pack_rows_kernel(mode 15) launch per source -- reads and writes a destination row once per source that
-// holds it and pays a launch per source; here a workgroup owns ACC_CHUNK consecutive destination rows: it loads them into
-// LDS, finds each source's rows of the chunk (the sources' rows ascend by index: a 32-ary search by 32 lanes per source,
-// all sources at once), adds them source after source -- the same order of additions per element as the per-source
-// launches, so the same bits -- and writes the chunk back: 7 x (launch + read + write) become 1 x.
-constexpr int ACC_CHUNK = 64;  // (measured at the metric size, eight ranks: 32 rows 0.088 ms, 48 0.075, 64 0.076, 128 0.096)
-struct AccSources {
-    int off[8], cnt[8];  // rows [off, off + cnt) of the buffer came from source i (ascending row indices)
-    int nsrc;
-    // the owner's own contribution (already in the segments' rows) takes position `own_pos` in the order of additions:
-    // 0 = first (own + s0 + s1 + ...), k = behind the first k sources (((0 + s0 + ... + s_{k-1}) + own) + s_k + ...): with the
-    // sources in rank order and own_pos = the owner's rank, every row is summed in RANK ORDER whoever owns it
-    // (g4s_accumulate_rows_ordered)
-    int own_pos;
-};
-__global__ void __launch_bounds__(256) accumulate_rows_kernel(RowSegs segs, AccSources src, const float* __restrict__ packed,
-                                                              int row_lo, int row_hi) {
-    extern __shared__ float s_tile[];  // [ACC_CHUNK][row_floats]
-    __shared__ int s_b0[8], s_b1[8];
-    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
-    int row_floats = 0;
-    for (int s = 0; s < segs.nseg; s++) row_floats += segs.width[s];
-    const int buf_floats = row_floats + 1;
-    const int chunk_lo = row_lo + (int)blockIdx.x * ACC_CHUNK;
-    const int chunk_hi = min(chunk_lo + ACC_CHUNK, row_hi);
-    const int rows = chunk_hi - chunk_lo;
-    // The chunk's rows into LDS.  This lane's (segment, column) for float f0 + lane of a row is fixed (as in
-    // pack_rows_kernel); a wave takes rows wave, wave + 4, ...: every load of the loop is in flight at once.  (Other
-    // resident workgroups -- up to ten per CU -- cover the latency of this copy and of the search below.)
-    for (int f0 = 0; f0 < row_floats; f0 += 64) {
-        const int f = f0 + lane;
-        int seg = -1, col = 0, w = 1;
-        {
-            int base = 0;
-            for (int s = 0; s < segs.nseg; s++) {
-                if (f >= base && f < base + segs.width[s]) { seg = s; col = f - base; w = segs.width[s]; }
-                base += segs.width[s];
-            }
-        }
-        if (seg >= 0) {
-            const float* sp = segs.ptr[seg] + (size_t)chunk_lo * w + col;
-            if (src.own_pos == 0) {
-#pragma unroll 4
-                for (int r = wave; r < rows; r += 4) s_tile[r * row_floats + f] = sp[(size_t)r * w];
-            } else {  // the owner's rows join the sum behind the first own_pos sources (below): start from zero
-#pragma unroll 4
-                for (int r = wave; r < rows; r += 4) s_tile[r * row_floats + f] = 0.0f;
-            }
-        }
-    }
-    // each source's rows of this chunk: group g = 32 lanes searches source g for both ends at once
+extern "C" int g4s_render_maps_forward(int width, int height, const float* allmap, const float* world_view_transform,
+                                       const float* full_proj_transform, float depth_ratio, float* rend_alpha,
+                                       float* rend_normal, float* rend_normal_cam, float* rend_depth, float* rend_dist,
+                                       float* surf_depth, float* surf_normal, float* surf_normal_cam, char* workspace,
+                                       size_t workspace_bytes, void* stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    clear_error();
+    if (width <= 0 || height <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "width, height must be positive");
+    if (!allmap || !world_view_transform || !full_proj_transform || !rend_alpha || !rend_normal || !rend_normal_cam ||
+        !rend_depth || !rend_dist || !surf_depth || !surf_normal || !surf_normal_cam)
+        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (!workspace || workspace_bytes < g4s_render_maps_workspace()) return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
     {
-        const int g = t >> 5, l32 = t & 31;
-        const bool live = g < src.nsrc;
-        const int off = live ? src.off[g] : 0, cnt = live ? src.cnt[g] : 0;
-        int lo[2] = {0, 0}, hi[2] = {cnt, cnt};
-        const int target[2] = {chunk_lo, chunk_hi};
-        for (int it = 0; it < 7; it++) {  // 32^7 > 2^31 rows (uniform trip count: the ballots need every lane)
-#pragma unroll
-            for (int e = 0; e < 2; e++) {
-                const int span = hi[e] - lo[e];
-                const int step = (span + 31) >> 5;
-                const int pos = lo[e] + l32 * step;
-                const bool valid = span > 0 && pos < hi[e];
-                int v = 0x7fffffff;
-                if (valid) v = __float_as_int(packed[(size_t)(off + pos) * buf_floats + row_floats]);
-                const uint64_t b = __ballot(valid && v < target[e]);
-                const uint64_t bv = __ballot(valid);
-                const int c = __popc((uint32_t)(b >> (32 * (lane >> 5))));    // probes below the target: a prefix
-                const int nv = __popc((uint32_t)(bv >> (32 * (lane >> 5))));  // valid probes
-                if (span > 0) {
-                    const int nlo = c == 0 ? lo[e] : lo[e] + (c - 1) * step + 1;
-                    const int nhi = c == 0 ? lo[e] : (c < nv ? lo[e] + c * step : hi[e]);
-                    lo[e] = nlo; hi[e] = nhi;
-                }
-            }
-            if (__syncthreads_or((hi[0] - lo[0]) | (hi[1] - lo[1])) == 0) break;  // every group has both ends
-        }
-        if (live && l32 == 0) { s_b0[g] = lo[0]; s_b1[g] = lo[1]; }
+        ProfScope ps(PF_MAPS_FWD, s);
+        MapsArgs a = maps_prepare(width, height, depth_ratio, allmap, world_view_transform, full_proj_transform, workspace, s);
+        a.rend_alpha = rend_alpha; a.rend_normal = rend_normal; a.rend_normal_cam = rend_normal_cam; a.rend_depth = rend_depth;
+        a.rend_dist = rend_dist; a.surf_depth = surf_depth; a.surf_normal = surf_normal; a.surf_normal_cam = surf_normal_cam;
+        hipLaunchKernelGGL(maps_fwd_kernel, maps_grid(width, height), dim3(MAPS_BX * MAPS_BY), 0, s, a);
     }
-    __syncthreads();
-    // Sources in order; a wave takes rows b0 + wave, + 4, ... of the source's sub-range, four of them in flight (a source
-    // holds a row once: the waves never meet on a tile row).
-    for (int s = 0; s <= src.nsrc; s++) {
-        if (s == src.own_pos && s != 0) {  // (uniform) the owner's own rows, in their place in the order
-            for (int f0 = 0; f0 < row_floats; f0 += 64) {
-                const int f = f0 + lane;
-                int seg = -1, col = 0, w = 1;
-                {
-                    int base = 0;
-                    for (int g = 0; g < segs.nseg; g++) {
-                        if (f >= base && f < base + segs.width[g]) { seg = g; col = f - base; w = segs.width[g]; }
-                        base += segs.width[g];
-                    }
-                }
-                if (seg >= 0) {
-                    const float* sp = segs.ptr[seg] + (size_t)chunk_lo * w + col;
-#pragma unroll 4
-                    for (int r = wave; r < rows; r += 4) s_tile[r * row_floats + f] += sp[(size_t)r * w];
-                }
-            }
-            __syncthreads();
-        }
-        if (s == src.nsrc) break;
-        const int b0 = s_b0[s], b1 = s_b1[s];
-        const float* base = packed + (size_t)src.off[s] * buf_floats;
-        for (int j0 = b0 + wave; j0 < b1; j0 += 16) {
-            int r[4];
-            float v[4][4];  // up to 4 x 64 floats per row (launch check: rows of at most 240 floats)
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const int j = j0 + 4 * u;
-                const bool ok = j < b1;
-                const float* rowp = base + (size_t)(ok ? j : b0) * buf_floats;
-                r[u] = ok ? __float_as_int(rowp[row_floats]) - chunk_lo : -1;
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const int f = lane + 64 * q;
-                    v[u][q] = f < row_floats ? rowp[f] : 0.0f;
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                // (unsigned: a received row whose index column lies outside this chunk -- a source that is not sorted, or
-                // that holds a row of another shard -- is dropped instead of being added outside the LDS tile)
-                if ((unsigned)r[u] < (unsigned)rows) {
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        const int f = lane + 64 * q;
-                        if (f < row_floats) s_tile[r[u] * row_floats + f] += v[u][q];
-                    }
-                }
-            }
-        }
-        __syncthreads();  // (the next source may hold the same rows)
-    }
-    for (int f0 = 0; f0 < row_floats; f0 += 64) {
-        const int f = f0 + lane;
-        int seg = -1, col = 0, w = 1;
-        {
-            int base = 0;
-            for (int s = 0; s < segs.nseg; s++) {
-                if (f >= base && f < base + segs.width[s]) { seg = s; col = f - base; w = segs.width[s]; }
-                base += segs.width[s];
-            }
-        }
-        if (seg >= 0) {
-            float* sp = segs.ptr[seg] + (size_t)chunk_lo * w + col;
-#pragma unroll 4
-            for (int r = wave; r < rows; r += 4) sp[(size_t)r * w] = s_tile[r * row_floats + f];
-        }
-    }
-}
-}  // namespace g4s
-
-extern "C" int g4s_accumulate_rows_launch_internal(int nseg, float* const* ptrs, const int* widths, int nsrc, const int* src_off,
-                                                   const int* src_cnt, const float* packed, int row_lo, int row_hi,
-                                                   hipStream_t s, int own_pos) {
-    g4s::RowSegs segs{};
-    segs.nseg = nseg;
-    int row_floats = 0;
-    for (int i = 0; i < nseg; i++) { segs.ptr[i] = ptrs[i]; segs.width[i] = widths[i]; row_floats += widths[i]; }
-    if (row_hi <= row_lo) return 0;
-    const size_t lds = (size_t)g4s::ACC_CHUNK * row_floats * sizeof(float);
-    if (lds > 60 * 1024) return -1;
-    const int blocks = (row_hi - row_lo + g4s::ACC_CHUNK - 1) / g4s::ACC_CHUNK;
-    if (own_pos != 0 && nsrc > 8) return -2;  // (the ordered form needs all sources in one launch)
-    for (int s0 = 0; s0 < nsrc; s0 += 8) {  // (more than eight sources: eight per launch, in order)
-        g4s::AccSources src{};
-        src.nsrc = nsrc - s0 < 8 ? nsrc - s0 : 8;
-        src.own_pos = own_pos;
-        for (int i = 0; i < src.nsrc; i++) { src.off[i] = src_off[s0 + i]; src.cnt[i] = src_cnt[s0 + i]; }
-        hipLaunchKernelGGL(g4s::accumulate_rows_kernel, dim3(blocks), dim3(256), lds, s, segs, src, packed, row_lo, row_hi);
-    }
-    return 0;
+    return stage_done("render_maps_forward", s);
 }
 
-extern "C" void g4s_pack_rows_launch_internal(int nseg, float* const* ptrs, const int* widths, const long long* idx, int n,
-                                              float* packed, int mode, hipStream_t s) {
-    RowSegs segs{};
-    segs.nseg = nseg;
-    for (int i = 0; i < nseg; i++) { segs.ptr[i] = ptrs[i]; segs.width[i] = widths[i]; }
-    if (n <= 0) return;
-    const int blocks = (n + 31) / 32 < 8192 ? (n + 31) / 32 : 8192;  // >= 8 rows per wave once n is large
-    hipLaunchKernelGGL(pack_rows_kernel, dim3(blocks), dim3(256), 0, s, segs, idx, n, packed, mode);
+extern "C" int g4s_render_maps_backward(int width, int height, const float* allmap, const float* surf_depth,
+                                        const float* world_view_transform, const float* full_proj_transform,
+                                        float depth_ratio, const float* dL_rend_alpha, const float* dL_rend_normal,
+                                        const float* dL_rend_normal_cam, const float* dL_rend_depth,
+                                        const float* dL_rend_dist, const float* dL_surf_depth, const float* dL_surf_normal,
+                                        const float* dL_surf_normal_cam, float* dL_dallmap, char* workspace,
+                                        size_t workspace_bytes, void* stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    clear_error();
+    if (width <= 0 || height <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "width, height must be positive");
+    if (!allmap || !surf_depth || !world_view_transform || !full_proj_transform || !dL_dallmap)
+        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (!workspace || workspace_bytes < g4s_render_maps_workspace()) return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
+    {
+        ProfScope ps(PF_MAPS_BWD, s);
+        MapsArgs a = maps_prepare(width, height, depth_ratio, allmap, world_view_transform, full_proj_transform, workspace, s);
+        a.surf_depth_in = surf_depth;
+        a.g_alpha = dL_rend_alpha; a.g_normal = dL_rend_normal; a.g_normal_cam = dL_rend_normal_cam; a.g_depth = dL_rend_depth;
+        a.g_dist = dL_rend_dist; a.g_surf_depth = dL_surf_depth; a.g_surf_normal = dL_surf_normal;
+        a.g_surf_normal_cam = dL_surf_normal_cam;
+        a.g_allmap = dL_dallmap;
+        hipLaunchKernelGGL(maps_bwd_kernel, maps_grid(width, height), dim3(MAPS_BX * MAPS_BY), 0, s, a);
+    }
+    return stage_done("render_maps_backward", s);
 }

@@ -543,10 +543,23 @@ __global__ void mark_visible_kernel(int P, const float* __restrict__ means3D, co
     const F3 p = mk3(means3D[3 * idx], means3D[3 * idx + 1], means3D[3 * idx + 2]);
     present[idx] = xform_point_4x3(p, view).z > 0.2f ? 1 : 0;
 }
-void launch_mark_visible(int P, const float* means3D, const float* viewmatrix, uint8_t* present, hipStream_t s) {
-    if (P <= 0) return;
-    hipLaunchKernelGGL(mark_visible_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, means3D, viewmatrix, present);
+}  // namespace g4s
+
+// Rasterizer::markVisible (rasterizer_impl.cu:141-153)
+extern "C" int g4s_rasterizer_mark_visible(int P, const float* means3D, const float* viewmatrix,
+                                           const float* projmatrix, uint8_t* present, void* stream_) {
+    using namespace g4s;
+    (void)projmatrix;
+    hipStream_t stream = (hipStream_t)stream_;
+    clear_error();
+    if (P < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "P < 0");
+    if (P == 0) return G4S_OK;
+    if (!means3D || !viewmatrix || !present) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL pointer");
+    hipLaunchKernelGGL(mark_visible_kernel, dim3((P + 255) / 256), dim3(256), 0, stream, P, means3D, viewmatrix, present);
+    return stage_done("mark_visible", stream);
 }
+
+namespace g4s {
 
 // ---- backward ----------------------------------------------------------------------------
 

@@ -640,7 +640,7 @@ class OwnerReduce:
 
 
 def adam_update_(p, g, m, v, lr, step, beta1=0.9, beta2=0.999, eps=1e-15):
-    """Plain Adam on host tensors, element by element what csrc/loss.hip's adam_kernel computes (torch.optim.Adam's
+    """Plain Adam on host tensors, element by element what csrc/optim.hip's adam_kernel computes (torch.optim.Adam's
     single-tensor formula): used by ShardedAdam on CPU (gloo tests) -- on a HIP device the kernel itself runs."""
     bc1 = 1.0 - beta1 ** step
     bc2 = 1.0 - beta2 ** step

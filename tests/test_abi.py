@@ -34,7 +34,7 @@ def test_library_exports_every_declared_symbol(hip_lib):
         assert name in exported, f"{name} declared in the header but not exported"
         assert hasattr(hip_lib, name)
     for name in exported:
-        if name.startswith("g4s_") and not name.endswith("_internal"):
+        if name.startswith("g4s_"):
             assert name in decls, f"{name} exported but not declared in include/*.h"
 
 
@@ -133,6 +133,42 @@ def test_argument_validation_is_host_side(hip_lib):
     wide = (ctypes.c_int * 2)(200, 48)
     rc = lib.g4s_accumulate_rows(2, segs, wide, 1, off, cnt, one, 0, 64, nul)
     assert rc < 0 and b"wider than 240" in lib.g4s_last_error()
+    expect(lib.g4s_accumulate_rows_ordered(2, segs, wid, 1, off, cnt, one, 0, 64, 2, nul), "0 <= own_position <= nsrc")
+    rc = lib.g4s_accumulate_rows_ordered(2, segs, wid, 9, off, cnt, one, 0, 64, 1, nul)
+    assert rc == -4 and b"at most 8 sources" in lib.g4s_last_error()  # G4S_ERR_UNSUPPORTED
+    # packed rows of the exchange (g4s_pack_rows)
+    expect(lib.g4s_pack_rows(9, segs, wid, one, 4, one, 0, nul), "1..8 segments, n >= 0")
+    expect(lib.g4s_pack_rows(2, segs, wid, one, 4, one, 4, nul), "mode: bit 0 unpack")
+    # row compaction
+    big = 1 << 20
+    expect(lib.g4s_compact_scan(-1, one, one, one, big, nul), "must not be negative")
+    expect(lib.g4s_compact_scan(5, one, nul, one, big, nul), "NULL required pointer")
+    expect(lib.g4s_compact_scan(5, one, one, one, 8, nul), "workspace too small")
+    src1, dst1 = (ctypes.c_void_p * 1)(256), (ctypes.c_void_p * 1)(512)
+    expect(lib.g4s_compact_gather(5, one, one, 1, src1, dst1, (ctypes.c_int * 1)(3), -1, nul), "must not be negative")
+    expect(lib.g4s_compact_gather(5, one, one, 1, src1, dst1, (ctypes.c_int * 1)(0), 0, nul),
+           "tensor 0: NULL pointer or width <= 0")
+    # activations: float2 / float4 accesses need aligned bases
+    expect(lib.g4s_activations_forward(5, one, ctypes.c_void_p(264), one, one, one, one, nul), "16-byte aligned")
+    expect(lib.g4s_activations_backward(5, ctypes.c_void_p(260), one, one, one, one, one, one, one, one, nul),
+           "scale tensors must be 8-byte")
+    # Adam
+    ptr1 = (ctypes.c_void_p * 1)(256)
+    numel, lr = (ctypes.c_longlong * 1)(5), (ctypes.c_double * 1)(1e-3)
+    expect(lib.g4s_adam_step(1, ptr1, ptr1, ptr1, ptr1, numel, lr, (ctypes.c_int * 1)(0), 0.9, 0.999, 1e-15, nul),
+           "segment 0: numel < 0 or step < 1")
+    expect(lib.g4s_adam_step_device(1, ptr1, ptr1, ptr1, ptr1, numel, one, ptr1, nul, 0.9, 0.999, 1e-15, nul), "NULL array")
+    # render maps
+    outs8 = (one,) * 8
+    expect(lib.g4s_render_maps_forward(0, 4, one, one, one, 0.5, *outs8, one, big, nul), "must be positive")
+    expect(lib.g4s_render_maps_forward(4, 4, one, one, one, 0.5, *outs8, one, 8, nul), "workspace too small")
+    expect(lib.g4s_render_maps_backward(4, 4, one, one, one, one, 0.5, *outs8, nul, one, big, nul), "NULL required pointer")
+    # kNN, markVisible, photometric loss
+    expect(lib.g4s_knn_mean_dist(-1, one, one, one, big, nul), "P < 0")
+    expect(lib.g4s_knn_mean_dist(5, one, nul, one, big, nul), "NULL pointer")
+    expect(lib.g4s_knn_mean_dist(5, one, one, one, 8, nul), "workspace too small")
+    expect(lib.g4s_rasterizer_mark_visible(-1, one, one, one, one, nul), "P < 0")
+    expect(lib.g4s_photometric_loss(4, 4, one, one, 0.2, one, nul, one, 8, nul), "workspace too small")
 
 
 def _layout(lib, P, R, W, H):
