@@ -124,6 +124,18 @@ SIGNATURES = {
     "g4s_voxel_downsample_count": (c_i, [c_i, c_p, c_f, c_p, c_p, c_sz, c_p]),
     "g4s_voxel_downsample_emit": (c_i, [c_i, c_p, c_i, c_p, c_p, c_sz, c_p]),
     "g4s_mesh_sample_surface": (c_i, [c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "g4s_visgrid_workspace": (c_sz, [c_i]),
+    "g4s_visgrid_build": (c_i, [c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_visgrid_sample": (c_i, [c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_visgrid_march": (c_i, [c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_sz, c_p]),
+    "g4s_visgrid_march_bytes": (c_i, [c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_sz, c_p]),
+    "g4s_visgrid_expand": (c_i, [c_i, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_visgrid_compact_workspace": (c_sz, [c_i]),
+    "g4s_visgrid_compact_count": (c_i, [c_i, c_p, c_i, c_p, c_p, c_sz, c_p]),
+    "g4s_visgrid_compact_emit": (c_i, [c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_sz, c_p]),
+    "g4s_view_counts_points": (c_i, [c_i, c_p, c_i, c_f, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_view_counts_pixels": (c_i, [c_i, c_i, c_p, c_p, c_i, c_f, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_depth_to_points": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_sz, c_p]),
 }
 
 _lib = None

@@ -142,6 +142,21 @@ def write_triangle_mesh(path, mesh):
         f.write(face.tobytes())
 
 
+def write_point_cloud(path, points):
+    """Binary little-endian PLY of a bare point cloud: one `vertex` element with x y z float (what trimesh's
+    PointCloud.export writes for the reference's invisible-voxel dump, without its colours).  A device tensor is copied
+    to the host here; read_ply_vertices reads the file back."""
+    if hasattr(points, "detach"):
+        points = points.detach().cpu().numpy()
+    p = np.ascontiguousarray(points, "<f4").reshape(-1, 3)
+    header = f"ply\nformat binary_little_endian 1.0\nelement vertex {len(p)}\nproperty float x\nproperty float y\n" \
+             "property float z\nend_header\n"
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(p.tobytes())
+
+
 def read_triangle_mesh(path):
     """-> (vertices [V,3] float32, vertex_colors [V,3] float32 in [0,1], triangles [F,3] int32) of a file written by
     write_triangle_mesh (binary little endian, that exact layout)."""

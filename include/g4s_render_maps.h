@@ -447,6 +447,112 @@ int g4s_mesh_sample_surface(int n_samples, const float* u, const double* cum_are
                             int n_vertices, const float* vertices, float* points_out, float* normals_out, int* face_out,
                             void* stream);
 
+/* =====================================================================================================================
+ * Visibility grid (g4splat_amd/csrc/tsdf/visibility.hip).
+ *
+ * The stage the reference puts between training and inpainting (2d-gaussian-splatting/render_novel_views.py,
+ * guidance/vis_grid.py VisibilityGrid, guidance/cam_utils.py project_points_to_image / check_valid_camera_center_by_depth /
+ * build_visibility_masks, planes/get_global_3Dpnts.py get_visible_mask_for_input_views): which voxels of the scene's box
+ * some input view sees in free space, which pixels of a candidate view look only through such voxels, and how many views
+ * confirm a point.  As above, the semantics are this library's own, stated exactly (tests/visibility_ref.py restates them
+ * in numpy): float32, round-to-nearest-even, correctly rounded /, no fused multiply-add except the one named below,
+ * evaluated left to right as written; min / max are IEEE minNum / maxNum (a NaN operand yields the other one).
+ *
+ * Views.  V views.  View v has world_view_transform Wv (16 floats, row-major, row-vector convention: M[r][c] = M[4r + c]),
+ *   focal = {fx, fy} and a depth map [H,W], a float32 device pointer; W and H may differ between views (sizes = {W0, H0,
+ *   W1, H1, ...}) and are the map's, whatever the camera says.  fx = W / (2 tan(FoVx / 2)), fy = H / (2 tan(FoVy / 2)), computed
+ *   by the caller in double and rounded to float.
+ * Projection of a point p into a view:  c_j = ((p0*Wv[0][j] + p1*Wv[1][j]) + p2*Wv[2][j]) + Wv[3][j] for j = 0, 1, 2; z = c_2;
+ *   u = (c_0 / z) * fx + W/2, v = (c_1 / z) * fy + H/2 (W/2 = float(W) * 0.5, exact).  in image iff u >= 0 && u < W &&
+ *   v >= 0 && v < H (every comparison with a NaN is false).  The tap is nearest by truncation:
+ *   d = depth[min(int(v), H - 1)][min(int(u), W - 1)]; it is read only when the point is in the image.
+ * Predicates per (point, view):  FREE (mode 0) = in image && z > 0 && z < d.  SURFACE (mode 1) = in image && z > 0 &&
+ *   |z - d| / (z + 1e-6) < depth_threshold.
+ * Grid.  resolution R >= 1, R^3 < 2^31, over the box bbox_min .. bbox_max (3 host floats each, finite, max > min on every
+ *   axis).  extent = bbox_max - bbox_min and grid_size = extent / float(R) per axis.  The centre of voxel (ix, iy, iz) is
+ *   bbox_min + (float(i) + 0.5) * grid_size per axis; its flat index is (ix * R + iy) * R + iz, z fastest.  A voxel is
+ *   visible iff some view passes FREE at its centre.  Storage: ceil(R^3 / 64) 64-bit words, bit (flat & 63) of word
+ *   (flat >> 6); the bits beyond R^3 are zero.  No atomics: every word is written once.
+ * Point -> voxel:  per axis i = int(min(max(((p - bbox_min) / extent) * float(R), 0), float(R - 1))), clamped as a float and
+ *   then truncated.  A point outside the box lands in a border voxel (the reference's behaviour); a NaN coordinate gives
+ *   index 0 (stated here; the reference leaves it undefined).
+ * Ray record of a camera:  twelve host floats, origin o[3] then D[3][3] row-major.  For integer pixel coordinates (x, y),
+ *   no half-pixel offset: dir_r = (D[r][0]*x + D[r][1]*y) + D[r][2], and the point at parameter t is o_r + t * dir_r.  The
+ *   caller computes the record in double (c2w = inverse of Wv^T; D = c2w[:3,:3] times the inverse of the pixel intrinsics
+ *   the reference derives from full_proj_transform and the map's size; o = c2w[:3,3]) and rounds it to float.
+ * Back-projection of a depth map [H,W]:  pixel i = y * W + x with depth q gives the point o_r + q * dir_r.
+ * Ray march of a depth map [H,W] with n_samples = S >= 1:  a pixel with depth <= 1e-6 is invalid and gets 0.  Any other
+ *   pixel with depth q gets 1 iff for every k in [0, S - 10) the voxel of the point at t = t_k * q is visible, else 0;
+ *   S <= 10 means no sample, every valid pixel gets 1.  t_k is element k of torch.linspace(0, 1, S) in float32:
+ *   step = 1 / float(S - 1); t_k = step * float(k) for k < S / 2 (integer division), otherwise
+ *   t_k = fma(-step, float(S - 1 - k), 1), a single rounding -- the one fused operation of this section, because torch's
+ *   kernel fuses it.  The caller chooses S; the reference's is int(m / min(grid_size)) + 1 with m the largest depth after
+ *   every invalid pixel was replaced by 1e-3.  The depth map is only read (the reference overwrites its invalid pixels).
+ * Compaction.  The centres of the visible (invisible != 0: of the invisible) voxels in ascending flat index, two-phase:
+ *   compact_count reads back their number (one host synchronisation); compact_emit, same resolution, words, `invisible`
+ *   and workspace, the workspace untouched in between, writes centres [n_points,3] and nothing beyond n_points.
+ * View counts.  counts[i] = the number of views v != skip_view (-1: none is skipped) that pass the predicate of `mode` at
+ *   point i -- an explicit point, or pixel i of pixel_depth back-projected with `ray`.
+ *
+ * world_view [V,16], focal [V,2], sizes [V,2] and the array of V map pointers are HOST arrays, read during the call (the
+ * library packs them into a table in the workspace, g4s_visgrid_workspace(V) bytes).  Every argument is checked on the
+ * host before anything is launched.  Every entry point takes workspace, workspace_bytes; those that name no size query use
+ * none and accept NULL, 0.
+ */
+
+/* Bytes of device workspace of g4s_visgrid_build / g4s_view_counts_points / g4s_view_counts_pixels for n_views views. */
+size_t g4s_visgrid_workspace(int n_views);
+
+/* words [ceil(resolution^3 / 64)]: the packed grid, every word written once.  n_views = 0: all zero. */
+int g4s_visgrid_build(int resolution, const float* bbox_min, const float* bbox_max, int n_views, const float* world_view,
+                      const float* focal, const int* sizes, const float* const* depth, unsigned long long* words,
+                      char* workspace, size_t workspace_bytes, void* stream);
+
+/* visible [n_points]: 1 iff the voxel of points [n_points,3] (device) is visible. */
+int g4s_visgrid_sample(int resolution, const float* bbox_min, const float* bbox_max, const unsigned long long* words,
+                       int n_points, const float* points, unsigned char* visible, char* workspace, size_t workspace_bytes,
+                       void* stream);
+
+/* visibility [height,width] float32, 0 or 1: the ray march of depth [height,width] with the ray record `ray`. */
+int g4s_visgrid_march(int resolution, const float* bbox_min, const float* bbox_max, const unsigned long long* words,
+                      int width, int height, const float* depth, const float* ray, int n_samples, float* visibility,
+                      char* workspace, size_t workspace_bytes, void* stream);
+
+/* The same march over a grid of one byte per voxel [resolution^3] (non-zero = visible) in flat-index order: the storage
+ * the packed words are measured against (tools/bench_visibility.py); the results are the same. */
+int g4s_visgrid_march_bytes(int resolution, const float* bbox_min, const float* bbox_max, const unsigned char* grid,
+                            int width, int height, const float* depth, const float* ray, int n_samples, float* visibility,
+                            char* workspace, size_t workspace_bytes, void* stream);
+
+/* grid [resolution^3] float32, 0 or 1 in flat-index order: the reference's `visibility_grid`. */
+int g4s_visgrid_expand(int resolution, const unsigned long long* words, float* grid, char* workspace, size_t workspace_bytes,
+                       void* stream);
+
+/* Bytes of device workspace of the compaction (0 for a resolution outside the grid's range). */
+size_t g4s_visgrid_compact_workspace(int resolution);
+
+int g4s_visgrid_compact_count(int resolution, const unsigned long long* words, int invisible, int* n_points,
+                              char* workspace, size_t workspace_bytes, void* stream);
+
+int g4s_visgrid_compact_emit(int resolution, const float* bbox_min, const float* bbox_max, const unsigned long long* words,
+                             int invisible, int n_points, float* centres, char* workspace, size_t workspace_bytes,
+                             void* stream);
+
+/* counts [n_points] int32 for points [n_points,3] (device). */
+int g4s_view_counts_points(int n_points, const float* points, int mode, float depth_threshold, int skip_view, int n_views,
+                           const float* world_view, const float* focal, const int* sizes, const float* const* depth,
+                           int* counts, char* workspace, size_t workspace_bytes, void* stream);
+
+/* counts [height,width] int32 for the pixels of pixel_depth [height,width] back-projected with `ray`. */
+int g4s_view_counts_pixels(int width, int height, const float* pixel_depth, const float* ray, int mode,
+                           float depth_threshold, int skip_view, int n_views, const float* world_view, const float* focal,
+                           const int* sizes, const float* const* depth, int* counts, char* workspace, size_t workspace_bytes,
+                           void* stream);
+
+/* points [height * width,3]: the back-projection of depth [height,width] with `ray`. */
+int g4s_depth_to_points(int width, int height, const float* depth, const float* ray, float* points, char* workspace,
+                        size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
