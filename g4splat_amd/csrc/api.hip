@@ -306,7 +306,7 @@ static int rasterizer_forward_impl(const ForwardCall& c) {
     uint32_t* ranges = (uint32_t*)(img + IL.ranges);
     float* final_T = (float*)(img + IL.final_T);
     uint32_t* n_contrib = (uint32_t*)(img + IL.n_contrib);
-    if (P <= 0) HIP_TRY(hipMemsetAsync(ranges, 0, (size_t)tiles * 8, stream));  // rasterizer_impl.cu:311 (P > 0: cleared by the totals scan)
+    if (P <= 0) HIP_TRY(hipMemsetAsync(ranges, 0, (size_t)tiles * 8, stream));  // rasterizer_impl.cu:311 (P > 0: cleared by the preprocess)
     const bool presized = c.capacity >= 0;
     if (presized && c.status_dev && P <= 0) HIP_TRY(hipMemsetAsync(c.status_dev, 0, 16, stream));
 
@@ -364,6 +364,7 @@ static int rasterizer_forward_impl(const ForwardCall& c) {
         pa.vis_block_sums = (uint32_t*)(geom + GL.vis_block_sums);
         pa.key_min_blocks = (uint32_t*)(geom + GL.key_min_blocks);
         pa.key_max_blocks = (uint32_t*)(geom + GL.key_max_blocks);
+        pa.zero_ptr = ranges; pa.zero_words = (uint32_t)tiles * 2u;  // rasterizer_impl.cu:311
         { ProfScope ps(PF_PREPROCESS_FWD, stream); launch_preprocess_fwd(pa, stream); }
         CHECK_LAUNCH("preprocess_fwd");
 
@@ -384,7 +385,7 @@ static int rasterizer_forward_impl(const ForwardCall& c) {
         }
         { ProfScope ps(PF_COUNT_SCAN, stream);
           launch_scan_totals(pa.idx_block_sums, idx_block_offs, pa.ref_block_sums, pa.vis_block_sums, vis_block_offs,
-                             d_total, GL.nblocks, ranges, tiles * 2, stream, presized ? (uint32_t)c.capacity : 0xFFFFFFFFu,
+                             d_total, GL.nblocks, nullptr, 0, stream, presized ? (uint32_t)c.capacity : 0xFFFFFFFFu,
                              h_total_dev, presized ? c.status_dev : nullptr, pa.key_min_blocks, pa.key_max_blocks); }
         CHECK_LAUNCH("scan totals");
         if (!presized) {

@@ -307,15 +307,24 @@ __global__ void __launch_bounds__(256) count_block_sums_kernel(int P, const uint
     const int r = (int)(blockIdx.x * 256 + threadIdx.x);
     uint32_t c = 0;
     if (r < P) c = tiles_touched[gidx[r]];
-    uint32_t total;
-    const uint32_t local = block256_excl_scan_u32(c, sm4, &total);
-    if (r < P) rank_local[r] = local;
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
+    const int w = (int)(threadIdx.x >> 6);
+    const uint32_t inc = wave_incl_scan_u32_full_wave(c);
+    if (lane_id() == 63) sm4[w] = inc;
+    __syncthreads();
+    const uint32_t s0 = sm4[0], s1 = sm4[1], s2 = sm4[2], s3 = sm4[3];
+    if (r < P) rank_local[r] = (w > 0 ? s0 : 0u) + (w > 1 ? s1 : 0u) + (w > 2 ? s2 : 0u) + inc - c;
+    if (threadIdx.x == 0) block_sums[blockIdx.x] = (s0 + s1) + (s2 + s3);
 }
 
 // Single block: exclusive scan of up to two arrays of block sums (b may be NULL), the sum of a third (ref, may be
-// NULL), and an optional clear of `zero_words` 32-bit words (the tile ranges, rasterizer_impl.cu:311 -- folded in
-// here to save a launch).  Totals: total_a[0] = sum(a), total_a[1] = sum(ref), total_b[0] = sum(b).
+// NULL), and an optional clear of `zero_words` 32-bit words (the rasterizer clears its tile ranges beside the preprocess
+// instead and passes 0).  Totals: total_a[0] = sum(a), total_a[1] = sum(ref), total_b[0] = sum(b).
+// One sweep: a pass covers SCAN_CHUNKS runs of 1 024 consecutive sums, thread t owning element t of every run, so all
+// loads of a pass are coalesced and in flight together; the values stay in registers, every run is scanned by its 16
+// waves, the 16 * SCAN_CHUNKS wave totals are scanned once more by every wave for itself, and the offsets are written
+// from the registers.  (The first form -- thread t walking `seg` consecutive sums twice, stride-`seg` loads, the second
+// walk behind the first -- took 9.1 us for the 5 860 blocks of S3 against a launch floor of 4.8.)
+constexpr int SCAN_CHUNKS = 8;
 __global__ void __launch_bounds__(1024) scan_block_sums_kernel(int nblocks, const uint32_t* __restrict__ a_sums,
                                                                uint32_t* __restrict__ a_offs,
                                                                const uint32_t* __restrict__ b_sums,
@@ -328,54 +337,101 @@ __global__ void __launch_bounds__(1024) scan_block_sums_kernel(int nblocks, cons
                                                                uint32_t* __restrict__ status_out,
                                                                const uint32_t* __restrict__ kmin_blocks,
                                                                const uint32_t* __restrict__ kmax_blocks) {
-    __shared__ uint32_t wa[16], wb[16], wr[16], wlo[16], whi[16];
-    const int t = (int)threadIdx.x;
+    __shared__ uint32_t s_wa[16 * SCAN_CHUNKS], s_wb[16 * SCAN_CHUNKS];  // wave totals of a pass, [run][wave]
+    __shared__ uint32_t wr[16], wlo[16], whi[16];
+    const int t = (int)threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
     for (int i = t; i < zero_words; i += 1024) zero_ptr[i] = 0u;
     if (d_n != nullptr) nblocks = (int)((*d_n + 255u) / 256u);  // blocks of a device-side element count
-    const int seg = (nblocks + 1023) / 1024;
-    const int b = imin_(nblocks, t * seg), e = imin_(nblocks, b + seg);
-    uint32_t sa = 0, sb = 0, sr = 0, klo = 0xFFFFFFFFu, khi = 0u;
-    for (int i = b; i < e; i++) {
-        sa += a_sums[i];
-        if (b_sums) sb += b_sums[i];
-        if (ref_sums) sr += ref_sums[i];
-        if (kmin_blocks) {  // range of the frame's depth keys
-            klo = min(klo, kmin_blocks[i]);
-            khi = max(khi, kmax_blocks[i]);
+    uint32_t all_a = 0, all_b = 0, sr = 0, klo = 0xFFFFFFFFu, khi = 0u;
+    const uint32_t* pb = b_sums != nullptr ? b_sums : a_sums;
+    const uint32_t* pr = ref_sums != nullptr ? ref_sums : a_sums;
+    const uint32_t* plo = kmin_blocks != nullptr ? kmin_blocks : a_sums;
+    const uint32_t* phi = kmin_blocks != nullptr ? kmax_blocks : a_sums;
+    int first = 0;
+    do {  // (uniform; one pass up to 8 192 blocks)
+        const bool last = first + 1024 * SCAN_CHUNKS >= nblocks;
+        uint32_t va[SCAN_CHUNKS], vb[SCAN_CHUNKS], vr[SCAN_CHUNKS], vlo[SCAN_CHUNKS], vhi[SCAN_CHUNKS];
+#pragma unroll
+        for (int c = 0; c < SCAN_CHUNKS; c++) {  // every load of the pass before the first use
+            // Straight-line: a lane past the end rereads word 0 (every array holds at least one) and an absent array
+            // stands in a_sums; both are dropped below.  (A load under a lane mask or behind a pointer test sits in a
+            // branch of its own, and hipcc put the first use, with its wait, into the first such branch.)
+            const int i = first + 1024 * c + t;
+            const int ic = i < nblocks ? i : 0;
+            va[c] = a_sums[ic];
+            vb[c] = pb[ic];
+            vr[c] = pr[ic];
+            vlo[c] = plo[ic];
+            vhi[c] = phi[ic];
         }
-    }
-    if (kmin_blocks) {
-        klo = ~wave_max_u32_full_wave(~klo);
-        khi = wave_max_u32_full_wave(khi);
-    }
-    const uint32_t ia = wave_incl_scan_u32(sa), ib = wave_incl_scan_u32(sb), ir = wave_incl_scan_u32(sr);
-    if ((t & 63) == 63) {
-        wa[t >> 6] = ia;
-        wb[t >> 6] = ib;
-        wr[t >> 6] = ir;
-        wlo[t >> 6] = klo;
-        whi[t >> 6] = khi;
-    }
-    __syncthreads();
-    uint32_t base_a = 0, base_b = 0, all_a = 0, all_b = 0, all_r = 0;
-    for (int w = 0; w < 16; w++) {
-        if (w < (t >> 6)) { base_a += wa[w]; base_b += wb[w]; }
-        all_a += wa[w];
-        all_b += wb[w];
-        all_r += wr[w];
-    }
-    uint32_t run_a = base_a + ia - sa, run_b = base_b + ib - sb;
-    for (int i = b; i < e; i++) {
-        a_offs[i] = run_a;
-        run_a += a_sums[i];
-        if (b_sums) { b_offs[i] = run_b; run_b += b_sums[i]; }
-    }
+#pragma unroll
+        for (int c = 0; c < SCAN_CHUNKS; c++) {
+            const bool in = first + 1024 * c + t < nblocks;
+            va[c] = in ? va[c] : 0u;
+            vb[c] = in && b_sums != nullptr ? vb[c] : 0u;
+            vr[c] = in && ref_sums != nullptr ? vr[c] : 0u;
+            vlo[c] = in && kmin_blocks != nullptr ? vlo[c] : 0xFFFFFFFFu;  // range of the frame's depth keys
+            vhi[c] = in && kmin_blocks != nullptr ? vhi[c] : 0u;
+        }
+        uint32_t ia[SCAN_CHUNKS], ib[SCAN_CHUNKS];
+#pragma unroll
+        for (int c = 0; c < SCAN_CHUNKS; c++) {
+            ia[c] = ib[c] = 0u;
+            if (first + 1024 * c < nblocks) {  // (uniform: a run past the end holds zeros)
+                ia[c] = wave_incl_scan_u32_full_wave(va[c]);
+                if (b_sums != nullptr) ib[c] = wave_incl_scan_u32_full_wave(vb[c]);
+                sr += vr[c];
+                klo = min(klo, vlo[c]);
+                khi = max(khi, vhi[c]);
+            }
+            if (lane == 63) {
+                s_wa[16 * c + w] = ia[c];
+                s_wb[16 * c + w] = ib[c];
+            }
+        }
+        if (last) {  // the sums and ranges that need no offsets, by wave: the barrier below publishes them too
+            const uint32_t ir = wave_sum_to_lane63(sr);
+            if (kmin_blocks) {
+                klo = ~wave_max_u32_full_wave(~klo);
+                khi = wave_max_u32_full_wave(khi);
+            }
+            if (lane == 63) {
+                wr[w] = ir;
+                wlo[w] = klo;
+                whi[w] = khi;
+            }
+        }
+        __syncthreads();
+        // exclusive scan of the wave totals in (run, wave) order, two per lane, by every wave for itself
+        const uint32_t a0 = s_wa[2 * lane], a1 = s_wa[2 * lane + 1], b0 = s_wb[2 * lane], b1 = s_wb[2 * lane + 1];
+        const uint32_t inc_a = wave_incl_scan_u32_full_wave(a0 + a1), inc_b = wave_incl_scan_u32_full_wave(b0 + b1);
+        const uint32_t ex_a = inc_a - (a0 + a1), ex_b = inc_b - (b0 + b1);
+#pragma unroll
+        for (int c = 0; c < SCAN_CHUNKS; c++) {
+            const int i = first + 1024 * c + t;
+            if (first + 1024 * c >= nblocks) break;  // (uniform)
+            const int src = (16 * c + w) >> 1;       // the lane that holds this wave's total of run c: its first word if w is even
+            const uint32_t pa = (uint32_t)__builtin_amdgcn_readlane((int)(w & 1 ? ex_a + a0 : ex_a), src);
+            const uint32_t pb = (uint32_t)__builtin_amdgcn_readlane((int)(w & 1 ? ex_b + b0 : ex_b), src);
+            if (i < nblocks) {
+                a_offs[i] = all_a + pa + (ia[c] - va[c]);
+                if (b_sums != nullptr) b_offs[i] = all_b + pb + (ib[c] - vb[c]);
+            }
+        }
+        all_a += (uint32_t)__builtin_amdgcn_readlane((int)inc_a, 63);
+        all_b += (uint32_t)__builtin_amdgcn_readlane((int)inc_b, 63);
+        first += 1024 * SCAN_CHUNKS;
+        if (last) break;
+        __syncthreads();  // (the next pass overwrites the wave totals)
+    } while (true);
     if (t == 0) {
+        uint32_t all_r = 0;
+        for (int k = 0; k < 16; k++) all_r += wr[k];
         total_a[0] = all_a;
         total_a[1] = all_r;
         if (kmin_blocks) {  // total[5] = smallest depth key of the frame (the sort subtracts it), total[6] = largest
             uint32_t lo = 0xFFFFFFFFu, hi = 0u;
-            for (int w = 0; w < 16; w++) { lo = min(lo, wlo[w]); hi = max(hi, whi[w]); }
+            for (int k = 0; k < 16; k++) { lo = min(lo, wlo[k]); hi = max(hi, whi[k]); }
             if (lo > hi) lo = hi = 0u;  // (no emitting Gaussian)
             total_a[5] = lo;
             total_a[6] = hi;
@@ -416,12 +472,20 @@ void launch_count_scan(int P, const uint32_t* gidx_sorted, const uint32_t* tiles
 // Load-balanced expansion, partitioned by OUTPUT: a block owns EMIT_SLOTS consecutive instance slots, whatever
 // Gaussians they belong to -- the nearest splats cover hundreds of tiles each, the far ones one or two, and a block
 // per 256 depth ranks (the first design) left the few blocks of the nearest ranks running ten times longer than the
-// rest.  Every depth rank emits at least one instance, so at most EMIT_SLOTS + 1 ranks reach into a block's window:
-// the first one is found with three block-wide counting steps over the monotone offset arrays (no serial binary
-// search over global memory), their offsets, indices and tile rects are staged in LDS, and every thread then
-// produces output slots: a binary search in the LDS offsets, one coalesced 8-byte store per slot.
+// rest.  Every depth rank emits at least one instance, so at most EMIT_SLOTS ranks own a slot of a block's window: the
+// one that reaches into it from before and those that begin inside.  The block lives as long as its chain of dependent loads, so the chain is kept to three:
+//   1. the group offsets (block_offs) in one coalesced probe: the 256-rank group g that holds slot w0 and the last
+//      group that begins below the window's end -- at most four groups further on, a full group holds >= 256 slots;
+//   2. rank_local and gidx of those groups' ranks, all at once: the first rank r_first is a count over group g;
+//   3. the tile rects of the ranks whose first slot lies below the window's end.
+// Every staged rank then marks its first slot of the window with its staging index, an inclusive max-scan over the
+// window's slots gives every slot its owner, and a thread produces four consecutive slots (two 16-byte stores).
+// (The first form found g in two dependent rounds, r_first in two more, staged behind a fifth and ran an 11-step
+// binary search over the staged offsets per slot: 27.8 us on S3, of which the 35 MB it writes explain about 11.)
 // The block also clears its slots of the forward's contribution masks (qhit), which saves a memset launch.
 constexpr int EMIT_SLOTS = 1024;
+constexpr int EMIT_PROBES = 8;   // group offsets a thread probes in step 1: up to 2 048 groups in one round
+constexpr int EMIT_GROUPS = 5;   // groups whose ranks can begin below the end of a window (see above)
 // d_counts != NULL (g4s_rasterizer_forward_presized: the host never learns the counts): V = d_counts[0] emitting
 // Gaussians, R_b = d_counts[1] instances (already clamped to the caller's capacity); the grid is sized for the
 // capacity and surplus blocks leave.
@@ -433,12 +497,11 @@ __global__ void __launch_bounds__(256) emit_kernel(int V, uint32_t R_b, int tile
                                                    uint64_t* __restrict__ entries, uint8_t* __restrict__ qhit,
                                                    uint8_t* __restrict__ rec_flag,
                                                    const uint32_t* __restrict__ d_counts) {
-    __shared__ uint32_t s_off[EMIT_SLOTS + 4];  // first slot of the staged ranks (ascending), then a sentinel
-    __shared__ uint32_t s_idx[EMIT_SLOTS + 4];
-    __shared__ uint32_t s_rect[EMIT_SLOTS + 4];   // x0 | y0 << 16
-    __shared__ uint32_t s_rect2[EMIT_SLOTS + 4];  // rect width in tiles
-    __shared__ uint32_t s_nr;
-    const int t = (int)threadIdx.x;
+    // staged ranks (ascending): first slot, Gaussian, rect origin x0 | y0 << 16, rect width in tiles
+    __shared__ __attribute__((aligned(16))) uint4 s_rank[EMIT_SLOTS];
+    __shared__ __attribute__((aligned(8))) uint16_t s_owner[EMIT_SLOTS];  // per slot of the window: staging index of the rank that begins there, else 0
+    __shared__ uint32_t s_cnt[4], s_wmax[4];
+    const int t = (int)threadIdx.x, lane = t & 63, wv = t >> 6;
     if (d_counts != nullptr) {
         V = (int)d_counts[0];
         R_b = d_counts[1];
@@ -458,56 +521,91 @@ __global__ void __launch_bounds__(256) emit_kernel(int V, uint32_t R_b, int tile
             for (uint32_t i = o; i < w1; i++) { qhit[i] = 0; rec_flag[i] = 0; }
         }
     }
-    if (t == 0) s_nr = 0;
-    // the 256-rank group that holds slot w0: last g with block_offs[g] <= w0 (block_offs[0] == 0)
+    *reinterpret_cast<uint2*>(&s_owner[4 * t]) = make_uint2(0u, 0u);
+    // step 1.  More than 2 044 groups (half a million emitting Gaussians): 256-way rounds first, as far as a segment
+    // that one round of EMIT_PROBES probes per thread covers together with the four groups behind it
     int lo = 0, n = nblocks_v;
-    while (n > 1) {  // uniform; two rounds up to 65 536 groups
+    while (n > 256 * EMIT_PROBES - (EMIT_GROUPS - 1)) {  // uniform
         const int S = (n + 255) / 256;
         const int j = lo + t * S;
         const int c = __syncthreads_count(t * S < n && block_offs[j] <= w0);
         lo += (c - 1) * S;
         n = imin_(S, n - (c - 1) * S);
     }
-    const int g = lo;
-    const uint32_t goff = block_offs[g];
-    int r_first;
+    n = imin_(n + (EMIT_GROUPS - 1), nblocks_v - lo);
+    uint32_t c_le = 0, c_lt = 0;  // this wave's probes <= w0 (block_offs[lo] is one) and < w1
     {
-        const int r = 256 * g + t;
-        const int c = __syncthreads_count(r < V && goff + rank_local[r] <= w0);
-        r_first = 256 * g + c - 1;
+        uint32_t v[EMIT_PROBES];
+#pragma unroll
+        for (int k = 0; k < EMIT_PROBES; k++) v[k] = t + 256 * k < n ? block_offs[lo + t + 256 * k] : 0xFFFFFFFFu;
+#pragma unroll
+        for (int k = 0; k < EMIT_PROBES; k++) {
+            const bool in = t + 256 * k < n;
+            c_le += (uint32_t)__popcll(__ballot(in && v[k] <= w0));
+            c_lt += (uint32_t)__popcll(__ballot(in && v[k] < w1));
+        }
     }
-    // stage the ranks whose first slot lies below w1
-    for (int i = t; i <= EMIT_SLOTS; i += 256) {
-        const int r = r_first + i;
-        if (r >= V) break;
-        const uint32_t off = block_offs[r >> 8] + rank_local[r];
-        if (off >= w1) break;  // offsets ascend with the rank: nothing further on for this thread either
-        const uint32_t idx = gidx[r];
-        const uint2 tr = tight_rect[idx];  // the rect the preprocess counted (x0 | y0 << 16, width)
-        s_off[i] = off;
-        s_idx[i] = idx;
-        s_rect[i] = tr.x;
-        s_rect2[i] = tr.y;
-        atomicMax(&s_nr, (uint32_t)i + 1u);
+    if (lane == 0) s_cnt[wv] = c_le | (c_lt << 16);
+    __syncthreads();
+    const uint32_t cnt = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+    const int g = lo + (int)(cnt & 0xFFFFu) - 1;                                  // the group that holds slot w0
+    const int ngroups = imin_((int)(cnt >> 16) - (int)(cnt & 0xFFFFu) + 1, EMIT_GROUPS);  // ... up to the last that begins below w1
+    // step 2
+    uint32_t off[EMIT_GROUPS], idx[EMIT_GROUPS];
+#pragma unroll
+    for (int m = 0; m < EMIT_GROUPS; m++) {
+        const int r = 256 * (g + m) + t;
+        const bool in = m < ngroups && r < V;
+        const uint32_t goff = in ? block_offs[g + m] : 0u;
+        off[m] = in ? goff + rank_local[r] : 0xFFFFFFFFu;
+        idx[m] = in ? gidx[r] : 0u;
+    }
+    // offsets ascend with the rank: the ranks of group g at or below w0 are its first c0, the last of them is r_first
+    const int c0 = __syncthreads_count(off[0] <= w0);
+    // step 3: staging index = rank - r_first
+#pragma unroll
+    for (int m = 0; m < EMIT_GROUPS; m++) {
+        const int i = 256 * m + t - (c0 - 1);
+        if (off[m] < w1 && i >= 0 && i < EMIT_SLOTS) {
+            const uint2 tr = tight_rect[idx[m]];  // the rect the preprocess counted (x0 | y0 << 16, width)
+            s_rank[i] = make_uint4(off[m], idx[m], tr.x, tr.y);
+            s_owner[max(off[m], w0) - w0] = (uint16_t)i;  // (rank r_first owns slot 0 wherever it began)
+        }
     }
     __syncthreads();
-    const int nr = (int)s_nr;  // >= 1: rank r_first always qualifies
-    // bisection steps for nr candidates (uniform; at most 11: 2^11 > EMIT_SLOTS + 1 -- a window of near splats holds a
-    // handful of ranks, one of far ones a thousand)
-    const int steps = 32 - __builtin_clz((uint32_t)nr | 1u);
-    for (uint32_t o = w0 + (uint32_t)t; o < w1; o += 256) {
-        // largest j < nr with s_off[j] <= o
-        int a = 0, b = nr - 1;
-        for (int it = 0; it < steps; it++) {
-            const int mid = (a + b + 1) >> 1;
-            if (s_off[mid] <= o) a = mid; else b = mid - 1;
-        }
-        const uint32_t k = o - s_off[a];
-        const uint32_t w = s_rect2[a];
-        const uint32_t rx0 = s_rect[a] & 0xFFFFu, ry0 = s_rect[a] >> 16;
-        const uint32_t ty = k / w, tx = k - ty * w;
+    // owners: inclusive max-scan of the marks over the window, four slots per thread
+    const uint2 mk = *reinterpret_cast<const uint2*>(&s_owner[4 * t]);
+    uint32_t own[4] = {mk.x & 0xFFFFu, mk.x >> 16, mk.y & 0xFFFFu, mk.y >> 16};
+    own[1] = max(own[1], own[0]);
+    own[2] = max(own[2], own[1]);
+    own[3] = max(own[3], own[2]);
+    const uint32_t run = wave_incl_max_u32_full_wave(own[3]);
+    if (lane == 63) s_wmax[wv] = run;
+    uint32_t before = (uint32_t)__shfl_up((int)run, 1, 64);  // owner of the last slot of the thread below
+    if (lane == 0) before = 0u;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+        if (k < wv) before = max(before, s_wmax[k]);
+    const uint32_t o0 = w0 + 4u * (uint32_t)t;
+    uint64_t e[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const uint4 rk = s_rank[max(own[k], before)];
+        const uint32_t inst = o0 + (uint32_t)k - rk.x;
+        const uint32_t w = rk.w;
+        const uint32_t rx0 = rk.z & 0xFFFFu, ry0 = rk.z >> 16;
+        const uint32_t ty = inst / w, tx = inst - ty * w;
         const uint64_t tile = (uint64_t)((ry0 + ty) * (uint32_t)tiles_x + rx0 + tx);
-        entries[o] = (tile << ENTRY_TILE_SHIFT) | (uint64_t)s_idx[a];
+        e[k] = (tile << ENTRY_TILE_SHIFT) | (uint64_t)rk.y;
+    }
+    if (o0 + 4u <= w1) {
+        *reinterpret_cast<ulonglong2*>(entries + o0) = make_ulonglong2(e[0], e[1]);
+        *reinterpret_cast<ulonglong2*>(entries + o0 + 2) = make_ulonglong2(e[2], e[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (o0 + (uint32_t)k < w1) entries[o0 + k] = e[k];
     }
 }
 
@@ -527,9 +625,21 @@ __global__ void __launch_bounds__(256) slots_and_compact_kernel(int P, const uin
     __shared__ uint32_t sm4[4], sm4b[4];
     const int idx = (int)(blockIdx.x * 256 + threadIdx.x);
     const uint32_t c = idx < P ? tiles_touched[idx] : 0u;
-    uint32_t total;
-    const uint32_t slot = block256_excl_scan_u32(c, sm4, &total);
-    const uint32_t local = block256_excl_scan_u32(c > 0 ? 1u : 0u, sm4b, &total);
+    // both block scans behind one barrier: the waves' inclusive scans, then the totals of the waves before
+    const int w = (int)(threadIdx.x >> 6);
+    const uint32_t inc_c = wave_incl_scan_u32_full_wave(c), inc_v = wave_incl_scan_u32_full_wave(c > 0 ? 1u : 0u);
+    if (lane_id() == 63) {
+        sm4[w] = inc_c;
+        sm4b[w] = inc_v;
+    }
+    __syncthreads();
+    uint32_t slot = inc_c - c, local = inc_v - (c > 0 ? 1u : 0u);
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+        if (k < w) {
+            slot += sm4[k];
+            local += sm4b[k];
+        }
     if (c > 0) {
         rec[(size_t)idx * REC_FLOATS + 2] = __uint_as_float(idx_block_offs[blockIdx.x] + slot);
         const uint32_t dst = vis_block_offs[blockIdx.x] + local;
@@ -605,33 +715,59 @@ __global__ void __launch_bounds__(256) tile_ranges_kernel(int R, const uint64_t*
 // SLOWER on S3: the blend kernels are VALU-bound, the splat records they share sit in the 256 MB MALL anyway,
 // and per-group ordering costs more balance than the L2 locality returns.)
 constexpr int ORDER_BUCKETS = 2048;
+constexpr int ORDER_HELD = 8;  // tiles per thread whose bucket stays in a register between the two sweeps (8 192 tiles)
 __global__ void __launch_bounds__(1024) tile_order_kernel(int tiles, const uint32_t* __restrict__ ranges,
                                                           uint32_t* __restrict__ order, uint32_t* __restrict__ zero_word) {
     __shared__ uint32_t hist[ORDER_BUCKETS];
     __shared__ uint32_t wsum[16];
     const int t = (int)threadIdx.x;
     if (t == 0 && zero_word != nullptr) *zero_word = 0u;  // (the backward's deep-tile counter: saves a memset launch)
-    for (int i = t; i < ORDER_BUCKETS; i += 1024) hist[i] = 0;
-    __syncthreads();
     auto bucket = [](uint32_t n) {  // descending: long lists -> small bucket index
         const uint32_t b = n >> 2;
         return (uint32_t)(ORDER_BUCKETS - 1) - (b < (uint32_t)(ORDER_BUCKETS - 1) ? b : (uint32_t)(ORDER_BUCKETS - 1));
     };
-    for (int i = t; i < tiles; i += 1024) atomicAdd(&hist[bucket(ranges[2 * i + 1] - ranges[2 * i])], 1u);
+    // One pass over the ranges of the first 8 192 tiles (a 1600 x 1200 frame has 7 500): a (start, end) pair per load, all
+    // of a thread's loads in flight before the first LDS atomic, and the buckets kept for the scatter.  (Both sweeps used
+    // to read start and end apiece, each load of the second sweep behind the atomic before it: 9.0 us against a launch
+    // floor of 4.8.)  Larger frames read the tiles beyond again.
+    const uint2* pairs = reinterpret_cast<const uint2*>(ranges);
+    uint2 held[ORDER_HELD];
+#pragma unroll
+    for (int k = 0; k < ORDER_HELD; k++) {
+        const int i = t + 1024 * k;
+        held[k] = i < tiles ? pairs[i] : make_uint2(0u, 0u);
+    }
+    for (int i = t; i < ORDER_BUCKETS; i += 1024) hist[i] = 0;
+    __syncthreads();
+    uint32_t bk[ORDER_HELD];
+#pragma unroll
+    for (int k = 0; k < ORDER_HELD; k++) {
+        bk[k] = bucket(held[k].y - held[k].x);
+        if (t + 1024 * k < tiles) atomicAdd(&hist[bk[k]], 1u);
+    }
+    for (int i = t + 1024 * ORDER_HELD; i < tiles; i += 1024) {
+        const uint2 r = pairs[i];
+        atomicAdd(&hist[bucket(r.y - r.x)], 1u);
+    }
     __syncthreads();
     // exclusive scan of the 2048 buckets: two per thread
     const uint32_t h0 = hist[2 * t], h1 = hist[2 * t + 1];
-    const uint32_t inc = wave_incl_scan_u32(h0 + h1);
+    const uint32_t inc = wave_incl_scan_u32_full_wave(h0 + h1);
     if ((t & 63) == 63) wsum[t >> 6] = inc;
     __syncthreads();
     uint32_t base = 0;
     for (int w = 0; w < (t >> 6); w++) base += wsum[w];
     const uint32_t ex = base + inc - (h0 + h1);
-    __syncthreads();
-    hist[2 * t] = ex;
+    hist[2 * t] = ex;  // (its own two buckets: nobody else reads them before the barrier)
     hist[2 * t + 1] = ex + h0;
     __syncthreads();
-    for (int i = t; i < tiles; i += 1024) order[atomicAdd(&hist[bucket(ranges[2 * i + 1] - ranges[2 * i])], 1u)] = (uint32_t)i;
+#pragma unroll
+    for (int k = 0; k < ORDER_HELD; k++)
+        if (t + 1024 * k < tiles) order[atomicAdd(&hist[bk[k]], 1u)] = (uint32_t)(t + 1024 * k);
+    for (int i = t + 1024 * ORDER_HELD; i < tiles; i += 1024) {
+        const uint2 r = pairs[i];
+        order[atomicAdd(&hist[bucket(r.y - r.x)], 1u)] = (uint32_t)i;
+    }
 }
 void launch_tile_order(int tiles, const uint32_t* ranges, uint32_t* tile_order, hipStream_t s, uint32_t* zero_word) {
     hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, s, tiles, ranges, tile_order, zero_word);

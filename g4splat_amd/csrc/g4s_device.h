@@ -188,6 +188,29 @@ __device__ __forceinline__ uint32_t wave_max_u32_full_wave(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 
+// Inclusive prefix sum / prefix maximum over a wave whose 64 lanes are all active, in six DPP instructions instead of six
+// trips through the LDS crossbar: Hillis-Steele inside the rows of 16 lanes (row_shr:1, 2, 4, 8 -- a lane without a
+// source reads 0, the identity of both), then the last lane of rows 0 / 2 onto rows 1 / 3 (row_bcast:15) and lane 31 onto
+// rows 2 and 3 (row_bcast:31).
+__device__ __forceinline__ uint32_t wave_incl_scan_u32_full_wave(uint32_t v) {
+    v += dpp_u32<0x111>(v);
+    v += dpp_u32<0x112>(v);
+    v += dpp_u32<0x114>(v);
+    v += dpp_u32<0x118>(v);
+    v += dpp_u32<0x142, 0xA>(v);
+    v += dpp_u32<0x143, 0xC>(v);
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_incl_max_u32_full_wave(uint32_t v) {
+    v = max(v, dpp_u32<0x111>(v));
+    v = max(v, dpp_u32<0x112>(v));
+    v = max(v, dpp_u32<0x114>(v));
+    v = max(v, dpp_u32<0x118>(v));
+    v = max(v, dpp_u32<0x142, 0xA>(v));
+    v = max(v, dpp_u32<0x143, 0xC>(v));
+    return v;
+}
+
 // Inclusive prefix sum over the wave (lane i gets sum of lanes 0..i).
 __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
     const int l = lane_id();

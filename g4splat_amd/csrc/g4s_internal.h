@@ -200,6 +200,10 @@ struct PreprocessArgs {
     uint2* tight_rect;  // (x0 | y0 << 16, width in tiles) of the rect counted in tiles_touched; written where that is > 0
     int* radii;
     uint32_t* depth_keys;
+    // 32-bit words the kernel clears on the side, every workgroup a 1/grid share (the frame's tile ranges,
+    // rasterizer_impl.cu:311: nothing reads them before launch_tile_ranges); zero_words == 0: nothing
+    uint32_t* zero_ptr;
+    uint32_t zero_words;
 };
 void launch_preprocess_fwd(const PreprocessArgs& a, hipStream_t s);
 
@@ -225,7 +229,8 @@ void launch_count_scan(int P, const uint32_t* gidx_sorted, const uint32_t* tiles
                        const uint32_t* d_n = nullptr);
 // Totals and block offsets that only need the preprocess' per-block partial sums (no sort): exclusive scans of
 // idx_block_sums and vis_block_sums; total[0] = instances binned, total[1] = the reference's num_rendered,
-// total[2] = number of emitting Gaussians.  Also clears zero_words 32-bit words at zero_ptr (the tile ranges).
+// total[2] = number of emitting Gaussians.  Also clears zero_words 32-bit words at zero_ptr (from its single workgroup:
+// the forward has the preprocess clear its tile ranges, PreprocessArgs::zero_ptr, and passes 0 here).
 void launch_scan_totals(const uint32_t* idx_block_sums, uint32_t* idx_block_offs, const uint32_t* ref_block_sums,
                         const uint32_t* vis_block_sums, uint32_t* vis_block_offs, uint32_t* total, int nblocks,
                         uint32_t* zero_ptr, int zero_words, hipStream_t s, uint32_t capacity = 0xFFFFFFFFu,

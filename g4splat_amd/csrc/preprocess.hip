@@ -387,6 +387,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))
     __shared__ __attribute__((aligned(16))) float s_cert[4][64 * CERT_SLOT_WORDS];
     __shared__ uint32_t s_cert_fail[4][64];
     const int idx = (int)(blockIdx.x * 256 + threadIdx.x);
+    // (the tile ranges of the frame: 60 KB at 1600 x 1200, spread over the grid and stored before this thread's first
+    // load -- a kernel that waits on memory anyway; the totals scan cleared them from its single workgroup before)
+    for (uint32_t i = (uint32_t)idx; i < a.zero_words; i += gridDim.x * 256u) a.zero_ptr[i] = 0u;
     const bool in_range = idx < a.P;
     int radius_out = 0;
     uint32_t touched_ref = 0, touched = 0, key = CULLED_KEY, clamp_bits = 0;
