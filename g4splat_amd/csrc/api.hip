@@ -92,7 +92,7 @@ inline bool trace_on() {
 const char* const kProfNames[PF_COUNT] = {"preprocess_fwd", "depth_sort", "count_scan", "emit", "tile_sort",
                                           "tile_ranges",    "blend_fwd",  "blend_bwd",  "preprocess_bwd",
                                           "maps_fwd",       "maps_bwd",   "photometric_loss",
-                                          "adam", "geometry_regularizers"};
+                                          "adam", "geometry_regularizers", "chart_prior"};
 struct ProfRec { int id; hipEvent_t a, b; };
 std::mutex g_prof_mu;
 bool g_prof_on = false;

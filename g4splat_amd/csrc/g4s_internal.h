@@ -171,7 +171,7 @@ inline bool misaligned(const void* p, size_t a) { return p != nullptr && ((size_
 
 // ---- optional per-kernel timing with HIP events on the launch stream (api.hip; bench.py reads the groups by name) ----
 enum ProfId { PF_PREPROCESS_FWD, PF_DEPTH_SORT, PF_COUNT_SCAN, PF_EMIT, PF_TILE_SORT, PF_TILE_RANGES, PF_BLEND_FWD,
-              PF_BLEND_BWD, PF_PREPROCESS_BWD, PF_MAPS_FWD, PF_MAPS_BWD, PF_PHOTO_LOSS, PF_ADAM, PF_GEO_REG, PF_COUNT };
+              PF_BLEND_BWD, PF_PREPROCESS_BWD, PF_MAPS_FWD, PF_MAPS_BWD, PF_PHOTO_LOSS, PF_ADAM, PF_GEO_REG, PF_CHART_PRIOR, PF_COUNT };
 // Times what is launched on `s` during its lifetime as one recording of group `id`; does nothing unless profiling is on.
 struct ProfScope {
     int id; hipStream_t s; hipEvent_t a = nullptr, b = nullptr; bool on = false;

@@ -2,10 +2,14 @@
 only: render() [HIP rasterizer + fused maps] -> fused L1+SSIM loss + normal-consistency and distortion regularisers
 (train_with_refine_depth.py:378-399) -> backward -> FusedAdam step + densification statistics.
 
-    python tools/train_iter_bench.py [--iters 40] [--torch-adam] [--graph]
+    python tools/train_iter_bench.py [--iters 40] [--torch-adam] [--graph] [--chart-priors {off,eager,fused}]
 
 --graph: the same iteration captured once in a HIP graph and replayed (g4splat_amd.graphed.TrainStepGraph; presized
 rasterizer state, FusedAdam with step counts and learning rates on the device): one launch from the host per iteration.
+
+--chart-priors: add the chart-prior half of the loss (train_with_refine_depth.py:403-492: log-depth, normal, curvature and
+depth-order priors against per-view prior maps, anisotropy penalty; iteration 2000 of the schedule, so the shifts are drawn)
+as the eager torch formulation or as the fused g4splat_amd.losses.chart_regularization; `off` is the 2DGS half alone.
 
 Prints wall time per iteration and the per-kernel-group milliseconds from the library's profiling hooks."""
 import argparse
@@ -24,7 +28,32 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from g4splat_amd import _lib, synthetic  # noqa: E402
 from g4splat_amd.gaussian_model import GaussianModel  # noqa: E402
 from g4splat_amd.gaussian_renderer import render  # noqa: E402
-from g4splat_amd.losses import geometry_regularizers, photometric_loss  # noqa: E402
+from g4splat_amd.losses import chart_regularization, geometry_regularizers, photometric_loss  # noqa: E402
+
+
+def eager_chart_regularization(out, priors, scaling, factor, lambda_order, depth_scale, extent):
+    """Lines 403-492 as a torch user writes them against the formulas of include/g4s_losses.h."""
+    rn, sn, sd = out["rend_normal"], out["surf_normal"], out["surf_depth"]
+    H, W = sd.shape[-2:]
+    p = torch.nn.functional.pad(rn[None], (1, 1, 1, 1), mode="replicate")[0]
+    curv = ((((p[:, :-2, 1:-1] - rn) + (p[:, 1:-1, :-2] - rn)) + (p[:, 2:, 1:-1] - rn)) + (p[:, 1:-1, 2:] - rn)).abs().sum(0, keepdim=True)
+    depth = factor * 0.75 * (0.5 * torch.log(1.0 + depth_scale * (priors["depth"] - sd).abs())).mean()
+    depth = depth + (factor * 0.5 * (1.0 - (sn * priors["normal"]).sum(dim=0))).mean()
+    normal = factor * 0.5 * (1.0 - (rn * priors["normal"]).sum(dim=0)).mean()
+    curvature = factor * 0.25 * (priors["curv"] - curv).abs().mean()
+    if lambda_order > 0:
+        m = round(0.05 * max(H, W))
+        shifts = torch.randint(-m, m + 1, (H * W, 2), device=sd.device)
+        rows = torch.arange(H, device=sd.device).view(H, 1).expand(H, W).reshape(-1)
+        cols = torch.arange(W, device=sd.device).view(1, W).expand(H, W).reshape(-1)
+        qy, qx = (rows + shifts[:, 0]).clamp(0, H - 1), (cols + shifts[:, 1]).clamp(0, W - 1)
+        d, pr = sd.reshape(H, W), priors["depth"].reshape(H, W)
+        diff = (d.reshape(-1) - d[qy, qx]) / extent
+        pd = (pr.reshape(-1) - pr[qy, qx]) / extent
+        pd = pd / pd.abs().clamp(min=1e-8)
+        depth = depth + lambda_order * torch.log(1.0 + 20.0 * -(diff * pd).clamp(max=0)).mean()
+    ratio = scaling.max(dim=1).values / scaling.min(dim=1).values
+    return depth + normal + curvature + 0.1 * (ratio.clamp_min(5.0) - 5.0).mean()
 
 
 def main():
@@ -35,6 +64,8 @@ def main():
     ap.add_argument("--height", type=int, default=1200)
     ap.add_argument("--torch-adam", action="store_true", help="torch.optim.Adam instead of the fused kernel")
     ap.add_argument("--graph", action="store_true", help="replay the iteration from a HIP graph")
+    ap.add_argument("--chart-priors", choices=("off", "eager", "fused"), default="off",
+                    help="add the chart-prior half of the loss: eager torch or the fused HIP op")
     ap.add_argument("--no-kernel-timing", action="store_true", help="leave the library's per-kernel event pairs off (they cost ~5 us each)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -57,12 +88,28 @@ def main():
     gts = [torch.rand((3, a.height, a.width), device=dev) for _ in cams]
     pipe = SimpleNamespace(depth_ratio=0.0, compute_cov3D_python=False)
     bg = torch.zeros(3, device=dev)
+    # prior maps of the chart-prior half, one set per view (with --graph the first view's set is baked into the graph)
+    gen = torch.Generator(device=dev).manual_seed(3)
+    rnd = lambda *s: torch.rand(s, device=dev, generator=gen)
+    priors = [{"depth": 1.0 + 3.0 * rnd(1, a.height, a.width),
+               "normal": torch.nn.functional.normalize(rnd(3, a.height, a.width) - 0.5, dim=0),
+               "curv": 0.2 * rnd(1, a.height, a.width)} for _ in cams] if a.chart_priors != "off" else None
+    chart_iteration, charts_scale_factor = 2000, 5.0  # depth-order weight 1: the shifts are drawn every iteration
+
+    def chart_term(out, view):
+        if a.chart_priors == "fused":
+            return chart_regularization(out, priors[view], model.get_scaling, chart_iteration, charts_scale_factor,
+                                        model.spatial_lr_scale)[0]
+        return eager_chart_regularization(out, priors[view], model.get_scaling, 0.125, 1.0, charts_scale_factor,
+                                          model.spatial_lr_scale)
 
     def iteration(i):
         out = render(cams[i % 8], model, pipe, bg)
         loss, _l1, _s = photometric_loss(out["render"], gts[i % 8], 0.2)
         normal_mean, dist_mean = geometry_regularizers(out["rend_normal"], out["surf_normal"], out["rend_dist"])
         total = loss + 0.05 * normal_mean + 100.0 * dist_mean
+        if priors is not None:
+            total = total + chart_term(out, i % 8)
         total.backward()
         with torch.no_grad():
             model.add_densification_stats(out["viewspace_points"], out["visibility_filter"], out["radii"])
@@ -85,7 +132,8 @@ def main():
         def body(out, gt):
             loss, _l1, _s = photometric_loss(out["render"], gt, 0.2)
             normal_mean, dist_mean = geometry_regularizers(out["rend_normal"], out["surf_normal"], out["rend_dist"])
-            return loss + 0.05 * normal_mean + 100.0 * dist_mean
+            total = loss + 0.05 * normal_mean + 100.0 * dist_mean
+            return total + chart_term(out, 0) if priors is not None else total
         step = TrainStepGraph(model, body, cams[0], (3, a.height, a.width), instance_capacity=int(R * 1.3), pipe=pipe, bg=bg)
 
         def iteration(i):  # noqa: F811
@@ -109,7 +157,7 @@ def main():
         if cnt.value:
             ker[lib.g4s_profile_name(k).decode()] = round(ms.value / a.iters, 4)
     print(json.dumps({"P": a.P, "resolution": [a.width, a.height], "iters": a.iters, "ms_per_iteration": round(wall, 3),
-                      "optimizer": "torch.optim.Adam" if a.torch_adam else "FusedAdam", "hip_graph": bool(a.graph),
+                      "optimizer": "torch.optim.Adam" if a.torch_adam else "FusedAdam", "hip_graph": bool(a.graph), "chart_priors": a.chart_priors,
                       "library_kernels_ms_per_iteration": ker, "library_kernels_sum_ms": round(sum(ker.values()), 3)}))
 
 
