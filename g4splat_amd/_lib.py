@@ -143,6 +143,14 @@ SIGNATURES = {
     "g4s_view_counts_points": (c_i, [c_i, c_p, c_i, c_f, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "g4s_view_counts_pixels": (c_i, [c_i, c_i, c_p, c_p, c_i, c_f, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "g4s_depth_to_points": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_plane_labels_workspace": (c_sz, [c_i, c_p]),
+    "g4s_plane_labels": (c_i, [c_i, c_p, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_plane_overlap": (c_i, [c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_plane_assign_workspace": (c_sz, [c_i]),
+    "g4s_plane_assign": (c_i, [c_i, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_sz, c_p]),
+    "g4s_plane_row_overlap": (c_i, [c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_sz, c_p]),
+    "g4s_plane_row_merge": (c_i, [c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_sz, c_p]),
+    "g4s_plane_row_mask": (c_i, [c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_sz, c_p]),
 }
 
 _lib = None

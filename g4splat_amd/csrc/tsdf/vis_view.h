@@ -1,0 +1,49 @@
+// What the two units over the Visibility section's views (visibility.hip, planes.hip) share: the head of a view record
+// -- world -> camera rotation, translation, focal lengths, then view_stack.h's maps --, its fill from the host arrays and
+// THE projection of include/g4s_render_maps.h ("Projection of a point p into a view").  There is no second one.
+#pragma once
+#include "view_stack.h"
+
+namespace g4s {
+
+// One view of the stack as the visibility kernels read it (80 bytes; the table is an array of these in the workspace).
+// A unit that needs more per view declares a record that begins with the same fields (planes.hip).
+struct VisView {
+    float R[9];  // world -> camera rotation, R[3 j + i] = world_view_transform[i][j]
+    float T[3];  // world_view_transform[3][j]
+    float fx, fy;
+    ViewMaps maps;
+};
+static_assert(sizeof(VisView) == 80, "g4s_visgrid_workspace is stated in records of 80 bytes");
+
+// z = c_2 and the image coordinates (u, v) of the contract
+struct VisProj {
+    float z, u, v;
+};
+
+// The projection; true iff the point is "in image" (every comparison with a NaN is false).  View: R, T, fx, fy, maps.
+template <class View>
+__device__ __forceinline__ bool vis_project(const View& v, float px, float py, float pz, VisProj& q) {
+    const float x = ((px * v.R[0] + py * v.R[1]) + pz * v.R[2]) + v.T[0];
+    const float y = ((px * v.R[3] + py * v.R[4]) + pz * v.R[5]) + v.T[1];
+    const float z = ((px * v.R[6] + py * v.R[7]) + pz * v.R[8]) + v.T[2];
+    const int W = v.maps.W, H = v.maps.H;
+    const float a = (x / z) * v.fx + (float)W * 0.5f;
+    const float b = (y / z) * v.fy + (float)H * 0.5f;
+    q = VisProj{z, a, b};
+    return a >= 0.0f && a < (float)W && b >= 0.0f && b < (float)H;
+}
+
+// host: the pose fields of view v's record from world_view [V,16] and focal [V,2]
+template <class View>
+inline void vis_pose(View& u, const float* world_view, const float* focal, int v) {
+    const float* M = world_view + 16 * (size_t)v;
+    for (int j = 0; j < 3; j++) {
+        for (int i = 0; i < 3; i++) u.R[3 * j + i] = M[4 * i + j];
+        u.T[j] = M[12 + j];
+    }
+    u.fx = focal[2 * (size_t)v];
+    u.fy = focal[2 * (size_t)v + 1];
+}
+
+}  // namespace g4s

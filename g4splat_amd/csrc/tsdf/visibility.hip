@@ -19,18 +19,9 @@
 #include "../../../include/g4s_render_maps.h"
 #include "mesh_common.h"
 #include "scan.h"
-#include "view_stack.h"
+#include "vis_view.h"
 
 namespace g4s {
-
-// One view of the stack as the kernels read it (80 bytes; the table is an array of these in the workspace).
-struct VisView {
-    float R[9];  // world -> camera rotation, R[3 j + i] = world_view_transform[i][j]
-    float T[3];  // world_view_transform[3][j]
-    float fx, fy;
-    ViewMaps maps;
-};
-static_assert(sizeof(VisView) == 80, "g4s_visgrid_workspace is stated in records of 80 bytes");
 
 struct VisGrid {
     float lo[3], extent[3], cell[3];  // bbox_min, bbox_max - bbox_min, extent / R
@@ -46,13 +37,10 @@ enum { VIS_FREE = 0, VIS_SURFACE = 1 };
 // The predicate of one (point, view) pair.  A NaN fails every comparison, so the map is read only at a pixel inside it.
 template <int MODE>
 __device__ __forceinline__ bool vis_pass(const VisView& v, float px, float py, float pz, float threshold) {
-    const float x = ((px * v.R[0] + py * v.R[1]) + pz * v.R[2]) + v.T[0];
-    const float y = ((px * v.R[3] + py * v.R[4]) + pz * v.R[5]) + v.T[1];
-    const float z = ((px * v.R[6] + py * v.R[7]) + pz * v.R[8]) + v.T[2];
+    VisProj q;
+    if (!vis_project(v, px, py, pz, q)) return false;
+    const float z = q.z, a = q.u, b = q.v;
     const int W = v.maps.W, H = v.maps.H;
-    const float a = (x / z) * v.fx + (float)W * 0.5f;
-    const float b = (y / z) * v.fy + (float)H * 0.5f;
-    if (!(a >= 0.0f && a < (float)W && b >= 0.0f && b < (float)H)) return false;
     const float d = v.maps.depth[(size_t)imin_((int)b, H - 1) * W + imin_((int)a, W - 1)];
     if (MODE == VIS_FREE) return z > 0.0f && z < d;
     return z > 0.0f && fabsf(z - d) / (z + 1e-6f) < threshold;
@@ -314,15 +302,8 @@ int check_mode(int mode, int skip_view) {
 int vis_table(int n_views, const float* world_view, const float* focal, const int* sizes, const float* const* depth,
               char* workspace, size_t workspace_bytes, hipStream_t stream, const VisView** table) {
     return stage_views("visibility", n_views, world_view != nullptr && focal != nullptr, sizes, depth, nullptr, false,
-                       workspace, workspace_bytes, stream, table, [=](VisView& u, int v) {
-                           const float* M = world_view + 16 * (size_t)v;
-                           for (int j = 0; j < 3; j++) {
-                               for (int i = 0; i < 3; i++) u.R[3 * j + i] = M[4 * i + j];
-                               u.T[j] = M[12 + j];
-                           }
-                           u.fx = focal[2 * (size_t)v];
-                           u.fy = focal[2 * (size_t)v + 1];
-                       });
+                       workspace, workspace_bytes, stream, table,
+                       [=](VisView& u, int v) { vis_pose(u, world_view, focal, v); });
 }
 
 }  // namespace

@@ -553,6 +553,86 @@ int g4s_view_counts_pixels(int width, int height, const float* pixel_depth, cons
 int g4s_depth_to_points(int width, int height, const float* depth, const float* ray, float* points, char* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* =====================================================================================================================
+ * Global planes (g4splat_amd/csrc/tsdf/planes.hip).
+ *
+ * The stage the reference puts between view selection and plane-aware depth refinement (2d-gaussian-splatting/
+ * planes/merge_global_3Dplane.py get_global_3Dplane over guidance/cam_utils.py get_pixel_to_points_tensor): which points of
+ * a chart cloud each view's plane mask claims, and which local planes of which views are one scene plane.  The library
+ * computes labels, the membership of points in global planes and integer counts; the sequential merge decisions are the
+ * caller's (g4splat_amd/planes.py), on the host, over those counts.  The semantics are this library's own, stated exactly
+ * (tests/planes_ref.py restates them in numpy): float32, round-to-nearest-even, correctly rounded /, no fused
+ * multiply-add, evaluated left to right as written.
+ *
+ * Views.  As in the Visibility section, with the view's map being its slot mask [H,W], an int32 device pointer whose values
+ *   are 0 (no plane) .. P (the caller remaps arbitrary mask ids to slots); W and H are the mask's, whatever the camera
+ *   says.  c_j, z, u, v and "in image" are the Visibility section's projection, the same device function.
+ * Candidates.  Point i of points [N,3] is a candidate of a view iff i != 0 && in image && z > 0 (index 0 is the reference's
+ *   "empty slot" and is never a member of anything).  Its pixel is px = min(int(rint(u)), W - 1), py = min(int(rint(v)),
+ *   H - 1), rint rounding half to even.
+ * Front points.  zmin[py][px] = the minimum of z over the view's candidates of that pixel, taken as an unsigned integer
+ *   atomic min of the floats' bit patterns (z > 0: the bits order like the values), so it does not depend on the order of
+ *   execution.  label[i] = mask[py][px] if i is a candidate and z < zmin[py][px] + depth_thresh (one float32 add, strict <),
+ *   otherwise 0.  depth_thresh < 0 turns the depth test off (the reference's use_depth_threshold=False): every candidate
+ *   takes its pixel's mask value.  A point has at most one label per view: the local planes S_p = {i : label[i] = p} of a
+ *   view are disjoint.
+ * Membership.  G global planes, n_words >= ceil(G / 64) 64-bit words per point: bit (g & 63) of member[(g >> 6) * N + i] says
+ *   that point i belongs to global plane g (point-major words, stored one block of N words per 64 planes; the caller
+ *   grows it by whole blocks and keeps the bits at and above G zero).  Row g = {i : that bit is set}.
+ * Overlap.  counts[(p - 1) * G + g] = |S_p ∩ row g| and sizes[p - 1] = |S_p| for p = 1 .. P; labels outside 1 .. P count as
+ *   0.  Integer sums by integer atomics: exact and independent of the order.  There is no float atomic in this section.
+ * Assign.  target[p - 1] (host, P ints) is -1 or a global plane below G: every point with label p gets that bit.
+ * Row overlap.  counts[h] = |row ∩ row h| for h < G; counts[row] is the row's size.
+ * Row merge.  Every point of row src joins row dst.   Row mask.  mask[i] = 1 iff point i is in the row, else 0; the
+ *   ascending indices of a row are the non-zero positions of its mask.
+ *
+ * Memory.  Labels are int32 [V,N] for the V views of one call, the workspace holds the view table (88 bytes per view) and one
+ *   zmin word per mask pixel; the caller chunks a long view list.  At N = 5 * 10^6: 20 MB of labels per view (1.2 GB if all
+ *   60 views are labelled in one call), 40 MB of membership per 64 global planes.
+ *
+ * Differences from the reference, on purpose.  No cap of 500 points per pixel (the reference drops the excess in an order
+ *   its unstable sort leaves undefined).  The mask's size stands in for the camera's.  The dense [H,W,K] pixel-to-points
+ *   map is not offered; labels carry the same information.  An empty global plane (the reference makes one from a view-0
+ *   mask id without front points and later divides by its size) has rate 0 against everything in the caller's decisions.
+ *   A decision at an edge -- a point on the image border, a u or v at .5, z at zmin + depth_thresh -- is made in this
+ *   section's float32 order, which is not torch's matmul order; the tests compare on the set where float32 and float64
+ *   agree.
+ *
+ * world_view [V,16], focal [V,2], sizes [V,2], the array of V mask pointers and `target` are HOST arrays, read during the
+ * call.  Every argument is checked on the host before anything is launched.  Every entry point takes workspace,
+ * workspace_bytes; those that name no size query use none and accept NULL, 0.
+ */
+
+/* Bytes of device workspace of g4s_plane_labels for views of these sizes (0 for sizes out of range). */
+size_t g4s_plane_labels_workspace(int n_views, const int* sizes);
+
+/* labels [n_views, n_points] int32 for points [n_points,3] (device).  n_views = 0: nothing is written. */
+int g4s_plane_labels(int n_points, const float* points, float depth_thresh, int n_views, const float* world_view,
+                     const float* focal, const int* sizes, const int* const* masks, int* labels, char* workspace,
+                     size_t workspace_bytes, void* stream);
+
+/* counts [n_planes * n_global] and sizes [n_planes] uint32 (device), cleared and filled; labels [n_points] of one view. */
+int g4s_plane_overlap(int n_points, const int* labels, int n_planes, int n_global, int n_words,
+                      const unsigned long long* member, unsigned int* counts, unsigned int* sizes, char* workspace,
+                      size_t workspace_bytes, void* stream);
+
+/* Bytes of device workspace of g4s_plane_assign. */
+size_t g4s_plane_assign_workspace(int n_planes);
+
+int g4s_plane_assign(int n_points, const int* labels, int n_planes, const int* target, int n_global, int n_words,
+                     unsigned long long* member, char* workspace, size_t workspace_bytes, void* stream);
+
+/* counts [n_global] uint32 (device), cleared and filled. */
+int g4s_plane_row_overlap(int n_points, int n_global, int n_words, const unsigned long long* member, int row,
+                          unsigned int* counts, char* workspace, size_t workspace_bytes, void* stream);
+
+int g4s_plane_row_merge(int n_points, int n_global, int n_words, unsigned long long* member, int src, int dst,
+                        char* workspace, size_t workspace_bytes, void* stream);
+
+/* mask [n_points] bytes (device). */
+int g4s_plane_row_mask(int n_points, int n_global, int n_words, const unsigned long long* member, int row,
+                       unsigned char* mask, char* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
