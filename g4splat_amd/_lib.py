@@ -151,6 +151,14 @@ SIGNATURES = {
     "g4s_plane_row_overlap": (c_i, [c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_sz, c_p]),
     "g4s_plane_row_merge": (c_i, [c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_sz, c_p]),
     "g4s_plane_row_mask": (c_i, [c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_sz, c_p]),
+    "g4s_consistency_points_workspace": (c_sz, [c_i, c_i, c_p]),
+    "g4s_consistency_points": (c_i, [c_i, c_p, c_f, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_sz,
+                                     c_p]),
+    "g4s_consistency_plane_counts_workspace": (c_sz, [c_i, c_i, c_i]),
+    "g4s_consistency_plane_counts": (c_i, [c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_sz,
+                                           c_p]),
+    "g4s_consistency_plane_repaint_workspace": (c_sz, [c_i, c_p, c_i]),
+    "g4s_consistency_plane_repaint": (c_i, [c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
 }
 
 _lib = None

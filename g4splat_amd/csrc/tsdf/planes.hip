@@ -27,6 +27,7 @@
 #include "../../../include/g4s_render_maps.h"
 #include "mesh_common.h"
 #include "vis_view.h"
+#include "wave_count.h"
 
 namespace g4s {
 
@@ -81,19 +82,6 @@ __global__ void __launch_bounds__(256) plane_label_kernel(int n, const float* __
         int label = 0;
         if (pix >= 0 && (!depth_test || z < __uint_as_float(views[v].zmin[pix]) + depth_thresh)) label = mask_of(views[v])[pix];
         labels[(size_t)v * (size_t)n + (size_t)i] = label;
-    }
-}
-
-// table[key] += the number of active lanes that hold `key`, one atomic per distinct key of the wave.  Every lane of the wave
-// must call it (inactive ones with active = false).
-__device__ __forceinline__ void wave_count(uint32_t* __restrict__ table, uint32_t key, bool active) {
-    unsigned long long todo = __ballot(active);
-    while (todo != 0ull) {  // wave-uniform
-        const int leader = __builtin_ctzll(todo);
-        const uint32_t k = (uint32_t)__shfl((int)key, leader);
-        const unsigned long long same = __ballot(active && key == k);
-        if (lane_id() == leader) atomicAdd(table + k, (uint32_t)__builtin_popcountll(same));
-        todo &= ~same;
     }
 }
 

@@ -1,13 +1,14 @@
-// What the two units over the Visibility section's views (visibility.hip, planes.hip) share: the head of a view record
-// -- world -> camera rotation, translation, focal lengths, then view_stack.h's maps --, its fill from the host arrays and
-// THE projection of include/g4s_render_maps.h ("Projection of a point p into a view").  There is no second one.
+// What the units over the Visibility section's views (visibility.hip, planes.hip, consistency.hip) share: the head of a
+// view record -- world -> camera rotation, translation, focal lengths, then view_stack.h's maps --, its fill from the host
+// arrays, THE projection of include/g4s_render_maps.h ("Projection of a point p into a view"), its truncating tap and the
+// SURFACE test.  There is no second one of any of them.
 #pragma once
 #include "view_stack.h"
 
 namespace g4s {
 
 // One view of the stack as the visibility kernels read it (80 bytes; the table is an array of these in the workspace).
-// A unit that needs more per view declares a record that begins with the same fields (planes.hip).
+// A unit that needs more per view declares a record that begins with the same fields (planes.hip, consistency.hip).
 struct VisView {
     float R[9];  // world -> camera rotation, R[3 j + i] = world_view_transform[i][j]
     float T[3];  // world_view_transform[3][j]
@@ -32,6 +33,17 @@ __device__ __forceinline__ bool vis_project(const View& v, float px, float py, f
     const float b = (y / z) * v.fy + (float)H * 0.5f;
     q = VisProj{z, a, b};
     return a >= 0.0f && a < (float)W && b >= 0.0f && b < (float)H;
+}
+
+// The truncating tap of a point that is in the image: the row-major index of depth[min(int(v), H-1)][min(int(u), W-1)].
+template <class View>
+__device__ __forceinline__ size_t vis_tap(const View& v, const VisProj& q) {
+    return (size_t)imin_((int)q.v, v.maps.H - 1) * v.maps.W + imin_((int)q.u, v.maps.W - 1);
+}
+
+// SURFACE of a point in the image with depth z whose tap reads d
+__device__ __forceinline__ bool vis_surface(float z, float d, float threshold) {
+    return z > 0.0f && fabsf(z - d) / (z + 1e-6f) < threshold;
 }
 
 // host: the pose fields of view v's record from world_view [V,16] and focal [V,2]

@@ -39,11 +39,10 @@ template <int MODE>
 __device__ __forceinline__ bool vis_pass(const VisView& v, float px, float py, float pz, float threshold) {
     VisProj q;
     if (!vis_project(v, px, py, pz, q)) return false;
-    const float z = q.z, a = q.u, b = q.v;
-    const int W = v.maps.W, H = v.maps.H;
-    const float d = v.maps.depth[(size_t)imin_((int)b, H - 1) * W + imin_((int)a, W - 1)];
+    const float z = q.z;
+    const float d = v.maps.depth[vis_tap(v, q)];
     if (MODE == VIS_FREE) return z > 0.0f && z < d;
-    return z > 0.0f && fabsf(z - d) / (z + 1e-6f) < threshold;
+    return vis_surface(z, d, threshold);
 }
 
 __device__ __forceinline__ float voxel_centre(const VisGrid& g, int axis, int i) {

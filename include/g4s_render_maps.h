@@ -633,6 +633,100 @@ int g4s_plane_row_merge(int n_points, int n_global, int n_words, unsigned long l
 int g4s_plane_row_mask(int n_points, int n_global, int n_words, const unsigned long long* member, int row,
                        unsigned char* mask, char* workspace, size_t workspace_bytes, void* stream);
 
+/* =====================================================================================================================
+ * Cross-view consistency (g4splat_amd/csrc/tsdf/consistency.hip).
+ *
+ * The third stage the reference runs between view selection and training (scripts/plane_refine_depth.py): one of two
+ * "inconsistency solvers", 2d-gaussian-splatting/guidance/inconsistence_solver.py (points) or guidance/
+ * plane_inconsistency_solver.py (planes), writes the confident maps train_with_refine_depth.py loads and repaints the
+ * inpainted images so that views agree on colour.  The semantics are this library's own, stated exactly
+ * (tests/consistency_ref.py restates them in numpy): float32, round-to-nearest-even, correctly rounded /, no fused
+ * multiply-add, evaluated left to right as written.
+ *
+ * Views.  As in the Visibility section: world_view, focal, sizes, a depth map [H,W] per view.  W and H are the depth map's;
+ *   every image, mask, confident map and point grid of a view has that size.  The projection, "in image", the truncating
+ *   tap and SURFACE are that section's, the same device functions.  vis(p, v) = SURFACE of point p in view v with
+ *   depth_threshold; pix(p, v) = the row-major index of its tap, min(int(v), H - 1) * W + min(int(u), W - 1).
+ *
+ * A. Point solver.  V views, the first I = n_input_views of them input views, the others inpainted views.  images[v] is float32,
+ *   [H,W,3] (image_chw[v] = 0) or [3,H,W] (image_chw[v] != 0), values in 0 .. 1.  points [N,3] float32 (device), N < 2^31.
+ *   seen(i) = vis(i, v) for some v < I.  visible(i) = vis(i, v) for some v < V.  For a point that is visible and not seen:
+ *   first(i) = the smallest v with vis(i, v) and colour(i)[c] = uint8(trunc(images[first][pix(i, first)][c] * 255.0f)) (a
+ *   product outside 0 .. 255 is clamped to that range first, a NaN gives 0).  images are only ever read; outputs are
+ *   separate buffers.
+ *   conf[v] [H,W] uint8 = 1 everywhere, except 0 at pix(i, v) of every i with v >= I, vis(i, v) and seen(i).
+ *   images_out[v] [H,W,3] float32 = images[v] (in [H,W,3] order), except that at every pixel that is pix(i, v) of at least
+ *   one i with v >= I, vis(i, v) and not seen(i), channel c becomes float(colour(w)[c]) / 255.0f, w being the LARGEST such
+ *   point index (an integer atomic max per pixel: independent of the order of execution).  An input view keeps conf = 1
+ *   and its image.
+ *   state [N] uint32: bits 0 .. 7, 8 .. 15, 16 .. 23 = colour(i)[0 .. 2] (0 unless visible and not seen), bit 24 = seen(i),
+ *   bit 25 = visible(i).  With resume != 0 the kernel starts from the state of an earlier call over EARLIER views of the
+ *   same list, so a caller may pass a long list in chunks: every chunk of input views before the first chunk with an
+ *   inpainted view, in the list's order; the outputs of a chunk's views are final when its call returns.
+ *   images_out and conf may both be NULL: no outputs, the state alone.  state may be NULL when no inpainted view needs
+ *   it (I = V, or N = 0); then, and with N = 0, nothing is launched beyond the fills of conf and images_out.
+ *   Storage: 4 bytes per point (state) and 4 bytes per pixel of the inpainted views (the workspace's winner words),
+ *   nothing per (point, view) pair; the view table takes 120 bytes per view.
+ *
+ * B. Plane solver.  Per view a uint8 image [H,W,3], a slot mask [H,W] int32 and pixel-aligned points [H*W,3] float32, all
+ *   device pointers.  The caller remaps arbitrary mask ids to slots 0 (no plane) .. P_v per view and flattens per-slot
+ *   tables: view v owns entries slot_offset[v] .. slot_offset[v + 1] - 1 (slot_offset [V + 1], slot_offset[0] = 0, at least
+ *   slot 0 per view; entry slot_offset[v] + s belongs to slot s; a mask value outside the view's slots counts as slot 0,
+ *   whose entries are -1).
+ *   Counts.  slot_plane[e] = the global plane k < n_planes of the slot, or -1.  counts[k * n_anchors + j] = the number of
+ *   pixels q of all views w whose slot names plane k and whose point points[w][q] passes SURFACE in view anchor_views[j].
+ *   Integer sums by integer atomics, folded across the wave first.  The anchor of a plane is the caller's decision.
+ *   Repaint.  slot_step[e] = the step t >= 0 of the slot's (view, plane) pair, or -1; slot_anchor[e] = the anchor view a of
+ *   its plane.  For pixel x = (w, q) whose slot has a step and whose point passes SURFACE in a: step(x) = t, src(x) = (a,
+ *   pix(points[w][q], a)).  Every other pixel has step(x) = infinity.  images_out[w][q] = value(x, infinity) with
+ *   value(x, T) = value(src(x), step(x)) if step(x) < T, otherwise images[view of x][pixel of x].  Steps strictly decrease
+ *   along a chain, so the walk ends.  This is exactly what repainting the images in place, step after step, the right-hand
+ *   side of a step evaluated before it is assigned, leaves behind: a read from an image that an EARLIER step repainted sees
+ *   the repainted colour, a read inside the same step (w = a) sees the state before the step.  images are only read.
+ *   Storage: 12 bytes per pixel of the views in the workspace (step, source view, source pixel), 128 bytes per view; the
+ *   views of one call have fewer than 2^31 pixels in all.
+ *
+ * Differences from the reference, on purpose.  Duplicate pixels of the point solver resolve to the largest point index (the
+ *   reference leaves the winner to index_put, undefined on a GPU; a single-threaded CPU run writes in index order, which is
+ *   this rule).  A decision at an edge -- a point on the image border, a u or v on an integer, a relative difference exactly
+ *   at the threshold -- is made in this section's float32 order, which is not torch's matmul order.  The [N,V] visibility
+ *   and coordinate tables are not offered.  There is no file I/O: the callers keep writing PNGs, the all-ones pseudo
+ *   confident maps of the plane solver and of the no-inpainting branch included.  The reference's unused color_eps is
+ *   dropped.  A point that no view sees has colour 0 (the reference gives it view 0's pixel (0, 0) and never uses it).
+ *
+ * world_view, focal, sizes, image_chw, the pointer arrays, slot_offset, slot_plane, slot_step, slot_anchor and anchor_views
+ * are HOST arrays, read during the call.  At most 65535 views per call.  Every argument is checked on the host before
+ * anything is launched.  Every entry point takes workspace, workspace_bytes.
+ */
+
+/* Bytes of device workspace of g4s_consistency_points for views of these sizes (0 for arguments out of range). */
+size_t g4s_consistency_points_workspace(int n_views, int n_input_views, const int* sizes);
+
+int g4s_consistency_points(int n_points, const float* points, float depth_threshold, int n_views, int n_input_views,
+                           const float* world_view, const float* focal, const int* sizes, const float* const* depth,
+                           const float* const* images, const int* image_chw, float* const* images_out,
+                           unsigned char* const* conf, int resume, unsigned int* state, char* workspace,
+                           size_t workspace_bytes, void* stream);
+
+/* Bytes of device workspace of g4s_consistency_plane_counts; n_slots = slot_offset[n_views]. */
+size_t g4s_consistency_plane_counts_workspace(int n_views, int n_slots, int n_anchors);
+
+/* counts [n_planes * n_anchors] uint32 (device), cleared and filled. */
+int g4s_consistency_plane_counts(float depth_threshold, int n_views, const float* world_view, const float* focal,
+                                 const int* sizes, const float* const* depth, const int* const* masks,
+                                 const float* const* points, const int* slot_offset, const int* slot_plane, int n_planes,
+                                 int n_anchors, const int* anchor_views, unsigned int* counts, char* workspace,
+                                 size_t workspace_bytes, void* stream);
+
+/* Bytes of device workspace of g4s_consistency_plane_repaint (0 for arguments out of range). */
+size_t g4s_consistency_plane_repaint_workspace(int n_views, const int* sizes, int n_slots);
+
+int g4s_consistency_plane_repaint(float depth_threshold, int n_views, const float* world_view, const float* focal,
+                                  const int* sizes, const float* const* depth, const int* const* masks,
+                                  const float* const* points, const unsigned char* const* images,
+                                  unsigned char* const* images_out, const int* slot_offset, const int* slot_step,
+                                  const int* slot_anchor, char* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,159 @@
+"""The numpy restatement of the cross-view consistency contract (tests/consistency_ref.py) and the host decisions of
+g4splat_amd/consistency.py against what the reference's two solver scripts wrote (tests/golden/make_golden_consistency.py):
+confident maps and repainted images on the agreed set, the anchors, the step order, the chain walk against a literal
+in-place repaint.  No GPU: the GPU tests (tests/test_gpu_consistency.py) hold the library to the restatement bit for bit."""
+import json
+import os
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+
+import consistency_ref as cr
+from g4splat_amd import consistency
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "consistency.npz")
+f32 = np.float32
+
+
+def load_golden():
+    g = np.load(GOLDEN)
+    V = len(g["wvt"])
+    cams = [SimpleNamespace(world_view_transform=g["wvt"][i], full_proj_transform=g["full"][i], FoVx=float(g["fov"][i, 0]),
+                            FoVy=float(g["fov"][i, 1])) for i in range(V)]
+    gdict = {int(k): [(int(v), int(p)) for v, p in pairs] for k, pairs in json.loads(str(g["dict"])).items()}
+    images = [im for im in g["images"]]
+
+    def agreed(key, shape):
+        return np.unpackbits(g[key])[: int(np.prod(shape))].astype(bool).reshape(shape)
+
+    return SimpleNamespace(
+        g=g, cams=cams, depths=[d for d in g["depths"]], clouds=[c for c in g["clouds"]], points=g["clouds"].reshape(-1, 3),
+        images=images, float_images=[im.astype(f32) / f32(255) for im in images],  # the cameras' original_image
+        masks=[m for m in g["masks"]], n_input=int(g["n_input"]), gdict=gdict, anchors=[int(a) for a in g["anchors"]],
+        threshold=float(g["depth_threshold"]), point_conf=g["point_conf"], point_png=g["point_png"], plane_png=g["plane_png"],
+        point_conf_agreed=agreed("point_conf_agreed", g["point_conf"].shape),
+        point_png_agreed=agreed("point_png_agreed", g["point_png"].shape[:3]),
+        plane_png_agreed=agreed("plane_png_agreed", g["plane_png"].shape[:3]), stats=json.loads(str(g["stats"])))
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return load_golden()
+
+
+@pytest.fixture(scope="module")
+def restated(golden):
+    """The restatement's float32 outputs of the golden scene, computed once and left unchanged."""
+    g = golden
+    stats = {}
+    outs, confs = cr.point_solver(g.cams, g.depths, g.float_images, g.points, g.n_input, g.threshold, f32, stats)
+    lengths = [np.zeros(m.size, np.int64) for m in g.masks]
+    b_outs, anchor_of_plane, counts = cr.plane_solver(g.cams, g.depths, g.images, g.masks, g.clouds, g.gdict, g.anchors,
+                                                      g.threshold, f32, lengths)
+    return SimpleNamespace(outs=outs, confs=confs, stats=stats, b_outs=b_outs, anchor_of_plane=anchor_of_plane, counts=counts,
+                           lengths=lengths)
+
+
+def test_restatement_equals_what_the_point_solver_script_wrote(golden, restated):
+    g, I = golden, golden.n_input
+    conf = np.stack(restated.confs) * 255
+    assert g.point_conf_agreed.mean() >= 0.999 and g.point_png_agreed.mean() >= 0.999
+    assert np.array_equal(conf[g.point_conf_agreed], g.point_conf[g.point_conf_agreed])
+    assert (conf[:I] == 255).all()
+    png = np.stack([cr.images_to_uint8(o) for o in restated.outs[I:]])
+    assert np.array_equal(png[g.point_png_agreed], g.point_png[g.point_png_agreed])
+    for v in range(I):  # an input view keeps its image
+        assert np.array_equal(restated.outs[v], g.float_images[v])
+
+
+def test_restatement_equals_what_the_plane_solver_script_wrote(golden, restated):
+    g = golden
+    png = np.stack(restated.b_outs[g.n_input:])
+    assert g.plane_png_agreed.mean() >= 0.999
+    assert np.array_equal(png[g.plane_png_agreed], g.plane_png[g.plane_png_agreed])
+
+
+def test_golden_scene_has_the_cases_the_solvers_need(golden, restated):
+    g, s = golden, restated.stats
+    assert s == {k: golden.stats[k] for k in s}  # as recorded when the scripts ran
+    assert s["duplicate_pixels_differing"] > 1000 and s["changed_pixels"] > 1000 and max(s["conf_zeros"]) > 100
+    chain = np.bincount(np.concatenate(restated.lengths[g.n_input:]), minlength=3)
+    assert chain[2:].sum() > 100 and chain.tolist() == golden.stats["chain_lengths"]
+    assert golden.stats["own_view_anchor_pixels"] > 100
+    anchors = [restated.anchor_of_plane[k] for k in g.gdict]
+    assert anchors == golden.stats["anchors"] and len(set(anchors) - {-1}) >= 2
+    assert restated.counts.tolist() == golden.stats["counts"]
+    assert len(cr.plane_steps(g.gdict, restated.anchor_of_plane)) == golden.stats["steps"]
+    # the float64 evaluation decides the same way but for a handful of (point, view) pairs
+    vis32, _ = cr.point_tables(g.cams, g.depths, g.points, g.threshold, f32)
+    vis64, _ = cr.point_tables(g.cams, g.depths, g.points, g.threshold, np.float64)
+    assert (vis32 != vis64).sum() <= 0.001 * vis32.size
+
+
+def test_choose_anchor_views():
+    choose = consistency.choose_anchor_views
+    assert choose([[3, 7, 7], [0, 0, 0], [5, 5, 5], [0, 1, 0]], [9, 4, 2]) == [4, -1, 9, 4]  # a tie: the first wins
+    assert choose([[2], [0]], [6]) == [6, -1]  # a single anchor
+    assert choose([], [1, 2]) == [] and choose([[], []], []) == [-1, -1]
+    assert choose(torch.tensor([[1, 2], [4, 3]]), [0, 1]) == [1, 0] and choose(np.array([[1, 2]]), (5, 8)) == [8]
+    rng = np.random.default_rng(0)
+    counts = rng.integers(0, 4, (50, 6))
+    assert choose(counts, list(range(10, 16))) == cr.choose_anchor_views(counts, list(range(10, 16)))
+
+
+def test_plane_steps():
+    gdict = {0: [(0, 5), (2, 7)], 1: [(1, 5)], 2: [(2, 9), (0, 8), (1, 1)]}
+    assert consistency.plane_steps(gdict, {0: 2, 1: -1, 2: 0}) == [(0, 5, 2), (2, 7, 2), (2, 9, 0), (0, 8, 0), (1, 1, 0)]
+    assert consistency.plane_steps(gdict, {0: -1, 1: -1, 2: -1}) == []
+    assert consistency.plane_steps({"3": [[1, 2]]}, {3: 0}) == [(1, 2, 0)]  # as loaded from JSON
+    assert consistency.plane_steps({7: [(1, 2)], 3: [(0, 2)]}, {3: 1, 7: 0}) == [(1, 2, 0), (0, 2, 1)]  # dict order, not key order
+    for bad in ({0: [(0, 5), (0, 5)]}, {0: [(0, 5)], 1: [(1, 1), (0, 5)]}):
+        with pytest.raises(ValueError, match="twice"):
+            consistency.plane_steps(bad, {0: 0, 1: 0})
+    with pytest.raises(ValueError, match="twice"):  # even in a plane without an anchor
+        consistency.plane_steps({0: [(0, 5)], 1: [(0, 5)]}, {0: 0, 1: -1})
+
+
+def test_images_to_uint8():
+    x = np.array([0.0, 0.5, 1.0, 0.999, 1.0 / 255.0, 254.9 / 255.0], f32)
+    want = np.array([0, 127, 255, 254, int(f32(1.0) / f32(255.0) * f32(255.0)), int(f32(254.9) / f32(255.0) * f32(255.0))], np.uint8)
+    assert np.array_equal(consistency.images_to_uint8(x), want)
+    got = consistency.images_to_uint8(torch.tensor(x))
+    assert got.dtype == torch.uint8 and np.array_equal(got.numpy(), want)
+    # float32 u8 / 255 * 255 comes back for every byte although the save step truncates: an untouched pixel keeps its colour
+    u8 = np.arange(256, dtype=np.uint8)
+    assert np.array_equal(consistency.images_to_uint8(u8.astype(f32) / f32(255)), u8)
+    assert np.array_equal(cr.images_to_uint8(u8.astype(f32) / f32(255)), u8)
+
+
+@pytest.mark.parametrize("seed", range(8))
+def test_chain_walk_equals_the_literal_in_place_repaint(seed):
+    """Random sources over three small views: every step has one target view and one anchor, a pixel is in at most one step,
+    anchors may be the view itself and may have been repainted by an earlier step."""
+    rng = np.random.default_rng(seed)
+    sizes = [(3, 4), (2, 5), (4, 4)]
+    images = [rng.integers(0, 256, (h, w, 3)).astype(np.uint8) for h, w in sizes]
+    src = [(np.full(h * w, cr.NO_STEP, np.int64), np.zeros(h * w, np.int64), np.zeros(h * w, np.int64)) for h, w in sizes]
+    n_steps = 9
+    for t in range(n_steps):
+        w, a = int(rng.integers(3)), int(rng.integers(3))
+        free = np.nonzero(src[w][0] == cr.NO_STEP)[0]
+        q = rng.permutation(free)[: int(rng.integers(0, 5))]
+        src[w][0][q], src[w][1][q] = t, a
+        src[w][2][q] = rng.integers(0, sizes[a][0] * sizes[a][1], len(q))
+    lengths = [np.zeros(h * w, np.int64) for h, w in sizes]
+    walked = cr.resolve_chains(images, src, lengths)
+    literal = cr.repaint_in_place(images, src, n_steps)
+    for a, b in zip(walked, literal):
+        assert np.array_equal(a, b)
+    assert max(l.max() for l in lengths) >= 1
+
+
+def test_same_step_read_sees_the_state_before_the_step():
+    """View 0 repaints itself from itself, shifted by one pixel: pixel q reads q + 1, which the same step repaints."""
+    image = np.arange(5 * 3, dtype=np.uint8).reshape(1, 5, 3)
+    src = [(np.array([0, 0, 0, 0, cr.NO_STEP]), np.zeros(5, np.int64), np.array([1, 2, 3, 4, 0]))]
+    for out in (cr.resolve_chains([image], src)[0], cr.repaint_in_place([image], src, 1)[0]):
+        assert np.array_equal(out[0, :4], image[0, 1:]) and np.array_equal(out[0, 4], image[0, 4])
