@@ -1,5 +1,6 @@
 // What include/g4s_optim.h declares, kernels and entry points: the fused Adam step, the activations of the Gaussian
-// parameters, the densification statistics and, last, the stream compaction of Gaussian rows.
+// parameters (with and without the mip filter), the densification statistics, the mip filter sizes and, last, the
+// stream compaction of Gaussian rows.
 #include "g4s_internal.h"
 #include "g4s_device.h"
 #include "../../include/g4s_optim.h"
@@ -262,6 +263,170 @@ extern "C" int g4s_activations_backward(int P, const float* scales, const float*
                        (const float4*)rotation_raw, opacities, (const float2*)dL_dscales, (const float4*)dL_drotations,
                        dL_dopacities, (float2*)dL_dscaling_raw, (float4*)dL_drotation_raw, dL_dopacity_raw);
     return stage_done("activations backward launch", s);
+}
+
+// ---- activations with the mip filter on (2dgs/scene/gaussian_model.py:157-192, use_mip_filter) and the filter sizes
+// themselves (compute_mip_filter, :388-434); the contract and the order of operations are in include/g4s_optim.h.
+namespace g4s {
+__global__ void __launch_bounds__(256) activations_mip_fwd_kernel(int P, const float2* __restrict__ scaling,
+                                                                  const float4* __restrict__ rotation,
+                                                                  const float* __restrict__ opacity,
+                                                                  const float* __restrict__ mip, float2* __restrict__ scales,
+                                                                  float4* __restrict__ rots, float* __restrict__ opac) {
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= P) return;
+    const float2 s = scaling[i];
+    const float f = mip[i], f2 = f * f;
+    const float ex = expf(s.x), ey = expf(s.y);
+    const float ex2 = ex * ex, ey2 = ey * ey;
+    const float ax = ex2 + f2, ay = ey2 + f2;
+    scales[i] = make_float2(sqrtf(ax), sqrtf(ay));
+    const float4 q = rotation[i];
+    const float n = fmaxf(sqrtf(((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w), 1e-12f);
+    rots[i] = make_float4(q.x / n, q.y / n, q.z / n, q.w / n);
+    const float coef = sqrtf((ex2 * ey2) / (ax * ay));
+    opac[i] = (1.0f / (1.0f + expf(-opacity[i]))) * coef;
+}
+
+// Recomputes the forward's intermediates from the raw parameters (4 floats per Gaussian re-read) instead of reading
+// saved activations (3 floats saved and read); the filter carries no gradient.
+__global__ void __launch_bounds__(256) activations_mip_bwd_kernel(int P, const float2* __restrict__ scaling,
+                                                                  const float4* __restrict__ rotation,
+                                                                  const float* __restrict__ opacity,
+                                                                  const float* __restrict__ mip,
+                                                                  const float2* __restrict__ g_scales,
+                                                                  const float4* __restrict__ g_rots,
+                                                                  const float* __restrict__ g_opac,
+                                                                  float2* __restrict__ d_scaling,
+                                                                  float4* __restrict__ d_rotation,
+                                                                  float* __restrict__ d_opacity) {
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= P) return;
+    const float2 s = scaling[i], gs = g_scales[i];
+    const float f = mip[i], f2 = f * f;
+    const float ex = expf(s.x), ey = expf(s.y);
+    const float ex2 = ex * ex, ey2 = ey * ey;
+    const float ax = ex2 + f2, ay = ey2 + f2;
+    const float coef = sqrtf((ex2 * ey2) / (ax * ay));
+    const float sg = 1.0f / (1.0f + expf(-opacity[i]));
+    const float go = g_opac[i];
+    const float t = (go * sg) * coef;  // g_op * opacity:  d ln(coef) / d s_k = f^2 / a_k
+    d_scaling[i] = make_float2(gs.x * (ex2 / sqrtf(ax)) + t * (f2 / ax), gs.y * (ey2 / sqrtf(ay)) + t * (f2 / ay));
+    d_opacity[i] = (go * coef) * (sg * (1.0f - sg));
+    const float4 q = rotation[i], g = g_rots[i];
+    const float norm = sqrtf(((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w);
+    if (norm > 1e-12f) {  // y = q / |q|:  dq = (g - y <y, g>) / |q|
+        const float inv = 1.0f / norm;
+        const float4 u = make_float4(q.x * inv, q.y * inv, q.z * inv, q.w * inv);
+        const float d = ((u.x * g.x + u.y * g.y) + u.z * g.z) + u.w * g.w;
+        d_rotation[i] = make_float4((g.x - u.x * d) * inv, (g.y - u.y * d) * inv, (g.z - u.z * d) * inv, (g.w - u.w * d) * inv);
+    } else {              // clamped denominator: y = q / 1e-12
+        d_rotation[i] = make_float4(g.x * 1e12f, g.y * 1e12f, g.z * 1e12f, g.w * 1e12f);
+    }
+}
+
+constexpr float MIP_UNSEEN = 100000.0f;  // the reference's initial distance (:395)
+
+// Launch 1 of g4s_mip_filter: the smallest clamped depth over the views that see the point, or MIP_UNSEEN.  The view
+// index is the same in every lane, so the sixteen table reads of a view are scalar loads.  The largest value a seen
+// point keeps is folded per wave and goes to *seen_max by an integer max on the float's bits (the values are positive:
+// the bits order like the values, and a maximum does not depend on the order of its operands).
+__global__ void __launch_bounds__(256) mip_filter_depth_kernel(int P, const float* __restrict__ xyz, int V,
+                                                               const float* __restrict__ cam, float znear,
+                                                               float* __restrict__ out, uint32_t* __restrict__ seen_max) {
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    const bool live = i < P;
+    const size_t i3 = 3 * (size_t)(live ? i : 0);
+    const float x = xyz[i3], y = xyz[i3 + 1], z = xyz[i3 + 2];
+    float d = MIP_UNSEEN;
+    bool seen = false;
+    for (int v = 0; v < V; v++) {
+        const float* __restrict__ c = cam + 16 * (size_t)v;
+        const float xc = ((x * c[0] + y * c[3]) + z * c[6]) + c[9];
+        const float yc = ((x * c[1] + y * c[4]) + z * c[7]) + c[10];
+        const float zc = ((x * c[2] + y * c[5]) + z * c[8]) + c[11];
+        const float zp = fmaxf(zc, 0.001f);
+        const float w = c[14], h = c[15];
+        const float pu = (xc / zp) * c[12] + 0.5f * w;
+        const float pv = (yc / zp) * c[13] + 0.5f * h;
+        const bool ok = zc > znear && pu >= -0.15f * w && pu <= 1.15f * w && pv >= -0.15f * h && pv <= 1.15f * h;
+        if (ok) d = fminf(d, zp);
+        seen = seen || ok;
+    }
+    if (live) out[i] = d;
+    const uint32_t m = wave_max_u32(live && seen ? __float_as_uint(d) : 0u);
+    if (lane_id() == 0 && m != 0u) atomicMax(seen_max, m);
+}
+
+// Launch 2: points that no view sees take the largest depth of the seen ones (:431; MIP_UNSEEN when there is none),
+// then the scale.  A seen point further than MIP_UNSEEN holds MIP_UNSEEN too, and then so does the maximum.
+__global__ void __launch_bounds__(256) mip_filter_scale_kernel(int P, float* __restrict__ out,
+                                                               const uint32_t* __restrict__ seen_max, float scale) {
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= P) return;
+    const uint32_t m = *seen_max;
+    const float far = m != 0u ? __uint_as_float(m) : MIP_UNSEEN;
+    const float d = out[i];
+    out[i] = (d == MIP_UNSEEN ? far : d) * scale;
+}
+}  // namespace g4s
+
+extern "C" int g4s_activations_mip_forward(int P, const float* scaling_raw, const float* rotation_raw, const float* opacity_raw,
+                                           const float* mip_filter, float* scales, float* rotations, float* opacities,
+                                           void* stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    clear_error();
+    if (P < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "P must not be negative");
+    if (P == 0) return G4S_OK;
+    if (!scaling_raw || !rotation_raw || !opacity_raw || !mip_filter || !scales || !rotations || !opacities)
+        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (misaligned(scaling_raw, 8) || misaligned(scales, 8) || misaligned(rotation_raw, 16) || misaligned(rotations, 16))
+        return fail(G4S_ERR_INVALID_ARGUMENT, "scaling / scales must be 8-byte, rotations 16-byte aligned");
+    hipLaunchKernelGGL(activations_mip_fwd_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, P,
+                       (const float2*)scaling_raw, (const float4*)rotation_raw, opacity_raw, mip_filter, (float2*)scales,
+                       (float4*)rotations, opacities);
+    return stage_done("activations (mip filter) launch", s);
+}
+
+extern "C" int g4s_activations_mip_backward(int P, const float* scaling_raw, const float* rotation_raw, const float* opacity_raw,
+                                            const float* mip_filter, const float* dL_dscales, const float* dL_drotations,
+                                            const float* dL_dopacities, float* dL_dscaling_raw, float* dL_drotation_raw,
+                                            float* dL_dopacity_raw, void* stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    clear_error();
+    if (P < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "P must not be negative");
+    if (P == 0) return G4S_OK;
+    if (!scaling_raw || !rotation_raw || !opacity_raw || !mip_filter || !dL_dscales || !dL_drotations || !dL_dopacities ||
+        !dL_dscaling_raw || !dL_drotation_raw || !dL_dopacity_raw)
+        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (misaligned(scaling_raw, 8) || misaligned(dL_dscales, 8) || misaligned(dL_dscaling_raw, 8) ||
+        misaligned(rotation_raw, 16) || misaligned(dL_drotations, 16) || misaligned(dL_drotation_raw, 16))
+        return fail(G4S_ERR_INVALID_ARGUMENT, "scale tensors must be 8-byte, rotation tensors 16-byte aligned");
+    hipLaunchKernelGGL(activations_mip_bwd_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, P,
+                       (const float2*)scaling_raw, (const float4*)rotation_raw, opacity_raw, mip_filter,
+                       (const float2*)dL_dscales, (const float4*)dL_drotations, dL_dopacities, (float2*)dL_dscaling_raw,
+                       (float4*)dL_drotation_raw, dL_dopacity_raw);
+    return stage_done("activations (mip filter) backward launch", s);
+}
+
+extern "C" size_t g4s_mip_filter_workspace(void) { return align_up(sizeof(uint32_t)) + 256; }  // one word, aligned here
+
+extern "C" int g4s_mip_filter(int P, const float* xyz, int V, const float* cameras, float znear, float scale,
+                              float* mip_filter_out, char* workspace, void* stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    clear_error();
+    if (P < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "P must not be negative");
+    if (V < 1) return fail(G4S_ERR_INVALID_ARGUMENT, "at least one view");
+    if (P == 0) return G4S_OK;
+    if (!xyz || !cameras || !mip_filter_out || !workspace) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (misaligned(xyz, 4) || misaligned(cameras, 4) || misaligned(mip_filter_out, 4))
+        return fail(G4S_ERR_INVALID_ARGUMENT, "float tensors must be 4-byte aligned");
+    uint32_t* seen_max = (uint32_t*)align_ptr(workspace);
+    if (hipMemsetAsync(seen_max, 0, sizeof(uint32_t), s) != hipSuccess) return fail(G4S_ERR_HIP, "memset failed");
+    const dim3 grid((unsigned)((P + 255) / 256));
+    hipLaunchKernelGGL(mip_filter_depth_kernel, grid, dim3(256), 0, s, P, xyz, V, cameras, znear, mip_filter_out, seen_max);
+    hipLaunchKernelGGL(mip_filter_scale_kernel, grid, dim3(256), 0, s, P, mip_filter_out, seen_max, scale);
+    return stage_done("mip_filter launch", s);
 }
 
 // ---- stream compaction of Gaussian rows: the device side of prune_points / densify_and_clone /

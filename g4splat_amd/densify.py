@@ -189,7 +189,26 @@ class DensifyMixin:
     @torch.no_grad()
     def compute_mip_filter(self, cameras, znear=0.2, filter_variance=0.2):
         """:388-434: per-Gaussian low-pass size = (depth of the closest camera that sees it) / (largest focal length)
-        * sqrt(filter_variance).  Cameras expose R, T, focal_x, focal_y, image_width, image_height."""
+        * sqrt(filter_variance).  Cameras expose R, T, focal_x, focal_y, image_width, image_height.
+
+        On a HIP model: one camera table, one copy, two launches (optim.mip_filter -> g4s_mip_filter), written IN PLACE
+        when `self.mip_filter` already has P rows -- the address a captured TrainStepGraph holds stays valid across
+        recomputations at constant P -- and into a new tensor otherwise.  If no view sees any point every row is
+        100000 * sqrt(filter_variance) / focal there (the torch loop below raises on the empty max(), like the
+        reference).  Host tensors take the reference's loop."""
+        xyz = self._xyz
+        if xyz.is_cuda:
+            from .optim import mip_filter
+            old = self.mip_filter
+            reuse = (torch.is_tensor(old) and old.device == xyz.device and old.dtype == torch.float32
+                     and tuple(old.shape) == (xyz.shape[0], 1) and old.is_contiguous())
+            self.mip_filter = mip_filter(xyz, cameras, znear, filter_variance, out=old if reuse else None)
+            return
+        self.mip_filter = self._mip_filter_torch(cameras, znear, filter_variance)
+
+    @torch.no_grad()
+    def _mip_filter_torch(self, cameras, znear=0.2, filter_variance=0.2):
+        """The reference's loop over the cameras (:394-434) on whatever device the model is on -> [P,1]."""
         xyz = self._xyz
         distance = torch.full((xyz.shape[0],), 100000.0, device=xyz.device)
         seen = torch.zeros((xyz.shape[0],), dtype=torch.bool, device=xyz.device)
@@ -207,4 +226,4 @@ class DensifyMixin:
             seen |= ok
             focal = max(focal, cam.focal_x)
         distance[~seen] = distance[seen].max()
-        self.mip_filter = (distance / focal * (filter_variance ** 0.5))[..., None]
+        return (distance / focal * (filter_variance ** 0.5))[..., None]

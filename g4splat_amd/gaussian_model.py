@@ -82,11 +82,15 @@ class GaussianModel(DensifyMixin):
 
     @property
     def get_activated(self):
-        """(get_scaling, get_rotation, get_opacity) at once: one fused HIP launch each way on a HIP device with the mip
-        filter off (optim.fused_activations), the three getters otherwise.  render() reads this when present."""
-        if self._scaling.is_cuda and not self.use_mip_filter:
+        """(get_scaling, get_rotation, get_opacity) at once: one fused HIP launch each way on a HIP device, with the mip
+        filter on or off (optim.fused_activations), the three getters otherwise.  render() reads this when present."""
+        if self.use_mip_filter and self.mip_filter is None:
+            raise RuntimeError("GaussianModel: the mip filter is on but has not been computed "
+                               "(call compute_mip_filter(cameras) after set_mip_filter(True))")
+        if self._scaling.is_cuda:
             from .optim import fused_activations
-            return fused_activations(self._scaling, self._rotation, self._opacity)
+            return fused_activations(self._scaling, self._rotation, self._opacity,
+                                     self.mip_filter if self.use_mip_filter else None)
         return self.get_scaling, self.get_rotation, self.get_opacity
 
     def oneupSHdegree(self):

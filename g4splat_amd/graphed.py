@@ -21,8 +21,10 @@ host synchronisation).  The graph's inputs are the camera's world_view_transform
 the target image.  EVERYTHING ELSE is baked in at capture and needs a new TrainStepGraph when it changes: image size and
 field of view (cameras with other intrinsics), the number of Gaussians and the storage of the optimiser's parameter
 tensors (any densify / prune / reset_opacity that replaces them: a replay would train on freed memory), the active SH
-degree (oneupSHdegree()), `pipe.depth_ratio` and whatever `body` closes over (loss weights).  The first three groups
-are recorded at capture and checked on every call -- a stale graph raises instead of replaying.  `step.overflowed()` reads the PresizedState's overflow flag (synchronises): a frame that binned more
+degree (oneupSHdegree()), `pipe.depth_ratio`, whether the mip filter is on and the storage of `gaussians.mip_filter`
+(compute_mip_filter writes in place at unchanged P, so a recomputed filter is read by the next replay; a filter that was
+switched or rebound is not) and whatever `body` closes over (loss weights).  All but the last are recorded at capture and
+checked on every call -- a stale graph raises instead of replaying.  `step.overflowed()` reads the PresizedState's overflow flag (synchronises): a frame that binned more
 instances than `instance_capacity` is invalid and so is the update made from it.
 """
 from types import SimpleNamespace
@@ -78,12 +80,15 @@ class TrainStepGraph:
         self._captured = self._signature()
 
     def _signature(self):
-        """What a replay silently depends on besides its inputs: P, the active SH degree, depth_ratio and the addresses of
-        the optimiser's parameter tensors."""
+        """What a replay silently depends on besides its inputs: P, the active SH degree, depth_ratio, the addresses of
+        the optimiser's parameter tensors, and whether the mip filter is on and where it lives (compute_mip_filter writes
+        in place at constant P, so a recomputed filter is simply what the next replay reads)."""
         g = self.gaussians
         params = [p for grp in g.optimizer.param_groups for p in grp["params"]]
+        mip = getattr(g, "mip_filter", None)
         return (int(g.get_xyz.shape[0]), int(g.active_sh_degree), float(getattr(self.pipe, "depth_ratio", 0.0)),
-                tuple(int(p.data_ptr()) for p in params))
+                tuple(int(p.data_ptr()) for p in params),
+                (bool(getattr(g, "use_mip_filter", False)), int(mip.data_ptr()) if torch.is_tensor(mip) else 0))
 
     def _snapshot(self):
         g = self.gaussians
@@ -131,7 +136,8 @@ class TrainStepGraph:
         now = self._signature()
         if now != self._captured:
             what = [n for n, a, b in zip(("number of Gaussians", "active SH degree", "pipe.depth_ratio",
-                                          "optimiser parameter tensors (densify / prune / reset_opacity replaced them)"),
+                                          "optimiser parameter tensors (densify / prune / reset_opacity replaced them)",
+                                          "mip filter (switched, or rebound to another tensor)"),
                                          self._captured, now) if a != b]
             raise RuntimeError("TrainStepGraph is stale -- changed since capture: " + ", ".join(what) +
                                "; build a new TrainStepGraph")

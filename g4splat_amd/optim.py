@@ -195,16 +195,89 @@ class _Activations(torch.autograd.Function):
         return ds, dr, do
 
 
-def fused_activations(scaling, rotation, opacity):
+class _ActivationsMip(torch.autograd.Function):
+    """The activations with the mip filter on.  The backward recomputes from the raw parameters, so those (and the
+    filter, a no_grad buffer) are what is saved."""
+
+    @staticmethod
+    def forward(ctx, scaling, rotation, opacity, mip_filter):
+        dev = scaling.device
+        P = int(scaling.shape[0])
+        s, r, o = scaling.detach().contiguous(), rotation.detach().contiguous(), opacity.detach().contiguous()
+        f = mip_filter.detach().contiguous()
+        with torch.cuda.device(dev):
+            scales, rots, opac = torch.empty_like(s), torch.empty_like(r), torch.empty_like(o)
+            _lib.call("g4s_activations_mip_forward", P, *map(_lib.ptr, (s, r, o, f, scales, rots, opac)), _lib.stream(dev))
+        ctx.save_for_backward(s, r, o, f)
+        return scales, rots, opac
+
+    @staticmethod
+    def backward(ctx, g_scales, g_rots, g_opac):
+        s, r, o, f = ctx.saved_tensors
+        dev = s.device
+        P = int(s.shape[0])
+        zero = lambda ref, g: torch.zeros_like(ref) if g is None else g.contiguous()
+        gs, gr, go = zero(s, g_scales), zero(r, g_rots), zero(o, g_opac)
+        with torch.cuda.device(dev):
+            ds, dr, do = torch.empty_like(s), torch.empty_like(r), torch.empty_like(o)
+            _lib.call("g4s_activations_mip_backward", P, *map(_lib.ptr, (s, r, o, f, gs, gr, go, ds, dr, do)),
+                      _lib.stream(dev))
+        return ds, dr, do, None
+
+
+def fused_activations(scaling, rotation, opacity, mip_filter=None):
     """-> (exp(scaling) [P,2], normalize(rotation) [P,4], sigmoid(opacity) [P,1]): the three getters render() reads
-    (gaussian_model.py:157-192, mip filter off) as one HIP launch each way (include/g4s_optim.h).  HIP tensors only."""
-    if not (scaling.is_cuda and rotation.is_cuda and opacity.is_cuda):
+    (gaussian_model.py:157-192) as one HIP launch each way (include/g4s_optim.h).  With `mip_filter` (float32 [P,1] or
+    [P], the buffer compute_mip_filter fills) they are the getters with the filter on: sqrt(exp(scaling)^2 + filter^2)
+    and the opacity rescaled by the ratio of the two determinants; the filter receives no gradient.  HIP tensors only."""
+    if not (scaling.is_cuda and rotation.is_cuda and opacity.is_cuda and (mip_filter is None or mip_filter.is_cuda)):
         raise RuntimeError("fused_activations: HIP tensors only")
     P = scaling.shape[0]
     if (tuple(scaling.shape) != (P, 2) or tuple(rotation.shape) != (P, 4) or opacity.numel() != P
             or any(t.dtype != torch.float32 for t in (scaling, rotation, opacity))):
         raise RuntimeError("fused_activations: expected float32 scaling [P,2], rotation [P,4], opacity [P,1]")
-    return _Activations.apply(scaling, rotation, opacity)
+    if mip_filter is None:
+        return _Activations.apply(scaling, rotation, opacity)
+    if mip_filter.numel() != P or mip_filter.dtype != torch.float32 or mip_filter.device != scaling.device:
+        raise RuntimeError("fused_activations: expected a float32 mip_filter [P,1] on the parameters' device")
+    return _ActivationsMip.apply(scaling, rotation, opacity, mip_filter)
+
+
+@torch.no_grad()
+def mip_filter(xyz, cameras, znear=0.2, filter_variance=0.2, out=None):
+    """GaussianModel.compute_mip_filter (gaussian_model.py:388-434) on the HIP device (include/g4s_optim.h,
+    g4s_mip_filter): the camera table is built once on the host and copied once, then two launches -- no loop over the
+    views in Python, no temporaries per view, no host synchronisation.  Cameras expose R, T, focal_x, focal_y,
+    image_width, image_height.  `out`: a contiguous float32 [P,1] tensor on xyz's device to fill in place (its address
+    stays what a captured graph holds); a new one otherwise.  Returns the filter [P,1]."""
+    import numpy as np
+    if not xyz.is_cuda:
+        raise RuntimeError("mip_filter: HIP tensors only")
+    P, dev = int(xyz.shape[0]), xyz.device
+    if tuple(xyz.shape) != (P, 3) or xyz.dtype != torch.float32:
+        raise RuntimeError("mip_filter: expected float32 xyz [P,3]")
+    cameras = list(cameras)
+    if not cameras:
+        raise RuntimeError("mip_filter: at least one camera")
+    host = lambda a: np.asarray(a.detach().cpu() if torch.is_tensor(a) else a, dtype=np.float32)
+    table = np.empty((len(cameras), 16), dtype=np.float32)
+    for row, cam in zip(table, cameras):
+        row[0:9] = host(cam.R).reshape(9)
+        row[9:12] = host(cam.T).reshape(3)
+        row[12:16] = (cam.focal_x, cam.focal_y, cam.image_width, cam.image_height)
+    focal = max(float(cam.focal_x) for cam in cameras)
+    scale = float(np.float32(float(filter_variance) ** 0.5 / focal))
+    if out is None:
+        out = torch.empty((P, 1), dtype=torch.float32, device=dev)
+    elif out.numel() != P or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+        raise RuntimeError("mip_filter: out must be a contiguous float32 [P,1] tensor on xyz's device")
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        cams = torch.from_numpy(table).to(dev)
+        ws = torch.empty(lib.g4s_mip_filter_workspace(), dtype=torch.uint8, device=dev)
+        _lib.call("g4s_mip_filter", P, _lib.ptr(xyz.detach().contiguous()), len(cameras), _lib.ptr(cams), float(znear), scale,
+                  _lib.ptr(out), _lib.ptr(ws), _lib.stream(dev))
+    return out
 
 
 @torch.no_grad()

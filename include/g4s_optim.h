@@ -57,7 +57,7 @@ int g4s_densify_stats(int P, const float* grad_mean2D, const unsigned char* upda
 
 /*
  * Parameter activations as render() reads them (2d-gaussian-splatting/scene/gaussian_model.py:157-192, mip filter
- * off): scales = exp(_scaling) [P,2], rotations = normalize(_rotation) [P,4] (x / max(|x|, 1e-12), as
+ * off; with the filter on: g4s_activations_mip_* below): scales = exp(_scaling) [P,2], rotations = normalize(_rotation) [P,4] (x / max(|x|, 1e-12), as
  * torch.nn.functional.normalize), opacities = sigmoid(_opacity) [P].  One launch each way instead of ~5 / ~9.
  * The backward takes the activated scales / opacities the forward produced and the raw rotations.
  * Scale tensors 8-byte, rotation tensors 16-byte aligned.
@@ -67,6 +67,59 @@ int g4s_activations_forward(int P, const float* scaling_raw, const float* rotati
 int g4s_activations_backward(int P, const float* scales, const float* rotation_raw, const float* opacities,
                              const float* dL_dscales, const float* dL_drotations, const float* dL_dopacities,
                              float* dL_dscaling_raw, float* dL_drotation_raw, float* dL_dopacity_raw, void* stream);
+
+/*
+ * The same activations with the mip filter ON (use_mip_filter, what G4Splat trains with), in the reference's order
+ * of operations; mip_filter is the float32 [P] buffer compute_mip_filter fills (its [P,1] tensor, contiguous), f below:
+ *
+ *   e_k = exp(s_k)   a_k = e_k e_k + f f   scales_k = sqrt(a_k)            (k = x, y)
+ *   coef = sqrt((e_x^2 e_y^2) / (a_x a_y))                                  opacity = sigmoid(o) coef
+ *
+ * and rotations exactly as above.  One launch each way, instead of ~18 element-wise launches forward and ~30 in
+ * autograd's backward.  The backward RECOMPUTES from the raw parameters (4 floats per Gaussian re-read, against 3
+ * activated floats saved and read); the filter is a no_grad buffer and receives no gradient.  With sg = sigmoid(o):
+ *
+ *   d o   = g_op coef sg (1 - sg)
+ *   d s_k = g_sc,k e_k^2 / scales_k + g_op sg coef f^2 / a_k              (d ln coef / d s_k = f^2 / a_k: no 1 - x)
+ *
+ * Rotation backward as g4s_activations_backward, clamped branch included.  Same alignment rules.
+ */
+int g4s_activations_mip_forward(int P, const float* scaling_raw, const float* rotation_raw, const float* opacity_raw,
+                                const float* mip_filter, float* scales, float* rotations, float* opacities, void* stream);
+int g4s_activations_mip_backward(int P, const float* scaling_raw, const float* rotation_raw, const float* opacity_raw,
+                                 const float* mip_filter, const float* dL_dscales, const float* dL_drotations,
+                                 const float* dL_dopacities, float* dL_dscaling_raw, float* dL_drotation_raw,
+                                 float* dL_dopacity_raw, void* stream);
+
+/*
+ * The mip filter sizes, GaussianModel.compute_mip_filter (2d-gaussian-splatting/scene/gaussian_model.py:388-434):
+ * per Gaussian the depth of the closest view that sees it, times `scale`.  The reference loops over the cameras in
+ * Python (~20 launches and several [P] / [P,3] temporaries per view); here the views are a device table and the
+ * whole thing is two launches (and a 4-byte memset), without a host synchronisation or a per-view temporary.
+ *
+ *   cameras  [V,16] float32 on the device, per view: R row-major (9), T (3), focal_x, focal_y, image_width, image_height
+ *            (R and T as the reference's cameras hold them: camera space = xyz @ R + T)
+ *   scale    sqrt(filter_variance) / max focal_x, formed on the host in double and rounded once
+ *   workspace  g4s_mip_filter_workspace() bytes of device scratch
+ *
+ * Per point (x, y, z) and view, in float32, every operation rounded on its own (no FMA; the library is built with
+ * -ffp-contract=off and correctly rounded division), in exactly this order:
+ *
+ *   x_c = ((x R00 + y R10) + z R20) + T0     y_c = ((x R01 + y R11) + z R21) + T1     z_c = ((x R02 + y R12) + z R22) + T2
+ *   z' = max(z_c, 0.001)       u = (x_c / z') focal_x + 0.5 W       v = (y_c / z') focal_y + 0.5 H
+ *   seen by the view  <=>  z_c > znear  and  -0.15f W <= u <= 1.15f W  and  -0.15f H <= v <= 1.15f H
+ *
+ * (-0.15f, 1.15f: the float32 constants, multiplied in float32).  d = min(100000, z' of the views that see the point);
+ * points seen by no view take the largest d of the seen ones; mip_filter_out[i] = d scale.  The largest d is folded by
+ * an integer maximum on the floats' bits (they are positive), so the result does not depend on any order and two runs
+ * give the same bits.  Against the reference: its xyz @ R is a GEMM whose summation order is the BLAS's, and it divides
+ * by the focal length and multiplies by sqrt(filter_variance) in two steps -- a few ulp.  ONE documented difference:
+ * when no view sees any point the reference raises (max() of an empty tensor); here every row gets 100000 scale, which
+ * needs no synchronisation to find out.  V >= 1.
+ */
+size_t g4s_mip_filter_workspace(void);
+int g4s_mip_filter(int P, const float* xyz, int V, const float* cameras, float znear, float scale, float* mip_filter_out,
+                   char* workspace, void* stream);
 
 /*
  * Stream compaction of Gaussian rows: the device side of prune_points / densify_and_clone / densify_and_split
