@@ -163,6 +163,11 @@ SIGNATURES = {
                                            c_p]),
     "g4s_consistency_plane_repaint_workspace": (c_sz, [c_i, c_p, c_i]),
     "g4s_consistency_plane_repaint": (c_i, [c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_view_bits_workspace": (c_sz, [c_i]),
+    "g4s_view_bits": (c_i, [c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_view_overlap": (c_i, [c_i, c_i, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_fps_workspace": (c_sz, [c_i, c_i]),
+    "g4s_fps": (c_i, [c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_sz, c_p]),
 }
 
 _lib = None

@@ -727,6 +727,60 @@ int g4s_consistency_plane_repaint(float depth_threshold, int n_views, const floa
                                   unsigned char* const* images_out, const int* slot_offset, const int* slot_step,
                                   const int* slot_anchor, char* workspace, size_t workspace_bytes, void* stream);
 
+/* =====================================================================================================================
+ * View selection (g4splat_amd/csrc/tsdf/view_select.hip).
+ *
+ * The two device pieces of the reference's novel-view stage that sit between the visibility maps and the camera file
+ * (2d-gaussian-splatting/render_novel_views.py over guidance/cam_utils.py): select_need_inpaint_views, which asks
+ * covisibility_check_by_gs for pairs of candidate cameras, and get_novel_cams_lookat_points, which runs
+ * farthest_point_sample once per input view.  The library computes bits, integer counts and samples; the sequential
+ * decisions and the random draws are the caller's (g4splat_amd/view_selection.py).  The semantics are this library's own,
+ * stated exactly (tests/view_selection_ref.py restates them in numpy): float32, round-to-nearest-even, correctly rounded /,
+ * no fused multiply-add, evaluated left to right as written; min is IEEE minNum.
+ *
+ * A. Visible bits and the covisibility table.  C >= 1 cameras, at most 65535, each with world_view, focal and sizes as in
+ *   the Visibility section; a camera here has a size {W, H} but no map.  points [P,3] float32 (device), 0 <= P <= 2^31 - 64.
+ *   Camera c sees point p iff in image && z > 0, with c_j, z, u, v and "in image" the Visibility section's projection, the
+ *   same device function (every comparison with a NaN is false: a point with a NaN coordinate is seen by no camera).
+ *   words [C, ceil(P / 64)] 64-bit: bit (p & 63) of words[c][p >> 6] is set iff camera c sees point p; the bits beyond P
+ *   are zero.  Every word is written once, no atomics.
+ *   counts [C,C] int32: counts[i][j] = sum over w of popcount(words[i][w] & words[j][w]), the number of points both
+ *   cameras see; the diagonal holds the visible counts, the matrix is symmetric.  Integer sums by integer atomics: the
+ *   result does not depend on the order of execution.  n_words = 0 gives zero counts and launches nothing.
+ *   The overlap takes any words [C, n_words] of that layout (n_words <= 2^25); it does not look at P.
+ *
+ * B. Farthest-point sampling, batched.  clouds [M,N,3] float32 (device), finite; 1 <= M <= 65535, 3 <= N <= 2^30; k samples
+ *   with 2 <= k < N and M k <= 2^30; first [M] (HOST) the index of each cloud's sample 0, 0 <= first[m] < N.
+ *   Per cloud: dist_0[n] = 1e10f.  For round i = 1 .. k - 1, with q the point chosen in round i - 1 (round 0: first):
+ *   dx = p_n.x - q.x, dy, dz alike; d[n] = (dx*dx + dy*dy) + dz*dz; dist_i[n] = min(dist_{i-1}[n], d[n]); the choice of round i
+ *   is the n of largest dist_i[n], the SMALLEST such n on ties (the key (bits of dist_i[n] << 32) | ~n, dist >= 0, taken by a
+ *   64-bit unsigned atomic max: independent of the order of execution).
+ *   indices [M,k] int32; samples [M,k,3] = the chosen points; dist [M,N] = dist_{k-1}, required: it is the running minimum
+ *   the rounds work on.  k launches for all clouds together (k - 1 rounds and the gather).  The behaviour for non-finite
+ *   coordinates is unspecified beyond memory safety (every index stays inside its cloud).
+ *
+ * world_view, focal, sizes and first are HOST arrays, read during the call.  Every argument is checked on the host before
+ * anything is launched.  Every entry point takes workspace, workspace_bytes; those that name no size query use none and
+ * accept NULL, 0.
+ */
+
+/* Bytes of device workspace of g4s_view_bits for n_views cameras (the view table, 80 bytes per camera). */
+size_t g4s_view_bits_workspace(int n_views);
+
+/* words [n_views, ceil(n_points / 64)] for points [n_points,3] (device).  n_points = 0: nothing is launched. */
+int g4s_view_bits(int n_points, const float* points, int n_views, const float* world_view, const float* focal,
+                  const int* sizes, unsigned long long* words, char* workspace, size_t workspace_bytes, void* stream);
+
+/* counts [n_views, n_views] int32 (device), cleared and filled from words [n_views, n_words]. */
+int g4s_view_overlap(int n_views, int n_words, const unsigned long long* words, int* counts, char* workspace,
+                     size_t workspace_bytes, void* stream);
+
+/* Bytes of device workspace of g4s_fps (0 for arguments out of range). */
+size_t g4s_fps_workspace(int n_clouds, int n_samples);
+
+int g4s_fps(int n_clouds, int n_points, const float* clouds, const int* first, int n_samples, int* indices, float* samples,
+            float* dist, char* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
