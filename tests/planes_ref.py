@@ -152,6 +152,33 @@ def get_global_3Dplane(points, cams, masks, previous=None, thresh=0.5, depth_thr
     return [np.array(sorted(s), np.int64) for s in sets], ids
 
 
+def overlap_counts(labels, n_planes, member, block=1 << 16):
+    """(sizes [P], counts [P][G]) as Python ints: what SetProvider.view_counts counts, for slot labels [N] (anything outside
+    1 .. P is no label) and a membership table bool [G,N], as the matrix product of the one-hot labels and the table.
+    float64 sums of 0/1 products are exact far beyond any N; a block of points at a time keeps the one-hot matrix small."""
+    labels, member = np.asarray(labels).reshape(-1), np.asarray(member, bool)
+    P, (G, N) = int(n_planes), member.shape
+    assert labels.shape == (N,)
+    sizes, counts = np.zeros(P, np.int64), np.zeros((P, G), np.int64)
+    planes = np.arange(1, P + 1)
+    for a in range(0, N, block):
+        onehot = (labels[None, a:a + block] == planes[:, None]).astype(np.float64)
+        sizes += onehot.sum(1).astype(np.int64)
+        counts += (onehot @ member[:, a:a + block].T.astype(np.float64)).astype(np.int64)
+    return sizes.tolist(), counts.tolist()
+
+
+def row_overlap_counts(member, row, block=1 << 16):
+    """[G] Python ints: |row ∩ h| for every row h of a membership table bool [G,N], as matrix-vector products over blocks
+    of points."""
+    member = np.asarray(member, bool)
+    out = np.zeros(member.shape[0], np.int64)
+    for a in range(0, member.shape[1], block):
+        part = member[:, a:a + block].astype(np.float64)
+        out += (part @ part[row]).astype(np.int64)
+    return out.tolist()
+
+
 class SetProvider:
     """The counts provider of g4splat_amd.planes.merge_global_planes over Python sets: the counts the device would read
     back, from labels of this restatement.  Asserts the two facts."""

@@ -151,6 +151,47 @@ def test_chain_walk_equals_the_literal_in_place_repaint(seed):
     assert max(l.max() for l in lengths) >= 1
 
 
+def _random_sources(seed, sizes=((3, 4), (2, 5), (4, 4)), n_steps=9):
+    rng = np.random.default_rng(seed)
+    images = [rng.integers(0, 256, (h, w, 3)).astype(np.uint8) for h, w in sizes]
+    src = [(np.full(h * w, cr.NO_STEP, np.int64), np.zeros(h * w, np.int64), np.zeros(h * w, np.int64)) for h, w in sizes]
+    for t in range(n_steps):
+        w, a = int(rng.integers(len(sizes))), int(rng.integers(len(sizes)))
+        free = np.nonzero(src[w][0] == cr.NO_STEP)[0]
+        q = rng.permutation(free)[: int(rng.integers(0, 5))]
+        src[w][0][q], src[w][1][q] = t, a
+        src[w][2][q] = rng.integers(0, sizes[a][0] * sizes[a][1], len(q))
+    return images, src
+
+
+@pytest.mark.parametrize("seed", range(8))
+def test_walking_all_chains_at_once_equals_the_walk_pixel_by_pixel(seed):
+    """cr.resolve_chains_at_once serves the GPU test whose views are too large for cr.resolve_chains; here both run, on
+    the random sources of the test above, with the chain lengths."""
+    images, src = _random_sources(seed)
+    lengths = [np.zeros(len(s[0]), np.int64) for s in src]
+    lengths_at_once = [np.full(len(s[0]), -1, np.int64) for s in src]
+    walked = cr.resolve_chains(images, src, lengths)
+    at_once = cr.resolve_chains_at_once(images, src, lengths_at_once)
+    for a, b, la, lb in zip(walked, at_once, lengths, lengths_at_once):
+        assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b) and np.array_equal(la, lb)
+    assert max(l.max() for l in lengths) >= 1
+    literal = cr.repaint_in_place(images, src, 9)
+    assert all(np.array_equal(a, b) for a, b in zip(at_once, literal))
+
+
+def test_walking_all_chains_at_once_on_the_golden_scene(golden, restated):
+    g = golden
+    lengths = [np.zeros(m.size, np.int64) for m in g.masks]
+    outs, anchor_of_plane, counts = cr.plane_solver(g.cams, g.depths, g.images, g.masks, g.clouds, g.gdict, g.anchors, g.threshold,
+                                                    f32, lengths, cr.resolve_chains_at_once)
+    assert anchor_of_plane == restated.anchor_of_plane and np.array_equal(counts, restated.counts)
+    for a, b, la, lb in zip(outs, restated.b_outs, lengths, restated.lengths):
+        assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b) and np.array_equal(la, lb)
+    assert max(l.max() for l in lengths) >= 2  # chains of more than one hop
+    assert cr.resolve_chains_at_once([], []) == []
+
+
 def test_same_step_read_sees_the_state_before_the_step():
     """View 0 repaints itself from itself, shifted by one pixel: pixel q reads q + 1, which the same step repaints."""
     image = np.arange(5 * 3, dtype=np.uint8).reshape(1, 5, 3)

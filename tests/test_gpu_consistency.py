@@ -133,9 +133,10 @@ def _solve_planes(cams, depths, images, masks, points, gdict, anchors, threshold
     return _np(outs), anchor_of_plane, counts.numpy()
 
 
-def _check_planes(cams, depths, images, masks, points, gdict, anchors, threshold):
+def _check_planes(cams, depths, images, masks, points, gdict, anchors, threshold, resolve=None):
     outs, anchor_of_plane, counts = _solve_planes(cams, depths, images, masks, points, gdict, anchors, threshold)
-    want_outs, want_anchor, want_counts = cr.plane_solver(cams, depths, images, masks, points, gdict, anchors, threshold)
+    want_outs, want_anchor, want_counts = cr.plane_solver(cams, depths, images, masks, points, gdict, anchors, threshold,
+                                                          resolve=resolve)
     assert counts.shape == want_counts.shape and np.array_equal(counts, want_counts)
     assert anchor_of_plane == want_anchor and list(anchor_of_plane) == list(want_anchor)
     _same(outs, want_outs)
@@ -430,6 +431,48 @@ def test_plane_views_of_different_sizes(hip_lib):
     gdict = {5: [(1, 3)], 2: [(0, 3), (0, 8)]}
     outs, anchor_of_plane, _counts = _check_planes(cams, depths, images, masks, [_grid_points(2.0), small], gdict, [0, 1], ETHRESH)
     assert anchor_of_plane == {5: 0, 2: 1} and (outs[1] != images[1]).any() and (outs[0] != images[0]).any()
+
+
+def _pixel_points(W, H, f, z):
+    """[H*W,3]: the point that an identity camera with focal length f sees in the centre of every pixel of a W x H image at
+    depth z; exact for the dyadic values used."""
+    y, x = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    return np.stack([(x.reshape(-1) + 0.5 - W / 2) / f * z, (y.reshape(-1) + 0.5 - H / 2) / f * z, np.full(W * H, z)], 1).astype(f32)
+
+
+def test_plane_counts_past_the_grid_cap(hip_lib):
+    """The count kernel launches at most CONS_COUNT_BLOCKS = 256 workgroups of 256 pixels per view: 65 536 pixels a pass.
+    Two 300 x 220 views (66 000 pixels: workgroup 0 takes a second block of 256 pixels, workgroup 1 one of 208) about a
+    5 x 3 view, whose 15 pixels end the loop of every workgroup but the first at once.  View 0 has depth 1 and points at
+    depth 2, view 2 depth 2 and points at depth 1: each is the other's anchor.  Plane id 77 covers the last row of view 0
+    only, pixels 65 700 and up: a kernel that stops after one pass counts nothing for it and leaves it without an
+    anchor."""
+    one_pass = 256 * 256  # CONS_COUNT_BLOCKS * 256 pixels
+    BW, BH, BF = 300, 220, 256.0
+    assert BW * BH > one_pass and (BH - 1) * BW >= one_pass
+    rng = np.random.default_rng(66)
+    cams = [_camera(BW, BH, BF, BF), _camera(5, 3, 2.0, 2.0), _camera(BW, BH, BF, BF)]
+    depths = [np.ones((BH, BW), f32), np.full((3, 5), 4.0, f32), np.full((BH, BW), 2.0, f32)]
+    images = [rng.integers(0, 256, d.shape + (3,)).astype(np.uint8) for d in depths]
+    masks = [rng.choice([0, 3, 8], (BH, BW)).astype(np.int32), rng.choice([0, 3], (3, 5)).astype(np.int32),
+             rng.choice([0, 3, 8], (BH, BW)).astype(np.int32)]
+    masks[0][BH - 1] = 77
+    points = [_pixel_points(BW, BH, BF, 2.0), _pixel_points(5, 3, 2.0, 1.0), _pixel_points(BW, BH, BF, 1.0)]
+    gdict = {5: [(1, 3)], 2: [(0, 3), (0, 8)], 9: [(0, 77)], 4: [(2, 8), (2, 3)]}
+    outs, anchor_of_plane, counts = _check_planes(cams, depths, images, masks, points, gdict, [0, 1, 2], ETHRESH,
+                                                  resolve=cr.resolve_chains_at_once)
+    assert anchor_of_plane == {5: 0, 2: 2, 9: 2, 4: 0}
+    assert counts[2].tolist() == [0, 0, BW] and np.nonzero(masks[0].reshape(-1) == 77)[0].min() == (BH - 1) * BW
+    # every plane of the large views has pixels in both passes, and the reference counts them all
+    assert counts[1].tolist() == [0, 0, int(np.isin(masks[0], (3, 8)).sum())] and counts[3].tolist() == [int((masks[2] != 0).sum()), 0, 0]
+    assert np.isin(masks[0].reshape(-1)[one_pass:], (3, 8)).sum() > 50 and (masks[2].reshape(-1)[one_pass:] != 0).sum() > 100
+    assert 0 < counts[0, 0] <= 15 and counts[0, 1:].tolist() == [0, 0]
+    # the last row of view 0 now shows view 2's last row
+    assert np.array_equal(outs[0][BH - 1], images[2][BH - 1]) and (outs[0][BH - 1] != images[0][BH - 1]).any()
+    # a pixel of view 2 reads the same pixel of view 0, which an earlier step repainted from view 2's original where it has a plane
+    there, chained = (masks[2] != 0) & (masks[0] == 0), (masks[2] != 0) & (masks[0] != 0)
+    assert np.array_equal(outs[2][there], images[0][there]) and np.array_equal(outs[2][chained], images[2][chained])
+    assert np.array_equal(outs[2][masks[2] == 0], images[2][masks[2] == 0]) and (outs[1] != images[1]).any()
 
 
 # ---- argument errors ------------------------------------------------------------------------------------------------------------

@@ -151,34 +151,39 @@ def test_labels_of_the_edge_cloud(hip_lib, n, depth_thresh):
 N_SETS = 1061  # five blocks, not a multiple of 64
 
 
-def _random_membership(G, rng):
-    """(PlaneMembership, bool [G, N]) built by three assign launches, so that points belong to several rows."""
-    member = planes.PlaneMembership(N_SETS, DEV)
-    want = np.zeros((G, N_SETS), bool)
+def _random_membership(G, rng, N=N_SETS, tail=None):
+    """(PlaneMembership, bool [G, N]) built by three assign launches, so that points belong to several rows.  With `tail`
+    the last row gets members at and above that index only."""
+    member = planes.PlaneMembership(N, DEV)
+    want = np.zeros((G, N), bool)
     for _round in range(3):
-        labels = rng.integers(0, G + 1, N_SETS).astype(np.int32)
-        labels[rng.integers(0, N_SETS, 40)] = G + 7  # outside 1 .. P: counts as no label
-        labels[rng.integers(0, N_SETS, 40)] = -3
+        labels = rng.integers(0, G + 1, N).astype(np.int32)
+        labels[rng.integers(0, N, 40)] = G + 7  # outside 1 .. P: counts as no label
+        labels[rng.integers(0, N, 40)] = -3
         target = rng.permutation(G).tolist()
         if G > 2 and target[1] != G - 1:
             target[1] = -1
+        if tail is not None:
+            head = labels[:tail]
+            head[head == target.index(G - 1) + 1] = 0
         member.assign(_dev(labels), target)
         for p, t in enumerate(target):
             if t >= 0:
                 want[t] |= labels == p + 1
     assert member.G == G and member.n_words >= (G + 63) // 64
+    assert tail is None or (want[G - 1, tail:].any() and not want[G - 1, :tail].any())
     return member, want
 
 
 def _check_words(member, want):
     words = member.words.cpu().numpy().view(np.uint64)
-    G = want.shape[0]
+    G, N = want.shape
     for w in range(member.n_words):
-        expect = np.zeros(N_SETS, np.uint64)
+        expect = np.zeros(N, np.uint64)
         for b in range(64):
             if 64 * w + b < G:
                 expect |= want[64 * w + b].astype(np.uint64) << np.uint64(b)
-        assert np.array_equal(words[w, :N_SETS], expect), w  # the bits at and above G stay zero
+        assert np.array_equal(words[w, :N], expect), w  # the bits at and above G stay zero
 
 
 @pytest.mark.parametrize("P", [1, 70])
@@ -222,6 +227,120 @@ def test_counts_beyond_the_workgroup_table(hip_lib):
     sizes, counts = member.overlap(_dev(labels), 2)
     assert sizes == [int((labels == p).sum()) for p in (1, 2)]
     assert counts == [(rows @ (labels == p).astype(np.int64)).tolist() for p in (1, 2)]
+
+
+# Both count kernels launch at most COUNT_MAX_BLOCKS = 2048 workgroups of 256 points and keep their table in LDS while it
+# has at most COUNT_LDS_MAX = 8192 entries.  Whoever changes one of the two moves the sizes below.
+ONE_PASS = 2048 * 256  # COUNT_MAX_BLOCKS * 256 points
+N_PAST = ONE_PASS + 300  # workgroup 0 takes a second block of 256 points, workgroup 1 one of 44
+LDS_MAX = 8192  # COUNT_LDS_MAX
+
+
+@pytest.mark.parametrize("P,G", [(3, 65), (70, 130)])
+def test_overlap_past_the_grid_cap(hip_lib, P, G):
+    """(3, 65): 198 entries, the LDS table over two words per point; (70, 130): 9 170 entries, the global table.  Label P
+    and global row G - 1 occur at and above point 524 288 only: a kernel that stops after its first pass leaves their
+    row and column at zero."""
+    assert (P * G + P <= LDS_MAX) == (P == 3)
+    rng = np.random.default_rng(100 * G + P)
+    member, want = _random_membership(G, rng, N_PAST, tail=ONE_PASS)
+    labels = rng.integers(0, P, N_PAST).astype(np.int32)
+    labels[ONE_PASS:] = rng.integers(0, P + 1, N_PAST - ONE_PASS)
+    labels[::97] = P + 1
+    labels[5::101] = -1
+    labels[ONE_PASS + 250: ONE_PASS + 290] = P  # a run of the tail's label across the last wave boundary
+    sizes, counts = member.overlap(_dev(labels), P)
+    want_sizes, want_counts = pr.overlap_counts(labels, P, want)
+    assert sizes == want_sizes and counts == want_counts
+    assert sizes[P - 1] == int((labels[ONE_PASS:] == P).sum()) >= 40 and not (labels[:ONE_PASS] == P).any()
+    assert sum(want_counts[P - 1]) > 0 and sum(row[G - 1] for row in want_counts) > 0  # the tail's row and column count
+    in_tail = pr.overlap_counts(labels[ONE_PASS:], P, want[:, ONE_PASS:])
+    assert in_tail[1][P - 1] == want_counts[P - 1] and [row[G - 1] for row in in_tail[1]] == [row[G - 1] for row in want_counts]
+
+
+def test_row_counts_past_the_grid_cap_with_a_workgroup_table(hip_lib):
+    """G = 130: the LDS table of the row kernel, flushed after two passes.  Row 0 holds half of all points, so that every
+    wave has lanes at work in both passes; row G - 1 has members in the second pass only."""
+    G = 130
+    rng = np.random.default_rng(130)
+    member, want = _random_membership(G, rng, N_PAST, tail=ONE_PASS)
+    half = rng.integers(0, 2, N_PAST).astype(np.int32)
+    member.assign(_dev(half), [0])
+    want[0] |= half == 1
+    for row in (0, G - 1):
+        got = member.row_counts(row)
+        assert got == pr.row_overlap_counts(want, row)
+        assert got[row] == int(want[row].sum()) > 0
+    assert any(member.row_counts(G - 1)[:G - 1])  # the tail's row shares points with other rows
+    head = pr.row_overlap_counts(want[:, :ONE_PASS], 0)
+    assert head != pr.row_overlap_counts(want, 0)  # the second pass changes row 0's counts
+
+
+def test_row_counts_past_the_grid_cap_with_the_global_table(hip_lib):
+    """G = 8 200 over 524 588 points (129 words per point): the row kernel adds straight into the global table.  Only five
+    rows have members, so the expected counts are five boolean rows and not 8 200; row 8 199 has members in the second
+    pass only."""
+    G, rows = 8200, [0, 63, 64, 4100, 8199]
+    assert G > LDS_MAX
+    rng = np.random.default_rng(8201)
+    member = planes.PlaneMembership(N_PAST, DEV)
+    some = np.zeros((len(rows), N_PAST), bool)
+    for _round in range(3):
+        labels = rng.integers(0, 2 * len(rows), N_PAST).astype(np.int32)  # half of the labels: no target
+        order = rng.permutation(len(rows)).tolist()
+        tail_label = order.index(len(rows) - 1) + 1
+        head = labels[:ONE_PASS]
+        head[head == tail_label] = 0
+        target = [-1] * G
+        for p, k in enumerate(order):
+            target[p] = rows[k]
+            some[k] |= labels == p + 1
+        member.assign(_dev(labels), target)
+    assert member.G == G and member.n_words >= 129
+    assert some[-1, ONE_PASS:].any() and not some[-1, :ONE_PASS].any() and (some.sum(0) > 1).any()
+    for k, row in enumerate(rows):
+        want = [0] * G
+        for h, c in zip(rows, pr.row_overlap_counts(some, k)):
+            want[h] = c
+        assert member.row_counts(row) == want, row
+        assert want[row] == int(some[k].sum()) > 0
+    assert member.row_counts(5) == [0] * G  # a row without members
+
+
+@pytest.mark.parametrize("P,G", [(64, 127), (64, 128)])
+def test_overlap_at_the_switch_between_the_workgroup_and_the_global_table(hip_lib, P, G):
+    """64 * 127 + 64 = 8 192 entries: the largest LDS table (32 KiB of dynamic LDS); 64 * 128 + 64 = 8 256: the first
+    global one."""
+    assert (P * G + P <= LDS_MAX) == (G == 127) and P * 127 + P == LDS_MAX
+    rng = np.random.default_rng(100 * G + P)
+    member, want = _random_membership(G, rng)
+    labels = rng.integers(0, P + 1, N_SETS).astype(np.int32)
+    labels[::97] = P + 1
+    labels[5::101] = -1
+    labels[200:400] = P  # the last table row, in runs
+    sizes, counts = member.overlap(_dev(labels), P)
+    want_sizes, want_counts = pr.overlap_counts(labels, P, want)
+    assert sizes == want_sizes and counts == want_counts
+    assert sizes[P - 1] >= 200 and min(sizes) > 0
+    assert any(want_counts[P - 1]) and any(row[G - 1] for row in want_counts)  # the table's last row and column are in use
+
+
+@pytest.mark.parametrize("G", [8192, 8193])
+def test_row_counts_at_the_switch_between_the_workgroup_and_the_global_table(hip_lib, G):
+    """G = 8 192 = COUNT_LDS_MAX: the largest LDS table of the row kernel; 8 193: the first global one."""
+    assert (G <= LDS_MAX) == (G == 8192)
+    rng = np.random.default_rng(G)
+    member, want = _random_membership(G, rng)
+    labels = rng.integers(0, 4, N_SETS).astype(np.int32)  # a thousand points spread over G rows leave most rows empty:
+    member.assign(_dev(labels), [0, 4100, G - 1])        # the rows asked for below get a quarter of the points each
+    for p, row in enumerate((0, 4100, G - 1)):
+        want[row] |= labels == p + 1
+    _check_words(member, want)
+    for row in (0, 4100, G - 1):
+        got = member.row_counts(row)
+        assert got == pr.row_overlap_counts(want, row)
+        assert got[row] == int(want[row].sum()) > 200 and sum(1 for c in got if c) > 100
+    assert got[G - 1] > 200  # the table's last entry is in use
 
 
 def test_membership_grows_across_a_word(hip_lib):

@@ -12,13 +12,14 @@ import pytest
 import torch
 
 import view_selection_ref as sr
-from g4splat_amd import synthetic, view_selection as vs
+from g4splat_amd import _lib, synthetic, view_selection as vs
 
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-P_MAX = 4097
+P_EDGE = 4097
+P_MAX = 64 * 129 + 1  # 130 words: a full chunk of the count kernel (OVERLAP_CHUNK = 128 words) and a second of two words
 
 
 def _dev(a):
@@ -37,10 +38,10 @@ def _world(cam, c):
 
 @pytest.fixture(scope="module")
 def scene():
-    """Seventy cameras of mixed sizes and 4 097 points whose every prefix holds edge cases: the first camera's centre
+    """Seventy cameras of mixed sizes and 8 257 points whose every prefix holds edge cases: the first camera's centre
     (z = 0), a NaN point, points on u = 0, u = W, v = 0 and v = H of the first two cameras, points behind them, further
-    camera centres; then a cloud in and about the scene.  The restatement's masks are computed once; a prefix of the
-    points and of the cameras is a slice of them."""
+    camera centres; then a cloud in and about the scene, 4 097 points in all, and after them 4 160 more random points.
+    The restatement's masks are computed once; a prefix of the points and of the cameras is a slice of them."""
     cams = sr.spiral_cameras(70, True)
     rng = np.random.default_rng(31)
     special = [np.asarray(cams[0].camera_center, np.float64), [np.nan, 0.1, 0.2]]
@@ -53,12 +54,12 @@ def scene():
             special.extend(_world(cam, edge))
     special.extend(np.asarray(c.camera_center, np.float64) for c in cams[1:12])
     special.append([0.0, np.inf, 0.0])
-    pts = rng.uniform(-4.0, 4.0, (P_MAX, 3))
+    pts = rng.uniform(-4.0, 4.0, (P_EDGE, 3))
     s = rng.normal(size=(400, 3))
     pts[-400:] = s / np.linalg.norm(s, axis=1, keepdims=True) * rng.uniform(0.9, 1.1, (400, 1))
     pts[: len(special)] = np.asarray(special)
     assert len(special) < 63
-    pts = pts.astype(np.float32)
+    pts = np.concatenate([pts, rng.uniform(-4.0, 4.0, (P_MAX - P_EDGE, 3))]).astype(np.float32)
     masks = sr.visible_masks(pts, cams)
     assert 0.1 < masks.mean() < 0.6 and not masks[:, 1].any() and masks[:2, 2:38].any() and not masks[:2, 2:38].all()
     return cams, pts, masks
@@ -68,6 +69,19 @@ def scene():
 @pytest.mark.parametrize("P", [0, 1, 63, 64, 65, 1023, 1025, 4097])
 def test_bits_and_counts_equal_the_restatement(hip_lib, scene, P, C):
     """P covers word tails and workgroup tails (a workgroup owns 1 024 points), C the camera tiles of 16."""
+    _check_table(scene, P, C)
+
+
+def test_bits_and_counts_across_the_chunk_boundary_of_the_count_kernel(hip_lib, scene):
+    """All 8 257 points: 130 words per camera, so the bits kernel's rows feed the count kernel a full chunk of 128 words
+    and a second of two, over the three tile pairs of 70 cameras."""
+    cams, _pts, masks = scene
+    assert P_MAX == 8257 and (P_MAX + 63) // 64 == 128 + 2  # OVERLAP_CHUNK = 128
+    _check_table(scene, P_MAX, 70)
+    assert masks[:, 64 * 128:].any(1).sum() > 35  # the second chunk holds bits of most cameras
+
+
+def _check_table(scene, P, C):
     cams, pts, masks = scene
     want = masks[:C, :P]
     table = vs.Covisibility(_dev(pts[:P]), cams[:C])
@@ -89,6 +103,39 @@ def test_bits_and_counts_equal_the_restatement(hip_lib, scene, P, C):
         assert table.ratio(0, c) == ratio(0, c)
     else:
         assert not got.any() and table.ratio(0, C - 1) == 0 and table.mask(0).shape == (0,)
+
+
+# The count kernel on words it did not make.  Its grid is (tile pairs, per_pair) with per_pair = clamp(2048 / pairs, 1, chunks):
+# OVERLAP_MAX_BLOCKS = 2048 workgroups for all pairs of tiles of CAM_TILE = 16 cameras, a chunk being OVERLAP_CHUNK = 128
+# words; a workgroup walks chunks blockIdx.y, blockIdx.y + per_pair, ...  Whoever changes one of these moves the sizes below.
+OVERLAP_CASES = [
+    (17, 127),            # 3 pairs, one chunk, one word short
+    (17, 128),            # one chunk exactly
+    (17, 129),            # a second chunk of one word
+    (70, 128 * 137 + 5),  # 15 pairs: per_pair = 136 < 138 chunks, workgroups 0 and 1 of a pair take two; the last has 5 words
+    (1040, 257),          # 65 tiles, 2145 pairs > 2048: per_pair clamps to 1, a workgroup walks three chunks, the last of one word
+]
+
+
+@pytest.mark.parametrize("C,n_words", OVERLAP_CASES)
+def test_counts_of_given_words_equal_the_matrix_product_of_their_bits(hip_lib, C, n_words):
+    tiles = (C + 15) // 16
+    pairs, chunks = tiles * (tiles + 1) // 2, (n_words + 127) // 128
+    per_pair = min(max(2048 // pairs, 1), chunks)
+    assert (pairs, per_pair, chunks, n_words - 128 * (chunks - 1)) == {
+        (17, 127): (3, 1, 1, 127), (17, 128): (3, 1, 1, 128), (17, 129): (3, 2, 2, 1), (70, 17541): (15, 136, 138, 5),
+        (1040, 257): (2145, 1, 3, 1)}[(C, n_words)]  # what the case is for
+    words = sr.random_words(C, n_words, 7 * C + n_words)
+    dev_words = _dev(words.view(np.int64))
+    counts = torch.empty((C, C), dtype=torch.int32, device=DEV)
+    with torch.cuda.device(DEV):
+        _lib.call("g4s_view_overlap", C, n_words, _lib.ptr(dev_words), _lib.ptr(counts), None, 0, _lib.stream(DEV))
+    got = counts.cpu().numpy()
+    want = sr.bit_counts(words)
+    assert np.array_equal(got, want) and np.array_equal(got, got.T)
+    assert got[1, 1] == 64 * n_words and not got[2].any() and not got[:, 2].any()  # the row of ones, the empty row
+    assert np.array_equal(got[1], np.diag(got)) and 1 <= got[C - 1, C - 1] <= 64 and got[1, C - 1] == got[C - 1, C - 1]
+    assert np.array_equal(dev_words.cpu().numpy().view(np.uint64), words)  # the words are only read
 
 
 def test_a_camera_that_sees_nothing(hip_lib, scene):
@@ -153,6 +200,23 @@ def test_sampling_ties_go_to_the_smallest_index(hip_lib):
     same = np.tile(np.array([[0.25, -1.5, 3.0]], np.float32), (2, 11, 1))
     idx, dist = _check_sampling(same, 5, [7, 0])
     assert idx.tolist() == [[7, 0, 0, 0, 0], [0, 0, 0, 0, 0]] and not dist.any()  # all-zero distances select index 0
+
+
+def test_sampling_past_the_grid_cap(hip_lib):
+    """A round launches at most FPS_MAX_BLOCKS = 1024 workgroups of 256 * FPS_ITEMS = 1024 points per cloud, so a cloud
+    of more than 1 048 576 points sends workgroups round their loop again: workgroup 0 for 1 024 more points, workgroup 1
+    for one.  Cloud 0's farthest point lies in that second pass; cloud 1 has the same far point twice, once in each pass,
+    and the smaller index has to win although the larger is folded later by the same thread."""
+    one_pass = 1024 * 1024  # FPS_MAX_BLOCKS * 256 * FPS_ITEMS
+    N = one_pass + 1025
+    rng = np.random.default_rng(1049)
+    clouds = rng.normal(size=(2, N, 3)).astype(np.float32)
+    far, low, high = one_pass + 517, 608, one_pass + 608  # `low` and `high` belong to the same thread of workgroup 0
+    clouds[0, far] = (50.0, -50.0, 50.0)
+    clouds[1, low] = clouds[1, high] = (40.0, 40.0, -40.0)
+    idx, dist = _check_sampling(clouds, 4, [N - 1, 0])
+    assert idx[0, 1] == far and idx[1, 1] == low and high not in idx[1].tolist()
+    assert dist[1, low] == 0 and dist[1, high] == 0 and (dist[:, one_pass:] > 0).sum() > 2000  # the tail's distances are written
 
 
 def test_farthest_point_sample_keeps_the_reference_quirk_and_draws_on_the_device(hip_lib):

@@ -143,6 +143,29 @@ def test_empty_plane_in_view_zero_keeps_its_entry_and_never_merges():
     assert [a.tolist() for a in idx] == [[1, 2, 3, 4], []]
 
 
+@pytest.mark.parametrize("P,G,N,block", [(1, 1, 64, 1 << 16), (3, 65, 1061, 1 << 16), (7, 13, 1061, 100), (5, 4, 300, 300)])
+def test_matrix_product_counts_equal_the_sets(P, G, N, block):
+    """pr.overlap_counts and pr.row_overlap_counts serve the GPU tests whose point counts are too large for Python sets;
+    here they run against SetProvider's own counts, whole and in blocks of points that do not divide N."""
+    rng = np.random.default_rng(1000 * P + G)
+    member = rng.random((G, N)) < 0.3
+    member[G - 1, : N // 2] = False  # a row with members in the tail only
+    labels = rng.integers(-1, P + 3, N)  # -1, 0, P + 1 and P + 2: no label
+    labels[N // 2:][labels[N // 2:] == 1] = 0  # a label in the first half only
+    view = [(p, set(np.nonzero(labels == p)[0].tolist())) for p in range(1, P + 1)]
+    provider = pr.SetProvider([view])
+    provider.rows = [set(np.nonzero(m)[0].tolist()) for m in member]
+    _ids, want_sizes, want_counts = provider.view_counts(0)
+    sizes, counts = pr.overlap_counts(labels, P, member, block)
+    assert sizes == want_sizes and counts == want_counts
+    assert all(type(c) is int for c in sizes) and all(type(c) is int for row in counts for c in row)
+    assert sum(sizes) == int(((labels >= 1) & (labels <= P)).sum()) > 0
+    for row in sorted({0, G // 2, G - 1}):
+        assert pr.row_overlap_counts(member, row, block) == provider.row_counts(row)
+    # the expression the GPU tests of small tables use
+    assert counts == [[int(((labels == p) & member[g]).sum()) for g in range(G)] for p in range(1, P + 1)]
+
+
 def test_previous_dict_is_validated():
     views = [[(1, {1})], [(1, {1})]]
     with pytest.raises(ValueError, match="keys 0 .. K-1"):

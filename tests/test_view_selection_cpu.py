@@ -48,6 +48,24 @@ def test_restated_counts_are_symmetric_and_equal_the_popcounts_of_the_bits(gold)
     assert np.array_equal(np.stack([sr.vr.unpack(w, 4000) for w in words]), masks)
 
 
+@pytest.mark.parametrize("C,n_words,chunk_words", [(1, 1, None), (4, 1, None), (17, 129, None), (33, 130, 64), (70, 63, 1)])
+def test_the_matrix_product_of_the_bits_equals_the_popcounts(gold, C, n_words, chunk_words):
+    """sr.bit_counts serves the GPU tests of the count kernel where sr.popcount_counts is too slow; here both run, on the
+    generator those tests use, whole and in slices that do not divide the row."""
+    w = sr.random_words(C, n_words, 1000 * C + n_words)
+    assert w.dtype == np.uint64 and w.shape == (C, n_words)
+    want = sr.popcount_counts(w)
+    got = sr.bit_counts(w, chunk_words)
+    assert got.dtype == np.int64 and np.array_equal(got, want) and np.array_equal(got, got.T)
+    if C > 3:
+        assert want[1, 1] == 64 * n_words and not want[2].any() and 1 <= want[C - 1, C - 1] <= 64
+        assert np.array_equal(want[1], np.diag(want)) and not w[C - 1, :-1].any()  # the row of ones counts every row's bits
+        assert 0.2 < want[0, 0] / (64.0 * n_words) < 0.3 or n_words == 1
+    if C == 70:  # and on the golden scene's own words
+        words = sr.words(gold["restated"])
+        assert np.array_equal(sr.bit_counts(words, 7), gold["table"])
+
+
 def ratio_from(common, visible1, visible2):
     return sr.ratio_of([[visible1, common], [common, visible2]])(0, 1)
 

@@ -71,6 +71,36 @@ def popcount_counts(w):
     return out
 
 
+def bit_counts(w, chunk_words=None):
+    """The same table as the integer matrix product of the unpacked bits, in float64 (every sum is an integer far below
+    2^53, so it is exact), a slice of the words at a time: seconds where popcount_counts takes C passes over C rows."""
+    w = np.ascontiguousarray(np.asarray(w).astype("<u8"))
+    C, W = w.shape
+    step = int(chunk_words) if chunk_words else max(1, (1 << 18) // max(C, 1))  # at most 2^24 doubles of bits at a time
+    out = np.zeros((C, C), np.float64)
+    for w0 in range(0, W, step):
+        part = np.ascontiguousarray(w[:, w0:w0 + step])
+        bits = np.unpackbits(part.view(np.uint8).reshape(C, -1), axis=1).astype(np.float64)
+        out += bits @ bits.T
+    return out.astype(np.int64)
+
+
+def random_words(C, n_words, seed):
+    """uint64 [C, n_words] for the count kernel alone: the AND of two random draws (a quarter of the bits set), with row 1
+    all ones, row 2 all zero and the last row non-zero in its last word only (rows that exist)."""
+    rng = np.random.default_rng(seed)
+    top = np.iinfo(np.uint64).max
+    w = rng.integers(0, top, (C, n_words), np.uint64, endpoint=True) & rng.integers(0, top, (C, n_words), np.uint64, endpoint=True)
+    if C > 1:
+        w[1] = top
+    if C > 2:
+        w[2] = 0
+    if C > 3:
+        w[C - 1, :-1] = 0
+        w[C - 1, -1] |= np.uint64(1) << np.uint64(63)
+    return w
+
+
 def ratio_of(table):
     """ratio(i, j) over a counts table, in Python numbers."""
     t = np.asarray(table).tolist()
