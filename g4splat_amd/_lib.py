@@ -168,6 +168,16 @@ SIGNATURES = {
     "g4s_view_overlap": (c_i, [c_i, c_i, c_p, c_p, c_p, c_sz, c_p]),
     "g4s_fps_workspace": (c_sz, [c_i, c_i]),
     "g4s_fps": (c_i, [c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_depth_align_workspace": (c_sz, [c_i, c_p]),
+    "g4s_depth_align": (c_i, [c_i, c_i, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_depth_align_apply_workspace": (c_sz, [c_i]),
+    "g4s_depth_align_apply": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_depth_cue_maps_workspace": (c_sz, [c_i]),
+    "g4s_depth_cue_maps": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_plane_depths_workspace": (c_sz, [c_i, c_i, c_i]),
+    "g4s_plane_depths": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_depth_refill_workspace": (c_sz, [c_i]),
+    "g4s_depth_refill": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
 }
 
 _lib = None

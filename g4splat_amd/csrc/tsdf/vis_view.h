@@ -1,7 +1,7 @@
-// What the units over the Visibility section's views (visibility.hip, planes.hip, consistency.hip) share: the head of a
-// view record -- world -> camera rotation, translation, focal lengths, then view_stack.h's maps --, its fill from the host
-// arrays, THE projection of include/g4s_render_maps.h ("Projection of a point p into a view"), its truncating tap and the
-// SURFACE test.  There is no second one of any of them.
+// What the units over the Visibility section's views (visibility.hip, planes.hip, consistency.hip, depth_cues.hip) share: the
+// head of a view record -- world -> camera rotation, translation, focal lengths, then view_stack.h's maps --, its fill from
+// the host arrays, THE projection of include/g4s_render_maps.h ("Projection of a point p into a view"), its truncating tap,
+// the SURFACE test, and the ray record with THE back-projection.  There is no second one of any of them.
 #pragma once
 #include "view_stack.h"
 
@@ -56,6 +56,26 @@ inline void vis_pose(View& u, const float* world_view, const float* focal, int v
     }
     u.fx = focal[2 * (size_t)v];
     u.fy = focal[2 * (size_t)v + 1];
+}
+
+// The ray record of the contract ("Ray record of a camera"): origin, then D row-major.
+struct VisRay {
+    float o[3], D[9];
+};
+
+// dir = D (x, y, 1) at integer pixel coordinates
+__device__ __forceinline__ void ray_dir(const VisRay& r, int x, int y, float (&dir)[3]) {
+    const float xf = (float)x, yf = (float)y;
+#pragma unroll
+    for (int c = 0; c < 3; c++) dir[c] = (r.D[3 * c] * xf + r.D[3 * c + 1] * yf) + r.D[3 * c + 2];
+}
+
+// THE back-projection: the point of pixel i = y * W + x at depth d (g4s_depth_to_points, the pixel view counts, the depth cues)
+__device__ __forceinline__ void pixel_point(const VisRay& ray, int W, int i, float d, float (&p)[3]) {
+    float dir[3];
+    ray_dir(ray, i % W, i / W, dir);
+#pragma unroll
+    for (int c = 0; c < 3; c++) p[c] = ray.o[c] + d * dir[c];
 }
 
 }  // namespace g4s

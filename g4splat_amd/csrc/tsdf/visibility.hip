@@ -28,10 +28,6 @@ struct VisGrid {
     int R;
 };
 
-struct VisRay {
-    float o[3], D[9];
-};
-
 enum { VIS_FREE = 0, VIS_SURFACE = 1 };
 
 // The predicate of one (point, view) pair.  A NaN fails every comparison, so the map is read only at a pixel inside it.
@@ -71,12 +67,6 @@ __device__ __forceinline__ bool voxel_bit(const unsigned long long* __restrict__
     return (words[flat >> 6] >> (flat & 63u)) & 1ull;
 }
 __device__ __forceinline__ bool voxel_bit(const unsigned char* __restrict__ bytes, uint32_t flat) { return bytes[flat] != 0; }
-
-__device__ __forceinline__ void ray_dir(const VisRay& r, int x, int y, float (&dir)[3]) {
-    const float xf = (float)x, yf = (float)y;
-#pragma unroll
-    for (int c = 0; c < 3; c++) dir[c] = (r.D[3 * c] * xf + r.D[3 * c + 1] * yf) + r.D[3 * c + 2];
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // grid
@@ -204,13 +194,6 @@ __global__ void __launch_bounds__(256) view_counts_points_kernel(int n, const fl
     if (i >= n) return;
     counts[i] = count_views<MODE>(views, n_views, skip_view, threshold, points[3 * (size_t)i], points[3 * (size_t)i + 1],
                                   points[3 * (size_t)i + 2]);
-}
-
-__device__ __forceinline__ void pixel_point(const VisRay& ray, int W, int i, float d, float (&p)[3]) {
-    float dir[3];
-    ray_dir(ray, i % W, i / W, dir);
-#pragma unroll
-    for (int c = 0; c < 3; c++) p[c] = ray.o[c] + d * dir[c];
 }
 
 template <int MODE>

@@ -781,6 +781,117 @@ size_t g4s_fps_workspace(int n_clouds, int n_samples);
 int g4s_fps(int n_clouds, int n_points, const float* clouds, const int* first, int n_samples, int* indices, float* samples,
             float* dist, char* workspace, size_t workspace_bytes, void* stream);
 
+/* =====================================================================================================================
+ * Depth cues (g4splat_amd/csrc/tsdf/depth_cues.hip).
+ *
+ * What the reference does to every inpainted view between the inpainter and the global-plane merge (2d-gaussian-splatting/
+ * guidance/see3d_dn_util.py, guidance/dense_dn_util.py: visibility, matcha/pointmap/depthanythingv2.py depth_linear_align,
+ * utils/point_utils.py depth_to_normal, the merge) and between the merge and the inconsistency solvers (planes/
+ * refine_depth_with_planes.py: compute_plane_aligned_depth pasted per (plane, view) pair, the second alignment, the refill).
+ * The plane FIT stays with the caller: fitted planes are an input.  The semantics are this library's own, stated exactly
+ * (tests/depth_cues_ref.py restates them in numpy): float32 unless float64 is named, round-to-nearest-even, correctly
+ * rounded / and sqrt, no fused multiply-add anywhere in this section, evaluated left to right as written; max is IEEE maxNum.
+ *
+ * Views.  V views, at most 65535 per call, sizes = {W0, H0, W1, H1, ...}, W H <= 2^30; the maps of view v are device pointers
+ *   to [H_v, W_v] arrays, passed as HOST arrays of V pointers.  Pixel q = y W + x.
+ *
+ * A. Alignment.  Per view a source map s, a target map g and a mask: uint8 [H,W], set iff non-zero, or (mask_is_map != 0) a
+ *   float32 map, set iff value > mask_threshold.  Per masked pixel, by `domain`:
+ *     0 (disparity)       t = 1 / g,  d = s          -- depth_linear_align
+ *     1 (depth)           t = g,      d = s          -- depth_linear_align_2
+ *     2 (inverse source)  t = 1 / g,  d = 1 / s      -- depth_linear_align of the disparity 1 / s, which is never stored
+ *   t and d are float32.  n = the number of masked pixels; St, Sd, Std, Sdd = the sums of t, d, t d, d d over them in
+ *   float64 (a product of two float32 values is exact there).  The order of the additions is fixed: a workgroup owns
+ *   G4S_DEPTH_ALIGN_SPAN consecutive pixels, a thread adds its pixels in ascending order, a fixed tree folds the threads, and
+ *   the workgroups' partials are added by index.  No floating-point atomics: two runs give the same bits.  Then, in float64,
+ *     beta = (Std - St Sd / n) / (Sdd - Sd Sd / n),   alpha = (St - beta Sd) / n,
+ *   both rounded to float32: coeffs[v] = {alpha, beta}, counts[v] = n (int32), both on the device.  A degenerate view
+ *   (n = 0, n = 1, no variance of d, a masked g = 0) gives what IEEE arithmetic gives: NaN or inf.  That is no error.
+ *   aligned(s) = 1 / (alpha + beta d) with d as above (domain 0, 2), alpha + beta d (domain 1): one multiplication, one
+ *   addition, one division, each rounded.
+ *   g4s_depth_align: 2 launches.  g4s_depth_align_apply: 1 launch.
+ *
+ * B. Cue maps of view v with coeffs[v] = {alpha, beta}, mono disparity d, rendered ("warp") depth and alpha map, 1 launch:
+ *   visibility = alpha_map > visible_threshold (uint8 0 / 1);  mono_depth = 1 / d;  aligned_depth = aligned(d), domain 0;
+ *   merged_depth = visibility ? warp_depth : aligned_depth.
+ *   normal_world [H,W,3]: 0 on the one-pixel border (so everywhere if W < 3 or H < 3).  Elsewhere P(x, y) = the back-
+ *   projection of the Visibility section (the same device function as g4s_depth_to_points) of pixel (x, y) with the view's
+ *   ray record at depth aligned(d(x, y)) -- recomputed from the neighbour's disparity, no finished map is read --;
+ *   dx = P(x, y + 1) - P(x, y - 1), dy = P(x + 1, y) - P(x - 1, y); n = dx x dy, n_0 = dx_1 dy_2 - dx_2 dy_1 and cyclic (two
+ *   rounded products, one subtraction); len = max(sqrt((n_0 n_0 + n_1 n_1) + n_2 n_2), 1e-12); normal_world = n / len.
+ *   normal_cam_j = (nw_0 Wv[0][j] + nw_1 Wv[1][j]) + nw_2 Wv[2][j], Wv = world_view_transform, row-major.
+ *   rays [V,12] are the views' ray records, world_view [V,16]: HOST arrays.
+ *
+ * C. Plane depths, 1 launch (and one memset of the counts).  cameras [V,14] (HOST): o[3] the camera centre, R[3][3] the
+ *   camera -> world rotation row-major (both from the inverse of world_view_transform, taken by the caller in double),
+ *   fx = W / (2 tan(FoVx / 2)), fy alike.  planes [P,6] (HOST, finite): normal n[3], centre c[3].  The table of fitted
+ *   (view, id) pairs: view v owns entries view_offset[v] .. view_offset[v + 1] - 1 (view_offset [V + 1], view_offset[0] = 0);
+ *   ids[e] > 0, strictly ascending inside a view; entry_plane[e] < P.  The caller builds it from global_3Dplane_ID_dict: a pair
+ *   listed under several fitted planes keeps the last in dict order, a pair whose plane was not fitted has no entry.
+ *   A pixel whose mask value (int32, any positive ids) has an entry with plane (n, c):
+ *     dcx = (float(x) - W/2) / fx, dcy = (float(y) - H/2) / fy (W/2 = float(W) * 0.5, exact);
+ *     w_r = (R[r][0] dcx + R[r][1] dcy) + R[r][2];  len = max(sqrt((w_0 w_0 + w_1 w_1) + w_2 w_2), 1e-12);  r = w / len;
+ *     nd = (n_0 r_0 + n_1 r_1) + n_2 r_2;  nd' = copysign(max(|nd|, 1e-8), nd);
+ *     num = (n_0 (c_0 - o_0) + n_1 (c_1 - o_1)) + n_2 (c_2 - o_2);  t = num / nd';  z = t / len
+ *   (z is the camera-space depth of o + t r: R is a rotation, so |w| = |dc| and z = t / |dc|).  depth_out = z if t > 0 and
+ *   z > 0, otherwise 0 -- the 0 is written, as the reference writes it.  Every other pixel: depth_out = depth.  depth_out[v]
+ *   may be depth[v].  nd = 0 exactly is outside the compared contract (the reference's sign(0) = 0 divides by zero).
+ *   counts [2,V] int32 (device), cleared and filled: counts[0][v] = pixels that took a z, counts[1][v] = pixels that took the
+ *   0.  Integer sums, one integer atomic per wave.
+ *
+ * D. Refill, 1 launch.  For views v >= n_input_views, with coeffs[v] of A in domain 2 on (mono_depth, the plane-refined depth,
+ *   the confident map): where mask == 0 and conf == 0, depth = aligned(mono_depth), domain 2, in place.  Nothing else is
+ *   written; coeffs [V,2] is indexed by the view, the rows of the input views are not read.
+ *
+ * E. The refined points are g4s_depth_to_points of each refined map: one launch per view, nothing new.
+ *
+ * Differences from the reference, on purpose.  compute_plane_aligned_depth's second result, the list of valid points, is
+ *   replaced by the validity the 0 encodes.  The focal lengths come from FoVx, FoVy and the map's size, not from the
+ *   camera's focal_x, focal_y.  The sums are float64 in a fixed order (torch sums float32 in an order of its own), so alpha
+ *   and beta are the correctly rounded least-squares coefficients to within one unit in the last place.  alpha is formed
+ *   from the unrounded beta.
+ *
+ * Every argument is checked on the host before anything is launched.  The size queries are pure host code and return 0 for
+ * arguments out of range.
+ */
+#define G4S_DEPTH_ALIGN_SPAN 4096 /* pixels per workgroup of the alignment sums */
+
+size_t g4s_depth_align_workspace(int n_views, const int* sizes);
+
+/* coeffs [n_views,2] float32 and counts [n_views] int32 (device). */
+int g4s_depth_align(int domain, int mask_is_map, float mask_threshold, int n_views, const int* sizes,
+                    const float* const* source, const float* const* target, const void* const* masks, float* coeffs,
+                    int* counts, char* workspace, size_t workspace_bytes, void* stream);
+
+size_t g4s_depth_align_apply_workspace(int n_views);
+
+/* aligned[v] [H,W] = aligned(source[v]) with coeffs[v]. */
+int g4s_depth_align_apply(int domain, int n_views, const int* sizes, const float* const* source, const float* coeffs,
+                          float* const* aligned, char* workspace, size_t workspace_bytes, void* stream);
+
+size_t g4s_depth_cue_maps_workspace(int n_views);
+
+int g4s_depth_cue_maps(int n_views, const float* world_view, const float* rays, const int* sizes,
+                       const float* const* disparity, const float* const* warp_depth, const float* const* alpha_map,
+                       float visible_threshold, const float* coeffs, unsigned char* const* visibility,
+                       float* const* mono_depth, float* const* aligned_depth, float* const* merged_depth,
+                       float* const* normal_world, float* const* normal_cam, char* workspace, size_t workspace_bytes,
+                       void* stream);
+
+/* n_entries = view_offset[n_views]. */
+size_t g4s_plane_depths_workspace(int n_views, int n_entries, int n_planes);
+
+int g4s_plane_depths(int n_views, const float* cameras, const int* sizes, const float* const* depth,
+                     float* const* depth_out, const int* const* masks, const int* view_offset, const int* ids,
+                     const int* entry_plane, int n_planes, const float* planes, int* counts, char* workspace,
+                     size_t workspace_bytes, void* stream);
+
+size_t g4s_depth_refill_workspace(int n_views);
+
+int g4s_depth_refill(int n_views, int n_input_views, const int* sizes, float* const* depth,
+                     const float* const* mono_depth, const int* const* masks, const unsigned char* const* conf,
+                     const float* coeffs, char* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
