@@ -178,6 +178,10 @@ SIGNATURES = {
     "g4s_plane_depths": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_sz, c_p]),
     "g4s_depth_refill_workspace": (c_sz, [c_i]),
     "g4s_depth_refill": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_chart_surfels_workspace": (c_sz, [c_i, c_i, c_i]),
+    "g4s_chart_surfels_count": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_f, c_p, c_p, c_sz, c_p]),
+    "g4s_chart_surfels_emit": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_f, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_voxel_downsample_emit_index": (c_i, [c_i, c_i, c_p, c_p, c_sz, c_p]),
 }
 
 _lib = None

@@ -264,6 +264,27 @@ __global__ void __launch_bounds__(256) vds_emit_kernel(int n, const float* __res
     out[3 * (size_t)o] = (float)(sx / count), out[3 * (size_t)o + 1] = (float)(sy / count), out[3 * (size_t)o + 2] = (float)(sz / count);
 }
 
+// The same walk for the index variant: s = sum of (double)i / (double)n in ascending input index, a = s / count, and the
+// voxel's index is a * (double)n rounded half to even (rint under the default rounding mode).
+__global__ void __launch_bounds__(256) vds_emit_index_kernel(int n, const unsigned long long* __restrict__ keys, int index_bits,
+                                                             const uint32_t* __restrict__ flag, const uint32_t* __restrict__ pos,
+                                                             int n_voxels, long long* __restrict__ out) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || flag[i] == 0u) return;
+    const uint32_t o = pos[i];
+    if (o >= (uint32_t)n_voxels) return;  // the caller's capacity
+    const unsigned long long mask = index_bits > 0 ? (1ull << index_bits) - 1ull : 0ull;
+    const double total = (double)n;
+    double sum = 0.0;
+    long e = i;
+    do {
+        sum += (double)(keys[e] & mask) / total;
+        e++;
+    } while (e < n && flag[e] == 0u);
+    const double mean = sum / (double)(e - i);
+    out[o] = (long long)rint(mean * total);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // C. surface sampling
 
@@ -422,6 +443,23 @@ extern "C" int g4s_voxel_downsample_emit(int n, const float* points, int n_voxel
                        (const unsigned long long*)(ws + L.keys_a), vds_index_bits(n), (const uint32_t*)(ws + L.flag),
                        (const uint32_t*)(ws + L.pos), n_voxels, points_out);
     return finish(hipSuccess, "voxel_downsample emit");
+}
+
+extern "C" int g4s_voxel_downsample_emit_index(int n, int n_voxels, long long* index_out, char* workspace,
+                                               size_t workspace_bytes, void* stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    clear_error();
+    if (check_count(n, "n") != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
+    if (n_voxels < 0 || n_voxels > n) return fail(G4S_ERR_INVALID_ARGUMENT, "n_voxels must lie in 0..n");
+    if (n_voxels == 0) return G4S_OK;
+    if (!index_out) return null_pointer();
+    if (check_workspace(workspace, workspace_bytes, g4s_voxel_downsample_workspace(n)) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
+    const VdsLayout L = vds_layout((size_t)n);
+    char* ws = align_ptr(workspace);
+    hipLaunchKernelGGL(vds_emit_index_kernel, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, s, n,
+                       (const unsigned long long*)(ws + L.keys_a), vds_index_bits(n), (const uint32_t*)(ws + L.flag),
+                       (const uint32_t*)(ws + L.pos), n_voxels, index_out);
+    return finish(hipSuccess, "voxel_downsample emit index");
 }
 
 extern "C" int g4s_mesh_sample_surface(int n_samples, const float* u, const double* cum_area, int n_triangles, const int* triangles,

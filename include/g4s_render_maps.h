@@ -892,6 +892,86 @@ int g4s_depth_refill(int n_views, int n_input_views, const int* sizes, float* co
                      const float* const* mono_depth, const int* const* masks, const unsigned char* const* conf,
                      const float* coeffs, char* workspace, size_t workspace_bytes, void* stream);
 
+/* =====================================================================================================================
+ * Chart surfels (g4splat_amd/csrc/tsdf/chart_init.hip; the index pick is in mesh_eval.hip).
+ *
+ * The trainer's first act (2d-gaussian-splatting/train_with_refine_depth.py, "Initialize gaussians", the path that is not
+ * the warp initialiser): the pixel grid of every view is triangulated (matcha/dm_scene/meshes.py
+ * get_manifold_meshes_from_pointmaps), elongated faces are dropped (matcha/dm_scene/charts.py
+ * get_gaussian_parameters_from_pa_data / _from_charts_data) and every surviving face carries one surfel
+ * (matcha/dm_scene/gaussians.py get_gaussian_surfel_parameters_from_mesh with one barycentre); voxel_downsample_gaussians
+ * then picks one surfel index per voxel.  tests/chart_init_ref.py restates this section in numpy.
+ *
+ * Views.  n_views views of height x width pixels, all of one size.  maps[v] is the point map [height,width,3]
+ *   (depth_form == 0) or the depth map [height,width] (depth_form != 0); in depth form the point of pixel i = y * width +
+ *   x is that of g4s_depth_to_points with rays[12 v .. 12 v + 11] (the Visibility section's ray record), computed in the
+ *   kernel by the same arithmetic; the point map is never stored.  images[v] is [height,width,3] float32, masks[v]
+ *   [height,width] uint8 (masks may be NULL: no mask).  Limit: 2 n_views (height-1)(width-1) < 2^31 and height * width
+ *   < 2^31.
+ *
+ * Faces and their order.  Cell (r, c) of view v, r < height-1, c < width-1, has face_1 = (p[r,c], p[r+1,c], p[r,c+1]) and
+ *   face_2 = (p[r+1,c+1], p[r,c+1], p[r+1,c]).  Order: all face_1 of view 0 in row-major cell order, all face_2 of view 0,
+ *   then view 1, ...  Surviving faces keep this order: output row m is the m-th surviving face.  height == 1 or width == 1
+ *   gives no face and succeeds with n_faces = 0.
+ *
+ * Keep test of a face (A, B, C).  float32, every operation rounded on its own (no contraction), this association:
+ *   x.y = (x0 y0 + x1 y1) + x2 y2, |x| = sqrt(x.x), floor(t) = t if t > 1e-12f else 1e-12f (also for a NaN t).
+ *   s0 = C - A, s1 = A - B, s2 = B - C;  n_i = s_i / floor(|s_i|) per component;
+ *   a_i = s_i - (s_i . n_((i+1) mod 3)) n_i per component;  l_i = |a_i|.
+ *   keep iff no l_i is a NaN and max(l) / min(l) < ratio_th (0 / 0 is a NaN: dropped; so is every face with a NaN or an
+ *   infinite vertex, whose l are NaN).  This is the code of charts.py, whose comment describes a different quantity.
+ *   Masks: iff masks is given and some byte of some view is non-zero (the reference's masks.any()), a face is also dropped
+ *   unless at least ONE of its three vertices is masked in (remove_verts_from_single_mesh's any(dim=-1)).  An all-zero
+ *   mask removes nothing.
+ *
+ * Surfel of a kept face.  b = (0x3eaaaaab, 0x3eaaaaab, 0x3eaaaaaa) as float32 bits (get_regular_triangle_bary_coords(1)).
+ *   mean = (b0 A + b1 B) + b2 C.  colour = the same weights on clamp(image at the three vertices), clamp(x) = 0 if x < 0,
+ *   1 if x > 1, else x (a NaN stays).  Axis shifts e^0 = (0xbf3504f3, 0x3f3504f3, 0), e^1 = (0xbed105ec, 0xbed105ec,
+ *   0x3f5105ec) as float32 bits: t^j = (e^j_0 A + e^j_1 B) + e^j_2 C, the zero term kept.  first = 0 if |t^0| >= |t^1|,
+ *   else 1.  u = t^first, w = the other; w' = w - ((w.u) u) / (u.u) per component; o^first = u, o^other = w'.
+ *   scale_j = |o^j * normalized_scales| (the product per component first), scale_2 = normal_scale.
+ *   x^j = o^j / floor(|o^j|) per component; n = x^0 x x^1 (each component one product minus the other: n0 = x^0_1 x^1_2 -
+ *   x^0_2 x^1_1, n1 = x^0_2 x^1_0 - x^0_0 x^1_2, n2 = x^0_0 x^1_1 - x^0_1 x^1_0); R has the columns (x^0, x^1, n),
+ *   m_ij = R[i][j].
+ *   Quaternion (w, x, y, z) of R, pytorch3d's matrix_to_quaternion:  sp(t) = sqrt(t) if t > 0 else 0;
+ *     q_abs = ( sp(((1 + m00) + m11) + m22), sp(((1 + m00) - m11) - m22), sp(((1 - m00) + m11) - m22),
+ *               sp(((1 - m00) - m11) + m22) ).  Candidate rows:
+ *       0: ( q_abs0^2, m21 - m12, m02 - m20, m10 - m01 )
+ *       1: ( m21 - m12, q_abs1^2, m10 + m01, m02 + m20 )
+ *       2: ( m02 - m20, m10 + m01, q_abs2^2, m12 + m21 )
+ *       3: ( m10 - m01, m20 + m02, m21 + m12, q_abs3^2 )
+ *   k = the first index of the largest q_abs; q = row k / (2 max(q_abs_k, 0.1f)) per component; if q_w < 0 every
+ *   component is negated (w >= 0; pytorch3d before the sign was standardised returns q or -q, the same rotation).
+ *
+ * Two phases.  count: *n_faces (host int; one host synchronisation).  emit, with the same views, maps and workspace, the
+ *   workspace untouched in between: means [n_faces,3], scales [n_faces,3], quaternions [n_faces,4], colors [n_faces,3]
+ *   float32; nothing is written beyond row n_faces - 1.  No float atomics: every output is a function of the inputs.
+ *
+ * Voxel pick of indices (g4s_voxel_downsample_emit_index, after g4s_voxel_downsample_count on the n means, same workspace):
+ *   per voxel, in float64, s = sum of (double)i / (double)n over the voxel's points in ascending input index, a = s /
+ *   count, index = a * (double)n rounded half to even, as int64 -- the arithmetic of voxel_downsample_gaussians, which
+ *   recovers an index from open3d's averaged colour.  The index is the rounded mean index of the voxel's points and may
+ *   name a surfel of another voxel; the trainer depends on it.  Voxels in ascending (cz, cy, cx) (open3d's order is a hash
+ *   map's).
+ *
+ * Every argument is checked on the host before anything is launched.  The size query is pure host code and returns 0 for
+ * arguments out of range.
+ */
+size_t g4s_chart_surfels_workspace(int n_views, int height, int width);
+
+int g4s_chart_surfels_count(int n_views, int height, int width, int depth_form, const float* const* maps, const float* rays,
+                            const unsigned char* const* masks, float ratio_th, int* n_faces, char* workspace,
+                            size_t workspace_bytes, void* stream);
+
+int g4s_chart_surfels_emit(int n_views, int height, int width, int depth_form, const float* const* maps, const float* rays,
+                           const float* const* images, float normalized_scales, float normal_scale, int n_faces, float* means,
+                           float* scales, float* quaternions, float* colors, char* workspace, size_t workspace_bytes,
+                           void* stream);
+
+/* index_out [n_voxels] int64. */
+int g4s_voxel_downsample_emit_index(int n, int n_voxels, long long* index_out, char* workspace, size_t workspace_bytes,
+                                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
