@@ -36,7 +36,7 @@ struct ChartLayout {
 static ChartLayout chart_layout(long long V, long long H, long long W) {
     ChartLayout L{};
     L.cells = (H - 1) * (W - 1);
-    L.groups = (L.cells + 255) / 256;
+    L.groups = blocks256(L.cells);
     L.entries = 2 * V * L.groups;
     const size_t e = L.entries > 0 ? (size_t)L.entries : 1;
     WorkspaceCursor c;
@@ -276,15 +276,6 @@ int check_chart_dims(int V, int H, int W) {
     return G4S_OK;
 }
 
-template <class T>
-int check_view_pointers(const char* name, T* const* a, int n_views) {
-    if (!a) return fail(G4S_ERR_INVALID_ARGUMENT, "%s: NULL array", name);
-    for (int v = 0; v < n_views; v++) {
-        if (!a[v]) return fail(G4S_ERR_INVALID_ARGUMENT, "%s[%d]: NULL pointer", name, v);
-    }
-    return G4S_OK;
-}
-
 // the view table of both phases: maps, rays (depth form), images (emit) and masks (count)
 int chart_table(const char* name, int V, int H, int W, const float* const* maps, const float* rays, const float* const* images,
                 const unsigned char* const* masks, char* workspace, size_t workspace_bytes, hipStream_t stream,
@@ -293,8 +284,7 @@ int chart_table(const char* name, int V, int H, int W, const float* const* maps,
     for (int v = 0; v < V; v++) sizes[2 * (size_t)v] = W, sizes[2 * (size_t)v + 1] = H;
     return stage_views(name, V, true, sizes.data(), maps, images, images != nullptr, workspace, workspace_bytes, stream, table,
                        [&](ChartView& u, int v) {
-                           for (int i = 0; i < 3; i++) u.ray.o[i] = rays ? rays[12 * (size_t)v + i] : 0.0f;
-                           for (int i = 0; i < 9; i++) u.ray.D[i] = rays ? rays[12 * (size_t)v + 3 + i] : 0.0f;
+                           u.ray = rays ? ray_record(rays + 12 * (size_t)v) : VisRay{};
                            u.mask = masks ? masks[v] : nullptr;
                        });
 }
@@ -303,7 +293,7 @@ int chart_table(const char* name, int V, int H, int W, const float* const* maps,
 
 extern "C" size_t g4s_chart_surfels_workspace(int n_views, int height, int width) {
     if (!chart_dims_ok(n_views, height, width)) return 0;
-    return chart_layout(n_views, height, width).bytes + 256;  // + alignment of the base pointer
+    return chart_layout(n_views, height, width).bytes + WORKSPACE_BASE_SLACK;
 }
 
 extern "C" int g4s_chart_surfels_count(int n_views, int height, int width, int depth_form, const float* const* maps,
@@ -316,9 +306,9 @@ extern "C" int g4s_chart_surfels_count(int n_views, int height, int width, int d
     *n_faces = 0;
     const ChartLayout L = chart_layout(n_views, height, width);
     if (L.entries == 0) return G4S_OK;  // no view, or a view one pixel high or wide: no face
-    if (check_view_pointers("maps", maps, n_views) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
+    if (check_pointers("maps", maps, n_views) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     if (depth_form && !rays) return null_pointer();
-    if (masks && check_view_pointers("masks", masks, n_views) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
+    if (masks && check_pointers("masks", masks, n_views) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     if (check_workspace(workspace, workspace_bytes, g4s_chart_surfels_workspace(n_views, height, width)) != G4S_OK)
         return G4S_ERR_INVALID_ARGUMENT;
     char* ws = align_ptr(workspace);
@@ -331,7 +321,7 @@ extern "C" int g4s_chart_surfels_count(int n_views, int height, int width, int d
                                workspace, workspace_bytes, s, &table);
     if (rc != G4S_OK) return rc;
     if (masks) {
-        const int pixels = height * width, per_view = (pixels + 255) / 256;
+        const int pixels = height * width, per_view = (int)blocks256(pixels);
         hipLaunchKernelGGL(chart_mask_any_kernel, dim3((unsigned)((long long)n_views * per_view)), dim3(256), 0, s, table, pixels,
                            per_view, words + 2);
     }
@@ -357,7 +347,7 @@ extern "C" int g4s_chart_surfels_emit(int n_views, int height, int width, int de
     if (n_faces < 0 || n_faces > n_views * L.cells * 2)
         return fail(G4S_ERR_INVALID_ARGUMENT, "n_faces must lie in 0 .. 2 * n_views * (height - 1) * (width - 1)");
     if (n_faces == 0) return G4S_OK;
-    if (check_view_pointers("maps", maps, n_views) != G4S_OK || check_view_pointers("images", images, n_views) != G4S_OK)
+    if (check_pointers("maps", maps, n_views) != G4S_OK || check_pointers("images", images, n_views) != G4S_OK)
         return G4S_ERR_INVALID_ARGUMENT;
     if ((depth_form && !rays) || !means || !scales || !quaternions || !colors) return null_pointer();
     if (check_workspace(workspace, workspace_bytes, g4s_chart_surfels_workspace(n_views, height, width)) != G4S_OK)

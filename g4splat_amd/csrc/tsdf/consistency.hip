@@ -221,58 +221,40 @@ using namespace g4s;
 // extern "C" entry points; every argument is checked before any launch
 namespace {
 
-constexpr int CONS_MAX_VIEWS = 65535;  // the views are the grid's y
 constexpr unsigned CONS_COUNT_BLOCKS = 256;
-
-inline unsigned blocks256(long long n) { return (unsigned)((n + 255) / 256); }
-
-// the largest pixel count of the views and the sum of the counts; false if a size is out of range
-bool view_pixels(int n_views, const int* sizes, long long* largest, long long* total) {
-    *largest = *total = 0;
-    for (int v = 0; v < n_views; v++) {
-        const int W = sizes[2 * v], H = sizes[2 * v + 1];
-        if (W <= 0 || H <= 0 || (long long)W * H > (1ll << 30)) return false;
-        *total += (long long)W * H;
-        if ((long long)W * H > *largest) *largest = (long long)W * H;
-    }
-    return true;
-}
-
-int check_views(int n_views, const int* sizes, long long* largest, long long* total) {
-    if (n_views < 0 || n_views > CONS_MAX_VIEWS) return fail(G4S_ERR_INVALID_ARGUMENT, "n_views must be in 0 .. 65535");
-    *largest = *total = 0;
-    if (n_views == 0) return G4S_OK;
-    if (!sizes) return null_pointer();
-    if (!view_pixels(n_views, sizes, largest, total))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "sizes: width, height must be positive and width * height at most 2^30");
-    return G4S_OK;
-}
 
 int check_threshold(float depth_threshold) {
     return depth_threshold == depth_threshold ? G4S_OK : fail(G4S_ERR_INVALID_ARGUMENT, "depth_threshold must not be NaN");
 }
 
-// a host pointer array with an entry per view
-template <class T>
-int check_pointers(const char* name, T* const* a, int n_views) {
-    if (!a) return fail(G4S_ERR_INVALID_ARGUMENT, "%s: NULL array", name);
-    for (int v = 0; v < n_views; v++) {
-        if (!a[v]) return fail(G4S_ERR_INVALID_ARGUMENT, "%s[%d]: NULL pointer", name, v);
-    }
-    return G4S_OK;
+struct ConsPointsLayout {  // byte offsets into the workspace, after the view table
+    std::vector<size_t> winner;  // per view; an input view has no winner map
+    size_t bytes;
+};
+ConsPointsLayout cons_points_layout(int n_views, int n_input_views, const int* sizes) {  // sizes have passed view_sizes_ok
+    ConsPointsLayout L{std::vector<size_t>((size_t)n_views, 0), 0};
+    WorkspaceCursor c;
+    take_view_table<ConsPointView>(c, n_views);
+    for (int v = n_input_views; v < n_views; v++) L.winner[(size_t)v] = c.take((size_t)sizes[2 * v] * sizes[2 * v + 1] * 4);
+    L.bytes = c.off;
+    return L;
 }
 
-size_t winner_bytes(int n_views, int n_input_views, const int* sizes) {
-    size_t bytes = 0;
-    for (int v = n_input_views; v < n_views; v++) bytes += align_up((size_t)sizes[2 * v] * sizes[2 * v + 1] * 4);
-    return bytes;
+struct ConsCountsLayout { size_t ints, bytes; };  // ints: slot_plane [n_slots], then anchor_views [n_anchors]
+ConsCountsLayout cons_counts_layout(int n_views, int n_slots, int n_anchors) {
+    WorkspaceCursor c;
+    take_view_table<ConsPlaneView>(c, n_views);
+    const size_t ints = c.take(((size_t)n_slots + (size_t)n_anchors) * 4);
+    return {ints, c.off};
 }
 
-// host ints -> the workspace; `host` is the caller's again on return
-hipError_t upload_ints(int* dev, const std::vector<int>& host, hipStream_t stream) {
-    hipError_t e = hipMemcpyAsync(dev, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    return e;
+struct ConsRepaintLayout { size_t ints, step, src_view, src_pix, bytes; };  // ints: slot_step, then slot_anchor [n_slots]
+ConsRepaintLayout cons_repaint_layout(int n_views, int n_slots, long long total_pixels) {
+    WorkspaceCursor c;
+    take_view_table<ConsPlaneView>(c, n_views);
+    const size_t ints = c.take((size_t)n_slots * 8), map = (size_t)total_pixels * 4;
+    const size_t step = c.take(map), src_view = c.take(map), src_pix = c.take(map);
+    return {ints, step, src_view, src_pix, c.off};
 }
 
 // The checks both plane entry points share.  *total_slots = slot_offset[n_views].
@@ -298,10 +280,9 @@ int check_plane_views(int n_views, const float* world_view, const float* focal, 
 
 extern "C" size_t g4s_consistency_points_workspace(int n_views, int n_input_views, const int* sizes) {
     long long largest, total;
-    if (n_views < 0 || n_views > CONS_MAX_VIEWS || n_input_views < 0 || n_input_views > n_views || (n_views > 0 && !sizes) ||
-        !view_pixels(n_views, sizes, &largest, &total))
+    if (!grid_views_ok(n_views) || n_input_views < 0 || n_input_views > n_views || !view_sizes_ok(n_views, sizes, &largest, &total))
         return 0;
-    return align_up(view_table_bytes<ConsPointView>(n_views)) + winner_bytes(n_views, n_input_views, sizes);
+    return cons_points_layout(n_views, n_input_views, sizes).bytes + WORKSPACE_BASE_SLACK;
 }
 
 extern "C" int g4s_consistency_points(int n_points, const float* points, float depth_threshold, int n_views,
@@ -314,7 +295,7 @@ extern "C" int g4s_consistency_points(int n_points, const float* points, float d
     if (n_points < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "n_points must be in 0 .. 2^31 - 1");
     if (check_threshold(depth_threshold) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     long long largest, total;
-    if (check_views(n_views, sizes, &largest, &total) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
+    if (check_grid_views(n_views, sizes, &largest, &total) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     if (n_input_views < 0 || n_input_views > n_views)
         return fail(G4S_ERR_INVALID_ARGUMENT, "n_input_views must be in 0 .. n_views");
     if ((images_out == nullptr) != (conf == nullptr))
@@ -335,13 +316,8 @@ extern "C" int g4s_consistency_points(int n_points, const float* points, float d
         return G4S_ERR_INVALID_ARGUMENT;
     if (!outputs && !point_pass) return G4S_OK;
     // nothing below can fail a check: the first device call comes after every one of them
-    char* wbase = align_ptr(workspace) + align_up((size_t)n_views * sizeof(ConsPointView));
-    std::vector<size_t> woff((size_t)n_views, 0);
-    size_t off = 0;
-    for (int v = n_input_views; v < n_views; v++) {
-        woff[(size_t)v] = off;
-        off += align_up((size_t)sizes[2 * v] * sizes[2 * v + 1] * 4);
-    }
+    const ConsPointsLayout L = cons_points_layout(n_views, n_input_views, sizes);
+    char* ws = align_ptr(workspace);
     const ConsPointView* table;
     const int rc = stage_views("consistency points", n_views, true, sizes, depth, nullptr, false, workspace,
                                view_table_bytes<ConsPointView>(n_views), stream, &table, [&](ConsPointView& u, int v) {
@@ -350,7 +326,7 @@ extern "C" int g4s_consistency_points(int n_points, const float* points, float d
                                    u.image = images[v];
                                    u.out = outputs ? images_out[v] : nullptr;
                                    u.conf = outputs ? conf[v] : nullptr;
-                                   u.winner = outputs && point_pass && v >= n_input_views ? (uint32_t*)(wbase + woff[(size_t)v]) : nullptr;
+                                   u.winner = outputs && point_pass && v >= n_input_views ? (uint32_t*)(ws + L.winner[(size_t)v]) : nullptr;
                                    u.pixel_stride = image_chw[v] ? 1 : 3;
                                    u.channel_stride = image_chw[v] ? W * H : 1;
                                });
@@ -365,8 +341,8 @@ extern "C" int g4s_consistency_points(int n_points, const float* points, float d
 }
 
 extern "C" size_t g4s_consistency_plane_counts_workspace(int n_views, int n_slots, int n_anchors) {
-    if (n_views < 0 || n_views > CONS_MAX_VIEWS || n_slots < 0 || n_anchors < 0) return 0;
-    return align_up(view_table_bytes<ConsPlaneView>(n_views)) + align_up(((size_t)n_slots + (size_t)n_anchors) * 4) + 256;
+    if (!grid_views_ok(n_views) || n_slots < 0 || n_anchors < 0) return 0;
+    return cons_counts_layout(n_views, n_slots, n_anchors).bytes + VIEW_TABLE_SLACK + WORKSPACE_BASE_SLACK;
 }
 
 extern "C" int g4s_consistency_plane_counts(float depth_threshold, int n_views, const float* world_view, const float* focal,
@@ -378,7 +354,7 @@ extern "C" int g4s_consistency_plane_counts(float depth_threshold, int n_views, 
     clear_error();
     if (check_threshold(depth_threshold) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     long long largest, total;
-    if (check_views(n_views, sizes, &largest, &total) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
+    if (check_grid_views(n_views, sizes, &largest, &total) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     if (n_planes < 0 || n_anchors < 0 || (long long)n_planes * n_anchors > (1ll << 30))
         return fail(G4S_ERR_INVALID_ARGUMENT, "n_planes, n_anchors must not be negative and n_planes * n_anchors at most 2^30");
     if (n_anchors > 0 && !anchor_views) return fail(G4S_ERR_INVALID_ARGUMENT, "anchor_views: NULL array");
@@ -402,10 +378,8 @@ extern "C" int g4s_consistency_plane_counts(float depth_threshold, int n_views, 
     hipError_t e = hipMemsetAsync(counts, 0, n_counts * 4, stream);
     if (e != hipSuccess) return finish(e, "consistency plane counts");
     if (n_views == 0) return G4S_OK;
-    int* ints = (int*)(align_ptr(workspace) + align_up((size_t)n_views * sizeof(ConsPlaneView)));
-    std::vector<int> host(slot_plane, slot_plane + n_slots);
-    host.insert(host.end(), anchor_views, anchor_views + n_anchors);
-    e = upload_ints(ints, host, stream);
+    int* ints = workspace_at<int>(workspace, cons_counts_layout(n_views, n_slots, n_anchors).ints);
+    e = upload_pair(ints, slot_plane, n_slots, anchor_views, n_anchors, stream);
     if (e != hipSuccess) return finish(e, "consistency plane counts");
     const ConsPlaneView* table;
     const int rc = stage_views("consistency plane counts", n_views, true, sizes, depth, nullptr, false, workspace,
@@ -429,10 +403,9 @@ extern "C" int g4s_consistency_plane_counts(float depth_threshold, int n_views, 
 
 extern "C" size_t g4s_consistency_plane_repaint_workspace(int n_views, const int* sizes, int n_slots) {
     long long largest, total;
-    if (n_views < 0 || n_views > CONS_MAX_VIEWS || n_slots < 0 || (n_views > 0 && !sizes) ||
-        !view_pixels(n_views, sizes, &largest, &total) || total >= (1ll << 31))
+    if (!grid_views_ok(n_views) || n_slots < 0 || !view_sizes_ok(n_views, sizes, &largest, &total) || total >= (1ll << 31))
         return 0;
-    return align_up(view_table_bytes<ConsPlaneView>(n_views)) + align_up((size_t)n_slots * 8) + 3 * align_up((size_t)total * 4) + 256;
+    return cons_repaint_layout(n_views, n_slots, total).bytes + VIEW_TABLE_SLACK + WORKSPACE_BASE_SLACK;
 }
 
 extern "C" int g4s_consistency_plane_repaint(float depth_threshold, int n_views, const float* world_view, const float* focal,
@@ -444,7 +417,7 @@ extern "C" int g4s_consistency_plane_repaint(float depth_threshold, int n_views,
     clear_error();
     if (check_threshold(depth_threshold) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     long long largest, total;
-    if (check_views(n_views, sizes, &largest, &total) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
+    if (check_grid_views(n_views, sizes, &largest, &total) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     if (total >= (1ll << 31)) return fail(G4S_ERR_INVALID_ARGUMENT, "sizes: the views must have fewer than 2^31 pixels in all");
     int n_slots;
     if (check_plane_views(n_views, world_view, focal, depth, masks, points, slot_offset, &n_slots) != G4S_OK)
@@ -461,16 +434,12 @@ extern "C" int g4s_consistency_plane_repaint(float depth_threshold, int n_views,
     }
     if (check_workspace(workspace, workspace_bytes, g4s_consistency_plane_repaint_workspace(n_views, sizes, n_slots)) != G4S_OK)
         return G4S_ERR_INVALID_ARGUMENT;
-    char* base = align_ptr(workspace) + align_up((size_t)n_views * sizeof(ConsPlaneView));
-    int* ints = (int*)base;
-    base += align_up((size_t)n_slots * 8);
-    const size_t plane = align_up((size_t)total * 4);
-    uint32_t* step = (uint32_t*)base;
-    int* src_view = (int*)(base + plane);
-    int* src_pix = (int*)(base + 2 * plane);
-    std::vector<int> host(slot_step, slot_step + n_slots);
-    host.insert(host.end(), slot_anchor, slot_anchor + n_slots);
-    const hipError_t e = upload_ints(ints, host, stream);
+    const ConsRepaintLayout L = cons_repaint_layout(n_views, n_slots, total);
+    int* ints = workspace_at<int>(workspace, L.ints);
+    uint32_t* step = workspace_at<uint32_t>(workspace, L.step);
+    int* src_view = workspace_at<int>(workspace, L.src_view);
+    int* src_pix = workspace_at<int>(workspace, L.src_pix);
+    const hipError_t e = upload_pair(ints, slot_step, n_slots, slot_anchor, n_slots, stream);
     if (e != hipSuccess) return finish(e, "consistency plane repaint");
     std::vector<uint32_t> pixel_base((size_t)n_views);
     uint32_t at = 0;

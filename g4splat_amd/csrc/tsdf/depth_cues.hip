@@ -258,40 +258,7 @@ using namespace g4s;
 // extern "C" entry points; every argument is checked before any launch
 namespace {
 
-constexpr int CUE_MAX_VIEWS = 65535;  // the views are the grid's y
-
-inline unsigned blocks256(long long n) { return (unsigned)((n + 255) / 256); }
 inline long long spans(long long pixels) { return (pixels + ALIGN_SPAN - 1) / ALIGN_SPAN; }
-
-// the largest pixel count of the views and the number of spans of all views; false if a size is out of range
-bool cue_sizes(int n_views, const int* sizes, long long* largest, long long* total_spans) {
-    *largest = *total_spans = 0;
-    if (n_views < 0 || n_views > CUE_MAX_VIEWS || (n_views > 0 && !sizes)) return false;
-    for (int v = 0; v < n_views; v++) {
-        const long long W = sizes[2 * v], H = sizes[2 * v + 1];
-        if (W <= 0 || H <= 0 || W * H > (1ll << 30)) return false;
-        if (W * H > *largest) *largest = W * H;
-        *total_spans += spans(W * H);
-    }
-    return true;
-}
-
-int check_cue_views(int n_views, const int* sizes, long long* largest, long long* total_spans) {
-    if (n_views < 0 || n_views > CUE_MAX_VIEWS) return fail(G4S_ERR_INVALID_ARGUMENT, "n_views must be in 0 .. 65535");
-    if (n_views > 0 && !sizes) return null_pointer();
-    if (!cue_sizes(n_views, sizes, largest, total_spans))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "sizes: width, height must be positive and width * height at most 2^30");
-    return G4S_OK;
-}
-
-template <class T>
-int check_maps(const char* name, T* const* a, int n_views) {
-    if (!a) return fail(G4S_ERR_INVALID_ARGUMENT, "%s: NULL array", name);
-    for (int v = 0; v < n_views; v++) {
-        if (!a[v]) return fail(G4S_ERR_INVALID_ARGUMENT, "%s[%d]: NULL pointer", name, v);
-    }
-    return G4S_OK;
-}
 
 int check_domain(int domain) {
     return domain >= ALIGN_DISPARITY && domain <= ALIGN_INVERSE_SOURCE
@@ -299,18 +266,31 @@ int check_domain(int domain) {
                : fail(G4S_ERR_INVALID_ARGUMENT, "domain must be 0 (disparity), 1 (depth) or 2 (inverse source)");
 }
 
-hipError_t upload(void* dev, const void* host, size_t bytes, hipStream_t stream) {
-    hipError_t e = hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);  // the host copy is the caller's again on return
-    return e;
+// byte offsets into the workspace, after the view table
+struct AlignLayout { size_t partials, bytes; };
+AlignLayout align_layout(int n_views, const int* sizes) {  // sizes have passed view_sizes_ok
+    long long total_spans = 0;
+    for (int v = 0; v < n_views; v++) total_spans += spans((long long)sizes[2 * v] * sizes[2 * v + 1]);
+    WorkspaceCursor c;
+    take_view_table<AlignView>(c, n_views);
+    const size_t partials = c.take((size_t)total_spans * ALIGN_TERMS * sizeof(double));
+    return {partials, c.off};
+}
+
+struct PlaneDepthsLayout { size_t ids, planes, bytes; };  // ids: the ids [n_entries], then entry_plane [n_entries]
+PlaneDepthsLayout plane_depths_layout(int n_views, int n_entries, int n_planes) {
+    WorkspaceCursor c;
+    take_view_table<PlaneView>(c, n_views);
+    const size_t ids = c.take((size_t)n_entries * 8), planes = c.take((size_t)n_planes * 24);
+    return {ids, planes, c.off};
 }
 
 }  // namespace
 
 extern "C" size_t g4s_depth_align_workspace(int n_views, const int* sizes) {
-    long long largest, total_spans;
-    if (!cue_sizes(n_views, sizes, &largest, &total_spans)) return 0;
-    return align_up(view_table_bytes<AlignView>(n_views)) + align_up((size_t)total_spans * ALIGN_TERMS * sizeof(double)) + 256;
+    long long largest, total;
+    if (!grid_views_ok(n_views) || !view_sizes_ok(n_views, sizes, &largest, &total)) return 0;
+    return align_layout(n_views, sizes).bytes + VIEW_TABLE_SLACK + WORKSPACE_BASE_SLACK;
 }
 
 extern "C" int g4s_depth_align(int domain, int mask_is_map, float mask_threshold, int n_views, const int* sizes,
@@ -320,16 +300,16 @@ extern "C" int g4s_depth_align(int domain, int mask_is_map, float mask_threshold
     clear_error();
     if (check_domain(domain) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     if (mask_is_map && mask_threshold != mask_threshold) return fail(G4S_ERR_INVALID_ARGUMENT, "mask_threshold must not be NaN");
-    long long largest, total_spans;
-    if (check_cue_views(n_views, sizes, &largest, &total_spans) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
+    long long largest, total;
+    if (check_grid_views(n_views, sizes, &largest, &total) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     if (n_views == 0) return G4S_OK;
-    if (check_maps("source", source, n_views) != G4S_OK || check_maps("target", target, n_views) != G4S_OK ||
-        check_maps("masks", masks, n_views) != G4S_OK)
+    if (check_pointers("source", source, n_views) != G4S_OK || check_pointers("target", target, n_views) != G4S_OK ||
+        check_pointers("masks", masks, n_views) != G4S_OK)
         return G4S_ERR_INVALID_ARGUMENT;
     if (!coeffs || !counts) return null_pointer();
     if (check_workspace(workspace, workspace_bytes, g4s_depth_align_workspace(n_views, sizes)) != G4S_OK)
         return G4S_ERR_INVALID_ARGUMENT;
-    double* partials = (double*)(align_ptr(workspace) + align_up((size_t)n_views * sizeof(AlignView)));
+    double* partials = workspace_at<double>(workspace, align_layout(n_views, sizes).partials);
     uint32_t base = 0, most = 0;
     const AlignView* table;
     const int rc = stage_views("depth align", n_views, true, sizes, source, nullptr, false, workspace,
@@ -351,7 +331,7 @@ extern "C" int g4s_depth_align(int domain, int mask_is_map, float mask_threshold
 }
 
 extern "C" size_t g4s_depth_align_apply_workspace(int n_views) {
-    return n_views < 0 || n_views > CUE_MAX_VIEWS ? 0 : view_table_bytes<AlignView>(n_views);
+    return !grid_views_ok(n_views) ? 0 : view_table_bytes<AlignView>(n_views);
 }
 
 extern "C" int g4s_depth_align_apply(int domain, int n_views, const int* sizes, const float* const* source,
@@ -360,10 +340,10 @@ extern "C" int g4s_depth_align_apply(int domain, int n_views, const int* sizes, 
     hipStream_t stream = (hipStream_t)stream_;
     clear_error();
     if (check_domain(domain) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
-    long long largest, total_spans;
-    if (check_cue_views(n_views, sizes, &largest, &total_spans) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
+    long long largest, total;
+    if (check_grid_views(n_views, sizes, &largest, &total) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     if (n_views == 0) return G4S_OK;
-    if (check_maps("source", source, n_views) != G4S_OK || check_maps("aligned", aligned, n_views) != G4S_OK)
+    if (check_pointers("source", source, n_views) != G4S_OK || check_pointers("aligned", aligned, n_views) != G4S_OK)
         return G4S_ERR_INVALID_ARGUMENT;
     if (!coeffs) return null_pointer();
     const AlignView* table;
@@ -381,7 +361,7 @@ extern "C" int g4s_depth_align_apply(int domain, int n_views, const int* sizes, 
 }
 
 extern "C" size_t g4s_depth_cue_maps_workspace(int n_views) {
-    return n_views < 0 || n_views > CUE_MAX_VIEWS ? 0 : view_table_bytes<CueView>(n_views);
+    return !grid_views_ok(n_views) ? 0 : view_table_bytes<CueView>(n_views);
 }
 
 extern "C" int g4s_depth_cue_maps(int n_views, const float* world_view, const float* rays, const int* sizes,
@@ -393,21 +373,20 @@ extern "C" int g4s_depth_cue_maps(int n_views, const float* world_view, const fl
     hipStream_t stream = (hipStream_t)stream_;
     clear_error();
     if (visible_threshold != visible_threshold) return fail(G4S_ERR_INVALID_ARGUMENT, "visible_threshold must not be NaN");
-    long long largest, total_spans;
-    if (check_cue_views(n_views, sizes, &largest, &total_spans) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
+    long long largest, total;
+    if (check_grid_views(n_views, sizes, &largest, &total) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     if (n_views == 0) return G4S_OK;
     if (!world_view || !rays || !coeffs) return null_pointer();
-    if (check_maps("disparity", disparity, n_views) != G4S_OK || check_maps("warp_depth", warp_depth, n_views) != G4S_OK ||
-        check_maps("alpha_map", alpha_map, n_views) != G4S_OK || check_maps("visibility", visibility, n_views) != G4S_OK ||
-        check_maps("mono_depth", mono_depth, n_views) != G4S_OK || check_maps("aligned_depth", aligned_depth, n_views) != G4S_OK ||
-        check_maps("merged_depth", merged_depth, n_views) != G4S_OK || check_maps("normal_world", normal_world, n_views) != G4S_OK ||
-        check_maps("normal_cam", normal_cam, n_views) != G4S_OK)
+    if (check_pointers("disparity", disparity, n_views) != G4S_OK || check_pointers("warp_depth", warp_depth, n_views) != G4S_OK ||
+        check_pointers("alpha_map", alpha_map, n_views) != G4S_OK || check_pointers("visibility", visibility, n_views) != G4S_OK ||
+        check_pointers("mono_depth", mono_depth, n_views) != G4S_OK || check_pointers("aligned_depth", aligned_depth, n_views) != G4S_OK ||
+        check_pointers("merged_depth", merged_depth, n_views) != G4S_OK || check_pointers("normal_world", normal_world, n_views) != G4S_OK ||
+        check_pointers("normal_cam", normal_cam, n_views) != G4S_OK)
         return G4S_ERR_INVALID_ARGUMENT;
     const CueView* table;
     const int rc = stage_views("depth cue maps", n_views, true, sizes, disparity, nullptr, false, workspace, workspace_bytes,
                                stream, &table, [&](CueView& u, int v) {
-                                   for (int i = 0; i < 3; i++) u.ray.o[i] = rays[12 * (size_t)v + i];
-                                   for (int i = 0; i < 9; i++) u.ray.D[i] = rays[12 * (size_t)v + 3 + i];
+                                   u.ray = ray_record(rays + 12 * (size_t)v);
                                    for (int i = 0; i < 3; i++) {
                                        for (int j = 0; j < 3; j++) u.Rw[3 * i + j] = world_view[16 * (size_t)v + 4 * i + j];
                                    }
@@ -427,8 +406,8 @@ extern "C" int g4s_depth_cue_maps(int n_views, const float* world_view, const fl
 }
 
 extern "C" size_t g4s_plane_depths_workspace(int n_views, int n_entries, int n_planes) {
-    if (n_views < 0 || n_views > CUE_MAX_VIEWS || n_entries < 0 || n_planes < 0) return 0;
-    return align_up(view_table_bytes<PlaneView>(n_views)) + align_up((size_t)n_entries * 8) + align_up((size_t)n_planes * 24) + 256;
+    if (!grid_views_ok(n_views) || n_entries < 0 || n_planes < 0) return 0;
+    return plane_depths_layout(n_views, n_entries, n_planes).bytes + VIEW_TABLE_SLACK + WORKSPACE_BASE_SLACK;
 }
 
 extern "C" int g4s_plane_depths(int n_views, const float* cameras, const int* sizes, const float* const* depth,
@@ -437,13 +416,13 @@ extern "C" int g4s_plane_depths(int n_views, const float* cameras, const int* si
                                 size_t workspace_bytes, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     clear_error();
-    long long largest, total_spans;
-    if (check_cue_views(n_views, sizes, &largest, &total_spans) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
+    long long largest, total;
+    if (check_grid_views(n_views, sizes, &largest, &total) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     if (n_planes < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "n_planes must not be negative");
     if (n_views == 0) return G4S_OK;
     if (!cameras || !counts) return null_pointer();
-    if (check_maps("depth", depth, n_views) != G4S_OK || check_maps("depth_out", depth_out, n_views) != G4S_OK ||
-        check_maps("masks", masks, n_views) != G4S_OK)
+    if (check_pointers("depth", depth, n_views) != G4S_OK || check_pointers("depth_out", depth_out, n_views) != G4S_OK ||
+        check_pointers("masks", masks, n_views) != G4S_OK)
         return G4S_ERR_INVALID_ARGUMENT;
     for (int i = 0; i < 14 * n_views; i++) {
         if (!finite(cameras[i])) return fail(G4S_ERR_INVALID_ARGUMENT, "cameras: view %d is not finite", i / 14);
@@ -473,16 +452,12 @@ extern "C" int g4s_plane_depths(int n_views, const float* cameras, const int* si
     }
     if (check_workspace(workspace, workspace_bytes, g4s_plane_depths_workspace(n_views, n_entries, n_planes)) != G4S_OK)
         return G4S_ERR_INVALID_ARGUMENT;
-    char* base = align_ptr(workspace) + align_up((size_t)n_views * sizeof(PlaneView));
-    int* dev_ids = (int*)base;
+    const PlaneDepthsLayout L = plane_depths_layout(n_views, n_entries, n_planes);
+    int* dev_ids = workspace_at<int>(workspace, L.ids);
     int* dev_plane = dev_ids + n_entries;
-    float* dev_planes = (float*)(base + align_up((size_t)n_entries * 8));
+    float* dev_planes = workspace_at<float>(workspace, L.planes);
     hipError_t e = hipMemsetAsync(counts, 0, (size_t)n_views * 8, stream);
-    if (e == hipSuccess && n_entries > 0) {
-        std::vector<int> host(ids, ids + n_entries);
-        host.insert(host.end(), entry_plane, entry_plane + n_entries);
-        e = upload(dev_ids, host.data(), host.size() * sizeof(int), stream);
-    }
+    if (e == hipSuccess && n_entries > 0) e = upload_pair(dev_ids, ids, n_entries, entry_plane, n_entries, stream);
     if (e == hipSuccess && n_planes > 0) e = upload(dev_planes, planes, (size_t)n_planes * 24, stream);
     if (e != hipSuccess) return finish(e, "plane depths");
     const PlaneView* table;
@@ -505,7 +480,7 @@ extern "C" int g4s_plane_depths(int n_views, const float* cameras, const int* si
 }
 
 extern "C" size_t g4s_depth_refill_workspace(int n_views) {
-    return n_views < 0 || n_views > CUE_MAX_VIEWS ? 0 : view_table_bytes<RefillView>(n_views);
+    return !grid_views_ok(n_views) ? 0 : view_table_bytes<RefillView>(n_views);
 }
 
 extern "C" int g4s_depth_refill(int n_views, int n_input_views, const int* sizes, float* const* depth,
@@ -513,23 +488,20 @@ extern "C" int g4s_depth_refill(int n_views, int n_input_views, const int* sizes
                                 const float* coeffs, char* workspace, size_t workspace_bytes, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     clear_error();
-    long long largest, total_spans;
-    if (check_cue_views(n_views, sizes, &largest, &total_spans) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
+    long long largest, total;
+    if (check_grid_views(n_views, sizes, &largest, &total) != G4S_OK) return G4S_ERR_INVALID_ARGUMENT;
     if (n_input_views < 0 || n_input_views > n_views)
         return fail(G4S_ERR_INVALID_ARGUMENT, "n_input_views must be in 0 .. n_views");
     if (n_views == 0) return G4S_OK;
-    if (check_maps("depth", depth, n_views) != G4S_OK || check_maps("mono_depth", mono_depth, n_views) != G4S_OK ||
-        check_maps("masks", masks, n_views) != G4S_OK || check_maps("conf", conf, n_views) != G4S_OK)
+    if (check_pointers("depth", depth, n_views) != G4S_OK || check_pointers("mono_depth", mono_depth, n_views) != G4S_OK ||
+        check_pointers("masks", masks, n_views) != G4S_OK || check_pointers("conf", conf, n_views) != G4S_OK)
         return G4S_ERR_INVALID_ARGUMENT;
     if (!coeffs) return null_pointer();
     if (check_workspace(workspace, workspace_bytes, g4s_depth_refill_workspace(n_views)) != G4S_OK)
         return G4S_ERR_INVALID_ARGUMENT;
     if (n_input_views == n_views) return G4S_OK;
-    long long largest_inpainted = 0;
-    for (int v = n_input_views; v < n_views; v++) {
-        const long long n = (long long)sizes[2 * v] * sizes[2 * v + 1];
-        if (n > largest_inpainted) largest_inpainted = n;
-    }
+    long long largest_inpainted;  // the sizes have passed: this only measures the inpainted views
+    view_sizes_ok(n_views - n_input_views, sizes + 2 * n_input_views, &largest_inpainted, &total);
     const RefillView* table;
     const int rc = stage_views("depth refill", n_views, true, sizes, mono_depth, nullptr, false, workspace, workspace_bytes,
                                stream, &table, [&](RefillView& u, int v) {

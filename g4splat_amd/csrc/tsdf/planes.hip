@@ -207,21 +207,29 @@ using namespace g4s;
 // extern "C" entry points; every argument is checked before any launch
 namespace {
 
-inline unsigned blocks256(int n) { return ((unsigned)n + 255u) / 256u; }
-
 int check_points(int n_points) {
     return n_points >= 0 && n_points <= (1 << 30) ? G4S_OK : fail(G4S_ERR_INVALID_ARGUMENT, "n_points must be in 0 .. 2^30");
 }
 
-// bytes of the zmin maps of a view stack; 0 if a size is out of range
-size_t zmin_bytes(int n_views, const int* sizes) {
-    size_t bytes = 0;
-    for (int v = 0; v < n_views; v++) {
-        const int W = sizes[2 * v], H = sizes[2 * v + 1];
-        if (W <= 0 || H <= 0 || (long long)W * H > (1ll << 30)) return 0;
-        bytes += align_up((size_t)W * H * 4);
-    }
-    return bytes;
+struct PlaneLabelsLayout {  // byte offsets into the workspace, after the view table
+    std::vector<size_t> zmin;  // per view; the maps are one run, from zmin[0] to the end
+    size_t bytes;
+};
+PlaneLabelsLayout plane_labels_layout(int n_views, const int* sizes) {  // sizes have passed view_sizes_ok
+    PlaneLabelsLayout L{std::vector<size_t>((size_t)n_views), 0};
+    WorkspaceCursor c;
+    take_view_table<PlaneView>(c, n_views);
+    for (int v = 0; v < n_views; v++) L.zmin[(size_t)v] = c.take((size_t)sizes[2 * v] * sizes[2 * v + 1] * 4);
+    L.bytes = c.off;
+    return L;
+}
+
+struct PlaneAssignLayout { size_t target, bytes; };
+PlaneAssignLayout plane_assign_layout(int n_planes) {
+    const size_t bytes = n_planes > 0 ? (size_t)n_planes * 4 : 0;
+    WorkspaceCursor c;
+    const size_t target = c.take(bytes);
+    return {target, target + bytes};  // the one range's own end, not c.off: the query has always been stated without the rounding
 }
 
 int check_member(int n_global, int n_words, const void* member) {
@@ -237,10 +245,9 @@ int check_row(int row, int n_global, const char* name) {
 }  // namespace
 
 extern "C" size_t g4s_plane_labels_workspace(int n_views, const int* sizes) {
-    if (n_views < 0 || (n_views > 0 && !sizes)) return 0;
-    const size_t z = zmin_bytes(n_views, sizes);
-    if (n_views > 0 && z == 0) return 0;
-    return align_up(view_table_bytes<PlaneView>(n_views)) + z;
+    long long largest, total;
+    if (!view_sizes_ok(n_views, sizes, &largest, &total)) return 0;  // no cap on n_views: the views are no grid dimension
+    return plane_labels_layout(n_views, sizes).bytes + WORKSPACE_BASE_SLACK;
 }
 
 extern "C" int g4s_plane_labels(int n_points, const float* points, float depth_thresh, int n_views, const float* world_view,
@@ -253,8 +260,9 @@ extern "C" int g4s_plane_labels(int n_points, const float* points, float depth_t
     if (n_views < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "n_views must not be negative");
     if (n_views == 0) return G4S_OK;
     if (!world_view || !focal || !sizes || !masks || (n_points > 0 && (!points || !labels))) return null_pointer();
-    const size_t zbytes = zmin_bytes(n_views, sizes);
-    if (zbytes == 0) return fail(G4S_ERR_INVALID_ARGUMENT, "width, height must be positive and width * height at most 2^30");
+    long long largest, total;
+    if (!view_sizes_ok(n_views, sizes, &largest, &total))  // this unit's own wording, and no cap on n_views
+        return fail(G4S_ERR_INVALID_ARGUMENT, "width, height must be positive and width * height at most 2^30");
     if (check_workspace(workspace, workspace_bytes, g4s_plane_labels_workspace(n_views, sizes)) != G4S_OK)
         return G4S_ERR_INVALID_ARGUMENT;
     for (int v = 0; v < n_views; v++) {
@@ -262,21 +270,17 @@ extern "C" int g4s_plane_labels(int n_points, const float* points, float depth_t
     }
     if (n_points == 0) return G4S_OK;
     // nothing below can fail a check: the first device call comes after every one of them
-    char* zbase = align_ptr(workspace) + align_up((size_t)n_views * sizeof(PlaneView));
-    std::vector<size_t> zoff((size_t)n_views);
-    size_t off = 0;
-    for (int v = 0; v < n_views; v++) {
-        zoff[(size_t)v] = off;
-        off += align_up((size_t)sizes[2 * v] * sizes[2 * v + 1] * 4);
-    }
+    const PlaneLabelsLayout L = plane_labels_layout(n_views, sizes);
+    char* ws = align_ptr(workspace);
     const bool depth_test = depth_thresh >= 0.0f;
-    hipError_t e = depth_test ? hipMemsetAsync(zbase, 0xFF, zbytes, stream) : hipSuccess;  // 0xFFFFFFFF: above the bits of every positive float
+    // 0xFFFFFFFF: above the bits of every positive float
+    hipError_t e = depth_test ? hipMemsetAsync(ws + L.zmin[0], 0xFF, L.bytes - L.zmin[0], stream) : hipSuccess;
     if (e != hipSuccess) return finish(e, "plane labels");
     const PlaneView* table;
     const int rc = stage_views("plane labels", n_views, true, sizes, (const float* const*)masks, nullptr, false, workspace,
                                view_table_bytes<PlaneView>(n_views), stream, &table, [&](PlaneView& u, int v) {
                                    vis_pose(u, world_view, focal, v);
-                                   u.zmin = (uint32_t*)(zbase + zoff[(size_t)v]);
+                                   u.zmin = (uint32_t*)(ws + L.zmin[(size_t)v]);
                                });
     if (rc != G4S_OK) return rc;
     if (depth_test)
@@ -314,7 +318,7 @@ extern "C" int g4s_plane_overlap(int n_points, const int* labels, int n_planes, 
     return finish(hipSuccess, "plane overlap");
 }
 
-extern "C" size_t g4s_plane_assign_workspace(int n_planes) { return (n_planes > 0 ? (size_t)n_planes * 4 : 0) + 256; }
+extern "C" size_t g4s_plane_assign_workspace(int n_planes) { return plane_assign_layout(n_planes).bytes + WORKSPACE_BASE_SLACK; }
 
 extern "C" int g4s_plane_assign(int n_points, const int* labels, int n_planes, const int* target, int n_global, int n_words,
                                 unsigned long long* member, char* workspace, size_t workspace_bytes, void* stream_) {
@@ -332,9 +336,8 @@ extern "C" int g4s_plane_assign(int n_points, const int* labels, int n_planes, c
     if (check_workspace(workspace, workspace_bytes, g4s_plane_assign_workspace(n_planes)) != G4S_OK)
         return G4S_ERR_INVALID_ARGUMENT;
     if (n_points == 0) return G4S_OK;
-    int* dev = (int*)align_ptr(workspace);
-    hipError_t e = hipMemcpyAsync(dev, target, (size_t)n_planes * 4, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);  // `target` is the caller's again on return
+    int* dev = workspace_at<int>(workspace, plane_assign_layout(n_planes).target);
+    const hipError_t e = upload(dev, target, (size_t)n_planes * 4, stream);
     if (e != hipSuccess) return finish(e, "plane assign");
     hipLaunchKernelGGL(plane_assign_kernel, dim3(blocks256(n_points)), dim3(256), 0, stream, n_points, labels, n_planes, dev, member);
     return finish(hipSuccess, "plane assign");

@@ -231,8 +231,7 @@ extern "C" int g4s_view_bits(int n_points, const float* points, int n_views, con
         host[(size_t)v].maps = ViewMaps{sizes[2 * v], sizes[2 * v + 1], nullptr, nullptr};
     }
     VisView* table = (VisView*)align_ptr(workspace);
-    hipError_t e = hipMemcpyAsync(table, host.data(), host.size() * sizeof(VisView), hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);  // `host` dies with this frame
+    const hipError_t e = upload(table, host.data(), host.size() * sizeof(VisView), stream);  // `host` dies with this frame
     if (e != hipSuccess) return fail(G4S_ERR_HIP, "view bits view table: %s", hipGetErrorString(e));
     const int n_words = (int)(((long long)n_points + 63) / 64);
     const unsigned blocks = (unsigned)(((long long)n_points + BITS_POINTS - 1) / BITS_POINTS);
@@ -283,8 +282,7 @@ extern "C" int g4s_fps(int n_clouds, int n_points, const float* clouds, const in
     unsigned long long* keys = (unsigned long long*)align_ptr(workspace);
     int* dev_first = (int*)((char*)keys + fps_keys_bytes(n_clouds, n_samples));
     hipError_t e = hipMemsetAsync(keys, 0, (size_t)n_clouds * (size_t)n_samples * 8, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dev_first, first, (size_t)n_clouds * 4, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);  // `first` is the caller's again on return
+    if (e == hipSuccess) e = upload(dev_first, first, (size_t)n_clouds * 4, stream);
     if (e != hipSuccess) return finish(e, "farthest-point sampling");
     const unsigned per_block = 256u * FPS_ITEMS;
     unsigned blocks = ((unsigned)n_points + per_block - 1u) / per_block;
@@ -293,7 +291,7 @@ extern "C" int g4s_fps(int n_clouds, int n_points, const float* clouds, const in
         hipLaunchKernelGGL(fps_round_kernel, dim3(blocks, (unsigned)n_clouds), dim3(256), 0, stream, n_points, n_samples, round,
                            clouds, dev_first, dist, keys);
     const unsigned total = (unsigned)(n_clouds * n_samples);
-    hipLaunchKernelGGL(fps_gather_kernel, dim3((total + 255u) / 256u), dim3(256), 0, stream, n_clouds, n_points, n_samples, clouds,
+    hipLaunchKernelGGL(fps_gather_kernel, dim3(blocks256(total)), dim3(256), 0, stream, n_clouds, n_points, n_samples, clouds,
                        dev_first, keys, indices, samples);
     return finish(hipSuccess, "farthest-point sampling");
 }

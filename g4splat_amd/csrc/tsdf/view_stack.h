@@ -1,6 +1,8 @@
-// What the two view-stack fields (unbounded.hip, tetra.hip) share: the tail of a view record, the bilinear tap into a
-// view's maps, the staging of the view table into the caller's workspace with its size, and the point-sample kernel.
-// A field differs in its matrices, in which points a view accepts and in its running-mean update; those stay in its unit.
+// What the units over a stack of views share.  All of them -- the two fields (unbounded.hip, tetra.hip) and, through
+// vis_view.h, visibility.hip, planes.hip, consistency.hip, view_select.hip, depth_cues.hip, chart_init.hip --: the tail of a
+// view record, the host checks of a view stack, and the staging of the view table into the caller's workspace with its size.
+// The two fields alone: the bilinear tap and the point-sample kernel; a field differs in its matrices, in which points a view
+// accepts and in its running-mean update, and those stay in its unit.
 #pragma once
 #include <vector>
 
@@ -36,11 +38,52 @@ struct ViewTap {
     }
 };
 
+// ---- host checks of a view stack ----
+constexpr int GRID_MAX_VIEWS = 65535;  // where the views are the grid's y
+inline bool grid_views_ok(int n_views) { return n_views >= 0 && n_views <= GRID_MAX_VIEWS; }
+
+// The sizes [n_views,2] = (W, H) are there and positive with W * H at most 2^30: the largest pixel count of the views and
+// the sum of the counts.  No cap on n_views: that is grid_views_ok, for the units it binds.
+inline bool view_sizes_ok(int n_views, const int* sizes, long long* largest, long long* total) {
+    *largest = *total = 0;
+    if (n_views < 0 || (n_views > 0 && !sizes)) return false;
+    for (int v = 0; v < n_views; v++) {
+        const long long W = sizes[2 * v], H = sizes[2 * v + 1];
+        if (W <= 0 || H <= 0 || W * H > (1ll << 30)) return false;
+        *total += W * H;
+        if (W * H > *largest) *largest = W * H;
+    }
+    return true;
+}
+// the same with the grid cap and the messages; a unit with a wording of its own calls the bool form
+inline int check_grid_views(int n_views, const int* sizes, long long* largest, long long* total) {
+    if (!grid_views_ok(n_views)) return fail(G4S_ERR_INVALID_ARGUMENT, "n_views must be in 0 .. 65535");
+    if (view_sizes_ok(n_views, sizes, largest, total)) return G4S_OK;
+    if (!sizes) return null_pointer();
+    return fail(G4S_ERR_INVALID_ARGUMENT, "sizes: width, height must be positive and width * height at most 2^30");
+}
+// a host pointer array with one non-NULL entry per view
+template <class T>
+int check_pointers(const char* name, T* const* a, int n_views) {
+    if (!a) return fail(G4S_ERR_INVALID_ARGUMENT, "%s: NULL array", name);
+    for (int v = 0; v < n_views; v++) {
+        if (!a[v]) return fail(G4S_ERR_INVALID_ARGUMENT, "%s[%d]: NULL pointer", name, v);
+    }
+    return G4S_OK;
+}
+
+// ---- the view table in the workspace ----
 // bytes of the workspace that holds a table of n_views records
 template <class View>
 size_t view_table_bytes(int n_views) {
-    return (n_views > 0 ? (size_t)n_views * sizeof(View) : 0) + 256;  // + alignment of the base pointer
+    return (n_views > 0 ? (size_t)n_views * sizeof(View) : 0) + WORKSPACE_BASE_SLACK;
 }
+// The table in a layout that holds more: stage_views puts it at the aligned base, so a layout takes this range first.
+template <class View>
+void take_view_table(WorkspaceCursor& c, int n_views) { c.take(n_views > 0 ? (size_t)n_views * sizeof(View) : 0); }
+// Some queries were stated as align_up(view_table_bytes) + ... + 256 and so count the base alignment twice.  Callers size
+// buffers by them: those queries add this to their layout besides WORKSPACE_BASE_SLACK.
+constexpr size_t VIEW_TABLE_SLACK = 256;
 
 // Checks the view stack, builds the table on the host and copies it into the workspace.  `matrices` says that the
 // field's matrix arrays are there; fill(record, v) copies those of view v.  `name` opens the message of a failed upload.
@@ -63,8 +106,7 @@ int stage_views(const char* name, int n_views, bool matrices, const int* sizes, 
         u.maps = ViewMaps{W, H, depth[v], need_rgb ? rgb[v] : nullptr};
     }
     View* dev = (View*)align_ptr(workspace);
-    hipError_t e = hipMemcpyAsync(dev, host.data(), host.size() * sizeof(View), hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);  // `host` dies with this frame
+    const hipError_t e = upload(dev, host.data(), host.size() * sizeof(View), stream);  // `host` dies with this frame
     if (e != hipSuccess) return fail(G4S_ERR_HIP, "%s view table: %s", name, hipGetErrorString(e));
     *table = dev;
     return G4S_OK;
@@ -95,7 +137,7 @@ template <class Field>
 void launch_point_sample(int n_points, const float* points, const typename Field::View* table, int n_views,
                          const typename Field::Params& a, float* tsdf, float* colour, hipStream_t stream) {
     const auto kernel = colour ? point_sample_kernel<Field, true> : point_sample_kernel<Field, false>;
-    hipLaunchKernelGGL(kernel, dim3(((unsigned)n_points + 255u) / 256u), dim3(256), 0, stream, n_points, points, table,
+    hipLaunchKernelGGL(kernel, dim3(blocks256(n_points)), dim3(256), 0, stream, n_points, points, table,
                        n_views, a, tsdf, colour);
 }
 

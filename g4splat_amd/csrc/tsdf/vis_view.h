@@ -1,7 +1,8 @@
-// What the units over the Visibility section's views (visibility.hip, planes.hip, consistency.hip, depth_cues.hip) share: the
+// What the units over the Visibility section's views share.  visibility.hip, planes.hip, consistency.hip, view_select.hip: the
 // head of a view record -- world -> camera rotation, translation, focal lengths, then view_stack.h's maps --, its fill from
-// the host arrays, THE projection of include/g4s_render_maps.h ("Projection of a point p into a view"), its truncating tap,
-// the SURFACE test, and the ray record with THE back-projection.  There is no second one of any of them.
+// the host arrays, THE projection of include/g4s_render_maps.h ("Projection of a point p into a view"), its truncating tap and
+// the SURFACE test.  visibility.hip, depth_cues.hip, chart_init.hip: the ray record with THE back-projection.  There is no
+// second one of any of them.  The host checks and the table's staging that all six share are view_stack.h's.
 #pragma once
 #include "view_stack.h"
 
@@ -62,6 +63,13 @@ inline void vis_pose(View& u, const float* world_view, const float* focal, int v
 struct VisRay {
     float o[3], D[9];
 };
+// host: ray != NULL, the twelve floats of a ray record
+inline VisRay ray_record(const float* ray) {
+    VisRay r;
+    for (int i = 0; i < 3; i++) r.o[i] = ray[i];
+    for (int i = 0; i < 9; i++) r.D[i] = ray[3 + i];
+    return r;
+}
 
 // dir = D (x, y, 1) at integer pixel coordinates
 __device__ __forceinline__ void ray_dir(const VisRay& r, int x, int y, float (&dir)[3]) {

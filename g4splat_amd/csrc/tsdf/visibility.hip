@@ -243,8 +243,6 @@ using namespace g4s;
 // extern "C" entry points; every argument is checked before any launch
 namespace {
 
-inline unsigned blocks256(uint32_t n) { return (n + 255u) / 256u; }
-
 bool grid_resolution_ok(int R) { return R >= 1 && (long long)R * R * R < (1ll << 31); }
 
 int check_grid(int R, const float* bbox_min, const float* bbox_max, VisGrid* g) {
@@ -265,14 +263,6 @@ int check_map(int width, int height) {
     return width > 0 && height > 0 && (long long)width * height <= (1ll << 30)
                ? G4S_OK
                : fail(G4S_ERR_INVALID_ARGUMENT, "width, height must be positive and width * height at most 2^30");
-}
-
-// ray != NULL: the twelve floats of a ray record
-VisRay ray_record(const float* ray) {
-    VisRay r;
-    for (int i = 0; i < 3; i++) r.o[i] = ray[i];
-    for (int i = 0; i < 9; i++) r.D[i] = ray[3 + i];
-    return r;
 }
 
 int check_mode(int mode, int skip_view) {
@@ -320,7 +310,7 @@ extern "C" int g4s_visgrid_sample(int resolution, const float* bbox_min, const f
     if (n_points < 0 || n_points > (1 << 30)) return fail(G4S_ERR_INVALID_ARGUMENT, "n_points must be in 0 .. 2^30");
     if (!words || (n_points > 0 && (!points || !visible))) return null_pointer();
     if (n_points == 0) return G4S_OK;
-    hipLaunchKernelGGL(visgrid_sample_kernel, dim3(blocks256((uint32_t)n_points)), dim3(256), 0, stream, g, words, n_points,
+    hipLaunchKernelGGL(visgrid_sample_kernel, dim3(blocks256(n_points)), dim3(256), 0, stream, g, words, n_points,
                        points, visible);
     return finish(hipSuccess, "visgrid sample");
 }
@@ -337,7 +327,7 @@ int visgrid_march(int resolution, const float* bbox_min, const float* bbox_max, 
     if (n_samples < 1) return fail(G4S_ERR_INVALID_ARGUMENT, "n_samples must be at least 1");
     if (!grid || !depth || !visibility || !ray) return null_pointer();
     const int n = width * height;
-    hipLaunchKernelGGL(visgrid_march_kernel<Grid>, dim3(blocks256((uint32_t)n)), dim3(256), 0, stream, g, grid, width, n, depth,
+    hipLaunchKernelGGL(visgrid_march_kernel<Grid>, dim3(blocks256(n)), dim3(256), 0, stream, g, grid, width, n, depth,
                        ray_record(ray), n_samples, visibility);
     return finish(hipSuccess, "visgrid march");
 }
@@ -379,7 +369,7 @@ extern "C" int g4s_visgrid_expand(int resolution, const unsigned long long* word
 }
 
 extern "C" size_t g4s_visgrid_compact_workspace(int resolution) {
-    return grid_resolution_ok(resolution) ? vis_compact_layout(resolution).bytes + 256 : 0;
+    return grid_resolution_ok(resolution) ? vis_compact_layout(resolution).bytes + WORKSPACE_BASE_SLACK : 0;
 }
 
 extern "C" int g4s_visgrid_compact_count(int resolution, const unsigned long long* words, int invisible, int* n_points,
@@ -442,7 +432,7 @@ extern "C" int g4s_view_counts_points(int n_points, const float* points, int mod
     if (rc != G4S_OK) return rc;
     if (n_points == 0) return G4S_OK;
     const auto kernel = mode == VIS_FREE ? view_counts_points_kernel<VIS_FREE> : view_counts_points_kernel<VIS_SURFACE>;
-    hipLaunchKernelGGL(kernel, dim3(blocks256((uint32_t)n_points)), dim3(256), 0, stream, n_points, points, table, n_views,
+    hipLaunchKernelGGL(kernel, dim3(blocks256(n_points)), dim3(256), 0, stream, n_points, points, table, n_views,
                        skip_view, depth_threshold, counts);
     return finish(hipSuccess, "view counts points");
 }
@@ -461,7 +451,7 @@ extern "C" int g4s_view_counts_pixels(int width, int height, const float* pixel_
     if (rc != G4S_OK) return rc;
     const int n = width * height;
     const auto kernel = mode == VIS_FREE ? view_counts_pixels_kernel<VIS_FREE> : view_counts_pixels_kernel<VIS_SURFACE>;
-    hipLaunchKernelGGL(kernel, dim3(blocks256((uint32_t)n)), dim3(256), 0, stream, width, n, pixel_depth, r, table, n_views,
+    hipLaunchKernelGGL(kernel, dim3(blocks256(n)), dim3(256), 0, stream, width, n, pixel_depth, r, table, n_views,
                        skip_view, depth_threshold, counts);
     return finish(hipSuccess, "view counts pixels");
 }
@@ -476,6 +466,6 @@ extern "C" int g4s_depth_to_points(int width, int height, const float* depth, co
     if (!depth || !points || !ray) return null_pointer();
     const VisRay r = ray_record(ray);
     const int n = width * height;
-    hipLaunchKernelGGL(depth_to_points_kernel, dim3(blocks256((uint32_t)n)), dim3(256), 0, stream, width, n, depth, r, points);
+    hipLaunchKernelGGL(depth_to_points_kernel, dim3(blocks256(n)), dim3(256), 0, stream, width, n, depth, r, points);
     return finish(hipSuccess, "depth to points");
 }

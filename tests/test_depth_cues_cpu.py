@@ -196,12 +196,16 @@ def test_library_argument_validation_is_host_side(hip_lib):
     expect(align(n=65536), "n_views must be in 0 .. 65535")
     expect(align(sizes=nul), "NULL required pointer")
     expect(align(sizes=(ctypes.c_int * 4)(64, 48, 0, 3)), "width, height must be positive")
+    expect(align(sizes=(ctypes.c_int * 4)(64, 48, 1 << 15, (1 << 15) + 1)), "sizes: width, height must be positive and width * height")
+    expect(align(n=65536, sizes=nul), "n_views must be in 0 .. 65535")  # the first of two bad arguments
+    expect(align(sizes=(ctypes.c_int * 4)(64, 48, 0, 3), source=nul), "sizes: width, height must be positive")
     expect(align(source=nul), "source: NULL array")
     expect(align(target=hole), "target[1]: NULL pointer")
     expect(align(masks=hole), "masks[1]: NULL pointer")
     expect(align(coeffs=nul), "NULL required pointer")
     expect(align(counts=nul), "NULL required pointer")
     expect(align(bytes=64), "workspace too small")
+    expect(align(bytes=lib.g4s_depth_align_workspace(2, sizes) - 1), "workspace too small")
     expect(align(ws=nul), "workspace too small")
     assert align(n=0, sizes=nul, source=nul, target=nul, masks=nul, coeffs=nul, counts=nul, ws=nul, bytes=0) == 0
 
@@ -209,6 +213,8 @@ def test_library_argument_validation_is_host_side(hip_lib):
         ("domain", 1), ("n", 2), ("sizes", sizes), ("source", maps), ("coeffs", one), ("aligned", maps), ("ws", one),
         ("bytes", big), ("stream", nul))])
     expect(apply(domain=-1), "domain must be")
+    expect(apply(n=65536), "n_views must be in 0 .. 65535")
+    expect(apply(sizes=(ctypes.c_int * 4)(64, 48, 3, 0)), "sizes: width, height must be positive")
     expect(apply(aligned=hole), "aligned[1]: NULL pointer")
     expect(apply(coeffs=nul), "NULL required pointer")
     expect(apply(bytes=8), "workspace too small")
@@ -221,6 +227,8 @@ def test_library_argument_validation_is_host_side(hip_lib):
                     ("merged", maps), ("normal_world", maps), ("normal_cam", maps), ("ws", one), ("bytes", big), ("stream", nul)]
     cue = lambda **k: lib.g4s_depth_cue_maps(*[k.get(n, d) for n, d in cue_defaults])  # noqa: E731
     expect(cue(threshold=float("nan")), "must not be NaN")
+    expect(cue(n=-1), "n_views must be in 0 .. 65535")
+    expect(cue(sizes=nul), "NULL required pointer")
     expect(cue(rays=nul), "NULL required pointer")
     expect(cue(world_view=nul), "NULL required pointer")
     expect(cue(coeffs=nul), "NULL required pointer")
@@ -239,6 +247,9 @@ def test_library_argument_validation_is_host_side(hip_lib):
                       ("counts", one), ("ws", one), ("bytes", big), ("stream", nul)]
     plane = lambda **k: lib.g4s_plane_depths(*[k.get(n, d) for n, d in plane_defaults])  # noqa: E731
     expect(plane(n_planes=-1), "n_planes must not be negative")
+    expect(plane(n=65536), "n_views must be in 0 .. 65535")
+    expect(plane(n_planes=-1, sizes=(ctypes.c_int * 4)(64, 48, 0, 3)), "sizes: width, height must be positive")
+    expect(plane(bytes=lib.g4s_plane_depths_workspace(2, 3, 2) - 1), "workspace too small")
     expect(plane(cameras=nul), "NULL required pointer")
     expect(plane(counts=nul), "NULL required pointer")
     expect(plane(out=hole), "depth_out[1]: NULL pointer")
@@ -268,6 +279,8 @@ def test_library_argument_validation_is_host_side(hip_lib):
     refill_defaults = [("n", 2), ("n_input", 1), ("sizes", sizes), ("depth", maps), ("mono", maps), ("masks", maps),
                        ("conf", maps), ("coeffs", one), ("ws", one), ("bytes", big), ("stream", nul)]
     refill = lambda **k: lib.g4s_depth_refill(*[k.get(n, d) for n, d in refill_defaults])  # noqa: E731
+    expect(refill(n=65536), "n_views must be in 0 .. 65535")
+    expect(refill(sizes=nul), "NULL required pointer")
     expect(refill(n_input=3), "n_input_views must be in 0 .. n_views")
     expect(refill(n_input=-1), "n_input_views must be in 0 .. n_views")
     expect(refill(mono=hole), "mono_depth[1]: NULL pointer")

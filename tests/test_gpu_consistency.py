@@ -560,6 +560,10 @@ def test_library_arguments_are_checked_on_the_host(hip_lib):
     expect(points(V=70000), "n_views must be in 0 .. 65535")
     expect(points(n_in=3), "n_input_views must be in 0 .. n_views")
     expect(points(sz=bad_sizes), "sizes: width, height must be positive")
+    expect(points(sz=(ctypes.c_int * 4)(4, 4, 1 << 15, (1 << 15) + 1)), "width * height at most 2^30")
+    expect(points(sz=nul), "NULL required pointer")
+    expect(points(sz=bad_sizes, n_in=3), "sizes: width, height must be positive")  # the first of two bad arguments
+    expect(points(ws_bytes=lib.g4s_consistency_points_workspace(2, 1, sizes) - 1), "workspace too small")
     expect(points(outs=nul), "images_out and conf must both be there or both be NULL")
     expect(points(state=nul), "state: NULL")
     expect(points(pts=nul), "points: NULL")
@@ -585,7 +589,9 @@ def test_library_arguments_are_checked_on_the_host(hip_lib):
                                                 ws_bytes, nul)
 
     expect(counts(thr=float("nan")), "depth_threshold must not be NaN")
+    expect(counts(V=65536), "n_views must be in 0 .. 65535")
     expect(counts(sz=bad_sizes), "sizes: width, height must be positive")
+    expect(counts(ws_bytes=lib.g4s_consistency_plane_counts_workspace(2, 3, 2) - 1), "workspace too small")
     expect(counts(K=-1), "n_planes, n_anchors must not be negative")
     expect(counts(anchor=nul), "anchor_views: NULL array")
     expect(counts(anchor=bad_anchors), "anchor_views[1] must be a view index below n_views")
@@ -609,7 +615,11 @@ def test_library_arguments_are_checked_on_the_host(hip_lib):
                                                  nul)
 
     expect(repaint(V=-1), "n_views must be in 0 .. 65535")
+    expect(repaint(V=65536), "n_views must be in 0 .. 65535")
+    expect(repaint(sz=nul), "NULL required pointer")
     expect(repaint(sz=bad_sizes), "sizes: width, height must be positive")
+    expect(repaint(sz=(ctypes.c_int * 4)(1 << 15, 1 << 15, 1 << 15, 1 << 15)), "fewer than 2^31 pixels in all")
+    expect(repaint(ws_bytes=lib.g4s_consistency_plane_repaint_workspace(2, sizes, 3) - 1), "workspace too small")
     expect(repaint(masks=nul), "masks: NULL array")
     expect(repaint(images=no_map), "images[1]: NULL pointer")
     expect(repaint(outs=nul), "images_out: NULL array")

@@ -450,7 +450,14 @@ def test_argument_validation_is_host_side(hip_lib):
     expect(lib.g4s_plane_labels(5, nul, 0.01, 1, wv, focal, sizes, masks, one, one, big, nul), "NULL required pointer")
     expect(lib.g4s_plane_labels(5, one, 0.01, 1, wv, focal, sizes, nul, one, one, big, nul), "NULL required pointer")
     expect(lib.g4s_plane_labels(5, one, 0.01, 1, wv, focal, bad_sizes, masks, one, one, big, nul), "must be positive")
+    huge_sizes = (ctypes.c_int * 2)(1 << 15, (1 << 15) + 1)
+    expect(lib.g4s_plane_labels(5, one, 0.01, 1, wv, focal, huge_sizes, masks, one, one, big, nul), "width * height at most 2^30")
+    expect(lib.g4s_plane_labels(5, one, 0.01, 1, wv, focal, nul, masks, one, one, big, nul), "NULL required pointer")
+    assert lib.g4s_plane_labels_workspace(70000, (ctypes.c_int * 140000)(*([2, 2] * 70000))) > 70000 * (88 + 256)  # no view cap
     expect(lib.g4s_plane_labels(5, one, 0.01, 1, wv, focal, sizes, masks, one, one, 8, nul), "workspace too small")
+    edge = lib.g4s_plane_labels_workspace(1, sizes) - 1
+    expect(lib.g4s_plane_labels(5, one, 0.01, 1, wv, focal, sizes, masks, one, one, edge, nul), "workspace too small")
+    expect(lib.g4s_plane_labels(5, one, 0.01, 1, wv, focal, sizes, no_mask, one, one, 8, nul), "workspace too small")  # checked first
     expect(lib.g4s_plane_labels(5, one, 0.01, 1, wv, focal, sizes, no_mask, one, one, big, nul), "NULL map pointer")
     assert lib.g4s_plane_labels(5, one, 0.01, 0, nul, nul, nul, nul, nul, nul, 0, nul) == 0  # no view: nothing to do
     expect(lib.g4s_plane_overlap(5, one, 2, 3, 0, one, one, one, nul, 0, nul), "n_words must be in")
@@ -464,6 +471,9 @@ def test_argument_validation_is_host_side(hip_lib):
     expect(lib.g4s_plane_assign(5, one, 2, bad_target, 3, 1, one, one, big, nul), "target[1] must be -1 or a global plane")
     expect(lib.g4s_plane_assign(5, one, 2, nul, 3, 1, one, one, big, nul), "NULL required pointer")
     expect(lib.g4s_plane_assign(5, one, 2, target, 3, 1, one, one, 4, nul), "workspace too small")
+    assert lib.g4s_plane_assign_workspace(2) == 8 + 256 and lib.g4s_plane_assign_workspace(-1) == 256
+    expect(lib.g4s_plane_assign(5, one, 2, target, 3, 1, one, one, 8 + 255, nul), "workspace too small")
+    expect(lib.g4s_plane_assign(5, one, 2, target, 3, 1, one, nul, big, nul), "workspace too small")
     expect(lib.g4s_plane_assign((1 << 30) + 1, one, 2, target, 3, 1, one, one, big, nul), "n_points must be in")
     expect(lib.g4s_plane_row_overlap(5, 3, 1, one, 3, one, nul, 0, nul), "row must be a global plane below n_global")
     expect(lib.g4s_plane_row_overlap(5, 3, 1, one, 0, nul, nul, 0, nul), "NULL required pointer")
