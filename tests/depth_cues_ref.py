@@ -3,6 +3,7 @@ float32 is the library's arithmetic bit for bit (the per-pixel stages) or to the
 are exact here -- math.fsum -- and float64 in a fixed order there); float64 is what tests/test_depth_cues_cpu.py holds
 against the reference's float64 run.  Nothing here imports the product."""
 import math
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -153,6 +154,29 @@ def plane_depth_image(normal, centre, cam, H, W, dtype):
     return z, (t > 0) & (z > 0)
 
 
+def plane_terms(normal, centre, cam, H, W, dtype):
+    """(nd [H,W], num, length [H,W]) of plane_depth_image: the normal against the unit ray, before the 1e-8 clamp; the
+    normal against centre - camera; the length of the ray at unit camera depth.  A test reads from them which pixels the
+    clamp decides and in which sign; z = num / copysign(max(|nd|, 1e-8), nd) / length."""
+    o, R, fx, fy = plane_camera(cam, W, H, dtype)
+    n, c = np.asarray(normal, dtype).reshape(3), np.asarray(centre, dtype).reshape(3)
+    x = np.arange(W, dtype=dtype)[None, :]
+    y = np.arange(H, dtype=dtype)[:, None]
+    with np.errstate(all="ignore"):
+        dcx = (x - dtype(W) * dtype(0.5)) / fx + np.zeros((H, 1), dtype)
+        dcy = (y - dtype(H) * dtype(0.5)) / fy + np.zeros((1, W), dtype)
+        w = [(R[r, 0] * dcx + R[r, 1] * dcy) + R[r, 2] for r in range(3)]
+        length = np.fmax(np.sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]), dtype(1e-12))
+        nd = (n[0] * (w[0] / length) + n[1] * (w[1] / length)) + n[2] * (w[2] / length)
+        num = (n[0] * (c[0] - o[0]) + n[1] * (c[1] - o[1])) + n[2] * (c[2] - o[2])
+    return nd, num, length
+
+
+def fitted_ids(gdict, planes, n_views):
+    """Per view the ascending mask ids that have a fitted plane: the runs the library's id table holds."""
+    return [sorted(pairs) for pairs in fitted_pairs(gdict, planes, n_views)]
+
+
 def apply_global_planes(cams, depths, masks, gdict, planes, dtype):
     """(new depths, replaced [V], zeroed [V], touched [V] bool maps, valid [V] bool maps)."""
     V = len(cams)
@@ -204,3 +228,60 @@ def refine_depths_with_planes(cams, depths, masks, confs, monos, gdict, planes, 
     planed, _r, _z, touched, valid = apply_global_planes(cams, depths, masks, gdict, planes, dtype)
     outs, coeffs, _counts = refill(planed, monos, masks, confs, n_input, dtype)
     return outs, coeffs, touched, valid
+
+
+# ---- scenes that two test files share: built here once, pinned without a GPU by tests/test_depth_cues_cpu.py -----------------
+ID_RUNS = (2, 0, 1, 3, 7, 64, 65)  # fitted ids per view: the view without any sits between two that have some
+ID_SIZES = ((45, 67), (48, 64), (45, 67), (48, 64), (45, 67), (48, 64), (45, 67))
+ID_TOP = 2 ** 31 - 1
+_ID_FORCED = {0: [], 1: [1000], 2: [5, 6], 3: [6, 1000, ID_TOP - 1], 7: [5, 6], 64: [5, 6, 1001], 65: [1, 5, 6, ID_TOP]}
+
+
+def id_search_scene(seed=31):
+    """A scene for the id search of the plane depths: per view of ID_SIZES a run of ID_RUNS sparse fitted ids between 1 and
+    2^31 - 1, spread over five planes whose indices do not ascend with the id, and a mask in which every fitted id occurs, and
+    beside them 0, negative values and unfitted ids below the first, between neighbours and above the last fitted one (two of
+    them listed under key 99, which has no plane; among them the table's entries just before and just behind the view's run,
+    which belong to other views).  A namespace: sizes, depths, masks, gdict, planes, fitted, unfitted."""
+    rng = np.random.default_rng(seed)
+    planes = {40: ((0.1, 0.2, 0.97), (0.0, 0.0, 0.3)), 7: ((0.9, -0.1, 0.2), (0.4, 0.0, 0.0)), 19: ((0.0, 1.0, 0.05), (0.0, 0.6, 0.0)),
+              3: ((-0.3, 0.1, 0.95), (0.0, 0.0, -0.2)), 88: ((0.2, -0.9, 0.3), (0.0, -0.5, 0.1))}
+    keys = list(planes)
+    gdict = {key: [] for key in keys + [99]}
+    interior = np.unique(rng.integers(2000, ID_TOP - 1000, 400)).tolist()
+    depths, masks, fitted, unfitted = [], [], [], []
+    for v, n in enumerate(ID_RUNS):
+        forced = _ID_FORCED[n]
+        ids = sorted(forced + rng.choice(interior, n - len(forced), replace=False).tolist())
+        assert len(set(ids)) == n
+        for p in ids:
+            gdict[keys[int(rng.integers(len(keys)))]].append((v, p))
+        fitted.append(ids)
+    table = [p for ids in fitted for p in ids]  # the library's id table: the runs one behind the other
+    for v, (ids, (H, W)) in enumerate(zip(fitted, ID_SIZES)):
+        first = sum(len(run) for run in fitted[:v])
+        beside = table[max(first - 1, 0):first] + table[first + len(ids):first + len(ids) + 1]  # the entries next to the run
+        near = [q for p in ids for q in (p - 1, p + 1)] + [(a + b) // 2 for a, b in zip(ids, ids[1:])] + [1, 2, ID_TOP, ID_TOP - 7]
+        others = sorted({q for q in near + beside if 1 <= q <= ID_TOP} - set(ids))
+        gdict[99] += [(v, others[0]), (v, others[-1])]
+        values = ids + others + [0, -1, -(2 ** 31)] + [-p for p in ids[:3]]
+        mask = rng.choice(np.array(values, np.int64), H * W)
+        mask[rng.permutation(H * W)[:len(values)]] = values  # every value occurs
+        depths.append(rng.uniform(1.0, 4.0, (H, W)).astype(np.float32))
+        masks.append(mask.astype(np.int32).reshape(H, W))
+        unfitted.append(others)
+    return SimpleNamespace(sizes=list(ID_SIZES), depths=depths, masks=masks, gdict=gdict, planes=planes, fitted=fitted,
+                           unfitted=unfitted)
+
+
+def clamp_scene(seed=41):
+    """A 48 x 64 view of an identity camera (w = (dcx, dcy, 1)) whose mask spreads three planes over the image: ids 1 and 2,
+    n = (+-1e-9, 0, 0) through (5, 0, 0), have |n.d| < 1e-8 in every pixel, in both signs and exactly zero in column W / 2;
+    id 3 passes through the camera centre (num = 0).  A namespace: cam, H, W, depth, mask, gdict, planes."""
+    rng = np.random.default_rng(seed)
+    H, W = 48, 64
+    cam = SimpleNamespace(world_view_transform=np.eye(4, dtype=np.float32), full_proj_transform=np.eye(4, dtype=np.float32),
+                          FoVx=1.0, FoVy=0.8, image_width=W, image_height=H)
+    planes = {1: ((1e-9, 0.0, 0.0), (5.0, 0.0, 0.0)), 2: ((-1e-9, 0.0, 0.0), (5.0, 0.0, 0.0)), 3: ((0.0, 0.0, 1.0), (2.0, -3.0, 0.0))}
+    return SimpleNamespace(cam=cam, H=H, W=W, depth=rng.uniform(1.0, 4.0, (H, W)).astype(np.float32),
+                           mask=rng.integers(0, 4, (H, W)).astype(np.int32), gdict={k: [(0, k)] for k in planes}, planes=planes)

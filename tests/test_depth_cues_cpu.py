@@ -118,6 +118,82 @@ def test_degenerate_alignments_follow_ieee(golden):
     assert n == 3 and np.isfinite(alpha) and np.isfinite(beta)
 
 
+# ---- the helpers and scenes of the GPU tests, pinned to the restatement above ------------------------------------------------
+@pytest.mark.parametrize("dtype", [f32, f64])
+def test_plane_terms_are_those_of_plane_depth_image(golden, dtype):
+    g = golden
+    scene = dr.clamp_scene()
+    cases = [(*g.planes[int(key)], g.cams[int(v)], g.H, g.W) for key, v in g.g["plane_full_pairs"]]
+    cases += [(*scene.planes[k], scene.cam, scene.H, scene.W) for k in scene.planes]
+    for normal, centre, cam, H, W in cases:
+        nd, num, length = dr.plane_terms(normal, centre, cam, H, W, dtype)
+        assert nd.dtype == length.dtype == dtype and nd.shape == length.shape == (H, W) and np.ndim(num) == 0
+        with np.errstate(all="ignore"):
+            t = num / np.copysign(np.fmax(np.abs(nd), dtype(1e-8)), nd)
+            z = t / length
+        want_z, want_valid = dr.plane_depth_image(normal, centre, cam, H, W, dtype)
+        assert np.array_equal(z, want_z) and np.array_equal(np.signbit(z), np.signbit(want_z))
+        assert np.array_equal((t > 0) & (z > 0), want_valid)
+
+
+def test_clamp_scene_reaches_the_clamp_in_both_signs_and_at_zero():
+    s = dr.clamp_scene()
+    o, R, _fx, _fy = dr.plane_camera(s.cam, s.W, s.H, f32)
+    assert not o.any() and np.array_equal(R, np.eye(3, dtype=f32))  # w = (dcx, dcy, 1)
+    for pid in (1, 2):
+        nd, num, _len = dr.plane_terms(*s.planes[pid], s.cam, s.H, s.W, f32)
+        here = s.mask == pid
+        assert (np.abs(nd) < f32(1e-8)).all() and num != 0
+        assert (nd[here] < 0).any() and (nd[here] == 0).any() and ((nd[here] > 0) & (nd[here] < f32(1e-8))).any()
+        assert not nd[:, s.W // 2].any() and here[:, s.W // 2].any()
+        _z, valid = dr.plane_depth_image(*s.planes[pid], s.cam, s.H, s.W, f32)
+        assert valid[here].any() and not valid[here].all()  # the sign of nd decides
+    nd, num, _len = dr.plane_terms(*s.planes[3], s.cam, s.H, s.W, f32)
+    assert num == 0 and (nd > f32(1e-8)).all() and any(s.planes[3][1])  # through the camera centre, not at it
+    assert not dr.plane_depth_image(*s.planes[3], s.cam, s.H, s.W, f32)[1].any() and (s.mask == 3).any()
+    _d, replaced, zeroed, touched, _v = dr.apply_global_planes([s.cam], [s.depth], [s.mask], s.gdict, s.planes, f32)
+    assert replaced[0] > 0 and zeroed[0] > (s.mask == 3).sum() and (s.mask == 0).any() and not touched[0][s.mask == 0].any()
+
+
+def test_id_search_scene_covers_what_it_claims(golden):
+    from g4splat_amd import depth_cues
+    s = dr.id_search_scene()
+    V = len(s.sizes)
+    assert [len(ids) for ids in s.fitted] == list(dr.ID_RUNS) == [2, 0, 1, 3, 7, 64, 65]
+    assert dr.fitted_ids(s.gdict, s.planes, V) == s.fitted
+    assert [sorted(pairs) for pairs in dr.fitted_pairs(s.gdict, s.planes, V)] == s.fitted
+    assert 99 in s.gdict and 99 not in s.planes
+    # the library's table is the restatement's
+    view_offset, ids, entry_plane, _rows, keys = depth_cues.plane_table(s.gdict, s.planes, V)
+    assert [ids[a:b] for a, b in zip(view_offset, view_offset[1:])] == s.fitted
+    pairs = dr.fitted_pairs(s.gdict, s.planes, V)
+    assert [keys[k] for k in entry_plane] == [pairs[v][p] for v in range(V) for p in s.fitted[v]]
+    for v, (fit, others, mask) in enumerate(zip(s.fitted, s.unfitted, s.masks)):
+        assert mask.dtype == np.int32 and mask.shape == s.sizes[v]
+        assert all((mask == p).any() for p in fit), v  # every entry of the run is searched for
+        assert not set(fit) & set(others) and all((mask == q).any() for q in others)
+        assert (mask == 0).any() and (mask < 0).any() and (mask == -2 ** 31).any()
+        a, b = view_offset[v], view_offset[v + 1]  # the table's entries beside the run belong to other views
+        beside = ([ids[a - 1]] if a > 0 else []) + ([ids[b]] if b < len(ids) else [])
+        assert len(beside) == (2 if 0 < v < V - 1 else 1) and all(q in fit or (mask == q).any() for q in beside)
+        assert v != 1 or (beside == [6, 1000] and not fit)  # without a run of its own, both neighbours' ends are in the mask
+        if fit:
+            assert any(q < fit[0] for q in others) or fit[0] == 1
+            assert any(q > fit[-1] for q in others) or fit[-1] == dr.ID_TOP
+            assert all(any(a < q < b for q in others) for a, b in zip(fit, fit[1:]) if b - a > 1)
+            planes_of = [entry_plane[view_offset[v] + i] for i in range(len(fit))]
+            if len(fit) >= 7:
+                assert len(set(planes_of)) < len(fit) and planes_of != sorted(planes_of)  # shared, and not ascending with the id
+    assert s.fitted[5][0] > 1 and s.fitted[5][-1] < dr.ID_TOP and (s.fitted[6][0], s.fitted[6][-1]) == (1, dr.ID_TOP)
+    assert (5 in s.fitted[0] and 6 in s.fitted[0])  # neighbours one apart
+    cams = [golden.cams[v % golden.V] for v in range(V)]
+    _d, replaced, zeroed, touched, _v = dr.apply_global_planes(cams, s.depths, s.masks, s.gdict, s.planes, f32)
+    assert replaced.sum() > 0 and zeroed.sum() > 0 and replaced[1] == zeroed[1] == 0 and not touched[1].any()
+    assert all(replaced[v] + zeroed[v] > 0 for v in range(V) if v != 1)
+    for v in range(V):
+        assert np.array_equal(touched[v], np.isin(s.masks[v], s.fitted[v]))
+
+
 # ---- the host table builder ------------------------------------------------------------------------------------------------
 def test_plane_table_last_wins_missing_planes_and_sparse_ids():
     from g4splat_amd import depth_cues

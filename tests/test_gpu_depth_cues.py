@@ -9,7 +9,12 @@ the exact value sits on a rounding boundary.
 Per-pixel stages.  Fed the device's own coefficients, every map equals the float32 restatement bit for bit.
 Golden.  The reference-named entry points and refine_depths_with_planes against the reference's float64 results, within
 twice the recorded yardstick (the device's float32 steps are not the reference's and may round the other way); decisions
-exactly, on the compared set."""
+exactly, on the compared set.
+Sizes.  The same bars where the kernels take another trip or another branch: views of more than 64 spans (the second and
+third trip of the coefficient kernel's fold, partial rows behind a long view), id runs of 0 to 65 sparse ids with masks
+that hold every fitted id and unfitted ones around them, an inpainted view larger than every input view, the float mask at
+equality, NaN and the infinities, the plane clamp in both signs and at zero, and the ends of the two workspaces that hold
+more than a view table."""
 import numpy as np
 import pytest
 import torch
@@ -129,6 +134,90 @@ def test_coefficients_of_degenerate_masks_follow_ieee():
         assert np.isfinite(got[4]).all() == (domain == "depth")  # 1 / 0 poisons the disparity domain only
 
 
+# ---- past 64 spans: lane l of the coefficient kernel's one wave adds the partials l, l + 64, ...; a view of more than
+# 64 * SPAN = 262 144 pixels (every real one: 800 x 600 has 118 spans) takes a second trip of that loop ----
+LONG_VIEWS = {"64span": [(1, 64 * SPAN)], "64span+1": [(1, 64 * SPAN + 1)], "65span-tail": [(1, 65 * SPAN)],
+              "128span+1": [(1, 128 * SPAN + 1)], "800x600": [(600, 800)],
+              "four-views": [(1, 64 * SPAN + 1), (45, 67), (600, 800), (1, SPAN)]}
+_long_scenes = {}
+
+
+def _long_scene(name):
+    """_scene(LONG_VIEWS[name], 17), made once and only read; "65span-tail" has its mask cleared below 64 spans, so that only
+    the partial of the second trip counts."""
+    if name not in _long_scenes:
+        disps, depths, masks = _scene(LONG_VIEWS[name], 17)
+        if name == "65span-tail":
+            masks[0][:, :64 * SPAN] = False
+            assert 0 < masks[0].sum() < SPAN
+        _long_scenes[name] = disps, depths, masks
+    return _long_scenes[name]
+
+
+@pytest.mark.parametrize("domain", ["disparity", "depth"])
+@pytest.mark.parametrize("name", list(LONG_VIEWS))
+def test_coefficients_past_64_spans(name, domain):
+    disps, depths, masks = _long_scene(name)
+    got = _check_coeffs(disps, depths, masks, domain)
+    assert np.isfinite(got).all()  # so _check_coeffs has asserted the two conditions of its bar for every view
+
+
+def _refill_scene(sizes, seed):
+    """Targets, mono depths, plane masks over 0 and 3, confidences: _scene's affine pair read in the third domain (1 / target
+    against 1 / mono), so the bar of the coefficients holds as it does there."""
+    disps, depths, confs = _scene(sizes, seed)
+    rng = np.random.default_rng(seed + 1)
+    monos = [(f32(1) / d).astype(f32) for d in disps]
+    masks = [rng.choice(np.array([0, 0, 3], np.int32), s).astype(np.int32) for s in sizes]
+    return depths, monos, masks, confs
+
+
+def _check_refill(sizes, n_input, seed=17):
+    """refill_unseen_regions against the restatement: counts exactly, coefficients within one unit, and -- fed the device's
+    coefficients -- every depth bit for bit.  Returns the unfilled regions."""
+    targets, monos, masks, confs = _refill_scene(sizes, seed)
+    args = _devs(targets), _devs(monos), _devs(masks), _devs(confs)
+    got, coeffs, counts = depth_cues.refill_unseen_regions(*args, n_input)
+    assert all(torch.equal(a, _dev(b)) for a, b in zip(args[0], targets))  # the inputs are only read
+    coeffs, counts = coeffs.cpu().numpy(), counts.cpu().numpy()
+    assert coeffs.shape == (len(sizes), 2) and counts.shape == (len(sizes),)
+    regions = []
+    for v in range(len(sizes)):
+        g = got[v].cpu().numpy()
+        region = (masks[v] == 0) & ~confs[v]
+        regions.append(region)
+        if v < n_input:
+            _same_bits(g, targets[v], f"input view {v}")
+            assert not coeffs[v].any() and counts[v] == 0
+            continue
+        alpha, beta, n = dr.align_coeffs(monos[v], targets[v], confs[v], dr.INVERSE_SOURCE, f32)
+        assert int(counts[v]) == n == int(confs[v].sum())
+        if np.isfinite(alpha) and np.isfinite(beta):  # the two conditions the one-ulp bar rests on
+            assert n <= 2 ** 20 and dr.variance_share(monos[v], targets[v], confs[v], dr.INVERSE_SOURCE, f32) >= 0.01
+        _within_one_ulp(coeffs[v, 0], alpha, f"refill {v} alpha")
+        _within_one_ulp(coeffs[v, 1], beta, f"refill {v} beta")
+        filled = dr.aligned(coeffs[v, 0], coeffs[v, 1], monos[v], dr.INVERSE_SOURCE, f32)
+        _same_bits(g, np.where(region, filled, targets[v]), f"refill {v}")
+    return regions, coeffs
+
+
+def test_refill_coefficients_past_64_spans():
+    """The third domain over a real view: an inpainted 800 x 600 behind a small input view."""
+    _regions, coeffs = _check_refill([(45, 67), (600, 800)], 1)
+    assert np.isfinite(coeffs[1]).all()
+
+
+# ---- the refill's grid is sized by the inpainted views alone ----
+@pytest.mark.parametrize("sizes, n_input, large", [([(3, 3), (2, 5), (48, 64)], 2, 2), ([(3, 3), (2, 5), (7, 5), (48, 64), (5, 7)], 2, 3),
+                                                   ([(3, 3), (2, 5), (48, 64)], 0, 2), ([(3, 3), (2, 5), (48, 64)], 3, 2)],
+                         ids=["large-last", "large-in-the-middle", "no-input-view", "input-views-only"])
+def test_refill_reaches_the_end_of_an_inpainted_view_larger_than_the_input_views(sizes, n_input, large):
+    pixels = [H * W for H, W in sizes]
+    assert pixels[large] == max(pixels) and all(pixels[v] <= 256 for v in range(len(sizes)) if v != large)
+    regions, _coeffs = _check_refill(sizes, n_input)
+    assert regions[large][-1].any() and regions[large][:-1].any()  # the unfilled region reaches the last row
+
+
 def _cams(golden, sizes):
     return [golden.cams[v % golden.V] for v in range(len(sizes))]
 
@@ -226,6 +315,155 @@ def test_plane_aligned_depth_of_a_whole_image(golden):
     z, ok = dr.plane_depth_image(n, c, cam, 45, 67, f32)
     assert valid.dtype == torch.bool and np.array_equal(valid.cpu().numpy(), ok) and ok.any() and not ok.all()
     _same_bits(depth.cpu().numpy(), np.where(ok, z, f32(0)), "plane_aligned_depth")
+
+
+# ---- the id search of the plane depths ----
+def _check_planes(cams, depths, masks, gdict, planes):
+    """apply_global_planes against the restatement: depths bit for bit, both counts exactly, untouched pixels keep their bits."""
+    out, replaced, zeroed = depth_cues.apply_global_planes(cams, _devs(depths), _devs(masks), gdict, planes)
+    want, want_replaced, want_zeroed, touched, _valid = dr.apply_global_planes(cams, depths, masks, gdict, planes, f32)
+    print("replaced", want_replaced.tolist(), "zeroed", want_zeroed.tolist())
+    assert replaced.dtype == zeroed.dtype == torch.int32
+    assert np.array_equal(replaced.cpu().numpy(), want_replaced) and np.array_equal(zeroed.cpu().numpy(), want_zeroed)
+    for v in range(len(cams)):
+        got = out[v].cpu().numpy()
+        _same_bits(got, want[v], f"plane depth {v}")
+        _same_bits(got[~touched[v]], depths[v][~touched[v]], f"untouched {v}")
+    return out, replaced, zeroed, (want_replaced, want_zeroed, touched)
+
+
+@pytest.fixture(scope="module")
+def id_scene():
+    return dr.id_search_scene()
+
+
+def test_plane_ids_are_found_in_runs_of_0_to_65_sparse_ids(golden, id_scene):
+    """Runs of 2, 0, 1, 3, 7, 64 and 65 fitted ids in one call; every entry of every run covers a pixel, and the masks hold
+    ids below, between and above the fitted ones, 0 and negative values (tests/test_depth_cues_cpu.py holds the scene to that)."""
+    s = id_scene
+    for v, ids in enumerate(dr.fitted_ids(s.gdict, s.planes, len(s.sizes))):
+        assert len(ids) == dr.ID_RUNS[v] and all((s.masks[v] == p).any() for p in ids)
+    _out, _r, _z, (replaced, zeroed, touched) = _check_planes(_cams(golden, s.sizes), s.depths, s.masks, s.gdict, s.planes)
+    assert replaced.sum() > 0 and zeroed.sum() > 0 and not touched[1].any()
+    for v in range(len(s.sizes)):
+        assert np.array_equal(touched[v], np.isin(s.masks[v], s.fitted[v]))
+
+
+def test_plane_depth_clamp_in_both_signs_at_zero_and_through_the_camera():
+    """|n.d| < 1e-8 in every pixel of two mirrored planes, negative, zero and positive; a third plane through the camera
+    centre (num = 0) is zeroed everywhere."""
+    s = dr.clamp_scene()
+    for pid in (1, 2):
+        nd, _num, _len = dr.plane_terms(*s.planes[pid], s.cam, s.H, s.W, f32)
+        nd = nd[s.mask == pid]
+        assert (nd < 0).any() and (nd == 0).any() and ((nd > 0) & (nd < f32(1e-8))).any() and (np.abs(nd) < f32(1e-8)).all()
+    assert dr.plane_terms(*s.planes[3], s.cam, s.H, s.W, f32)[1] == 0
+    out, _r, _z, (replaced, zeroed, touched) = _check_planes([s.cam], [s.depth], [s.mask], s.gdict, s.planes)
+    assert replaced[0] > 0 and zeroed[0] > (s.mask == 3).sum() > 0
+    assert not out[0].cpu().numpy()[s.mask == 3].any()
+    for pid in (1, 2):  # each plane alone, over the whole image
+        n, c = (np.array(x, f32) for x in s.planes[pid])
+        depth, valid = depth_cues.plane_aligned_depth(_dev(n), _dev(c), s.cam, (s.H, s.W))
+        z, ok = dr.plane_depth_image(*s.planes[pid], s.cam, s.H, s.W, f32)
+        assert ok.any() and not ok.all() and np.array_equal(valid.cpu().numpy(), ok)
+        _same_bits(depth.cpu().numpy(), np.where(ok, z, f32(0)), f"clamped plane {pid}")
+
+
+# ---- the float mask at its edges ----
+@pytest.mark.parametrize("threshold", [0.9, 0.1], ids=["0.9", "0.1"])
+def test_float_mask_at_equality_nan_and_infinities(golden, threshold):
+    """alpha > threshold in float32: equal, one float32 above and below, NaN, +inf and -inf, each in pixels of their own."""
+    sizes = [(45, 67), (48, 64)]
+    cams = _cams(golden, sizes)
+    disps, warps, _m = _scene(sizes, 23)
+    rng = np.random.default_rng(29)
+    t = f32(threshold)
+    edges = [t, np.nextafter(t, f32(np.inf)), np.nextafter(t, f32(-np.inf)), f32(np.nan), f32(np.inf), f32(-np.inf)]
+    visible = [False, True, False, False, True, False]
+    alphas = []
+    for d in disps:
+        a = np.where(rng.random(d.shape) < 0.7, 0.97, 0.04).astype(f32).reshape(-1)
+        where = rng.permutation(a.size)[:60 * len(edges)].reshape(len(edges), 60)
+        for e, seen, idx in zip(edges, visible, where):
+            a[idx] = e
+            with np.errstate(invalid="ignore"):
+                assert ((a[idx] > t) == seen).all()
+        alphas.append(a.reshape(d.shape))
+    cues = depth_cues.view_geometry_cues(cams, _devs(disps), _devs(warps), _devs(alphas), visible_threshold=threshold)
+    coeffs, counts = cues.coeffs.cpu().numpy(), cues.counts.cpu().numpy()
+    for v in range(len(sizes)):
+        with np.errstate(invalid="ignore"):
+            vis = alphas[v] > t
+        assert cues.visibility[v].dtype == torch.bool and np.array_equal(cues.visibility[v].cpu().numpy(), vis)
+        assert counts[v] == int(vis.sum())
+        alpha, beta, n = dr.align_coeffs(disps[v], warps[v], vis, dr.DISPARITY, f32)
+        assert n == counts[v] and n <= 2 ** 20 and dr.variance_share(disps[v], warps[v], vis, dr.DISPARITY, f32) >= 0.01
+        _within_one_ulp(coeffs[v, 0], alpha, f"view {v} alpha")
+        _within_one_ulp(coeffs[v, 1], beta, f"view {v} beta")
+        want = dr.cue_maps(cams[v], disps[v], warps[v], alphas[v], threshold, coeffs[v, 0], coeffs[v, 1], f32)
+        assert np.array_equal(want["visibility"], vis)
+        for name in ("mono_depth", "aligned_depth", "depth", "normal_world", "normal_cam"):
+            _same_bits(getattr(cues, name)[v].cpu().numpy(), want[name], f"{name} {v}")
+
+
+# ---- nothing is written behind the workspaces the two larger layouts ask for ----
+def _canary(nbytes, shift):
+    """A buffer of 0xA5 whose workspace of `nbytes` starts `shift` bytes in (the library aligns the base itself), its 4 KiB tail."""
+    buf = torch.full((shift + nbytes + 4096,), 0xA5, dtype=torch.uint8, device=DEV)
+    return buf, buf[shift:], buf[shift + nbytes:]
+
+
+@pytest.mark.parametrize("shift", [0, 1], ids=["aligned", "base+1"])
+def test_align_workspace_is_enough(hip_lib, shift):
+    """g4s_depth_align keeps its view table and the partials of 65 + 1 spans inside g4s_depth_align_workspace."""
+    from g4splat_amd import _lib
+    sizes = [(1, 64 * SPAN + 1), (45, 67)]
+    disps, depths, masks = _scene(sizes, 17)
+    src, tgt, msk = _devs(disps), _devs(depths), [m.view(torch.uint8) for m in _devs(masks)]
+    c_sizes = _lib.array(_lib.c_i, [x for H, W in sizes for x in (W, H)])
+    nbytes = int(hip_lib.g4s_depth_align_workspace(len(sizes), c_sizes))
+    assert nbytes >= (65 + 1) * 5 * 8
+    _buf, ws, tail = _canary(nbytes, shift)
+    coeffs = torch.zeros((2, 2), dtype=torch.float32, device=DEV)
+    counts = torch.zeros(2, dtype=torch.int32, device=DEV)
+    rc = hip_lib.g4s_depth_align(dr.DISPARITY, 0, 0.0, len(sizes), c_sizes, _lib.ptrs(src), _lib.ptrs(tgt), _lib.ptrs(msk),
+                                 _lib.ptr(coeffs), _lib.ptr(counts), _lib.ptr(ws), nbytes, _lib.stream(DEV))
+    assert rc == 0, hip_lib.g4s_last_error()
+    torch.cuda.synchronize()
+    assert (tail == 0xA5).all().item(), "bytes behind the advertised workspace were written"
+    _aligned, want_coeffs, want_counts = depth_cues.align_disparities(src, tgt, _devs(masks), "disparity")
+    assert coeffs.cpu().numpy().tobytes() == want_coeffs.cpu().numpy().tobytes() and torch.equal(counts, want_counts)
+    assert np.isfinite(coeffs.cpu().numpy()).all() and counts.cpu().numpy().tolist() == [int(m.sum()) for m in masks]
+
+
+@pytest.mark.parametrize("shift", [0, 1], ids=["aligned", "base+1"])
+def test_plane_depths_workspace_is_enough(hip_lib, golden, id_scene, shift):
+    """g4s_plane_depths keeps its view table, the 142 ids with their planes and the plane rows inside g4s_plane_depths_workspace."""
+    from g4splat_amd import _lib
+    s = id_scene
+    V = len(s.sizes)
+    cams = _cams(golden, s.sizes)
+    view_offset, ids, entry_plane, rows, _keys = depth_cues.plane_table(s.gdict, s.planes, V)
+    assert view_offset[-1] == len(ids) == sum(dr.ID_RUNS) and len(rows) == 5
+    records = np.concatenate([depth_cues.plane_camera_record(c, W, H) for c, (H, W) in zip(cams, s.sizes)])
+    depth, masks = _devs(s.depths), _devs(s.masks)
+    out = [torch.zeros_like(d) for d in depth]
+    counts = torch.full((2, V), -1, dtype=torch.int32, device=DEV)
+    c_sizes = _lib.array(_lib.c_i, [x for H, W in s.sizes for x in (W, H)])
+    nbytes = int(hip_lib.g4s_plane_depths_workspace(V, len(ids), len(rows)))
+    assert nbytes >= 8 * len(ids) + 24 * len(rows)
+    _buf, ws, tail = _canary(nbytes, shift)
+    rc = hip_lib.g4s_plane_depths(V, _lib.array(_lib.c_f, records.tolist()), c_sizes, _lib.ptrs(depth), _lib.ptrs(out), _lib.ptrs(masks),
+                                  _lib.array(_lib.c_i, view_offset), _lib.array(_lib.c_i, ids), _lib.array(_lib.c_i, entry_plane),
+                                  len(rows), _lib.array(_lib.c_f, rows.reshape(-1).tolist()), _lib.ptr(counts), _lib.ptr(ws), nbytes,
+                                  _lib.stream(DEV))
+    assert rc == 0, hip_lib.g4s_last_error()
+    torch.cuda.synchronize()
+    assert (tail == 0xA5).all().item(), "bytes behind the advertised workspace were written"
+    want, replaced, zeroed = depth_cues.apply_global_planes(cams, depth, masks, s.gdict, s.planes)
+    assert torch.equal(counts[0], replaced) and torch.equal(counts[1], zeroed) and int(replaced.sum()) > 0
+    for v in range(V):
+        _same_bits(out[v].cpu().numpy(), want[v].cpu().numpy(), f"plane depth {v}")
 
 
 def _bounded(got, want, bound, keep=None, what=""):
