@@ -20,7 +20,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .mesh import _hip_device, _host_f32
+from ._device import (check_dtype, check_view_count, drop_leading_one, host_f32, launch, mask_bytes, same_device, view_list,
+                      voxel_downsample_count)
 from .visibility import ray_record
 
 
@@ -29,21 +30,15 @@ def _views(maps, name, trailing, dtypes=(torch.float32,), shape=None, n=None):
     """The views of `maps` -- one stacked tensor [V,H,W,*trailing] or a list of [H,W,*trailing] -- as a list of tensors of
     one shape and an accepted dtype (the device is _device's).  Returns (list, (H, W))."""
     tail = "".join(",%d" % t for t in trailing)
-    if isinstance(maps, torch.Tensor):
-        if maps.dim() != 3 + len(trailing):
-            raise ValueError(f"{name}: a stacked tensor must be [V,H,W{tail}] (got {tuple(maps.shape)})")
-        maps = list(maps.unbind(0))
-    maps = list(maps)
-    if n is not None and len(maps) != n:
-        raise ValueError(f"{n} views but {len(maps)} {name}")
+    maps = view_list(maps, name, tail)
+    check_view_count(maps, name, n)
     out = []
     for v, t in enumerate(maps):
         if not isinstance(t, torch.Tensor):
             raise ValueError(f"{name}[{v}] must be a tensor on a HIP device")
-        if t.dtype not in dtypes:
-            raise ValueError(f"{name}[{v}] must be {' or '.join(str(d) for d in dtypes)} (got {t.dtype})")
-        if not trailing and t.dim() == 3 and t.size(0) == 1:
-            t = t[0]
+        check_dtype(t, dtypes, f"{name}[{v}]")
+        if not trailing:
+            t = drop_leading_one(t)
         if t.dim() != 2 + len(trailing) or tuple(t.shape[2:]) != tuple(trailing) or t.numel() == 0:
             raise ValueError(f"{name}[{v}] must be a non-empty [H,W{tail}] map (got {tuple(t.shape)})")
         if shape is None:
@@ -62,18 +57,9 @@ def _device(*groups):
             out.append(None)
             continue
         for v, t in enumerate(maps):
-            if t.device.type != "cuda":
-                raise ValueError(f"{name}[{v}] must be a tensor on a HIP device")
-            if dev is None:
-                dev = _hip_device(t.device)
-            if t.device != dev:
-                raise ValueError(f"{name}[{v}] must be on {dev} (got {t.device})")
+            dev = same_device(t, dev, f"{name}[{v}]")
         out.append([t.detach().contiguous() for t in maps])
     return dev, out
-
-
-def _bytes(mask):
-    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
 
 
 def _empty(dev):
@@ -92,22 +78,18 @@ def _surfels(dev, maps, rays, images, masks, shape, ratio_th, normalized_scales,
     if nbytes == 0:
         raise ValueError(f"{V} views of {H} x {W}: 2 V (H-1)(W-1) must be below 2^31")
     depth_form = 0 if rays is None else 1
-    rays = None if rays is None else _host_f32(rays)
-    with torch.cuda.device(dev):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        st = _lib.stream(dev)
-        count = ctypes.c_int(0)
-        _lib.call("g4s_chart_surfels_count", V, H, W, depth_form, _lib.ptrs(maps), rays,
-                  None if masks is None else _lib.ptrs([_bytes(m) for m in masks]), float(ratio_th), ctypes.byref(count), _lib.ptr(ws),
-                  ws.numel(), st)
-        M = count.value
-        out = {"means": torch.empty((M, 3), dtype=torch.float32, device=dev), "scales": torch.empty((M, 3), dtype=torch.float32, device=dev),
-               "quaternions": torch.empty((M, 4), dtype=torch.float32, device=dev),
-               "colors": torch.empty((M, 3), dtype=torch.float32, device=dev)}
-        _lib.call("g4s_chart_surfels_emit", V, H, W, depth_form, _lib.ptrs(maps), rays, _lib.ptrs(images), float(normalized_scales),
-                  float(normal_scale), M, _lib.ptr(out["means"]), _lib.ptr(out["scales"]), _lib.ptr(out["quaternions"]),
-                  _lib.ptr(out["colors"]), _lib.ptr(ws), ws.numel(), st)
-        torch.cuda.current_stream(dev).synchronize()  # `ws` and contiguous copies may go once the kernels have run
+    rays = None if rays is None else host_f32(rays)
+    count = ctypes.c_int(0)
+    ws = launch(dev, "g4s_chart_surfels_count", V, H, W, depth_form, _lib.ptrs(maps), rays,
+                None if masks is None else _lib.ptrs([mask_bytes(m) for m in masks]), float(ratio_th), ctypes.byref(count),
+                workspace=nbytes)
+    M = count.value
+    out = {"means": torch.empty((M, 3), dtype=torch.float32, device=dev), "scales": torch.empty((M, 3), dtype=torch.float32, device=dev),
+           "quaternions": torch.empty((M, 4), dtype=torch.float32, device=dev),
+           "colors": torch.empty((M, 3), dtype=torch.float32, device=dev)}
+    launch(dev, "g4s_chart_surfels_emit", V, H, W, depth_form, _lib.ptrs(maps), rays, _lib.ptrs(images), float(normalized_scales),
+           float(normal_scale), M, _lib.ptr(out["means"]), _lib.ptr(out["scales"]), _lib.ptr(out["quaternions"]),
+           _lib.ptr(out["colors"]), workspace=ws, sync=True)
     return out
 
 
@@ -174,22 +156,12 @@ def voxel_downsample_gaussians(gaussian_params, voxel_size=0.01):
         raise ValueError("gaussian_params['means'] must be a tensor on a HIP device")
     if means.dtype != torch.float32 or means.dim() != 2 or means.size(1) != 3 or means.size(0) == 0:
         raise ValueError(f"gaussian_params['means'] must be a non-empty float32 [N,3] (got {means.dtype} {tuple(means.shape)})")
-    dev = _hip_device(means.device)
     pts = means.detach().contiguous()
     n = pts.size(0)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        ws = torch.empty(lib.g4s_voxel_downsample_workspace(n), dtype=torch.uint8, device=dev)
-        st = _lib.stream(dev)
-        count = ctypes.c_int(0)
-        rc = lib.g4s_voxel_downsample_count(n, _lib.ptr(pts), float(voxel_size), ctypes.byref(count), _lib.ptr(ws), ws.numel(), st)
-        if rc != 0:
-            raise ValueError(f"voxel_downsample_gaussians: {_lib.last_error()}") if rc == -1 else RuntimeError(
-                f"g4s_voxel_downsample_count failed ({rc}): {_lib.last_error()}")
-        idx = torch.empty(count.value, dtype=torch.int64, device=dev)
-        _lib.call("g4s_voxel_downsample_emit_index", n, count.value, _lib.ptr(idx), _lib.ptr(ws), ws.numel(), st)
-        torch.cuda.current_stream(dev).synchronize()
-    return idx, n / count.value
+    ws, count = voxel_downsample_count(pts, voxel_size, "voxel_downsample_gaussians")
+    idx = torch.empty(count, dtype=torch.int64, device=pts.device)
+    launch(pts.device, "g4s_voxel_downsample_emit_index", n, count, _lib.ptr(idx), workspace=ws, sync=True)
+    return idx, n / count
 
 
 # ---- the trainer's lines -----------------------------------------------------------------------------------------------------

@@ -22,8 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib, planes
-from .mesh import _device_points, _hip_device
-from .visibility import _Views
+from ._device import camera_views, device_points, hip_device, host_array, launch, on_device
 
 MAX_VIEWS_PER_CALL = 4096  # a longer view list of the point solver is passed in chunks
 
@@ -90,10 +89,6 @@ def _same_length(n, **lists):
             raise ValueError(f"{n} cameras but {len(l)} {name}")
 
 
-def _size(views, v):
-    return views.stack.sizes[2 * v + 1], views.stack.sizes[2 * v]  # H, W
-
-
 # ---- A. point solver -------------------------------------------------------------------------------------------------------
 def _view_chunks(n_views, n_input):
     """(lo, hi, input views of the chunk): the whole list if it fits one call, otherwise the input views in chunks and then
@@ -113,37 +108,31 @@ def _solve_points(cameras, depths, images, points, n_input_views, depth_threshol
         raise ValueError(f"n_input_views must be in 0 .. {V} (got {I})")
     if not isinstance(points, torch.Tensor) or not points.dtype.is_floating_point:
         raise RuntimeError("points must be a floating-point tensor on a HIP device")
-    dev, pts = _device_points(points)
+    dev, pts = device_points(points)
     n = pts.size(0)
     lib = _lib.load()
     need_state = n > 0 and (not outputs or I < V)
     state = torch.zeros(max(n, 1), dtype=torch.int32, device=dev) if need_state else None
     for v, d in enumerate(depths):  # every view is checked before the first chunk is launched
-        if not isinstance(d, torch.Tensor) or d.device != dev:
-            raise RuntimeError(f"depth must be a tensor on {dev}")
-        if d.dim() < 2:
+        if on_device(d, dev, "depth").dim() < 2:
             raise RuntimeError(f"depth must be [H,W] or [1,H,W] (got {tuple(d.shape)})")
         H, W = d.shape[-2:]
         images[v] = _check_tensor(images[v], "images", v, dev, torch.float32, ((H, W, 3), (3, H, W)))
     images_out, conf = [], []
     first = True
     for lo, hi, n_in in _view_chunks(V, I):
-        views = _Views(cameras[lo:hi], depths[lo:hi], dev)
+        views = camera_views(cameras[lo:hi], depths[lo:hi], dev)
         imgs, chw, outs, confs = images[lo:hi], [], [], []
         for v in range(lo, hi):
-            H, W = _size(views, v - lo)
+            H, W = views.size(v - lo)
             chw.append(0 if tuple(images[v].shape) == (H, W, 3) else 1)
             if outputs:
                 outs.append(torch.empty((H, W, 3), dtype=torch.float32, device=dev))
                 confs.append(torch.empty((H, W), dtype=torch.uint8, device=dev))
-        with torch.cuda.device(dev):
-            ws = torch.empty(lib.g4s_consistency_points_workspace(views.n, n_in, views.stack.sizes), dtype=torch.uint8,
-                             device=dev)
-            _lib.call("g4s_consistency_points", n, _lib.ptr(pts), float(depth_threshold), views.n, n_in, *views.args[1:],
-                      _lib.ptrs(imgs), _lib.array(_lib.c_i, chw), _lib.ptrs(outs) if outputs else None,
-                      _lib.ptrs(confs) if outputs else None, 0 if first else 1, _lib.ptr(state), _lib.ptr(ws), ws.numel(),
-                      _lib.stream(dev))
-            torch.cuda.current_stream(dev).synchronize()  # the stack's tensors and `ws` may go once the kernels have run
+        launch(dev, "g4s_consistency_points", n, _lib.ptr(pts), float(depth_threshold), views.n, n_in, *views.head[1:],
+               _lib.ptrs(imgs), _lib.array(_lib.c_i, chw), _lib.ptrs(outs) if outputs else None,
+               _lib.ptrs(confs) if outputs else None, 0 if first else 1, _lib.ptr(state),
+               workspace=lib.g4s_consistency_points_workspace(views.n, n_in, views.sizes), sync=True)
         first = False
         images_out += outs
         conf += confs
@@ -188,13 +177,13 @@ def solve_plane_inconsistency(cameras, depths, images, plane_masks, points, glob
         return [], {k: -1 for k in pairs}, torch.zeros((K, A), dtype=torch.int64)
     if not isinstance(depths[0], torch.Tensor):
         raise RuntimeError("depth must be a tensor on a HIP device")
-    dev = _hip_device(depths[0].device)
-    views = _Views(cameras, depths, dev)
+    dev = hip_device(depths[0].device)
+    views = camera_views(cameras, depths, dev)
     imgs, slots, clouds, outs, slot_of = [], [], [], [], []
     for v in range(V):
-        H, W = _size(views, v)
+        H, W = views.size(v)
         imgs.append(_check_tensor(images[v], "images", v, dev, torch.uint8, ((H, W, 3),)))
-        s, ids = planes._slot_mask(plane_masks[v], dev)
+        s, ids = planes.slot_mask(plane_masks[v], dev)
         if tuple(s.shape) != (H, W):
             raise ValueError(f"plane_masks[{v}] must have shape {(H, W)} (got {tuple(s.shape)})")
         slots.append(s)
@@ -213,14 +202,13 @@ def solve_plane_inconsistency(cameras, depths, images, plane_masks, points, glob
             if p in slot_of[v]:  # a plane id the mask does not hold is an empty set
                 slot_plane[slot_offset[v] + slot_of[v][p]] = n
     lib = _lib.load()
-    head = [float(depth_threshold), *views.args, _lib.ptrs(slots), _lib.ptrs(clouds)]
+    head = [float(depth_threshold), *views.head, _lib.ptrs(slots), _lib.ptrs(clouds)]
     offsets = _lib.array(_lib.c_i, slot_offset)
     counts = torch.zeros(max(K * A, 1), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        ws = torch.empty(lib.g4s_consistency_plane_counts_workspace(V, n_slots, A), dtype=torch.uint8, device=dev)
-        _lib.call("g4s_consistency_plane_counts", *head, offsets, _lib.array(_lib.c_i, slot_plane), K, A,
-                  _lib.array(_lib.c_i, anchor_view_ids or [0]), _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream(dev))
-        counts = counts[: K * A].cpu().to(torch.int64).reshape(K, A)  # the one read-back
+    launch(dev, "g4s_consistency_plane_counts", *head, offsets, _lib.array(_lib.c_i, slot_plane), K, A,
+           host_array(_lib.c_i, anchor_view_ids), _lib.ptr(counts),
+           workspace=lib.g4s_consistency_plane_counts_workspace(V, n_slots, A))
+    counts = counts[: K * A].cpu().to(torch.int64).reshape(K, A)  # the one read-back
     anchors = choose_anchor_views(counts.tolist(), anchor_view_ids)
     anchor_of_plane = dict(zip(pairs, anchors))
     slot_step, slot_anchor = [-1] * n_slots, [0] * n_slots
@@ -228,11 +216,7 @@ def solve_plane_inconsistency(cameras, depths, images, plane_masks, points, glob
         if p in slot_of[v]:
             e = slot_offset[v] + slot_of[v][p]
             slot_step[e], slot_anchor[e] = t, a
-    with torch.cuda.device(dev):
-        ws = torch.empty(lib.g4s_consistency_plane_repaint_workspace(V, views.stack.sizes, n_slots), dtype=torch.uint8,
-                         device=dev)
-        _lib.call("g4s_consistency_plane_repaint", *head, _lib.ptrs(imgs), _lib.ptrs(outs), offsets,
-                  _lib.array(_lib.c_i, slot_step), _lib.array(_lib.c_i, slot_anchor), _lib.ptr(ws), ws.numel(),
-                  _lib.stream(dev))
-        torch.cuda.current_stream(dev).synchronize()  # the stack's tensors and `ws` may go once the kernels have run
+    launch(dev, "g4s_consistency_plane_repaint", *head, _lib.ptrs(imgs), _lib.ptrs(outs), offsets,
+           _lib.array(_lib.c_i, slot_step), _lib.array(_lib.c_i, slot_anchor),
+           workspace=lib.g4s_consistency_plane_repaint_workspace(V, views.sizes, n_slots), sync=True)
     return outs, anchor_of_plane, counts

@@ -17,13 +17,12 @@ A camera is anything with world_view_transform, full_proj_transform, FoVx, FoVy 
 read: a view's size is its maps').  Maps are lists of [H_v, W_v] device tensors, or one stacked [V,H,W] tensor; views may
 differ in size.  There is no file I/O.  INTEGRATION.md section P lists the differences from the reference.
 """
-import math
-
 import numpy as np
 import torch
 
 from . import _lib
-from .mesh import _ViewStack, _hip_device, _host_f32, _to_np
+from ._device import (ViewStack, check_dtype, check_view_count, drop_leading_one, focal_lengths, hip_device, host_array, host_f32,
+                      launch, mask_bytes, same_device, to_np, view_list)
 from .visibility import depths_to_points, ray_record
 
 _DOMAINS = {"disparity": 0, "depth": 1, "inverse_source": 2}
@@ -39,31 +38,15 @@ class GeometryCues:
 
 
 # ---- host side: argument checks and tables (no device code: tests/test_depth_cues_cpu.py runs them) -------------------------
-def _map_list(maps, name):
-    if isinstance(maps, torch.Tensor):
-        if maps.dim() != 3:
-            raise ValueError(f"{name}: a stacked tensor must be [V,H,W] (got {tuple(maps.shape)})")
-        return list(maps.unbind(0))
-    return list(maps)
-
-
 def _check_maps(maps, name, dev, dtypes, shapes=None, n=None):
     """The maps as contiguous [H,W] tensors on one HIP device; ValueError for anything else.  Returns (device, list)."""
-    maps = _map_list(maps, name)
-    if n is not None and len(maps) != n:
-        raise ValueError(f"{n} views but {len(maps)} {name}")
+    maps = view_list(maps, name)
+    check_view_count(maps, name, n)
     out = []
     for v, t in enumerate(maps):
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise ValueError(f"{name}[{v}] must be a tensor on a HIP device")
-        if dev is None:
-            dev = _hip_device(t.device)
-        if t.device != dev:
-            raise ValueError(f"{name}[{v}] must be on {dev} (got {t.device})")
-        if t.dtype not in dtypes:
-            raise ValueError(f"{name}[{v}] must be {' or '.join(str(d) for d in dtypes)} (got {t.dtype})")
-        if t.dim() == 3 and t.size(0) == 1:
-            t = t[0]
+        dev = same_device(t, dev, f"{name}[{v}]")
+        check_dtype(t, dtypes, f"{name}[{v}]")
+        t = drop_leading_one(t)
         if t.dim() != 2 or t.numel() == 0:
             raise ValueError(f"{name}[{v}] must be a non-empty [H,W] map (got {tuple(t.shape)})")
         if shapes is not None and tuple(t.shape) != shapes[v]:
@@ -76,26 +59,19 @@ def _shapes(maps):
     return [tuple(t.shape) for t in maps]
 
 
-def _bytes(mask):
-    """A bool or uint8 map as the uint8 the library reads (no copy)."""
-    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
-
-
-def _stack(maps, dev, cameras=None, workspace="g4s_depth_align_apply_workspace"):
-    """mesh._ViewStack over the maps: sizes, the pointer array and the view-table workspace of `workspace`."""
+def _stack(maps, dev, cameras=None):
+    """ViewStack over checked maps: sizes and the pointer array, and with cameras their world_view_transform."""
     if cameras is None:
-        return _ViewStack([(None, m, None) for m in maps], dev, False, 0, lambda cam: [], workspace)
-    return _ViewStack([(c, m, None) for c, m in zip(cameras, maps)], dev, False, 1, lambda cam: [cam.world_view_transform],
-                      workspace)
+        return ViewStack([(None, m, None) for m in maps], dev)
+    return ViewStack([(c, m, None) for c, m in zip(cameras, maps)], dev, False, 1, lambda cam: [cam.world_view_transform])
 
 
 def plane_camera_record(camera, width, height):
     """The fourteen floats of the contract's plane camera: centre o[3], camera -> world rotation R[3][3] row-major (from the
     inverse of world_view_transform, in double), fx = W / (2 tan(FoVx / 2)), fy alike."""
-    wvt = np.asarray(_to_np(camera.world_view_transform), np.float64).reshape(4, 4)
+    wvt = np.asarray(to_np(camera.world_view_transform), np.float64).reshape(4, 4)
     c2w = np.linalg.inv(wvt).T
-    fx = width / (2.0 * math.tan(float(camera.FoVx) / 2.0))
-    fy = height / (2.0 * math.tan(float(camera.FoVy) / 2.0))
+    fx, fy = focal_lengths(camera, width, height)
     return np.concatenate([c2w[:3, 3], c2w[:3, :3].reshape(9), [fx, fy]]).astype(np.float32)
 
 
@@ -117,7 +93,7 @@ def plane_table(global_3Dplane_ID_dict, planes, n_views):
         if key not in planes:
             continue
         normal, centre = planes[key]
-        row = np.concatenate([np.asarray(_to_np(normal), np.float64).reshape(-1), np.asarray(_to_np(centre), np.float64).reshape(-1)])
+        row = np.concatenate([np.asarray(to_np(normal), np.float64).reshape(-1), np.asarray(to_np(centre), np.float64).reshape(-1)])
         with np.errstate(over="ignore"):
             finite = row.shape == (6,) and np.isfinite(row.astype(np.float32)).all()
         if not finite:
@@ -136,10 +112,6 @@ def plane_table(global_3Dplane_ID_dict, planes, n_views):
     return view_offset, ids, entry_plane, plane_rows, keys
 
 
-def _ints(values):
-    return _lib.array(_lib.c_i, list(values) or [0])
-
-
 # ---- A. alignment ----------------------------------------------------------------------------------------------------------
 def _align_coeffs(dev, sources, targets, masks, domain, threshold=None, coeffs=None, counts=None):
     """g4s_depth_align over the views: (coeffs [V,2], counts [V]) on the device.  threshold: `masks` are float maps."""
@@ -149,13 +121,9 @@ def _align_coeffs(dev, sources, targets, masks, domain, threshold=None, coeffs=N
         counts = torch.empty(max(V, 1), dtype=torch.int32, device=dev)
     if V:
         stack = _stack(sources, dev)
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            ws = torch.empty(lib.g4s_depth_align_workspace(V, stack.sizes), dtype=torch.uint8, device=dev)
-            _lib.call("g4s_depth_align", _DOMAINS[domain], 0 if threshold is None else 1,
-                      0.0 if threshold is None else float(threshold), V, stack.sizes, stack.depth, _lib.ptrs(targets),
-                      _lib.ptrs(masks), _lib.ptr(coeffs), _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream(dev))
-            torch.cuda.current_stream(dev).synchronize()  # `ws` and contiguous copies may go once the kernels have run
+        launch(dev, "g4s_depth_align", _DOMAINS[domain], 0 if threshold is None else 1,
+               0.0 if threshold is None else float(threshold), V, stack.sizes, stack.depth, _lib.ptrs(targets), _lib.ptrs(masks),
+               _lib.ptr(coeffs), _lib.ptr(counts), workspace=_lib.load().g4s_depth_align_workspace(V, stack.sizes), sync=True)
     return coeffs[:V], counts[:V]
 
 
@@ -172,13 +140,11 @@ def align_disparities(disps, targets, masks, domain="disparity"):
     _d, masks = _check_maps(masks, "masks", dev, (torch.bool, torch.uint8), _shapes(disps), V)
     if V == 0:
         return [], torch.zeros((0, 2)), torch.zeros(0, dtype=torch.int32)
-    coeffs, counts = _align_coeffs(dev, disps, targets, [_bytes(m) for m in masks], domain)
+    coeffs, counts = _align_coeffs(dev, disps, targets, [mask_bytes(m) for m in masks], domain)
     aligned = [torch.empty_like(d) for d in disps]
     stack = _stack(disps, dev)
-    with torch.cuda.device(dev):
-        _lib.call("g4s_depth_align_apply", _DOMAINS[domain], V, stack.sizes, stack.depth, _lib.ptr(coeffs), _lib.ptrs(aligned),
-                  _lib.ptr(stack.ws), stack.ws.numel(), _lib.stream(dev))
-        torch.cuda.current_stream(dev).synchronize()
+    launch(dev, "g4s_depth_align_apply", _DOMAINS[domain], V, stack.sizes, stack.depth, _lib.ptr(coeffs), _lib.ptrs(aligned),
+           workspace=_lib.load().g4s_depth_align_apply_workspace(V), sync=True)
     return aligned, coeffs, counts
 
 
@@ -220,14 +186,12 @@ def view_geometry_cues(cameras, mono_disps, warp_depths, alphas, visible_thresho
     vis = [torch.empty(d.shape, dtype=torch.bool, device=dev) for d in disps]
     mono, aligned, merged = ([torch.empty_like(d) for d in disps] for _ in range(3))
     nw, nc = ([torch.empty((*d.shape, 3), dtype=torch.float32, device=dev) for d in disps] for _ in range(2))
-    stack = _stack(disps, dev, cameras, "g4s_depth_cue_maps_workspace")
+    stack = _stack(disps, dev, cameras)
     rays = np.concatenate([ray_record(c, d.shape[1], d.shape[0]) for c, d in zip(cameras, disps)])
     n, world_view, sizes, dptr = stack.head
-    with torch.cuda.device(dev):
-        _lib.call("g4s_depth_cue_maps", n, world_view, _host_f32(rays), sizes, dptr, _lib.ptrs(warps), _lib.ptrs(alphas), threshold,
-                  _lib.ptr(coeffs), _lib.ptrs([_bytes(m) for m in vis]), _lib.ptrs(mono), _lib.ptrs(aligned), _lib.ptrs(merged),
-                  _lib.ptrs(nw), _lib.ptrs(nc), _lib.ptr(stack.ws), stack.ws.numel(), _lib.stream(dev))
-        torch.cuda.current_stream(dev).synchronize()
+    launch(dev, "g4s_depth_cue_maps", n, world_view, host_f32(rays), sizes, dptr, _lib.ptrs(warps), _lib.ptrs(alphas), threshold,
+           _lib.ptr(coeffs), _lib.ptrs([mask_bytes(m) for m in vis]), _lib.ptrs(mono), _lib.ptrs(aligned), _lib.ptrs(merged),
+           _lib.ptrs(nw), _lib.ptrs(nc), workspace=_lib.load().g4s_depth_cue_maps_workspace(n), sync=True)
     return GeometryCues(visibility=vis, mono_depth=mono, aligned_depth=aligned, depth=merged, normal_world=nw, normal_cam=nc,
                         coeffs=coeffs, counts=counts)
 
@@ -252,13 +216,10 @@ def apply_global_planes(cameras, depths, plane_masks, global_3Dplane_ID_dict, pl
     out = [torch.empty_like(d) for d in depths]
     counts = torch.empty((2, V), dtype=torch.int32, device=dev)
     stack = _stack(depths, dev)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        ws = torch.empty(lib.g4s_plane_depths_workspace(V, len(ids), len(rows)), dtype=torch.uint8, device=dev)
-        _lib.call("g4s_plane_depths", V, _host_f32(records), stack.sizes, stack.depth, _lib.ptrs(out), _lib.ptrs(masks),
-                  _ints(view_offset), _ints(ids), _ints(entry_plane), len(rows), _host_f32(rows.reshape(-1) if len(rows) else [0.0]),
-                  _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream(dev))
-        torch.cuda.current_stream(dev).synchronize()
+    launch(dev, "g4s_plane_depths", V, host_f32(records), stack.sizes, stack.depth, _lib.ptrs(out), _lib.ptrs(masks),
+           host_array(_lib.c_i, view_offset), host_array(_lib.c_i, ids), host_array(_lib.c_i, entry_plane), len(rows),
+           host_array(_lib.c_f, rows.reshape(-1).tolist()), _lib.ptr(counts),
+           workspace=_lib.load().g4s_plane_depths_workspace(V, len(ids), len(rows)), sync=True)
     return out, counts[0], counts[1]
 
 
@@ -269,7 +230,7 @@ def plane_aligned_depth(plane_normal, plane_center, camera, img_shape):
     H, W = (int(s) for s in img_shape)
     if H <= 0 or W <= 0:
         raise ValueError(f"img_shape must be positive (got {tuple(img_shape)})")
-    dev = _hip_device(plane_normal.device if isinstance(plane_normal, torch.Tensor) and plane_normal.is_cuda else "cuda")
+    dev = hip_device(plane_normal.device if isinstance(plane_normal, torch.Tensor) and plane_normal.is_cuda else "cuda")
     depth = torch.zeros((H, W), dtype=torch.float32, device=dev)
     mask = torch.ones((H, W), dtype=torch.int32, device=dev)
     out, _replaced, _zeroed = apply_global_planes([camera], [depth], [mask], {0: [(0, 1)]}, {0: (plane_normal, plane_center)})
@@ -284,14 +245,12 @@ def _refill(dev, depths, monos, masks, confs, n_input):
     counts = torch.zeros(V, dtype=torch.int32, device=dev)
     if n_input == V:
         return coeffs, counts
-    confs8 = [_bytes(c) for c in confs]
+    confs8 = [mask_bytes(c) for c in confs]
     _align_coeffs(dev, monos[n_input:], depths[n_input:], confs8[n_input:], "inverse_source", None, coeffs[n_input:],
                   counts[n_input:])
-    stack = _stack(monos, dev, None, "g4s_depth_refill_workspace")
-    with torch.cuda.device(dev):
-        _lib.call("g4s_depth_refill", V, n_input, stack.sizes, _lib.ptrs(depths), stack.depth, _lib.ptrs(masks),
-                  _lib.ptrs(confs8), _lib.ptr(coeffs), _lib.ptr(stack.ws), stack.ws.numel(), _lib.stream(dev))
-        torch.cuda.current_stream(dev).synchronize()
+    stack = _stack(monos, dev)
+    launch(dev, "g4s_depth_refill", V, n_input, stack.sizes, _lib.ptrs(depths), stack.depth, _lib.ptrs(masks), _lib.ptrs(confs8),
+           _lib.ptr(coeffs), workspace=_lib.load().g4s_depth_refill_workspace(V), sync=True)
     return coeffs, counts
 
 

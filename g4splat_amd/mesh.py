@@ -33,6 +33,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._device import ViewStack, default_device, device_points, hip_device, host_f32, launch, on_device, to_np
 
 VOXELS_PER_BLOCK = 512
 
@@ -49,17 +50,11 @@ class DeviceMesh(NamedTuple):
     triangles: torch.Tensor      # [F,3] int32, indices into vertices
 
 
-def _to_np(x):
-    if isinstance(x, torch.Tensor):
-        return x.detach().cpu().numpy()
-    return np.asarray(x)
-
-
 def _projection_matrix(camera):
     """The camera's projection_matrix (row-vector convention, = Proj^T), or the one of its FoV and clip planes."""
     pm = getattr(camera, "projection_matrix", None)
     if pm is not None:
-        return _to_np(pm).astype(np.float32)
+        return to_np(pm).astype(np.float32)
     from .synthetic import projection_matrix
     return projection_matrix(getattr(camera, "znear", 0.01), getattr(camera, "zfar", 100.0), camera.FoVx,
                              camera.FoVy).T.astype(np.float32)
@@ -76,12 +71,7 @@ def camera_intrinsics(camera):
 
 def camera_extrinsic(camera):
     """world -> camera 4x4, = world_view_transform.T (mesh_utils.py:62)."""
-    return np.ascontiguousarray(_to_np(camera.world_view_transform).astype(np.float32).T)
-
-
-def _host_f32(a):
-    a = np.ascontiguousarray(a, np.float32).reshape(-1)
-    return (ctypes.c_float * len(a))(*a.tolist())
+    return np.ascontiguousarray(to_np(camera.world_view_transform).astype(np.float32).T)
 
 
 class TSDFVolume:
@@ -131,39 +121,32 @@ class TSDFVolume:
         depth = self._map(depth, (H, W), "depth")
         rgb = self._map(rgb, (3, H, W), "rgb")
         mask = None if mask is None else self._map(mask, (H, W), "mask")
-        intr, ext = _host_f32(camera_intrinsics(camera)), _host_f32(camera_extrinsic(camera))
+        intr, ext = host_f32(camera_intrinsics(camera)), host_f32(camera_extrinsic(camera))
         v, T, D = self.voxel_size, self.sdf_trunc, self.depth_trunc
         cap = lib.g4s_tsdf_blocks_per_pixel(W, H, intr, v, T)
         if cap < 0:
             raise RuntimeError(f"g4s_tsdf_blocks_per_pixel failed ({cap}): {_lib.last_error()}")
-        with torch.cuda.device(self.device):
-            nws = lib.g4s_tsdf_workspace(W, H, cap, 0)
-            ws = self._workspace(nws)
-            st = _lib.stream(self.device)
-            counts = (ctypes.c_int * 2)()
-            _lib.call("g4s_tsdf_alloc_count", W, H, _lib.ptr(depth), _lib.ptr(mask), intr, ext, v, T, D, cap,
-                      _lib.ptr(self.keys), self.num_blocks, counts, _lib.ptr(ws), ws.numel(), st)
-            m, n_new = counts[0], counts[1]
-            n = self.num_blocks + n_new
-            if n > self.pool_blocks:  # capacity is decided here, before anything is written
-                self._grow(n)
-            if m > 0:  # the merge writes the new table and gives every touched block its slot
-                keys = torch.empty(n, dtype=torch.int64, device=self.device)
-                slots = torch.empty(n, dtype=torch.int32, device=self.device)
-                _lib.call("g4s_tsdf_merge", W, H, cap, _lib.ptr(self.keys), _lib.ptr(self.slots), self.num_blocks, m, n_new,
-                          _lib.ptr(keys), _lib.ptr(slots), _lib.ptr(self.tsdf), _lib.ptr(self.weight), _lib.ptr(self.color),
-                          self.pool_blocks, _lib.ptr(ws), ws.numel(), st)
-                self.keys, self.slots, self.num_blocks = keys, slots, n
-            if m > 0:
-                _lib.call("g4s_tsdf_integrate", W, H, _lib.ptr(depth), _lib.ptr(mask), _lib.ptr(rgb), intr, ext, v, T, D,
-                          cap, m, _lib.ptr(self.tsdf), _lib.ptr(self.weight), _lib.ptr(self.color), self.pool_blocks,
-                          _lib.ptr(ws), ws.numel(), st)
+        dev, ws = self.device, self._workspace(lib.g4s_tsdf_workspace(W, H, cap, 0))
+        counts = (ctypes.c_int * 2)()
+        launch(dev, "g4s_tsdf_alloc_count", W, H, _lib.ptr(depth), _lib.ptr(mask), intr, ext, v, T, D, cap, _lib.ptr(self.keys),
+               self.num_blocks, counts, workspace=ws)
+        m, n_new = counts[0], counts[1]
+        n = self.num_blocks + n_new
+        if n > self.pool_blocks:  # capacity is decided here, before anything is written
+            self._grow(n)
+        if m > 0:  # the merge writes the new table and gives every touched block its slot
+            keys = torch.empty(n, dtype=torch.int64, device=dev)
+            slots = torch.empty(n, dtype=torch.int32, device=dev)
+            launch(dev, "g4s_tsdf_merge", W, H, cap, _lib.ptr(self.keys), _lib.ptr(self.slots), self.num_blocks, m, n_new,
+                   _lib.ptr(keys), _lib.ptr(slots), _lib.ptr(self.tsdf), _lib.ptr(self.weight), _lib.ptr(self.color),
+                   self.pool_blocks, workspace=ws)
+            self.keys, self.slots, self.num_blocks = keys, slots, n
+            launch(dev, "g4s_tsdf_integrate", W, H, _lib.ptr(depth), _lib.ptr(mask), _lib.ptr(rgb), intr, ext, v, T, D, cap, m,
+                   _lib.ptr(self.tsdf), _lib.ptr(self.weight), _lib.ptr(self.color), self.pool_blocks, workspace=ws)
         return m, n_new
 
     def _map(self, t, shape, name):
-        if not isinstance(t, torch.Tensor) or t.device != self.device:
-            raise RuntimeError(f"{name} must be a tensor on {self.device}")
-        t = t.detach()
+        t = on_device(t, self.device, name)
         if t.dim() == len(shape) + 1 and t.size(0) == 1:
             t = t[0]
         if tuple(t.shape) != tuple(shape):
@@ -191,23 +174,18 @@ class TSDFVolume:
             if not to_host:
                 return _empty_device_mesh(self.device)
             return TriangleMesh(np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32))
-        with torch.cuda.device(self.device):
-            nws = lib.g4s_tsdf_workspace(0, 0, 0, n)
-            ws = self._workspace(nws)
-            st = _lib.stream(self.device)
-            totals = (ctypes.c_int * 2)()
-            _lib.call("g4s_tsdf_extract_count", _lib.ptr(self.keys), _lib.ptr(self.slots), n, _lib.ptr(self.tsdf),
-                      _lib.ptr(self.weight), self.pool_blocks, totals, _lib.ptr(ws), ws.numel(), st)
-            V, F = totals[0], totals[1]
-            verts = torch.empty((max(V, 1), 3), dtype=torch.float32, device=self.device)
-            cols = torch.empty_like(verts)
-            tris = torch.empty((max(F, 1), 3), dtype=torch.int32, device=self.device)
-            _lib.call("g4s_tsdf_extract_emit", _lib.ptr(self.keys), _lib.ptr(self.slots), n, _lib.ptr(self.tsdf),
-                      _lib.ptr(self.weight), _lib.ptr(self.color), self.pool_blocks, self.voxel_size, _lib.ptr(verts),
-                      _lib.ptr(cols), _lib.ptr(tris), V, F, _lib.ptr(ws), ws.numel(), st)
-            if not to_host:
-                return DeviceMesh(verts[:V], cols[:V], tris[:F])
-            return TriangleMesh(verts[:V].cpu().numpy(), cols[:V].cpu().numpy(), tris[:F].cpu().numpy())
+        dev, ws = self.device, self._workspace(lib.g4s_tsdf_workspace(0, 0, 0, n))
+        totals = (ctypes.c_int * 2)()
+        launch(dev, "g4s_tsdf_extract_count", _lib.ptr(self.keys), _lib.ptr(self.slots), n, _lib.ptr(self.tsdf),
+               _lib.ptr(self.weight), self.pool_blocks, totals, workspace=ws)
+        V, F = totals[0], totals[1]
+        verts = torch.empty((max(V, 1), 3), dtype=torch.float32, device=dev)
+        cols = torch.empty_like(verts)
+        tris = torch.empty((max(F, 1), 3), dtype=torch.int32, device=dev)
+        launch(dev, "g4s_tsdf_extract_emit", _lib.ptr(self.keys), _lib.ptr(self.slots), n, _lib.ptr(self.tsdf),
+               _lib.ptr(self.weight), _lib.ptr(self.color), self.pool_blocks, self.voxel_size, _lib.ptr(verts), _lib.ptr(cols),
+               _lib.ptr(tris), V, F, workspace=ws)
+        return _returned(DeviceMesh(verts[:V], cols[:V], tris[:F]), to_host)
 
 
 # ---- mesh operations (include/g4s_render_maps.h, "mesh operations"; csrc/tsdf/mesh_ops.hip) ---------------------------
@@ -216,13 +194,7 @@ def _empty_device_mesh(device):
     return DeviceMesh(z, z.clone(), torch.zeros((0, 3), dtype=torch.int32, device=device))
 
 
-def _default_device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("mesh operations need a HIP device (there is no CPU path)")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _as_device_mesh(mesh, device=None):
+def as_device_mesh(mesh, device=None):
     """(DeviceMesh, was_host): a TriangleMesh is uploaded (to `device` or the current HIP device)."""
     if isinstance(mesh, DeviceMesh):
         dev = mesh.vertices.device
@@ -230,7 +202,7 @@ def _as_device_mesh(mesh, device=None):
             raise RuntimeError("a DeviceMesh lives on one HIP device")
         host = False
     else:
-        dev = torch.device(device) if device is not None else _default_device()
+        dev = torch.device(device) if device is not None else default_device()
         host = True
     v = torch.as_tensor(np.ascontiguousarray(mesh.vertices, np.float32) if host else mesh.vertices, device=dev)
     c = torch.as_tensor(np.ascontiguousarray(mesh.vertex_colors, np.float32) if host else mesh.vertex_colors, device=dev)
@@ -260,20 +232,17 @@ def compact_mesh(mesh, keep=None, compact_vertices=True):
     v, c, t = mesh
     dev = v.device
     V, F = v.size(0), t.size(0)
-    with torch.cuda.device(dev):
-        ws = torch.empty(lib.g4s_mesh_compact_workspace(V, F), dtype=torch.uint8, device=dev)
-        st = _lib.stream(dev)
-        totals = (ctypes.c_int * 2)()
-        _lib.call("g4s_mesh_compact_count", V, F, _lib.ptr(t), _lib.ptr(keep), int(compact_vertices), totals, _lib.ptr(ws),
-                  ws.numel(), st)
-        Vo, Fo = totals[0], totals[1]
-        to = torch.empty((max(Fo, 1), 3), dtype=torch.int32, device=dev)
-        vo = co = None
-        if compact_vertices:
-            vo = torch.empty((max(Vo, 1), 3), dtype=torch.float32, device=dev)
-            co = torch.empty_like(vo)
-        _lib.call("g4s_mesh_compact_emit", V, F, _lib.ptr(v), _lib.ptr(c), _lib.ptr(t), int(compact_vertices), _lib.ptr(vo),
-                  _lib.ptr(co), _lib.ptr(to), Vo, Fo, _lib.ptr(ws), ws.numel(), st)
+    totals = (ctypes.c_int * 2)()
+    ws = launch(dev, "g4s_mesh_compact_count", V, F, _lib.ptr(t), _lib.ptr(keep), int(compact_vertices), totals,
+                workspace=lib.g4s_mesh_compact_workspace(V, F))
+    Vo, Fo = totals[0], totals[1]
+    to = torch.empty((max(Fo, 1), 3), dtype=torch.int32, device=dev)
+    vo = co = None
+    if compact_vertices:
+        vo = torch.empty((max(Vo, 1), 3), dtype=torch.float32, device=dev)
+        co = torch.empty_like(vo)
+    launch(dev, "g4s_mesh_compact_emit", V, F, _lib.ptr(v), _lib.ptr(c), _lib.ptr(t), int(compact_vertices), _lib.ptr(vo),
+           _lib.ptr(co), _lib.ptr(to), Vo, Fo, workspace=ws)
     if compact_vertices:
         return DeviceMesh(vo[:Vo], co[:Vo], to[:Fo])
     return DeviceMesh(v, c, to[:Fo])
@@ -297,7 +266,7 @@ def observed_face_mask(mesh, cameras, near_trunc):
     wv, fp = _camera_matrices(cameras, dev)
     observed = _keep_mask(V, dev)
     keep = _keep_mask(F, dev)
-    with torch.cuda.device(dev):
+    with torch.cuda.device(dev):  # these entry points take a stream and no workspace
         st = _lib.stream(dev)
         _lib.call("g4s_mesh_observed_vertices", V, _lib.ptr(v), wv.size(0), _lib.ptr(wv), _lib.ptr(fp), float(near_trunc),
                   _lib.ptr(observed), st)
@@ -307,7 +276,7 @@ def observed_face_mask(mesh, cameras, near_trunc):
 
 def cull_observed_faces(mesh, cameras, near_trunc):
     """Drop the faces a finer level already covers (observed_face_mask), then the vertices nothing names any more."""
-    dm, host = _as_device_mesh(mesh)
+    dm, host = as_device_mesh(mesh)
     return _returned(compact_mesh(dm, observed_face_mask(dm, cameras, near_trunc)), host)
 
 
@@ -340,17 +309,15 @@ def _cluster(dm):
     dev, F = t.device, t.size(0)
     labels = torch.empty(max(F, 1), dtype=torch.int32, device=dev)
     sizes = torch.empty_like(labels)
-    with torch.cuda.device(dev):
-        ws = torch.empty(lib.g4s_mesh_cluster_workspace(F), dtype=torch.uint8, device=dev)
-        _lib.call("g4s_mesh_cluster_triangles", F, _lib.ptr(t), _lib.ptr(labels), _lib.ptr(sizes), _lib.ptr(ws), ws.numel(),
-                  _lib.stream(dev))
+    launch(dev, "g4s_mesh_cluster_triangles", F, _lib.ptr(t), _lib.ptr(labels), _lib.ptr(sizes),
+           workspace=lib.g4s_mesh_cluster_workspace(F))
     return labels[:F], sizes[:F]
 
 
 def cluster_connected_triangles(mesh):
     """(labels [F], sizes [F]) int32: the smallest triangle index of each triangle's edge-connected cluster and that
     cluster's triangle count (open3d returns dense cluster numbers and per-cluster counts: the same partition)."""
-    dm, host = _as_device_mesh(mesh)
+    dm, host = as_device_mesh(mesh)
     labels, sizes = _cluster(dm)
     return (labels.cpu().numpy(), sizes.cpu().numpy()) if host else (labels, sizes)
 
@@ -361,7 +328,7 @@ def post_process_mesh(mesh, cluster_to_keep=1000):
     cluster_to_keep the reference raises IndexError; here the smallest cluster size stands in for the k-th largest."""
     if cluster_to_keep < 1:
         raise ValueError("cluster_to_keep must be at least 1")
-    dm, host = _as_device_mesh(mesh)
+    dm, host = as_device_mesh(mesh)
     dev, F = dm.triangles.device, dm.triangles.size(0)
     if F == 0:
         return _returned(compact_mesh(dm), host)
@@ -382,7 +349,7 @@ def post_process_mesh(mesh, cluster_to_keep=1000):
 
 def filter_mesh(mesh, length_threshold=0.05):
     """utils/mesh_filter.py:6-32: drop the faces with an edge longer than length_threshold, then unreferenced vertices."""
-    dm, host = _as_device_mesh(mesh)
+    dm, host = as_device_mesh(mesh)
     dev, F = dm.triangles.device, dm.triangles.size(0)
     keep = _keep_mask(F, dev)
     with torch.cuda.device(dev):
@@ -391,86 +358,35 @@ def filter_mesh(mesh, length_threshold=0.05):
     return _returned(compact_mesh(dm, keep), host)
 
 
-# ---- the view stack of the unbounded and the tetrahedral extraction (csrc/tsdf/view_stack.h)
-class _ViewStack:
-    """The host arrays the utsdf / atsdf entry points take, and the device tensors they point into (kept alive here).
-    views: (camera, depth [H,W] / [1,H,W], rgb [3,H,W] or None) per view, maps on `device`.  matrices(camera) gives the
-    n_matrices 4x4 the field reads per view; workspace names the entry point that sizes the view table."""
-
-    def __init__(self, views, device, need_rgb, n_matrices, matrices, workspace):
-        self.maps, sizes, dptr, cptr = [], [], [], []
-        mats = [[] for _ in range(n_matrices)]
-        for cam, depth, rgb in views:
-            for m, M in zip(mats, matrices(cam)):
-                m.extend(np.asarray(_to_np(M), np.float32).reshape(16).tolist())
-            depth = self._map(depth, device, "depth")
-            if depth.dim() == 3 and depth.size(0) == 1:
-                depth = depth[0]
-            if depth.dim() != 2:
-                raise RuntimeError(f"depth must be [H,W] or [1,H,W] (got {tuple(depth.shape)})")
-            H, W = depth.shape
-            depth = depth.contiguous()
-            self.maps.append(depth)
-            dptr.append(depth.data_ptr())
-            if need_rgb:
-                if rgb is None:
-                    raise RuntimeError("colours need the rgb map of every view")
-                rgb = self._map(rgb, device, "rgb").contiguous()
-                if tuple(rgb.shape) != (3, H, W):
-                    raise RuntimeError(f"rgb must have shape {(3, H, W)} (got {tuple(rgb.shape)})")
-                self.maps.append(rgb)
-                cptr.append(rgb.data_ptr())
-            sizes.extend([W, H])
-        self.n = len(dptr)
-        self.sizes = (ctypes.c_int * max(len(sizes), 1))(*sizes)
-        self.depth = (ctypes.c_void_p * max(self.n, 1))(*dptr)
-        self.rgb = (ctypes.c_void_p * max(self.n, 1))(*cptr) if need_rgb else None
-        # the run of arguments every entry point has: n_views, the matrices, sizes, depth
-        self.head = [self.n] + [(ctypes.c_float * max(len(m), 1))(*m) for m in mats] + [self.sizes, self.depth]
-        self.ws = torch.empty(getattr(_lib.load(), workspace)(self.n), dtype=torch.uint8, device=device)
-
-    @staticmethod
-    def _map(t, device, name):
-        if not isinstance(t, torch.Tensor) or t.device != device:
-            raise RuntimeError(f"{name} must be a tensor on {device}")
-        return t.detach().float()
-
-
+# ---- the views of the unbounded and the tetrahedral extraction (_device.ViewStack; csrc/tsdf/view_stack.h)
 def _view_and_projection(cam):
     Wv, Pm = (cam.world_view_transform, _projection_matrix(cam)) if hasattr(cam, "world_view_transform") else cam
     return Wv, Pm
 
 
-# The two fields' (n_matrices, matrices, workspace) of _ViewStack.  In place of a camera the unbounded field takes the bare
-# 4x4 full_proj_transform and the adaptive one the pair (world_view_transform, projection_matrix) of 4x4.
+# The two fields' (n_matrices, matrices) of ViewStack and the query that sizes their view table.  In place of a camera the
+# unbounded field takes the bare 4x4 full_proj_transform and the adaptive one the pair (world_view_transform,
+# projection_matrix) of 4x4.
 _UTSDF_VIEWS = (1, lambda cam: [getattr(cam, "full_proj_transform", cam)], "g4s_utsdf_workspace")
 _ATSDF_VIEWS = (2, _view_and_projection, "g4s_atsdf_workspace")
 
 
-def _hip_device(device):
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("the mesh kernels need tensors on a HIP device (there is no CPU path)")
-    return torch.device("cuda", torch.cuda.current_device() if device.index is None else device.index)
-
-
-def _device_points(points, what="points"):
-    if not isinstance(points, torch.Tensor):
-        raise RuntimeError(f"{what} must be a tensor on a HIP device")
-    return _hip_device(points.device), points.detach().float().reshape(-1, 3).contiguous()
+def _field_views(views, dev, need_rgb, field):
+    """(ViewStack, bytes of its view table) of one of the two fields."""
+    n_matrices, matrices, query = field
+    stack = ViewStack(views, dev, need_rgb, n_matrices, matrices)
+    return stack, getattr(_lib.load(), query)(stack.n)
 
 
 def _sample_views(entry, field, points, views, return_rgb, *field_args):
     """One g4s_*tsdf_sample call: tsdf [n] of `views` at points [n,3], and with return_rgb (tsdf, colour [n,3])."""
-    dev, pts = _device_points(points)
+    dev, pts = device_points(points)
     n = pts.size(0)
-    stack = _ViewStack(views, dev, return_rgb, *field)
+    stack, nbytes = _field_views(views, dev, return_rgb, field)
     tsdf = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
     col = torch.empty((max(n, 1), 3), dtype=torch.float32, device=dev) if return_rgb else None
-    with torch.cuda.device(dev):
-        _lib.call(entry, n, _lib.ptr(pts), *field_args, *stack.head, stack.rgb, _lib.ptr(tsdf), _lib.ptr(col),
-                  _lib.ptr(stack.ws), stack.ws.numel(), _lib.stream(dev))
-        torch.cuda.current_stream(dev).synchronize()  # the stack's tensors may go once the kernel has run
+    launch(dev, entry, n, _lib.ptr(pts), *field_args, *stack.head, stack.rgb, _lib.ptr(tsdf), _lib.ptr(col), workspace=nbytes,
+           sync=True)
     return (tsdf[:n], col[:n]) if return_rgb else tsdf[:n]
 
 
@@ -480,22 +396,20 @@ def unbounded_tsdf(points, views, center, radius, voxel_size, contracted=True, r
     points of the contracted, normalised space (contracted=True; center, radius map them to the world) or world points
     (contracted=False).  Returns tsdf [n], and with return_rgb (tsdf, colour [n,3])."""
     return _sample_views("g4s_utsdf_sample", _UTSDF_VIEWS, points, views, return_rgb, int(bool(contracted)),
-                         _host_f32(_to_np(center)), float(radius), float(voxel_size))
+                         host_f32(to_np(center)), float(radius), float(voxel_size))
 
 
 def unbounded_tsdf_grid(resolution, R, views, center, radius, voxel_size, device=None):
     """g4s_utsdf_grid: the same evaluation at the resolution^3 lattice over [-R, R]^3 of the contracted space, generated in
     the kernel; returns tsdf [resolution^3] (x fastest) on the device."""
-    dev = _hip_device(device if device is not None else _default_device())
+    dev = hip_device(device if device is not None else default_device())
     N = int(resolution)
     if N < 2 or N ** 3 >= 2 ** 31:
         raise ValueError("resolution must be at least 2 and resolution^3 below 2^31")
-    stack = _ViewStack(views, dev, False, *_UTSDF_VIEWS)
+    stack, nbytes = _field_views(views, dev, False, _UTSDF_VIEWS)
     tsdf = torch.empty(N ** 3, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.call("g4s_utsdf_grid", N, float(R), _host_f32(_to_np(center)), float(radius), float(voxel_size), *stack.head,
-                  _lib.ptr(tsdf), _lib.ptr(stack.ws), stack.ws.numel(), _lib.stream(dev))
-        torch.cuda.current_stream(dev).synchronize()
+    launch(dev, "g4s_utsdf_grid", N, float(R), host_f32(to_np(center)), float(radius), float(voxel_size), *stack.head,
+           _lib.ptr(tsdf), workspace=nbytes, sync=True)
     return tsdf
 
 
@@ -504,25 +418,21 @@ def dense_marching_cubes(tsdf, R, center, radius, max_range=32.0, to_host=True):
     over [-R, R]^3: (vertices [V,3] world, clamped to +-max_range; triangles [F,3] int32), numpy or -- to_host=False --
     device tensors.  A field without a sign change gives (0,3) arrays."""
     if not isinstance(tsdf, torch.Tensor):
-        tsdf = torch.as_tensor(np.ascontiguousarray(tsdf, np.float32), device=_default_device())
-    dev = _hip_device(tsdf.device)
+        tsdf = torch.as_tensor(np.ascontiguousarray(tsdf, np.float32), device=default_device())
+    dev = hip_device(tsdf.device)
     f = tsdf.detach().float().contiguous().reshape(-1)
     N = round(f.numel() ** (1.0 / 3.0))
     if N ** 3 != f.numel() or N < 2 or N ** 3 >= 2 ** 31:
         raise ValueError("tsdf must hold N^3 values, N at least 2 and N^3 below 2^31")
     lib = _lib.load()
-    c = _host_f32(_to_np(center))
-    with torch.cuda.device(dev):
-        ws = torch.empty(lib.g4s_dense_mc_workspace(N), dtype=torch.uint8, device=dev)
-        st = _lib.stream(dev)
-        totals = (ctypes.c_int * 2)()
-        _lib.call("g4s_dense_mc_count", N, _lib.ptr(f), totals, _lib.ptr(ws), ws.numel(), st)
-        V, F = totals[0], totals[1]
-        verts = torch.empty((max(V, 1), 3), dtype=torch.float32, device=dev)
-        tris = torch.empty((max(F, 1), 3), dtype=torch.int32, device=dev)
-        _lib.call("g4s_dense_mc_emit", N, _lib.ptr(f), float(R), c, float(radius), float(max_range), _lib.ptr(verts),
-                  _lib.ptr(tris), V, F, _lib.ptr(ws), ws.numel(), st)
-        torch.cuda.current_stream(dev).synchronize()  # `ws` is released on return
+    c = host_f32(to_np(center))
+    totals = (ctypes.c_int * 2)()
+    ws = launch(dev, "g4s_dense_mc_count", N, _lib.ptr(f), totals, workspace=lib.g4s_dense_mc_workspace(N))
+    V, F = totals[0], totals[1]
+    verts = torch.empty((max(V, 1), 3), dtype=torch.float32, device=dev)
+    tris = torch.empty((max(F, 1), 3), dtype=torch.int32, device=dev)
+    launch(dev, "g4s_dense_mc_emit", N, _lib.ptr(f), float(R), c, float(radius), float(max_range), _lib.ptr(verts),
+           _lib.ptr(tris), V, F, workspace=ws, sync=True)
     if to_host:
         return verts[:V].cpu().numpy(), tris[:F].cpu().numpy()
     return verts[:V], tris[:F]
@@ -564,7 +474,7 @@ def marching_tetrahedra(points, tets, sdf):
     """g4s_mtet_count / g4s_mtet_emit (utils/tetmesh.py:97-138): tets [T,4] over points [n,3] with the field sdf [n]
     (occupied: sdf > 0), all device tensors.  Returns (edges [E,2] int32: the crossing edges (lo, hi) in ascending order --
     vertex i of the mesh lies on edge i --, faces [F,3] int32 in tet order).  No crossing: (0,2) and (0,3) tensors."""
-    dev, pts = _device_points(points)
+    dev, pts = device_points(points)
     n = pts.size(0)
     tets = _index_rows(tets, 4, "tets", "[T,4]", sdf, dev)
     f = _point_sdf(sdf, n)
@@ -575,37 +485,30 @@ def marching_tetrahedra(points, tets, sdf):
     if tets.data_ptr() % 16:  # a view at an odd offset: the kernels read a tet as one 16-byte row
         tets = tets.clone()
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        ws = torch.empty(lib.g4s_mtet_workspace(T), dtype=torch.uint8, device=dev)
-        st = _lib.stream(dev)
-        totals = (ctypes.c_int * 2)()
-        _lib.call("g4s_mtet_count", n, T, _lib.ptr(tets), _lib.ptr(f), totals, _lib.ptr(ws), ws.numel(), st)
-        E, F = totals[0], totals[1]
-        edges = torch.empty((max(E, 1), 2), dtype=torch.int32, device=dev)
-        faces = torch.empty((max(F, 1), 3), dtype=torch.int32, device=dev)
-        _lib.call("g4s_mtet_emit", n, T, _lib.ptr(tets), _lib.ptr(f), _lib.ptr(edges), _lib.ptr(faces), E, F, _lib.ptr(ws),
-                  ws.numel(), st)
-        torch.cuda.current_stream(dev).synchronize()  # `ws` is released on return
+    totals = (ctypes.c_int * 2)()
+    ws = launch(dev, "g4s_mtet_count", n, T, _lib.ptr(tets), _lib.ptr(f), totals, workspace=lib.g4s_mtet_workspace(T))
+    E, F = totals[0], totals[1]
+    edges = torch.empty((max(E, 1), 2), dtype=torch.int32, device=dev)
+    faces = torch.empty((max(F, 1), 3), dtype=torch.int32, device=dev)
+    launch(dev, "g4s_mtet_emit", n, T, _lib.ptr(tets), _lib.ptr(f), _lib.ptr(edges), _lib.ptr(faces), E, F, workspace=ws,
+           sync=True)
     return edges[:E], faces[:F]
 
 
 def bisect_surface(points, edges, sdf, views, trunc_margin, steps=8, znear=1e-6, zfar=1e6):
     """g4s_atsdf_bisect (extract_mesh_adaptive_tsdf.py:319-349): every crossing edge of marching_tetrahedra bisected `steps`
     times against the field of `views`, all steps in one launch.  Returns vertices [E,3] on the device."""
-    dev, pts = _device_points(points)
+    dev, pts = device_points(points)
     n = pts.size(0)
     e = _rows_in_range(_index_rows(edges, 2, "edges", "[E,2]", sdf, dev), "edges", n)
     E = e.size(0)
     f = _point_sdf(sdf, n)
     if not 0 <= int(steps) <= 64:
         raise ValueError("steps must be in 0 .. 64")
-    stack = _ViewStack(views, dev, False, *_ATSDF_VIEWS)
+    stack, nbytes = _field_views(views, dev, False, _ATSDF_VIEWS)
     verts = torch.empty((max(E, 1), 3), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.call("g4s_atsdf_bisect", E, _lib.ptr(e), n, _lib.ptr(pts), _lib.ptr(f), int(steps), float(trunc_margin),
-                  float(znear), float(zfar), *stack.head, _lib.ptr(verts), _lib.ptr(stack.ws), stack.ws.numel(),
-                  _lib.stream(dev))
-        torch.cuda.current_stream(dev).synchronize()
+    launch(dev, "g4s_atsdf_bisect", E, _lib.ptr(e), n, _lib.ptr(pts), _lib.ptr(f), int(steps), float(trunc_margin),
+           float(znear), float(zfar), *stack.head, _lib.ptr(verts), workspace=nbytes, sync=True)
     return verts[:E]
 
 
@@ -658,7 +561,7 @@ def triangulate(points):
     except ImportError as e:
         raise RuntimeError("triangulate needs scipy (scipy.spatial.Delaunay); install it or pass the cells") from e
     dev = points.device if isinstance(points, torch.Tensor) else None
-    cells = Delaunay(_to_np(points).astype(np.float64).reshape(-1, 3)).simplices
+    cells = Delaunay(to_np(points).astype(np.float64).reshape(-1, 3)).simplices
     return torch.as_tensor(np.ascontiguousarray(cells, np.int32), device=dev)
 
 

@@ -19,13 +19,13 @@ with the reference statistically and not sample for sample; the sampler's face s
 zero area is never chosen; an empty cloud raises ValueError (the reference returns NaN).
 """
 import argparse
-import ctypes
 
 import numpy as np
 import torch
 
 from . import _lib
-from .mesh import TriangleMesh, _as_device_mesh, _default_device
+from ._device import default_device, launch, voxel_downsample_count
+from .mesh import TriangleMesh, as_device_mesh
 
 METRIC_KEYS = ("Acc", "Comp", "Chamfer-L1", "Prec", "Recal", "F-score", "Normal-Acc", "Normal-Comp", "Normal-Consistency")
 
@@ -37,7 +37,7 @@ def _cloud(points, device=None, what="points"):
             raise RuntimeError(f"{what} must be a HIP tensor or a numpy array (there is no CPU path)")
         t = points
     else:
-        dev = torch.device(device) if device is not None else _default_device()
+        dev = torch.device(device) if device is not None else default_device()
         t = torch.as_tensor(np.ascontiguousarray(points, np.float32), device=dev)
     if t.dim() != 2 or t.size(1) != 3:
         raise ValueError(f"{what} must be [n,3], got {tuple(t.shape)}")
@@ -59,30 +59,20 @@ def nearest_neighbors(ref, query):
     dev = ref.device
     d2 = torch.empty(n_query, dtype=torch.float32, device=dev)
     idx = torch.empty(n_query, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        ws = torch.empty(lib.g4s_nn_workspace(n_ref, n_query), dtype=torch.uint8, device=dev)
-        _lib.call("g4s_nn_search", n_ref, _lib.ptr(ref), n_query, _lib.ptr(query), _lib.ptr(d2), _lib.ptr(idx), _lib.ptr(ws),
-                  ws.numel(), _lib.stream(dev))
+    launch(dev, "g4s_nn_search", n_ref, _lib.ptr(ref), n_query, _lib.ptr(query), _lib.ptr(d2), _lib.ptr(idx),
+           workspace=lib.g4s_nn_workspace(n_ref, n_query))
     return torch.sqrt(d2), idx
 
 
 def voxel_down_sample(points, voxel_size):
     """One point per occupied voxel of edge `voxel_size`: the float64 mean of the voxel's points, as float32."""
-    lib = _lib.load()
     pts = _cloud(points)
     n, dev = pts.size(0), pts.device
     if n == 0:
         raise ValueError("voxel_down_sample: the cloud is empty")
-    with torch.cuda.device(dev):
-        ws = torch.empty(lib.g4s_voxel_downsample_workspace(n), dtype=torch.uint8, device=dev)
-        st = _lib.stream(dev)
-        count = ctypes.c_int(0)
-        rc = lib.g4s_voxel_downsample_count(n, _lib.ptr(pts), float(voxel_size), ctypes.byref(count), _lib.ptr(ws), ws.numel(), st)
-        if rc != 0:
-            raise ValueError(f"voxel_down_sample: {_lib.last_error()}") if rc == -1 else RuntimeError(
-                f"g4s_voxel_downsample_count failed ({rc}): {_lib.last_error()}")
-        out = torch.empty((count.value, 3), dtype=torch.float32, device=dev)
-        _lib.call("g4s_voxel_downsample_emit", n, _lib.ptr(pts), count.value, _lib.ptr(out), _lib.ptr(ws), ws.numel(), st)
+    ws, count = voxel_downsample_count(pts, voxel_size, "voxel_down_sample")
+    out = torch.empty((count, 3), dtype=torch.float32, device=dev)
+    launch(dev, "g4s_voxel_downsample_emit", n, _lib.ptr(pts), count, _lib.ptr(out), workspace=ws)
     return out
 
 
@@ -102,7 +92,7 @@ def sample_surface(mesh, count, generator=None, u=None, cum_area=None):
     """`count` points uniform over the mesh's area: (points [count,3], normals [count,3] = their faces' unit normals,
     face_index [count] int32), device tensors.  The three random numbers of a sample come from torch.rand under
     `generator` (a generator of the mesh's device), or from `u` [count,3]; `cum_area` defaults to cumulative_areas."""
-    dm, _host = _as_device_mesh(mesh)
+    dm, _host = as_device_mesh(mesh)
     dev = dm.vertices.device
     n_tri, n_vert = dm.triangles.size(0), dm.vertices.size(0)
     if n_tri == 0 or n_vert == 0:
@@ -149,8 +139,8 @@ def evaluate(mesh_pred, mesh_trgt, threshold=0.05, down_sample=0.02, n_samples=2
     """The reference's metrics of a predicted mesh against the target (eval/mesh_eval.py evaluate): distances between the
     voxel-down-sampled vertex clouds (down_sample = 0 or None: the vertices as they are), and the agreement of the face
     normals at `n_samples` surface samples a mesh, each paired with the nearest sample of the other mesh."""
-    pred, _ = _as_device_mesh(mesh_pred)
-    trgt, _ = _as_device_mesh(mesh_trgt, pred.vertices.device)
+    pred, _ = as_device_mesh(mesh_pred)
+    trgt, _ = as_device_mesh(mesh_trgt, pred.vertices.device)
     if pred.vertices.size(0) == 0 or trgt.vertices.size(0) == 0:
         raise ValueError("evaluate: a mesh has no vertices")
     verts_pred, verts_trgt = pred.vertices, trgt.vertices

@@ -21,8 +21,7 @@ import json
 import torch
 
 from . import _lib
-from .mesh import _device_points
-from .visibility import _Views
+from ._device import camera_views, device_points, launch
 
 
 # ---- the decisions (host, no device code: tests/test_planes_cpu.py runs them over sets) ------------------------------------
@@ -141,7 +140,7 @@ def load_global_3Dplane_ID_dict(path):
 
 
 # ---- device path ---------------------------------------------------------------------------------------------------------------
-def _slot_mask(mask, dev):
+def slot_mask(mask, dev):
     """(slot mask int32 [H,W] with values 0 .. P, the P plane ids ascending as a device tensor): torch.unique and
     bucketize over the mask's pixels."""
     if not isinstance(mask, torch.Tensor) or mask.device != dev:
@@ -161,14 +160,14 @@ class _LabelledViews:
     MAX_LABEL_BYTES = 1 << 28
 
     def __init__(self, cameras, points, plane_masks, depth_thresh):
-        self.dev, self.points = _device_points(points)
+        self.dev, self.points = device_points(points)
         self.n = self.points.size(0)
         self.cameras, masks = list(cameras), list(plane_masks)
         if len(self.cameras) != len(masks):
             raise ValueError(f"{len(self.cameras)} cameras but {len(masks)} plane masks")
         self.slots, self.ids = [], []
         for m in masks:
-            s, ids = _slot_mask(m, self.dev)
+            s, ids = slot_mask(m, self.dev)
             self.slots.append(s)
             self.ids.append(ids)
         self.id_lists = [ids.tolist() for ids in self.ids]
@@ -186,14 +185,10 @@ class _LabelledViews:
     def _launch(self, lo, hi):
         dev, n = self.dev, self.n
         # the view plumbing of the Visibility section; a float view of the int32 mask only carries its address and shape
-        views = _Views(self.cameras[lo:hi], [s.view(torch.float32) for s in self.slots[lo:hi]], dev)
-        lib = _lib.load()
+        views = camera_views(self.cameras[lo:hi], [s.view(torch.float32) for s in self.slots[lo:hi]], dev)
         labels = torch.empty((hi - lo, max(n, 1)), dtype=torch.int32, device=dev)[:, :n].contiguous()
-        with torch.cuda.device(dev):
-            ws = torch.empty(lib.g4s_plane_labels_workspace(views.n, views.stack.sizes), dtype=torch.uint8, device=dev)
-            _lib.call("g4s_plane_labels", n, _lib.ptr(self.points), self.depth_thresh, *views.args, _lib.ptr(labels),
-                      _lib.ptr(ws), ws.numel(), _lib.stream(dev))
-            torch.cuda.current_stream(dev).synchronize()  # the stack's tensors and `ws` may go once the kernels have run
+        launch(dev, "g4s_plane_labels", n, _lib.ptr(self.points), self.depth_thresh, *views.head, _lib.ptr(labels),
+               workspace=_lib.load().g4s_plane_labels_workspace(views.n, views.sizes), sync=True)
         return labels
 
 
@@ -228,9 +223,8 @@ class PlaneMembership:
         """(sizes [P], counts [P][G]) as Python ints for the slot labels of one view."""
         P, G = int(n_planes), self.G
         out = torch.empty(max(P * (G + 1), 1), dtype=torch.int32, device=self.dev)
-        with torch.cuda.device(self.dev):
-            _lib.call("g4s_plane_overlap", self.n, _lib.ptr(labels), P, *self._args(), _lib.ptr(out),
-                      ctypes.c_void_p(out.data_ptr() + 4 * P * G), None, 0, _lib.stream(self.dev))
+        launch(self.dev, "g4s_plane_overlap", self.n, _lib.ptr(labels), P, *self._args(), _lib.ptr(out),
+               ctypes.c_void_p(out.data_ptr() + 4 * P * G))
         self.launches += 1
         flat = self._read(out)
         return flat[P * G: P * G + P], [flat[k * G: (k + 1) * G] for k in range(P)]
@@ -240,29 +234,23 @@ class PlaneMembership:
         if not target:
             return
         self._grow(max(max(target) + 1, self.G))
-        with torch.cuda.device(self.dev):
-            ws = torch.empty(_lib.load().g4s_plane_assign_workspace(len(target)), dtype=torch.uint8, device=self.dev)
-            _lib.call("g4s_plane_assign", self.n, _lib.ptr(labels), len(target), _lib.array(ctypes.c_int, target),
-                      *self._args(), _lib.ptr(ws), ws.numel(), _lib.stream(self.dev))
-            torch.cuda.current_stream(self.dev).synchronize()  # `ws` is released on return
+        launch(self.dev, "g4s_plane_assign", self.n, _lib.ptr(labels), len(target), _lib.array(ctypes.c_int, target),
+               *self._args(), workspace=_lib.load().g4s_plane_assign_workspace(len(target)), sync=True)
         self.launches += 1
 
     def row_counts(self, row):
         out = torch.empty(max(self.G, 1), dtype=torch.int32, device=self.dev)
-        with torch.cuda.device(self.dev):
-            _lib.call("g4s_plane_row_overlap", self.n, *self._args(), int(row), _lib.ptr(out), None, 0, _lib.stream(self.dev))
+        launch(self.dev, "g4s_plane_row_overlap", self.n, *self._args(), int(row), _lib.ptr(out))
         self.launches += 1
         return self._read(out)[: self.G]
 
     def merge_rows(self, dst, src):
-        with torch.cuda.device(self.dev):
-            _lib.call("g4s_plane_row_merge", self.n, *self._args(), int(src), int(dst), None, 0, _lib.stream(self.dev))
+        launch(self.dev, "g4s_plane_row_merge", self.n, *self._args(), int(src), int(dst))
         self.launches += 1
 
     def row_mask(self, row):
         mask = torch.empty(max(self.n, 1), dtype=torch.uint8, device=self.dev)
-        with torch.cuda.device(self.dev):
-            _lib.call("g4s_plane_row_mask", self.n, *self._args(), int(row), _lib.ptr(mask), None, 0, _lib.stream(self.dev))
+        launch(self.dev, "g4s_plane_row_mask", self.n, *self._args(), int(row), _lib.ptr(mask))
         self.launches += 1
         return mask[: self.n]
 

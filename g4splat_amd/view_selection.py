@@ -15,14 +15,13 @@ A camera is anything with world_view_transform, FoVx, FoVy, image_width and imag
 tensors.  INTEGRATION.md section O lists the differences from the reference.
 """
 import ctypes
-import math
 import random
 
 import numpy as np
 import torch
 
 from . import _lib
-from .mesh import _hip_device, _host_f32, _to_np
+from ._device import focal_lengths, hip_device, host_f32, launch, to_np
 from .planes import covisibility_rate
 
 MAX_POINTS = 2 ** 31 - 64
@@ -36,16 +35,16 @@ def _camera_arrays(cameras):
         raise ValueError("at least one camera is needed")
     world_view, focal, sizes = [], [], []
     for i, cam in enumerate(cameras):
-        M = np.asarray(_to_np(cam.world_view_transform), np.float32)
+        M = np.asarray(to_np(cam.world_view_transform), np.float32)
         if M.size != 16:
             raise ValueError(f"camera {i}: world_view_transform must be 4 x 4")
         W, H = int(cam.image_width), int(cam.image_height)
         if W <= 0 or H <= 0:
             raise ValueError(f"camera {i}: image_width and image_height must be positive")
         world_view.extend(M.reshape(16).tolist())
-        focal += [W / (2.0 * math.tan(float(cam.FoVx) / 2.0)), H / (2.0 * math.tan(float(cam.FoVy) / 2.0))]
+        focal += focal_lengths(cam, W, H)
         sizes += [W, H]
-    return len(cameras), _host_f32(world_view), _host_f32(focal), (ctypes.c_int * len(sizes))(*sizes)
+    return len(cameras), host_f32(world_view), host_f32(focal), (ctypes.c_int * len(sizes))(*sizes)
 
 
 def _check_points(points):
@@ -70,26 +69,21 @@ class Covisibility:
     def __init__(self, points, cameras):
         _check_points(points)
         self.n_cameras, world_view, focal, sizes = _camera_arrays(cameras)
-        dev, pts = _hip_device(points.device), points.detach().float().contiguous()
+        dev, pts = hip_device(points.device), points.detach().float().contiguous()
         self.device, self.n_points = dev, pts.size(0)
         C, P = self.n_cameras, self.n_points
         self.n_words = (P + 63) // 64
         self.words = torch.empty((C, self.n_words), dtype=torch.int64, device=dev)
         self._counts = self._table = None
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            ws = torch.empty(lib.g4s_view_bits_workspace(C), dtype=torch.uint8, device=dev)
-            _lib.call("g4s_view_bits", P, _lib.ptr(pts), C, world_view, focal, sizes, _lib.ptr(self.words), _lib.ptr(ws),
-                      ws.numel(), _lib.stream(dev))
-            torch.cuda.current_stream(dev).synchronize()  # `pts` and `ws` may be temporaries
+        launch(dev, "g4s_view_bits", P, _lib.ptr(pts), C, world_view, focal, sizes, _lib.ptr(self.words),
+               workspace=_lib.load().g4s_view_bits_workspace(C), sync=True)
 
     @property
     def counts(self):
         if self._counts is None:
             C, dev = self.n_cameras, self.device
             counts = torch.empty((C, C), dtype=torch.int32, device=dev)
-            with torch.cuda.device(dev):
-                _lib.call("g4s_view_overlap", C, self.n_words, _lib.ptr(self.words), _lib.ptr(counts), None, 0, _lib.stream(dev))
+            launch(dev, "g4s_view_overlap", C, self.n_words, _lib.ptr(self.words), _lib.ptr(counts))
             self._counts = counts
         return self._counts
 
@@ -201,17 +195,13 @@ def farthest_point_indices(clouds, num_samples, first_indices, return_dist=False
     reference.  Sample 0 of cloud m is first_indices[m]; every further one is the point farthest from the samples so far,
     the smallest index among equals.  k launches for all clouds together."""
     M, N, k, first = _check_sampling(clouds, num_samples, first_indices)
-    dev = _hip_device(clouds.device)
+    dev = hip_device(clouds.device)
     pts = clouds.detach().float().contiguous()
     indices = torch.empty((M, k), dtype=torch.int32, device=dev)
     samples = torch.empty((M, k, 3), dtype=torch.float32, device=dev)
     dist = torch.empty((M, N), dtype=torch.float32, device=dev)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        ws = torch.empty(lib.g4s_fps_workspace(M, k), dtype=torch.uint8, device=dev)
-        _lib.call("g4s_fps", M, N, _lib.ptr(pts), _lib.array(ctypes.c_int, first), k, _lib.ptr(indices), _lib.ptr(samples),
-                  _lib.ptr(dist), _lib.ptr(ws), ws.numel(), _lib.stream(dev))
-        torch.cuda.current_stream(dev).synchronize()  # `pts` and `ws` may be temporaries
+    launch(dev, "g4s_fps", M, N, _lib.ptr(pts), _lib.array(ctypes.c_int, first), k, _lib.ptr(indices), _lib.ptr(samples),
+           _lib.ptr(dist), workspace=_lib.load().g4s_fps_workspace(M, k), sync=True)
     return (indices, samples, dist) if return_dist else (indices, samples)
 
 

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib, ply_io
-from .mesh import _ViewStack, _default_device, _device_points, _hip_device, _host_f32, _to_np
+from ._device import camera_views, default_device, depth_map, device_points, hip_device, host_f32, launch, to_np
 
 _MODES = {"free": 0, "surface": 1}
 
@@ -26,8 +26,8 @@ def ray_record(camera, width, height):
     """The twelve floats (origin o[3], D[3][3] row-major) of the contract: dir = D @ (x, y, 1) for integer pixel
     coordinates, point = o + t * dir.  Computed in double the way matcha/dm_scene/charts.py depths_to_points_parallel
     derives its rays (c2w from world_view_transform, pixel intrinsics from full_proj_transform and the map's size)."""
-    wvt = np.asarray(_to_np(camera.world_view_transform), np.float64).reshape(4, 4)
-    full = np.asarray(_to_np(camera.full_proj_transform), np.float64).reshape(4, 4)
+    wvt = np.asarray(to_np(camera.world_view_transform), np.float64).reshape(4, 4)
+    full = np.asarray(to_np(camera.full_proj_transform), np.float64).reshape(4, 4)
     c2w = np.linalg.inv(wvt.T)
     W, H = float(width), float(height)
     ndc2pix = np.array([[W / 2, 0, 0, W / 2], [0, H / 2, 0, H / 2], [0, 0, 0, 1]], np.float64).T
@@ -36,38 +36,8 @@ def ray_record(camera, width, height):
     return np.concatenate([c2w[:3, 3], D.reshape(9)]).astype(np.float32)
 
 
-class _Views:
-    """The view table's host arrays for a list of cameras and depth maps (mesh._ViewStack plus the focal lengths)."""
-
-    def __init__(self, cameras, depths, device):
-        cameras, depths = list(cameras), list(depths)
-        if len(cameras) != len(depths):
-            raise ValueError(f"{len(cameras)} cameras but {len(depths)} depth maps")
-        self.stack = _ViewStack([(c, d, None) for c, d in zip(cameras, depths)], device, False, 1,
-                                lambda cam: [cam.world_view_transform], "g4s_visgrid_workspace")
-        focal = []
-        for v, cam in enumerate(cameras):
-            W, H = self.stack.sizes[2 * v], self.stack.sizes[2 * v + 1]
-            focal += [W / (2.0 * math.tan(float(cam.FoVx) / 2.0)), H / (2.0 * math.tan(float(cam.FoVy) / 2.0))]
-        n, world_view, sizes, depth = self.stack.head
-        self.n = n
-        self.args = [n, world_view, _host_f32(focal) if focal else (ctypes.c_float * 1)(), sizes, depth]
-        self.ws = self.stack.ws
-
-
-def _depth_map(depth, device=None):
-    """A depth map as a contiguous float32 [H,W] device tensor (never written)."""
-    if not isinstance(depth, torch.Tensor):
-        raise RuntimeError("depth must be a tensor on a HIP device")
-    dev = _hip_device(depth.device if device is None else device)
-    if depth.device != dev:
-        raise RuntimeError(f"depth must be a tensor on {dev}")
-    d = depth.detach().float()
-    if d.dim() == 3 and d.size(0) == 1:
-        d = d[0]
-    if d.dim() != 2:
-        raise RuntimeError(f"depth must be [H,W] or [1,H,W] (got {tuple(depth.shape)})")
-    return dev, d.contiguous()
+def _view_table(views):
+    return _lib.load().g4s_visgrid_workspace(views.n)
 
 
 # ---- view counts ----------------------------------------------------------------------------------------------------------
@@ -75,42 +45,34 @@ def view_counts(points, cameras, depths, mode="free", depth_threshold=0.1, skip_
     """int32 [n]: for every point [n,3] (device tensor) the number of views that pass the FREE (in image, in front of
     the camera, nearer than the view's depth) or the SURFACE (relative depth difference below depth_threshold)
     predicate; skip_view names a view to leave out."""
-    dev, pts = _device_points(points)
+    dev, pts = device_points(points)
     n = pts.size(0)
-    views = _Views(cameras, depths, dev)
+    views = camera_views(cameras, depths, dev)
     counts = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.call("g4s_view_counts_points", n, _lib.ptr(pts), _MODES[mode], float(depth_threshold),
-                  -1 if skip_view is None else int(skip_view), *views.args, _lib.ptr(counts), _lib.ptr(views.ws),
-                  views.ws.numel(), _lib.stream(dev))
-        torch.cuda.current_stream(dev).synchronize()  # the stack's tensors may go once the kernel has run
+    launch(dev, "g4s_view_counts_points", n, _lib.ptr(pts), _MODES[mode], float(depth_threshold),
+           -1 if skip_view is None else int(skip_view), *views.head, _lib.ptr(counts), workspace=_view_table(views), sync=True)
     return counts[:n]
 
 
 def pixel_view_counts(camera, depth, cameras, depths, mode="surface", depth_threshold=0.1, skip_view=None):
     """int32 [H,W]: view_counts of the pixels of `depth` back-projected through `camera`, fused: the points are formed
     in the kernel and never stored.  Bit-identical to view_counts(depths_to_points(depth, camera), ...)."""
-    dev, d = _depth_map(depth)
+    dev, d = depth_map(depth)
     H, W = d.shape
-    views = _Views(cameras, depths, dev)
+    views = camera_views(cameras, depths, dev)
     counts = torch.empty((H, W), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.call("g4s_view_counts_pixels", W, H, _lib.ptr(d), _host_f32(ray_record(camera, W, H)), _MODES[mode],
-                  float(depth_threshold), -1 if skip_view is None else int(skip_view), *views.args, _lib.ptr(counts),
-                  _lib.ptr(views.ws), views.ws.numel(), _lib.stream(dev))
-        torch.cuda.current_stream(dev).synchronize()
+    launch(dev, "g4s_view_counts_pixels", W, H, _lib.ptr(d), host_f32(ray_record(camera, W, H)), _MODES[mode],
+           float(depth_threshold), -1 if skip_view is None else int(skip_view), *views.head, _lib.ptr(counts),
+           workspace=_view_table(views), sync=True)
     return counts
 
 
 def depths_to_points(depth, camera):
     """float32 [H*W,3]: the world points of a depth map's pixels, origin + depth * direction."""
-    dev, d = _depth_map(depth)
+    dev, d = depth_map(depth)
     H, W = d.shape
     points = torch.empty((H * W, 3), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.call("g4s_depth_to_points", W, H, _lib.ptr(d), _host_f32(ray_record(camera, W, H)), _lib.ptr(points), None, 0,
-                  _lib.stream(dev))
-        torch.cuda.current_stream(dev).synchronize()  # `d` may be a temporary
+    launch(dev, "g4s_depth_to_points", W, H, _lib.ptr(d), host_f32(ray_record(camera, W, H)), _lib.ptr(points), sync=True)
     return points
 
 
@@ -131,7 +93,7 @@ def build_visibility_masks(cameras, depths, points=None, depth_threshold=0.1, le
     cameras, depths = list(cameras), list(depths)
     masks = []
     for i, (cam, depth) in enumerate(zip(cameras, depths)):
-        _dev, d = _depth_map(depth)
+        _dev, d = depth_map(depth)
         H, W = d.shape
         if points is None:
             n = pixel_view_counts(cam, d, cameras, depths, "surface", depth_threshold, skip_view=i)
@@ -153,15 +115,15 @@ class VisibilityGrid:
 
     def __init__(self, bbox_min, bbox_max, resolution, input_cameras, input_depths, device=None):
         if device is None:
-            device = bbox_min.device if isinstance(bbox_min, torch.Tensor) and bbox_min.is_cuda else _default_device()
-        self.device = _hip_device(device)
+            device = bbox_min.device if isinstance(bbox_min, torch.Tensor) and bbox_min.is_cuda else default_device()
+        self.device = hip_device(device)
         R = int(resolution)
         if R < 1 or R ** 3 >= 2 ** 31:
             raise ValueError("resolution must be at least 1 and resolution^3 below 2^31")
         self.resolution = R
-        lo = np.asarray(_to_np(bbox_min), np.float32).reshape(3)
-        hi = np.asarray(_to_np(bbox_max), np.float32).reshape(3)
-        self._lo, self._hi = _host_f32(lo), _host_f32(hi)
+        lo = np.asarray(to_np(bbox_min), np.float32).reshape(3)
+        hi = np.asarray(to_np(bbox_max), np.float32).reshape(3)
+        self._lo, self._hi = host_f32(lo), host_f32(hi)
         cell = (hi - lo) / np.float32(R)
         self.bbox_min = torch.as_tensor(lo, device=self.device)
         self.bbox_max = torch.as_tensor(hi, device=self.device)
@@ -170,20 +132,17 @@ class VisibilityGrid:
         self.input_cameras, self.input_depths = list(input_cameras), list(input_depths)
         self._grid = None
         dev = self.device
-        views = _Views(self.input_cameras, self.input_depths, dev)
+        views = camera_views(self.input_cameras, self.input_depths, dev)
         self.words = torch.empty((R ** 3 + 63) // 64, dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            _lib.call("g4s_visgrid_build", R, self._lo, self._hi, *views.args, _lib.ptr(self.words), _lib.ptr(views.ws),
-                      views.ws.numel(), _lib.stream(dev))
-            torch.cuda.current_stream(dev).synchronize()
+        launch(dev, "g4s_visgrid_build", R, self._lo, self._hi, *views.head, _lib.ptr(self.words), workspace=_view_table(views),
+               sync=True)
 
     @property
     def visibility_grid(self):
         if self._grid is None:
             R, dev = self.resolution, self.device
             grid = torch.empty((R, R, R), dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                _lib.call("g4s_visgrid_expand", R, _lib.ptr(self.words), _lib.ptr(grid), None, 0, _lib.stream(dev))
+            launch(dev, "g4s_visgrid_expand", R, _lib.ptr(self.words), _lib.ptr(grid))
             self._grid = grid
         return self._grid
 
@@ -191,13 +150,11 @@ class VisibilityGrid:
         """bool [...]: the voxel each point [...,3] falls into is visible (points outside the box count as their
         border voxel, as in the reference)."""
         shape = tuple(points.shape[:-1])
-        _dev, pts = _device_points(points.to(self.device))
+        _dev, pts = device_points(points.to(self.device))
         n = pts.size(0)
         out = torch.empty(max(n, 1), dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.call("g4s_visgrid_sample", self.resolution, self._lo, self._hi, _lib.ptr(self.words), n, _lib.ptr(pts),
-                      _lib.ptr(out), None, 0, _lib.stream(self.device))
-            torch.cuda.current_stream(self.device).synchronize()  # `pts` may be a temporary
+        launch(self.device, "g4s_visgrid_sample", self.resolution, self._lo, self._hi, _lib.ptr(self.words), n, _lib.ptr(pts),
+               _lib.ptr(out), sync=True)
         return out[:n].bool().reshape(shape)
 
     def n_samples(self, depth):
@@ -214,29 +171,23 @@ class VisibilityGrid:
         maps = []
         dev = self.device
         for cam, depth in zip(cameras, depths):
-            _d, d = _depth_map(depth, dev)
+            _d, d = depth_map(depth, dev)
             H, W = d.shape
             out = torch.empty((H, W), dtype=torch.float32, device=dev)
             S = self.n_samples(d)
-            with torch.cuda.device(dev):
-                _lib.call("g4s_visgrid_march", self.resolution, self._lo, self._hi, _lib.ptr(self.words), W, H, _lib.ptr(d),
-                          _host_f32(ray_record(cam, W, H)), S, _lib.ptr(out), None, 0, _lib.stream(dev))
-                torch.cuda.current_stream(dev).synchronize()  # `d` may be a temporary
+            launch(dev, "g4s_visgrid_march", self.resolution, self._lo, self._hi, _lib.ptr(self.words), W, H, _lib.ptr(d),
+                   host_f32(ray_record(cam, W, H)), S, _lib.ptr(out), sync=True)
             maps.append(out)
         return maps
 
     def _centres(self, invisible):
         lib, dev, R = _lib.load(), self.device, self.resolution
-        with torch.cuda.device(dev):
-            ws = torch.empty(lib.g4s_visgrid_compact_workspace(R), dtype=torch.uint8, device=dev)
-            st = _lib.stream(dev)
-            n = ctypes.c_int(0)
-            _lib.call("g4s_visgrid_compact_count", R, _lib.ptr(self.words), int(invisible), ctypes.byref(n), _lib.ptr(ws),
-                      ws.numel(), st)
-            out = torch.empty((max(n.value, 1), 3), dtype=torch.float32, device=dev)
-            _lib.call("g4s_visgrid_compact_emit", R, self._lo, self._hi, _lib.ptr(self.words), int(invisible), n.value,
-                      _lib.ptr(out), _lib.ptr(ws), ws.numel(), st)
-            torch.cuda.current_stream(dev).synchronize()  # `ws` is released on return
+        n = ctypes.c_int(0)
+        ws = launch(dev, "g4s_visgrid_compact_count", R, _lib.ptr(self.words), int(invisible), ctypes.byref(n),
+                    workspace=lib.g4s_visgrid_compact_workspace(R))
+        out = torch.empty((max(n.value, 1), 3), dtype=torch.float32, device=dev)
+        launch(dev, "g4s_visgrid_compact_emit", R, self._lo, self._hi, _lib.ptr(self.words), int(invisible), n.value,
+               _lib.ptr(out), workspace=ws, sync=True)
         return out[:n.value]
 
     def get_all_visible_pnts(self):

@@ -267,6 +267,12 @@ def test_entry_points_refuse_what_they_cannot_take():
         chart_init.pointmap_surfels(p, p[:1])
     with pytest.raises(ValueError, match="2 views but 3 depths"):
         chart_init.depthmap_surfels(torch.zeros((3, 4, 5)), cams, p)
+    with pytest.raises(ValueError, match="2 views but 0 masks"):
+        chart_init.pointmap_surfels(p, p, [])
+    with pytest.raises(ValueError, match="0 views but 2 depths"):
+        chart_init.depthmap_surfels(d, [], p)
+    assert {k: tuple(v.shape) for k, v in chart_init.pointmap_surfels([], []).items()} == {
+        "means": (0, 3), "scales": (0, 3), "quaternions": (0, 4), "colors": (0, 3)}  # no views: no device is asked for
     with pytest.raises(ValueError, match=r"\[V,H,W,3\]"):
         chart_init.pointmap_surfels(p[0], p)
     with pytest.raises(ValueError, match=r"\[H,W,3\]"):

@@ -198,3 +198,31 @@ def test_same_step_read_sees_the_state_before_the_step():
     src = [(np.array([0, 0, 0, 0, cr.NO_STEP]), np.zeros(5, np.int64), np.array([1, 2, 3, 4, 0]))]
     for out in (cr.resolve_chains([image], src)[0], cr.repaint_in_place([image], src, 1)[0]):
         assert np.array_equal(out[0, :4], image[0, 1:]) and np.array_equal(out[0, 4], image[0, 4])
+
+
+def test_solver_arguments_are_checked_before_the_device():
+    d, img, pts = torch.ones((3, 4)), torch.zeros((3, 4, 3)), torch.zeros((5, 3))
+    point, plane = consistency.solve_point_inconsistency, consistency.solve_plane_inconsistency
+    with pytest.raises(ValueError, match="1 cameras but 0 depths"):
+        point([None], [], [img], pts, 0)
+    with pytest.raises(ValueError, match="1 cameras but 0 images"):
+        point([None], [d], [], pts, 0)
+    for n_input in (-1, 2):
+        with pytest.raises(ValueError, match=r"n_input_views must be in 0 \.\. 1"):
+            point([None], [d], [img], pts, n_input)
+    for bad in ([[0.0, 0.0, 0.0]], pts.long()):
+        with pytest.raises(RuntimeError, match="floating-point tensor on a HIP device"):
+            consistency.point_states([None], [d], [img], bad, 1)
+    with pytest.raises(RuntimeError, match="HIP device"):
+        point([None], [d], [img], pts, 1)
+    masks, clouds = [torch.zeros((3, 4), dtype=torch.int32)], [torch.zeros((12, 3))]
+    with pytest.raises(ValueError, match="1 cameras but 0 plane_masks"):
+        plane([None], [d], [img], [], clouds, {}, [0])
+    with pytest.raises(ValueError, match="twice"):
+        plane([None], [d], [img], masks, clouds, {0: [(0, 1)], 1: [(0, 1)]}, [0])
+    with pytest.raises(RuntimeError, match="depth must be a tensor on a HIP device"):
+        plane([None], [[1.0]], [img], masks, clouds, {}, [0])
+    with pytest.raises(RuntimeError, match="HIP device"):
+        plane([None], [d], [img], masks, clouds, {0: [(0, 1)]}, [0])
+    outs, anchors, counts = plane([], [], [], [], [], {0: [(0, 1)], "3": []}, [0, 1])  # no views: nothing is asked of a device
+    assert outs == [] and anchors == {0: -1, 3: -1} and counts.shape == (2, 2) and counts.dtype == torch.int64

@@ -236,6 +236,26 @@ def test_python_argument_checks_need_no_device():
         depth_cues.view_geometry_cues([None], m, m, m)
     with pytest.raises(ValueError, match="1 views but 2"):
         depth_cues.view_geometry_cues([None], [m, m], [m], [m])
+    with pytest.raises(ValueError, match="0 views but 1 targets"):
+        depth_cues.align_disparities([], [m], [])
+    with pytest.raises(ValueError, match="1 views but 0 depths"):
+        depth_cues.apply_global_planes([None], [], [], {}, {})
+    with pytest.raises(ValueError, match="names view 0 but there are 0 views"):
+        depth_cues.apply_global_planes([], [], [], {0: [(0, 1)]}, {})
+    with pytest.raises(ValueError, match="0 views but 1 mono_depths"):
+        depth_cues.refill_unseen_regions([], [m], [], [], 0)
+    with pytest.raises(ValueError, match=r"n_input_views must be in 0 \.\. 0 \(got 1\)"):
+        depth_cues.refill_unseen_regions([], [], [], [], 1)
+    with pytest.raises(ValueError, match="1 cameras but 0 depths"):
+        depth_cues.refine_depths_with_planes([None], [], [], [], [], {}, {}, 0)
+    with pytest.raises(ValueError, match="must not be NaN"):
+        depth_cues.view_geometry_cues([], [], [], [], float("nan"))
+    with pytest.raises(ValueError, match="img_shape must be positive"):
+        depth_cues.plane_aligned_depth(m[0, :3], m[0, :3], None, (0, 4))
+    # without views every entry point answers with its empty result, and asks for no device
+    assert depth_cues.refine_depths_with_planes([], [], [], [], [], {}, {}, 0, return_points=True) == ([], [])
+    assert depth_cues.view_geometry_cues([], [], [], []).coeffs.shape == (0, 2)
+    assert depth_cues.align_disparities([], [], [])[0] == [] and depth_cues.refill_unseen_regions([], [], [], [], 0)[0] == []
 
 
 # ---- host-side argument validation of the library ---------------------------------------------------------------------------

@@ -228,7 +228,7 @@ def _evaluate_both_ways(pred, trgt, device_meshes, threshold=0.05, down_sample=0
     g.manual_seed(50)
     u_pred = torch.rand((N_SAMPLES, 3), dtype=torch.float32, device=DEV, generator=g).cpu().numpy()
     u_trgt = torch.rand((N_SAMPLES, 3), dtype=torch.float32, device=DEV, generator=g).cpu().numpy()
-    cums = [me.cumulative_areas(me._as_device_mesh(mesh_mod.TriangleMesh(*m), DEV)[0]).cpu().numpy() for m in (pred, trgt)]
+    cums = [me.cumulative_areas(me.as_device_mesh(mesh_mod.TriangleMesh(*m), DEV)[0]).cpu().numpy() for m in (pred, trgt)]
     want = ref.evaluate(pred, trgt, u_pred, u_trgt, threshold, down_sample, cums[0], cums[1])
     return got, want
 

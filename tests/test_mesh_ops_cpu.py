@@ -299,3 +299,23 @@ def test_mesh_ops_argument_validation_is_host_side(hip_lib):
     expect(emit(w=nul), "workspace too small")
     assert _lib.last_error() != ""
     assert lib.g4s_mesh_keep_nondegenerate(0, nul, nul, nul) == 0 and _lib.last_error() == ""  # a good call clears it
+
+
+def test_mesh_arguments_are_checked_before_the_device():
+    import torch
+    host = mesh_mod.TriangleMesh(np.zeros((3, 3), np.float32), np.zeros((3, 3), np.float32), np.array([[0, 1, 2]], np.int32))
+    on_cpu = mesh_mod.DeviceMesh(torch.zeros((3, 3)), torch.zeros((3, 3)), torch.tensor([[0, 1, 2]], dtype=torch.int32))
+    for op in (mesh_mod.cluster_connected_triangles, mesh_mod.post_process_mesh, mesh_mod.filter_mesh,
+               lambda m: mesh_mod.cull_observed_faces(m, [], 1.0)):
+        with pytest.raises(RuntimeError, match="a DeviceMesh lives on one HIP device"):
+            op(on_cpu)
+    with pytest.raises(RuntimeError, match=r"vertex_colors \(2, 3\) must match vertices \(3, 3\)"):
+        mesh_mod.as_device_mesh(host._replace(vertex_colors=np.zeros((2, 3), np.float32)), "cpu")
+    with pytest.raises(ValueError, match="cluster_to_keep must be at least 1"):
+        mesh_mod.post_process_mesh(host, 0)
+    with pytest.raises(ValueError, match="at least one mesh"):
+        mesh_mod.join_meshes([])
+    with pytest.raises(TypeError, match="meshes of one kind"):
+        mesh_mod.join_meshes([host, on_cpu])
+    with pytest.raises(ValueError, match="quantile of an empty tensor"):
+        mesh_mod.quantile_linear(torch.zeros(0), 0.5)

@@ -184,3 +184,18 @@ def test_json_round_trip(golden, tmp_path):
     assert all(isinstance(p, list) and len(p) == 2 for pairs in raw.values() for p in pairs)
     assert raw == json.loads(str(golden.g["ids"]))
     assert planes.load_global_3Dplane_ID_dict(path) == golden.ids
+
+
+def test_plane_masks_are_checked_before_the_device():
+    import torch
+    cpu, hip = torch.device("cpu"), torch.device("cuda", 0)
+    for bad in (torch.zeros((3, 4), dtype=torch.int32), [[0]]):
+        with pytest.raises(RuntimeError, match="plane masks must be tensors on cuda:0"):
+            planes.slot_mask(bad, hip)
+    for bad in (torch.zeros((3, 4)), torch.zeros((1, 3, 4), dtype=torch.int32)):
+        with pytest.raises(RuntimeError, match=r"a plane mask must be an integer tensor \[H,W\]"):
+            planes.slot_mask(bad, cpu)
+    slots, ids = planes.slot_mask(torch.tensor([[0, 7, 7], [3, 0, -2]]), cpu)
+    assert slots.dtype == torch.int32 and slots.tolist() == [[0, 3, 3], [2, 0, 1]] and ids.tolist() == [-2, 3, 7]
+    with pytest.raises(RuntimeError, match="points must be a tensor on a HIP device"):
+        planes.front_point_labels([None], [[0.0, 0.0, 0.0]], [torch.zeros((3, 4), dtype=torch.int32)])

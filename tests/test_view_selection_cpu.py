@@ -260,3 +260,23 @@ def test_the_library_checks_its_arguments_on_the_host(hip_lib):
     assert lib.g4s_fps_workspace(0, 10) == 0 and lib.g4s_fps_workspace(3, 1) == 0
     # a call that succeeds clears the message of the last one that did not
     assert lib.g4s_view_bits(0, nul, 1, wv, focal, sizes, nul, one, big, nul) == 0 and lib.g4s_last_error() == b""
+
+
+def test_cameras_and_centres_are_checked_before_the_device(gold):
+    from types import SimpleNamespace
+    cam, pts = gold["cams"][0], torch.zeros(5, 3)
+    small = SimpleNamespace(world_view_transform=torch.eye(3), FoVx=1.0, FoVy=1.0, image_width=4, image_height=3)
+    with pytest.raises(ValueError, match="camera 1: world_view_transform must be 4 x 4"):
+        vs.Covisibility(pts, [cam, small])
+    for W, H in ((0, 3), (4, -1)):
+        flat = SimpleNamespace(world_view_transform=torch.eye(4), FoVx=1.0, FoVy=1.0, image_width=W, image_height=H)
+        with pytest.raises(ValueError, match="camera 0: image_width and image_height must be positive"):
+            vs.Covisibility(pts, [flat])
+    with pytest.raises(ValueError, match="points must be a tensor"):
+        vs.Covisibility([[0.0, 0.0, 0.0]], [cam])
+    with pytest.raises(ValueError, match="at least one cloud"):
+        vs.farthest_point_indices(torch.zeros(0, 6, 3), 2, [])
+    with pytest.raises(ValueError, match="gs_train_view_points must be a tensor"):
+        vs.get_novel_cams_lookat_points(torch.zeros(2, 3), torch.zeros(6, 3), torch.zeros(1, 3))
+    with pytest.raises(ValueError, match="train_cam_centers must be"):
+        vs.get_novel_cams_lookat_points(torch.zeros(3, 3), torch.zeros(2, 6, 3), torch.zeros(1, 3))

@@ -29,7 +29,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from g4splat_amd import _lib, synthetic, visibility  # noqa: E402
-from g4splat_amd.mesh import _host_f32  # noqa: E402
+from g4splat_amd._device import host_f32  # noqa: E402
 
 DEV = torch.device("cuda:0")
 R, SIZE = 256, 512
@@ -140,7 +140,7 @@ def march_raw(entry, grid, storage, cam, depth, S):
     """One march call on the given storage of the grid (the packed words or one byte per voxel), S given."""
     H, W = depth.shape
     out = torch.empty((H, W), dtype=torch.float32, device=DEV)
-    _lib.call(entry, R, grid._lo, grid._hi, _lib.ptr(storage), W, H, _lib.ptr(depth), _host_f32(visibility.ray_record(cam, W, H)),
+    _lib.call(entry, R, grid._lo, grid._hi, _lib.ptr(storage), W, H, _lib.ptr(depth), host_f32(visibility.ray_record(cam, W, H)),
               S, _lib.ptr(out), None, 0, _lib.stream(DEV))
     return out
 
