@@ -77,12 +77,13 @@ class _HostRows:
     def accumulate(self, buf, srcs, lo, hi, path, own_pos):
         """Adds the rows of `buf` (row-major, index column) that arrived from the sources srcs = [(offset, count)] to the
         owner's rows [lo, hi), source after source, in OwnerReduce.addition_order()'s `path`.  "rank": the zero-then-add
-        form -- the first `own_pos` sources into a zero shard, then the owner's rows, then the others."""
+        form -- the first `own_pos` sources into a zero shard, then the owner's rows, then the others (own_pos 0: the owner's
+        rows come first as they are, not behind a zero, as in g4s_accumulate_rows_ordered -- an own -0.0 stays -0.0)."""
         def add(targets, o, c, shift):
             ridx = buf[o:o + c, self.W].contiguous().view(torch.int32).to(torch.int64) - shift
             for t, part in zip(targets, self._parts(buf[o:o + c], c)):
                 t.index_add_(0, ridx, part)
-        if path != "rank":
+        if path != "rank" or own_pos == 0:
             for o, c in srcs:
                 add(self.rows, o, c, 0)
             return

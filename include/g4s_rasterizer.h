@@ -335,7 +335,9 @@ int g4s_pack_rows(int nseg, float* const* segments, const int* widths, const lon
  * [src_offsets[i], src_offsets[i] + src_counts[i]), every index in [row_lo, row_hi) (the owner's shard), ASCENDING inside
  * a source and distinct inside a source.  Adds them to the segments' rows, source after source: element for element the
  * same sequence of additions -- the same bits -- as one g4s_pack_rows(mode 15) call per source in that order, with one
- * read and one write of the shard instead of one per source.  `src_offsets` / `src_counts` are HOST arrays.
+ * read and one write of the shard instead of one per source.  `src_offsets` / `src_counts` are HOST arrays.  A row of an
+ * ascending source whose index lies below row_lo or at or above row_hi is skipped: it is added to no row, the rows inside
+ * the shard get the same sums as without it, and nothing outside [row_lo, row_hi) is written.
  */
 int g4s_accumulate_rows(int nseg, float* const* segments, const int* widths, int nsrc, const int* src_offsets,
                         const int* src_counts, const float* packed, int row_lo, int row_hi, void* stream);
