@@ -182,6 +182,17 @@ SIGNATURES = {
     "g4s_chart_surfels_count": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_f, c_p, c_p, c_sz, c_p]),
     "g4s_chart_surfels_emit": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_f, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "g4s_voxel_downsample_emit_index": (c_i, [c_i, c_i, c_p, c_p, c_sz, c_p]),
+    "g4s_kmeans_normals_workspace": (c_sz, [c_i, c_p]),
+    "g4s_kmeans_normals": (c_i, [c_i, c_p, c_p, c_i, c_p, c_i, ctypes.c_double, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_normal_components_workspace": (c_sz, [c_i, c_p]),
+    "g4s_normal_components_count": (c_i, [c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_normal_components_sizes": (c_i, [c_i, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_plane_pair_counts_workspace": (c_sz, [c_i]),
+    "g4s_plane_pair_counts": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_plane_paint_workspace": (c_sz, [c_i, c_i, c_i]),
+    "g4s_plane_paint": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_plane_relabel_workspace": (c_sz, [c_i, c_i]),
+    "g4s_plane_relabel": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
 }
 
 _lib = None

@@ -78,13 +78,6 @@ __device__ __forceinline__ float align_value(int domain, float alpha, float beta
     return domain == ALIGN_DEPTH ? lin : 1.0f / lin;
 }
 
-// lane 0 receives ((...) + lanes 32..63 folded alike): the same tree whatever the values
-__device__ __forceinline__ double wave_fold(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
-
 __global__ void __launch_bounds__(256) align_sums_kernel(const AlignView* __restrict__ views, int domain, int mask_is_map,
                                                          float threshold, double* __restrict__ partials) {
     const AlignView& v = views[blockIdx.y];

@@ -1,6 +1,6 @@
 // What the units under tsdf/ share that is not about views -- the mesh units (tsdf.hip, unbounded.hip, tetra.hip, mesh_ops.hip,
 // mesh_eval.hip) and the view-stack units (visibility.hip, planes.hip, consistency.hip, view_select.hip, depth_cues.hip,
-// chart_init.hip): the argument checks of their entry points, the grid of a thread-per-item launch, the upload of host values
+// chart_init.hip, plane_masks.hip): the argument checks of their entry points, the grid of a thread-per-item launch, the upload of host values
 // and the read-back of the two scan totals; for the mesh units alone, the index arithmetic of the marching-cubes table
 // (tsdf_mc_table.h).  What is about a stack of views is in view_stack.h.
 #pragma once

@@ -972,6 +972,108 @@ int g4s_chart_surfels_emit(int n_views, int height, int width, int depth_form, c
 int g4s_voxel_downsample_emit_index(int n, int n_voxels, long long* index_out, char* workspace, size_t workspace_bytes,
                                     void* stream);
 
+/* =====================================================================================================================
+ * Plane masks (g4splat_amd/csrc/tsdf/plane_masks.hip).
+ *
+ * What the reference does per view in 2d-gaussian-splatting/planes/plane_excavator.py after the SAM network has run: KMeans
+ * over the view's normals, planes/tools.py merge_normal_clusters and remove_small_isolated_areas, the double loop over masks
+ * and normal components, the repaint and the mean normal per plane.  The network stays with the caller: its masks are an
+ * input.  The pick and merge of clusters, the order of the masks and the numbering of ids run on the host over a few
+ * numbers (g4splat_amd/plane_masks.py); this section states what the library computes.  The semantics are the library's own,
+ * stated exactly (tests/plane_masks_ref.py restates them in numpy): float32 unless float64 is named, round-to-nearest-even, no
+ * fused multiply-add, evaluated left to right as written.  No floating-point atomics; integer atomics only where the result
+ * does not depend on the order.  Two runs give the same bits.
+ *
+ * Views as in "Depth cues": V <= 65535, sizes = {W0, H0, ...}, maps as HOST arrays of V device pointers, pixel q = y W + x.
+ *
+ * A. k-means (g4s_kmeans_normals).  normals[v] is [H,W,3] float32, k <= G4S_KMEANS_MAX_K, init [V,k,3] (HOST, finite).  A
+ *   pixel with a NaN component is invalid: label -1, part of no sum.  Lloyd's algorithm per view, iterations i = 1, 2, ...:
+ *   Assignment.  d_j = ((dx dx + dy dy) + dz dz), dx = x - c_j.x and alike, per centre j; the label is the smallest j whose d_j
+ *     is below every earlier one (strict <, from d_0): ties go to the smallest index.
+ *   Update.  Per cluster the count n_j and the float64 sums of x, y, z of its members in a fixed order: a workgroup owns
+ *     G4S_KMEANS_SPAN consecutive pixels, thread t adds pixels t, t + 256, ... of the span in ascending order, a fixed tree
+ *     folds the 64 lanes of a wave (lane l += lane l + 32, then 16, ... 1), the four waves are added in order, and lane l of
+ *     one wave adds the workgroups' partials l, l + 64, ... in ascending order before the same tree.  new c_j = float32(sum /
+ *     n_j); a cluster without members keeps its centre (sklearn relocates it).  shift_j = (ex ex + ey ey) + ez ez in float64,
+ *     e = new c_j - c_j.
+ *   Stop.  After iteration i >= 2 whose labels all equal those of i - 1: stop, the centres are the new ones, labels stay.
+ *     Otherwise if the sum over j in ascending order of shift_j <= tol * ((var_x + var_y) + var_z) / 3, or i = max_iter:
+ *     stop, and the pixels are assigned once more with the new centres.  var_x = (Sxx - Sx Sx / n) / n in float64 over the
+ *     valid pixels, sums in the fixed order above (the product x x of a float32 is exact in float64).
+ *   Outputs: labels[v] int8 [H,W]; centres [V,k,3] float32 and counts [V,k] int32, the members of the final labels (device);
+ *     n_iter [V] (HOST) = the last i.  The host waits once per 8 iterations, not once per iteration: a one-wave launch per
+ *     iteration writes the view's state, the launches of later iterations return at once for a view that has stopped.
+ *
+ * B. Opening and components (g4s_normal_components_count / _sizes).  labels[v] int8 [H,W]; lut [V,16] (HOST): label -> rank in
+ *   0 .. 15 or -1 (dropped); a label outside 0 .. 15 has rank -1.
+ *   Opening (open != 0) with the 9x9 square, all ranks at once.  Pixel p survives the erode iff rank(p) >= 0 and every pixel
+ *     of the 9x9 window around p that lies inside the image has rank(p) (pixels outside the image count as members: OpenCV's
+ *     default border of an erode).  opened(p) = rank(p) if some pixel of the window around p inside the image survived (pixels
+ *     outside count as non-members), else -1.  A survivor in the window of p has p in its own window, so it has p's rank: the
+ *     opened masks of the ranks are disjoint.  open == 0: opened = rank.  opened[v], if given, receives it as int8 [H,W].
+ *   Components: 8-connectivity among pixels of equal opened rank >= 0.  size = the pixel count.  Components with size >=
+ *     min_size[v] (>= 1) are kept and numbered 0 .. n - 1 ascending by (rank, first pixel in raster order); components[v] int32
+ *     [H,W] = the number, or -1.  n [V] (HOST) is read back: the one host synchronisation.  g4s_normal_components_sizes, with
+ *     the same views and the workspace untouched in between, writes component_sizes[v] int32 [n_v].
+ *   This is remove_small_isolated_areas (whose median blur is discarded and whose Otsu threshold of a {0, 255} image is the
+ *   identity) followed by the reference's second labelling, which finds the same components again.
+ *   Limit: the views have fewer than 2^31 pixels together.
+ *
+ * C. Join with the masks.  masks[v] is uint8 [M_v,H,W], set iff non-zero (may be NULL for M_v = 0); components[v] as in B
+ *   with n_v components (values outside 0 .. n_v - 1 are "none").
+ *   g4s_plane_pair_counts: areas [sum M_v] int32 = the set pixels of every mask; pairs [sum M_v n_v] int32, view after view,
+ *     pairs[m n_v + c] = the pixels of mask m inside component c.  Both device, cleared and filled.
+ *   g4s_plane_paint: order [sum M_v] (HOST) per view a permutation of its masks; pair_ids [sum M_v n_v] (HOST), 0 or an id in
+ *     1 .. n_ids[v].  seg[v][p] = pair_ids[m n_v + c] of the LAST mask m of the order with a non-zero id for the pixel's
+ *     component c that holds p; 0 if there is none.  id_areas [sum (n_ids[v] + 1)] int32 (device): the pixels per id.
+ *   g4s_plane_relabel: relabel [sum (n_ids[v] + 1)] (HOST), relabel[0] = 0, values in 0 .. n_planes[v].  seg[v][p] =
+ *     relabel[seg[v][p]] in place.  sums [sum (n_planes[v] + 1), 3] int64 (device): per new id the sum over its pixels of
+ *     round-half-even(clamp(x, -2, 2) 2^32) of every normal component x, 0 for a NaN; an integer sum, so independent of the
+ *     order (it cannot overflow for fewer than 2^30 pixels).  The caller divides by 2^32 and the area in float64.
+ *
+ * Differences from the reference, on purpose.  Ids are int32 (the reference's uint8 seg_mask wraps beyond 255 pair ids).
+ *   The inputs are never written.  The k-means seeds are the caller's; an empty cluster keeps its centre; the sums are
+ *   float64 in a fixed order (sklearn sums float32 in chunks).
+ *
+ * Every argument is checked on the host before anything is launched.  The size queries are pure host code and return 0 for
+ * arguments out of range.
+ */
+#define G4S_KMEANS_SPAN 4096 /* pixels per workgroup of the k-means sums */
+#define G4S_KMEANS_MAX_K 16
+
+size_t g4s_kmeans_normals_workspace(int n_views, const int* sizes);
+
+int g4s_kmeans_normals(int n_views, const int* sizes, const float* const* normals, int k, const float* init, int max_iter,
+                       double tol, signed char* const* labels, float* centres, int* counts, int* n_iter, char* workspace,
+                       size_t workspace_bytes, void* stream);
+
+size_t g4s_normal_components_workspace(int n_views, const int* sizes);
+
+int g4s_normal_components_count(int n_views, const int* sizes, const signed char* const* labels, const int* lut, int open,
+                                const int* min_size, signed char* const* opened, int* const* components, int* n,
+                                char* workspace, size_t workspace_bytes, void* stream);
+
+int g4s_normal_components_sizes(int n_views, const int* sizes, const int* n, int* const* component_sizes, char* workspace,
+                                size_t workspace_bytes, void* stream);
+
+size_t g4s_plane_pair_counts_workspace(int n_views);
+
+int g4s_plane_pair_counts(int n_views, const int* sizes, const int* const* components, const unsigned char* const* masks,
+                          const int* n_masks, const int* n_components, int* areas, int* pairs, char* workspace,
+                          size_t workspace_bytes, void* stream);
+
+size_t g4s_plane_paint_workspace(int n_views, int total_masks, int total_pairs);
+
+int g4s_plane_paint(int n_views, const int* sizes, const int* const* components, const unsigned char* const* masks,
+                    const int* n_masks, const int* n_components, const int* order, const int* pair_ids, const int* n_ids,
+                    int* const* seg, int* id_areas, char* workspace, size_t workspace_bytes, void* stream);
+
+size_t g4s_plane_relabel_workspace(int n_views, int total_ids);
+
+int g4s_plane_relabel(int n_views, const int* sizes, int* const* seg, const float* const* normals, const int* n_ids,
+                      const int* relabel, const int* n_planes, long long* sums, char* workspace, size_t workspace_bytes,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
