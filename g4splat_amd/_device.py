@@ -1,4 +1,4 @@
-"""What the scene-stage wrappers (mesh, mesh_eval, visibility, planes, consistency, view_selection, depth_cues, chart_init, plane_masks)
+"""What the scene-stage wrappers (mesh, mesh_eval, visibility, planes, consistency, view_selection, depth_cues, chart_init, plane_masks, plane_fit)
 share on the Python side of a library call: host arrays, device resolution, the per-view map checks, the view stack and the
 one launch helper.  The C++ counterpart is csrc/tsdf/mesh_common.h and view_stack.h ("The Python side of a
 wrapper")."""

@@ -193,6 +193,18 @@ SIGNATURES = {
     "g4s_plane_paint": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "g4s_plane_relabel_workspace": (c_sz, [c_i, c_i]),
     "g4s_plane_relabel": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_plane_fit_gather_workspace": (c_sz, [c_i, c_p, c_i, c_p]),
+    "g4s_plane_fit_gather_count": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_plane_fit_gather_emit": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, ctypes.c_longlong, c_p, c_p,
+                                        c_p, c_sz, c_p]),
+    "g4s_plane_fit_members_workspace": (c_sz, [c_i, c_i, c_i]),
+    "g4s_plane_fit_members_count": (c_i, [c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_plane_fit_members_emit": (c_i, [c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_sz, c_p]),
+    "g4s_plane_fit_workspace": (c_sz, [c_i, c_p]),
+    "g4s_plane_fit_hypotheses": (c_i, [c_i, c_p, c_p, c_i, c_p, c_p, ctypes.c_double, c_p, c_p, c_sz, c_p]),
+    "g4s_plane_fit_score": (c_i, [c_i, c_p, c_p, c_i, c_p, ctypes.c_double, c_p, c_p, c_sz, c_p]),
+    "g4s_plane_fit_refit": (c_i, [c_i, c_p, c_p, c_i, c_p, c_p, ctypes.c_double, c_p, ctypes.c_double, c_p, c_p, c_p, c_p, c_sz,
+                                  c_p]),
 }
 
 _lib = None

@@ -11,7 +11,7 @@ guidance/dense_dn_util.py) and between the merge and the inconsistency solvers (
   refill_unseen_regions, refine_depths_with_planes   the second alignment, the refill, the refined clouds.
 
 Everything per pixel runs in the library, all views in a number of launches that does not depend on the number of views or
-planes; there is no torch path.  The plane FIT (KMeans, RANSAC, SLSQP) stays with the caller: `planes` is an input.
+planes; there is no torch path.  `planes` is an input: plane_fit.fit_global_planes produces it, or the caller does.
 
 A camera is anything with world_view_transform, full_proj_transform, FoVx, FoVy (image_width and image_height are not
 read: a view's size is its maps').  Maps are lists of [H_v, W_v] device tensors, or one stacked [V,H,W] tensor; views may

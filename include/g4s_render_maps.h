@@ -1074,6 +1074,118 @@ int g4s_plane_relabel(int n_views, const int* sizes, int* const* seg, const floa
                       const int* relabel, const int* n_planes, long long* sums, char* workspace, size_t workspace_bytes,
                       void* stream);
 
+/* =====================================================================================================================
+ * Plane fit (g4splat_amd/csrc/tsdf/plane_fit.hip).
+ *
+ * What the reference does per global plane id in 2d-gaussian-splatting/planes/refine_depth_with_planes.py between loading its
+ * maps and pasting the plane depths: the valid points of every (plane, view) pair, KMeans over their rendered normals, the
+ * points of the largest cluster of every pair joined per plane, and RANSACRegressor over a GeneralPlaneRegressor with the
+ * mean cluster normal as prior.  The k-means is g4s_kmeans_normals of "Plane masks", unchanged, over [n,1,3] views.  The
+ * seeds, the top cluster, the prior, the sample triples and the walk over the inlier counts that picks a trial run on the
+ * host over a few numbers (g4splat_amd/plane_fit.py); this section states what the library computes.  The semantics are the
+ * library's own, stated exactly (tests/plane_fit_ref.py restates them in numpy): float64 where named, round-to-nearest-even, no
+ * fused multiply-add, evaluated left to right as written.  No floating-point atomics; integer atomics only for sums.  Two
+ * runs give the same bits.
+ *
+ * Views as in "Plane masks".  Per view depth [H,W] float32, normals [H,W,3] float32, plane_masks [H,W] int32, conf [H,W]
+ * uint8 (set iff non-zero), rays [V,12] (HOST): the Visibility section's ray record.
+ *
+ * A. Gather (g4s_plane_fit_gather_count / _emit).  Pairs e = 0 .. n_pairs - 1 (at most 65535), pair_view and pair_id (HOST).
+ *   Pixel q of the pair's view is valid iff plane_masks[q] == pair_id[e], conf[q] is set, and the three normal components and
+ *   the depth are finite.  _count writes pair_count [n_pairs] (HOST), the valid pixels per pair: the one host
+ *   synchronisation.  The caller decides which pairs to keep and where: pair_row [n_pairs] (HOST, int64) is a pair's first
+ *   output row or -1.  _emit, with the same views and pairs and the workspace untouched in between, writes for every kept
+ *   pair, in raster order, points [n_rows,3] = the back-projection of g4s_depth_to_points (the same device function) and
+ *   out_normals [n_rows,3] = the normals, both float32.  A pair may be listed several times.  Limit: the views of all pairs
+ *   have fewer than 2^31 pixels together.
+ *
+ * B. Members (g4s_plane_fit_members_count / _emit).  The gathered rows of pair e are pair_offset[e] .. pair_offset[e + 1] - 1
+ *   (HOST, from 0 to n_rows); labels [n_rows] int8 (device); top [n_pairs] (HOST).  A row is a member iff its label equals
+ *   its pair's top.  Plane p owns pairs plane_pair[p] .. plane_pair[p + 1] - 1 (HOST, from 0 to n_pairs).  _count writes
+ *   plane_offset [n_planes + 1] (HOST): the members before each plane, the last entry their number.  _emit, with the
+ *   workspace untouched in between, writes plane_points [n_members,3]: the members' points in row order.
+ *
+ * C. The solver.  Given a centroid c, a covariance C (symmetric 3x3) and optionally a unit prior p with alpha > 0, the
+ *   unit normal n that minimises  n^T C n + alpha (1 - |n . p|)^2  -- GeneralPlaneRegressor's objective with the best offset
+ *   substituted -- and d = -n . c.  All float64, only + - * / sqrt and comparisons:
+ *   A = C, or with a prior A_ij = C_ij + (alpha p_i) p_j (i <= j).  V = I.  G4S_PLANE_FIT_SWEEPS cyclic Jacobi sweeps, each
+ *   the rotations (0,1), (0,2), (1,2); a rotation (p,q) with r the third index:
+ *     theta = (a_qq - a_pp) / (2 a_pq); tf = 1 / (|theta| + sqrt(theta theta + 1)); t = 0 if a_pq == 0, else -tf if theta < 0,
+ *     else tf; c = 1 / sqrt(t t + 1); s = t c; h = t a_pq; a_pp -= h; a_qq += h; a_pq = 0;
+ *     (a_rp, a_rq) = (c a_rp - s a_rq, s a_rp + c a_rq); for every row k of V: (v_kp, v_kq) = (c v_kp - s v_kq, s v_kp + c v_kq).
+ *   Eigenvalues l_i = a_ii with the columns of V, ordered by the exchanges (0,1), (1,2), (0,1), each made iff the later value is
+ *   strictly smaller (ascending, stable); then every column is negated iff its component of largest magnitude (the first of
+ *   equals) is negative.
+ *   Without a prior y = (1, 0, 0).  With one: b_i = alpha ((v_0i p_0 + v_1i p_1) + v_2i p_2), g_i = l_i - l_0, and with
+ *   ratio(b, x) = 0 if b == 0 else b / x: h_i = ratio(b_i, g_i) for i = 1, 2 and hh = h_1 h_1 + h_2 h_2.  The hard case, b_0 == 0
+ *   and hh < 1: y = (sqrt(1 - hh), h_1, h_2), the positive root.  Otherwise the root mu of the secular equation sum_i (b_i / (g_i + mu))^2 = 1
+ *   is bisected on [0, alpha]: lo = 0, hi = alpha, G4S_PLANE_FIT_BISECTIONS times mid = (lo + hi) 0.5, s = (t_0 t_0 + t_1 t_1) +
+ *   t_2 t_2 with t_i = ratio(b_i, g_i + mid) (g_0 + mid = mid), lo = mid if s > 1 else hi = mid; y_i = ratio(b_i, g_i + hi).
+ *   n_k = (v_k0 y_0 + v_k1 y_1) + v_k2 y_2, divided by sqrt((n_0 n_0 + n_1 n_1) + n_2 n_2); d = -((n_0 c_0 + n_1 c_1) + n_2 c_2).
+ *
+ * D. Hypotheses (g4s_plane_fit_hypotheses).  Plane p owns rows plane_offset[p] .. plane_offset[p + 1] - 1 of points (HOST
+ *   offsets, at most 65535 planes).  samples [P,T,3] int32 (device) index a plane's own rows; priors [P,3] float64 (HOST) or
+ *   NULL.  hypotheses [P,T,4] float64 (device) = (n, d) of C. for the three points x_0, x_1, x_2 promoted to float64: c =
+ *   ((x_0 + x_1) + x_2) / 3, e_i = x_i - c, C_jk = ((e_0j e_0k + e_1j e_1k) + e_2j e_2k) / 3.  A triple with an index outside the
+ *   plane gives four NaN; nothing is read outside.
+ *
+ * E. Scoring (g4s_plane_fit_score).  counts [P,T] int32 (device) = the number of the plane's points with
+ *   |((x a + y b) + z c) + d| <= threshold in float64, the point promoted.  A NaN is within no threshold.
+ *
+ * F. Refit (g4s_plane_fit_refit).  best [P] (HOST) = a trial or -1.  inlier_mask [plane_offset[P]] uint8 = the test of E. against the
+ *   plane's hypothesis `best` (0 throughout for -1).  moments [P,10] float64 = the sums over the inliers of 1, x, y, z, xx, xy,
+ *   xz, yy, yz, zz in the order of "Plane masks" A. (spans of G4S_PLANE_FIT_SUM_SPAN points, thread t adds points t, t + 256,
+ *   ..., the tree, the four waves, the fold of the partials by index).  coefficients [P,4] float64 = (n, d) of C. with c_j =
+ *   S_j / S_1 and C_jk = S_jk / S_1 - c_j c_k; four NaN for a plane without inliers.
+ *
+ * Differences from the reference, on purpose.  Pixels with a non-finite normal or depth are dropped (sklearn raises on them).
+ *   The solver returns the global minimiser; the reference's SLSQP run from the prior stops up to 5e-5 above it in the
+ *   objective and 3.3 degrees away on the 400 cases of tests/test_plane_fit_cpu.py.  Distances are float64 throughout.  Samples and k-means seeds are the caller's.
+ *
+ * Every argument is checked on the host before anything is launched.  The size queries are pure host code and return 0 for
+ * arguments out of range.
+ */
+#define G4S_PLANE_FIT_SWEEPS 8
+#define G4S_PLANE_FIT_BISECTIONS 80
+#define G4S_PLANE_FIT_SCORE_SPAN 2048 /* points per workgroup of the scoring kernel */
+#define G4S_PLANE_FIT_SUM_SPAN 4096   /* points per workgroup of the refit's sums */
+
+size_t g4s_plane_fit_gather_workspace(int n_views, const int* sizes, int n_pairs, const int* pair_view);
+
+int g4s_plane_fit_gather_count(int n_views, const int* sizes, const float* const* depth, const float* const* normals,
+                               const int* const* plane_masks, const unsigned char* const* conf, int n_pairs,
+                               const int* pair_view, const int* pair_id, int* pair_count, char* workspace,
+                               size_t workspace_bytes, void* stream);
+
+int g4s_plane_fit_gather_emit(int n_views, const int* sizes, const float* rays, const float* const* depth,
+                              const float* const* normals, const int* const* plane_masks, const unsigned char* const* conf,
+                              int n_pairs, const int* pair_view, const int* pair_id, const int* pair_count,
+                              const long long* pair_row, long long n_rows, float* points, float* out_normals, char* workspace,
+                              size_t workspace_bytes, void* stream);
+
+size_t g4s_plane_fit_members_workspace(int n_rows, int n_pairs, int n_planes);
+
+int g4s_plane_fit_members_count(int n_rows, int n_pairs, const int* pair_offset, const signed char* labels, const int* top,
+                                int n_planes, const int* plane_pair, int* plane_offset, char* workspace, size_t workspace_bytes,
+                                void* stream);
+
+int g4s_plane_fit_members_emit(int n_rows, int n_pairs, int n_planes, const float* points, int n_members, float* plane_points,
+                               char* workspace, size_t workspace_bytes, void* stream);
+
+/* The workspace of D., E. and F. */
+size_t g4s_plane_fit_workspace(int n_planes, const int* plane_offset);
+
+int g4s_plane_fit_hypotheses(int n_planes, const int* plane_offset, const float* points, int n_trials, const int* samples,
+                             const double* priors, double alpha, double* hypotheses, char* workspace, size_t workspace_bytes,
+                             void* stream);
+
+int g4s_plane_fit_score(int n_planes, const int* plane_offset, const float* points, int n_trials, const double* hypotheses,
+                        double threshold, int* counts, char* workspace, size_t workspace_bytes, void* stream);
+
+int g4s_plane_fit_refit(int n_planes, const int* plane_offset, const float* points, int n_trials, const double* hypotheses,
+                        const int* best, double threshold, const double* priors, double alpha, unsigned char* inlier_mask,
+                        double* moments, double* coefficients, char* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
