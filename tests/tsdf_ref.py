@@ -61,8 +61,12 @@ def valid_pixels(depth, mask, depth_trunc):
     return ok
 
 
-def view_blocks(depth, mask, intr, E, voxel_size, sdf_trunc, depth_trunc):
-    """Block coordinates the DDA of every valid pixel visits ([N,3], with repeats)."""
+def pixel_walks(depth, mask, intr, E, voxel_size, sdf_trunc, depth_trunc):
+    """The DDA of every valid pixel, one row per pixel in raster order:
+    pixel [n,2] (u, v); a, b [n,3] float32 segment ends in block units; inside [n] (both ends within COORD_LIMIT: the others
+    allocate nothing, length 0); path [n,cap,3] the blocks in walk order, length [n] how many of them count; cut [n] (the
+    walk stopped at cap before it reached floor(b)); ties [n] (steps whose smallest t was shared by two or three axes);
+    cap (the key slots per pixel)."""
     H, W = depth.shape
     fx, fy, cx, cy = (f32(v) for v in intr)
     T, bs = f32(sdf_trunc), f32(8.0) * f32(voxel_size)
@@ -75,27 +79,86 @@ def view_blocks(depth, mask, intr, E, voxel_size, sdf_trunc, depth_trunc):
     a = np.stack(_affine(C, rx * z0, ry * z0, z0), 1) / bs
     b = np.stack(_affine(C, rx * z1, ry * z1, z1), 1) / bs
     ok = np.all((np.abs(a) < COORD_LIMIT) & (np.abs(b) < COORD_LIMIT), 1)
-    a, b = a[ok], b[ok]
-    cell, end = np.floor(a).astype(np.int64), np.floor(b).astype(np.int64)
-    dirv = b - a
+    n = len(d)
+    sel = np.nonzero(ok)[0]
+    path = np.zeros((n, cap, 3), np.int64)
+    length = np.zeros(n, np.int64)
+    ties = np.zeros(n, np.int64)
+    cut = np.zeros(n, bool)
+    a_, b_ = a[sel], b[sel]
+    cell, end = np.floor(a_).astype(np.int64), np.floor(b_).astype(np.int64)
+    dirv = b_ - a_
     step = np.where(end > cell, 1, -1)
-    out = [cell.copy()]
+    path[sel, 0] = cell
+    length[sel] = 1
     with np.errstate(divide="ignore", invalid="ignore"):
         for _ in range(cap - 1):
             live = np.any(cell != end, 1)
             if not live.any():
                 break
-            t = ((cell + (step > 0)).astype(f32) - a) / dirv
+            t = ((cell + (step > 0)).astype(f32) - a_) / dirv
             t = np.where(cell != end, t, np.inf)
             best = np.argmin(t, 1)  # first minimum: ties go to the lower axis
             idx = np.nonzero(live)[0]
+            ties[sel[idx]] += (t[idx] == t[idx, best[idx]][:, None]).sum(1) > 1
             cell[idx, best[idx]] += step[idx, best[idx]]
-            out.append(cell[idx].copy())
-    return np.concatenate(out, 0)
+            path[sel[idx], length[sel[idx]]] = cell[idx]
+            length[sel[idx]] += 1
+    cut[sel] = np.any(cell != end, 1)
+    return dict(pixel=np.stack([vx, vy], 1), a=a, b=b, inside=ok, path=path, length=length, cut=cut, ties=ties, cap=cap)
+
+
+def view_blocks(depth, mask, intr, E, voxel_size, sdf_trunc, depth_trunc):
+    """Block coordinates the DDA of every valid pixel visits ([N,3], with repeats)."""
+    w = pixel_walks(np.asarray(depth), mask, intr, E, voxel_size, sdf_trunc, depth_trunc)
+    path, length = w["path"], w["length"]
+    steps = [path[length > k, k] for k in range(int(length.max()) if len(length) else 0)]
+    return np.concatenate(steps, 0) if steps else np.zeros((0, 3), np.int64)
 
 
 def quantise(rgb):
     return np.floor(np.fmin(np.fmax(np.asarray(rgb, f32), f32(0)), f32(1)) * f32(255)).astype(f32)
+
+
+INTEGRATED, BEHIND, OUTSIDE, INVALID, TRUNCATED = range(5)
+
+
+def voxel_fates(touched, depth, mask, intr, E, voxel_size, sdf_trunc, depth_trunc):
+    """What one view does to the voxels of the blocks `touched` (sorted keys), each [m,512] in lane order:
+    fate -- INTEGRATED, or why the voxel is left alone: BEHIND (not z > 0), OUTSIDE (the frame), INVALID (its pixel),
+    TRUNCATED (not sdf > -sdf_trunc);  z (camera depth of the centre);  u, v (its pixel, -1 if BEHIND or OUTSIDE);
+    sdf (NaN unless INTEGRATED or TRUNCATED)."""
+    depth = np.asarray(depth, f32)
+    H, W = depth.shape
+    v_, T = f32(voxel_size), f32(sdf_trunc)
+    lane = np.arange(512)
+    loc = np.stack([lane & 7, (lane >> 3) & 7, lane >> 6], 1)
+    g = (unpack_keys(touched)[:, None, :] * 8 + loc[None]).reshape(-1, 3)
+    p = (g.astype(f32) + f32(0.5)) * v_
+    E4 = np.asarray(E, f32).reshape(4, 4)
+    x, y, z = _affine(E4, p[:, 0], p[:, 1], p[:, 2])
+    fx, fy, cx, cy = (f32(q) for q in intr)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        fu = np.floor((fx * x) / z + cx + f32(0.5))
+        fv = np.floor((fy * y) / z + cy + f32(0.5))
+    front = z > 0
+    ok = front & (fu >= 0) & (fu <= W - 1) & (fv >= 0) & (fv <= H - 1)
+    fate = np.where(front, OUTSIDE, BEHIND)
+    U, V = np.full(len(z), -1, np.int64), np.full(len(z), -1, np.int64)
+    S = np.full(len(z), np.nan, f32)
+    idx = np.nonzero(ok)[0]
+    u, v = fu[idx].astype(np.int64), fv[idx].astype(np.int64)
+    U[idx], V[idx] = u, v
+    good = valid_pixels(depth, mask, depth_trunc)[v, u]
+    fate[idx[~good]] = INVALID
+    idx, u, v = idx[good], u[good], v[good]
+    d = depth[v, u]
+    a, b = (fu[idx] - cx) / fx, (fv[idx] - cy) / fy
+    sdf = (d - z[idx]) * np.sqrt((f32(1) + a * a) + b * b)
+    S[idx] = sdf
+    fate[idx] = np.where(sdf > -T, INTEGRATED, TRUNCATED)
+    m = len(touched)
+    return dict(fate=fate.reshape(m, 512), z=z.reshape(m, 512), u=U.reshape(m, 512), v=V.reshape(m, 512), sdf=S.reshape(m, 512))
 
 
 class RefVolume:
@@ -106,10 +169,11 @@ class RefVolume:
         self.tsdf = np.zeros((0, 512), f32)
         self.weight = np.zeros((0, 512), f32)
         self.color = np.zeros((0, 512, 3), f32)
+        self.last_touched = np.zeros(0, np.int64)  # sorted keys of the blocks the latest view touched
 
     def integrate(self, depth, rgb, intr, E, mask=None):
+        """Fuse one view; returns (touched blocks, new blocks) like TSDFVolume.integrate.  last_touched: their keys."""
         depth = np.asarray(depth, f32)
-        H, W = depth.shape
         blocks = view_blocks(depth, mask, intr, E, self.v, self.T, self.depth_trunc)
         touched = np.unique(pack_keys(blocks)) if len(blocks) else np.zeros(0, np.int64)
         new = np.setdiff1d(touched, self.keys)
@@ -122,39 +186,22 @@ class RefVolume:
         self.tsdf = np.concatenate([self.tsdf, np.zeros((len(new), 512), f32)])
         self.weight = np.concatenate([self.weight, np.zeros((len(new), 512), f32)])
         self.color = np.concatenate([self.color, np.zeros((len(new), 512, 3), f32)])
+        self.last_touched = touched
         if len(touched) == 0:
-            return
+            return 0, 0
         tslot = self.slots[np.searchsorted(self.keys, touched)]
-        lane = np.arange(512)
-        loc = np.stack([lane & 7, (lane >> 3) & 7, lane >> 6], 1)
-        g = (unpack_keys(touched)[:, None, :] * 8 + loc[None]).reshape(-1, 3)
-        slot = np.repeat(tslot, 512)
-        ln = np.tile(lane, len(touched))
-        p = (g.astype(f32) + f32(0.5)) * self.v
-        E4 = np.asarray(E, f32).reshape(4, 4)
-        x, y, z = _affine(E4, p[:, 0], p[:, 1], p[:, 2])
-        fx, fy, cx, cy = (f32(q) for q in intr)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            fu = np.floor((fx * x) / z + cx + f32(0.5))
-            fv = np.floor((fy * y) / z + cy + f32(0.5))
-        ok = (z > 0) & (fu >= 0) & (fu <= W - 1) & (fv >= 0) & (fv <= H - 1)
-        idx = np.nonzero(ok)[0]
-        u, v = fu[idx].astype(np.int64), fv[idx].astype(np.int64)
-        good = valid_pixels(depth, mask, self.depth_trunc)[v, u]
-        idx, u, v = idx[good], u[good], v[good]
-        d = depth[v, u]
-        a, b = (fu[idx] - cx) / fx, (fv[idx] - cy) / fy
-        sdf = (d - z[idx]) * np.sqrt((f32(1) + a * a) + b * b)
-        keep = sdf > -self.T
-        idx, u, v, sdf = idx[keep], u[keep], v[keep], sdf[keep]
+        f = voxel_fates(touched, depth, mask, intr, E, self.v, self.T, self.depth_trunc)
+        idx = np.nonzero(f["fate"].reshape(-1) == INTEGRATED)[0]
+        u, v, sdf = f["u"].reshape(-1)[idx], f["v"].reshape(-1)[idx], f["sdf"].reshape(-1)[idx]
         t = np.fmin(f32(1), sdf / self.T)
-        s, l = slot[idx], ln[idx]
+        s, l = np.repeat(tslot, 512)[idx], idx % 512
         w = self.weight[s, l]
         w1 = w + f32(1)
         self.tsdf[s, l] = (self.tsdf[s, l] * w + t) / w1
         q = quantise(np.asarray(rgb, f32)[:, v, u]).T
         self.color[s, l] = (self.color[s, l] * w[:, None] + q) / w1[:, None]
         self.weight[s, l] = w1
+        return len(touched), len(new)
 
     def voxels(self):
         """(tsdf, weight, colour) in table order: [n,512], [n,512], [n,512,3]."""
