@@ -13,7 +13,7 @@ AXIS0_BITS = (0xBF3504F3, 0x3F3504F3, 0x00000000)
 AXIS1_BITS = (0xBED105EC, 0xBED105EC, 0x3F5105EC)
 
 
-def _bits(bits, dtype):
+def _from_bits(bits, dtype):
     return np.array(bits, np.uint32).view(f32).astype(dtype)
 
 
@@ -114,7 +114,7 @@ def surfels_of_faces(A, B, C, ca, cb, cc, normalized_scales, normal_scale):
     """The surfels of the faces (A, B, C) [F,3] with vertex colours ca, cb, cc [F,3] (not yet clamped); every array already
     in the working dtype.  Returns means, scales, quaternions, colors and the rotation matrices."""
     dt = A.dtype.type
-    b, e0, e1 = _bits(BARY_BITS, dt), _bits(AXIS0_BITS, dt), _bits(AXIS1_BITS, dt)
+    b, e0, e1 = _from_bits(BARY_BITS, dt), _from_bits(AXIS0_BITS, dt), _from_bits(AXIS1_BITS, dt)
     ns = dt(f32(normalized_scales))
 
     def clamp(x):
@@ -187,3 +187,44 @@ def select_init_views(n_input, n_extra):
     ids = list(range(n_input)) if n_input <= 50 else [int(x) for x in np.linspace(0, n_input - 1, 50, dtype=int)]
     extra = list(range(n_extra)) if n_extra <= 30 else list(range(10)) + list(range(15, 25)) + list(range(30, n_extra))
     return ids, extra
+
+
+def check_against_golden(g, got, factor):
+    """`got`: means, scales, quaternions, colors of the kept faces in order, and the keep mask of all faces."""
+    near, ref_keep = g["near"], g["ref64_keep"]
+    assert near.sum() <= 0.01 * len(near)
+    assert np.array_equal(np.asarray(got["keep"])[~near], ref_keep[~near])
+    both = np.asarray(got["keep"]) & ref_keep
+    mine, theirs = (np.cumsum(got["keep"]) - 1)[both], (np.cumsum(ref_keep) - 1)[both]
+    assert both.sum() >= 100
+    for key in ("means", "scales", "colors"):
+        err = np.abs(np.asarray(got[key], f64)[mine] - g["ref64_" + key][theirs]).max()
+        print(f"{key}: largest error {err:.3e}, bound {factor * g['yard'][key]:.3e}")
+        assert err <= factor * g["yard"][key], key
+    R = quaternion_to_matrix(np.asarray(got["quaternions"])[mine])
+    for name, want in (("rotation of the quaternion", quaternion_to_matrix(g["ref64_quaternions"][theirs])),
+                       ("the reference's rotation", g["ref64_rotations"][theirs])):
+        err = np.abs(R - want).max()
+        print(f"{name}: largest error {err:.3e}, bound {factor * g['yard']['rotations']:.3e}")
+        assert err <= factor * g["yard"]["rotations"], name
+    q = np.asarray(got["quaternions"])
+    assert (q[:, 0] >= 0).all()
+
+
+def pair_cloud(n_pairs=40, seed=5):
+    """Two points per voxel of edge 0.1, the pairs' indices i and a partner of the other parity: every index sum is odd, so
+    every mean index ends in .5 -- the half-way case."""
+    rng = np.random.default_rng(seed)
+    centres = (np.stack(np.meshgrid(np.arange(4), np.arange(5), np.arange(2), indexing="ij"), -1).reshape(-1, 3)[:n_pairs] + 0.5) * 0.1
+    order = rng.permutation(n_pairs)
+    evens, odds = np.arange(0, 2 * n_pairs, 2), np.arange(1, 2 * n_pairs, 2)
+    pts = np.zeros((2 * n_pairs, 3))
+    pts[evens] = centres[order] + rng.uniform(-0.01, 0.01, (n_pairs, 3))
+    pts[odds] = centres[rng.permutation(order)] + rng.uniform(-0.01, 0.01, (n_pairs, 3))
+    return pts.astype(f32)
+
+
+def random_cloud(n=1000, seed=8):
+    """About three points per voxel of edge 0.1."""
+    rng = np.random.default_rng(seed)
+    return rng.uniform(0.0, 0.1 * round((n / 3) ** (1 / 3)), (n, 3)).astype(f32)

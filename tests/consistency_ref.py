@@ -18,7 +18,7 @@ def surface(points, cam, depth, depth_threshold=0.1, dtype=f32):
     """(vis bool [n], pix int64 [n]): SURFACE of every point in one view and the row-major index of its tap (-1 where
     the point does not pass)."""
     ft = dtype
-    depth = vr._np(depth, ft)
+    depth = vr._as(depth, ft)
     H, W = depth.shape
     z, u, v, inside = vr.project(points, cam, W, H, ft)
     vis = np.zeros(len(z), bool)

@@ -237,3 +237,19 @@ def fit_global_planes(cams, depths, normals, masks, confs, gdict, threshold=0.01
     for i, (key, pts, prior, mine) in enumerate(planes):
         out[key] = dict(fit_points(pts, prior, samples[i], threshold, alpha), points=pts, prior=prior, pairs=mine)
     return out
+
+
+def within_yardstick(g, key, normal, centre, factor=2.0):
+    """The plane lies within `factor` times the recorded yardstick of EVERY one of the reference's eight results: the angle
+    between the normals, and the offset along the normal at the common point.  Returns the two largest figures."""
+    angle_bar, offset_bar = factor * g[f"yardstick_{key}"]
+    common = g[f"common_{key}"]
+    normal, centre = np.asarray(normal, np.float64), np.asarray(centre, np.float64)
+    worst_angle = worst_offset = 0.0
+    for rn, rc in zip(g[f"ref_normal_{key}"], g[f"ref_centre_{key}"]):
+        n = normal * (1.0 if np.dot(normal, rn) >= 0 else -1.0)
+        worst_angle = max(worst_angle, float(np.arccos(min(1.0, np.dot(n, rn)))))
+        worst_offset = max(worst_offset, abs(float(np.dot(n, common - centre)) - float(np.dot(rn, common - rc))))
+    print(f"plane {key}: angle {worst_angle:.3e} (bar {angle_bar:.3e}), offset {worst_offset:.3e} (bar {offset_bar:.3e})")
+    assert worst_angle <= angle_bar and worst_offset <= offset_bar, (key, worst_angle, angle_bar, worst_offset, offset_bar)
+    return worst_angle, worst_offset

@@ -262,3 +262,9 @@ def excavate_planes(normals, masks, comps, n, min_plane_size, max_planes=100):
     if not areas:
         return new, None, None, count
     return new, np.stack(avg_normals), np.array(areas, np.int64), count
+
+
+def unit_normals(rng, H, W, n_dirs=5, noise=0.2):
+    dirs = rng.normal(size=(n_dirs, 3))
+    n = dirs[rng.integers(0, n_dirs, (H, W))] + noise * rng.normal(size=(H, W, 3))
+    return (n / np.linalg.norm(n, axis=2, keepdims=True)).astype(np.float32)

@@ -15,7 +15,7 @@ import visibility_ref as vr
 f32 = np.float32
 
 
-def _np(a):
+def _host(a):
     if hasattr(a, "detach"):
         a = a.detach().cpu().numpy()
     return np.asarray(a)
@@ -36,7 +36,7 @@ def candidates(points, cam, W, H, dtype=f32):
 
 def front_labels(points, cam, mask, depth_thresh=0.01, dtype=f32):
     """int64 [n]: the mask value of every front point, 0 elsewhere.  depth_thresh < 0: no depth test."""
-    mask = _np(mask)
+    mask = _host(mask)
     H, W = mask.shape
     cand, pix, z = candidates(points, cam, W, H, dtype)
     idx = np.nonzero(cand)[0]
@@ -69,7 +69,7 @@ def local_planes(labels):
 
 
 def mask_plane_ids(mask):
-    return [int(i) for i in np.unique(_np(mask)) if i != 0]
+    return [int(i) for i in np.unique(_host(mask)) if i != 0]
 
 
 def rate(G, S):

@@ -13,16 +13,6 @@ MODES = (0, 1, 2, 3, 7, 10, 15)
 CHUNK = 64  # destination rows per workgroup of the accumulate kernel
 
 
-def same_bits(got, want, what=""):
-    """Equal bit for bit; a NaN has to meet a NaN (its payload is not compared)."""
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.dtype == want.dtype == f32 and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
-    nan = np.isnan(want)
-    assert np.array_equal(np.isnan(got), nan), (what, "NaN positions differ")
-    g, w = got[~nan].view(np.uint32), want[~nan].view(np.uint32)
-    assert np.array_equal(g, w), (what, int((g != w).sum()), "elements differ")
-
-
 # ---- the operations --------------------------------------------------------------------------------------------------
 def pack_rows(segs, idx, n, packed, mode):
     """g4s_pack_rows over the float32 [P, w_s] arrays `segs` and the flat float32 array `packed`, row after row."""

@@ -9,49 +9,20 @@ restatement within twice it.  The keep mask is compared exactly on the faces who
 than the ratio's (relative) yardstick; the generator asserts that at most 1 % of the faces are nearer, and so does this
 file.  Rotations are compared as matrices rebuilt from the quaternions, so q and -q are the same answer."""
 import ctypes
-import json
-import os
 
 import numpy as np
 import pytest
 
 import chart_init_ref as cr
+from chart_init_ref import check_against_golden, pair_cloud, random_cloud
+from support import load_chart_init_golden
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 f32, f64 = np.float32, np.float64
-
-
-def load_golden():
-    g = dict(np.load(os.path.join(HERE, "golden", "chart_init.npz")))
-    g["yard"] = json.loads(str(g["yardstick"]))
-    return g
 
 
 @pytest.fixture(scope="module")
 def golden():
-    return load_golden()
-
-
-def check_against_golden(g, got, factor):
-    """`got`: means, scales, quaternions, colors of the kept faces in order, and the keep mask of all faces."""
-    near, ref_keep = g["near"], g["ref64_keep"]
-    assert near.sum() <= 0.01 * len(near)
-    assert np.array_equal(np.asarray(got["keep"])[~near], ref_keep[~near])
-    both = np.asarray(got["keep"]) & ref_keep
-    mine, theirs = (np.cumsum(got["keep"]) - 1)[both], (np.cumsum(ref_keep) - 1)[both]
-    assert both.sum() >= 100
-    for key in ("means", "scales", "colors"):
-        err = np.abs(np.asarray(got[key], f64)[mine] - g["ref64_" + key][theirs]).max()
-        print(f"{key}: largest error {err:.3e}, bound {factor * g['yard'][key]:.3e}")
-        assert err <= factor * g["yard"][key], key
-    R = cr.quaternion_to_matrix(np.asarray(got["quaternions"])[mine])
-    for name, want in (("rotation of the quaternion", cr.quaternion_to_matrix(g["ref64_quaternions"][theirs])),
-                       ("the reference's rotation", g["ref64_rotations"][theirs])):
-        err = np.abs(R - want).max()
-        print(f"{name}: largest error {err:.3e}, bound {factor * g['yard']['rotations']:.3e}")
-        assert err <= factor * g["yard"]["rotations"], name
-    q = np.asarray(got["quaternions"])
-    assert (q[:, 0] >= 0).all()
+    return load_chart_init_golden()
 
 
 def test_golden_covers_what_it_claims(golden):
@@ -139,25 +110,6 @@ def replay_index_recovery(points, voxel_size):
         s, k = out.get(key, (0.0, 0))
         out[key] = (s + colour[i], k + 1)
     return np.array([np.round(out[key][0] / out[key][1] * n) for key in sorted(out)]).astype(np.int64)
-
-
-def pair_cloud(n_pairs=40, seed=5):
-    """Two points per voxel of edge 0.1, the pairs' indices i and a partner of the other parity: every index sum is odd, so
-    every mean index ends in .5 -- the half-way case."""
-    rng = np.random.default_rng(seed)
-    centres = (np.stack(np.meshgrid(np.arange(4), np.arange(5), np.arange(2), indexing="ij"), -1).reshape(-1, 3)[:n_pairs] + 0.5) * 0.1
-    order = rng.permutation(n_pairs)
-    evens, odds = np.arange(0, 2 * n_pairs, 2), np.arange(1, 2 * n_pairs, 2)
-    pts = np.zeros((2 * n_pairs, 3))
-    pts[evens] = centres[order] + rng.uniform(-0.01, 0.01, (n_pairs, 3))
-    pts[odds] = centres[rng.permutation(order)] + rng.uniform(-0.01, 0.01, (n_pairs, 3))
-    return pts.astype(f32)
-
-
-def random_cloud(n=1000, seed=8):
-    """About three points per voxel of edge 0.1."""
-    rng = np.random.default_rng(seed)
-    return rng.uniform(0.0, 0.1 * round((n / 3) ** (1 / 3)), (n, 3)).astype(f32)
 
 
 @pytest.mark.parametrize("cloud", [pair_cloud(), pair_cloud(33, 6), random_cloud(), random_cloud(1, 2), random_cloud(300, 4) * f32(0.01)])

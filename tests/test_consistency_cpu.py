@@ -2,8 +2,6 @@
 g4splat_amd/consistency.py against what the reference's two solver scripts wrote (tests/golden/make_golden_consistency.py):
 confident maps and repainted images on the agreed set, the anchors, the step order, the chain walk against a literal
 in-place repaint.  No GPU: the GPU tests (tests/test_gpu_consistency.py) hold the library to the restatement bit for bit."""
-import json
-import os
 from types import SimpleNamespace
 
 import numpy as np
@@ -12,35 +10,14 @@ import torch
 
 import consistency_ref as cr
 from g4splat_amd import consistency
+from support import load_consistency_golden
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "consistency.npz")
 f32 = np.float32
-
-
-def load_golden():
-    g = np.load(GOLDEN)
-    V = len(g["wvt"])
-    cams = [SimpleNamespace(world_view_transform=g["wvt"][i], full_proj_transform=g["full"][i], FoVx=float(g["fov"][i, 0]),
-                            FoVy=float(g["fov"][i, 1])) for i in range(V)]
-    gdict = {int(k): [(int(v), int(p)) for v, p in pairs] for k, pairs in json.loads(str(g["dict"])).items()}
-    images = [im for im in g["images"]]
-
-    def agreed(key, shape):
-        return np.unpackbits(g[key])[: int(np.prod(shape))].astype(bool).reshape(shape)
-
-    return SimpleNamespace(
-        g=g, cams=cams, depths=[d for d in g["depths"]], clouds=[c for c in g["clouds"]], points=g["clouds"].reshape(-1, 3),
-        images=images, float_images=[im.astype(f32) / f32(255) for im in images],  # the cameras' original_image
-        masks=[m for m in g["masks"]], n_input=int(g["n_input"]), gdict=gdict, anchors=[int(a) for a in g["anchors"]],
-        threshold=float(g["depth_threshold"]), point_conf=g["point_conf"], point_png=g["point_png"], plane_png=g["plane_png"],
-        point_conf_agreed=agreed("point_conf_agreed", g["point_conf"].shape),
-        point_png_agreed=agreed("point_png_agreed", g["point_png"].shape[:3]),
-        plane_png_agreed=agreed("plane_png_agreed", g["plane_png"].shape[:3]), stats=json.loads(str(g["stats"])))
 
 
 @pytest.fixture(scope="module")
 def golden():
-    return load_golden()
+    return load_consistency_golden()
 
 
 @pytest.fixture(scope="module")

@@ -6,40 +6,19 @@ The yardstick of every float output is the largest |float32 run - float64 run| o
 recorded by the generator: the float64 restatement has to be within it of the reference's float64 results, the float32
 restatement within twice it."""
 import ctypes
-import json
-import os
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 
 import depth_cues_ref as dr
+from support import load_depth_cues_golden
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 f32, f64 = np.float32, np.float64
-
-
-def load_golden():
-    g = np.load(os.path.join(HERE, "golden", "depth_cues.npz"))
-    V = len(g["wvt"])
-    H, W = g["depths"].shape[1:]
-    cams = [SimpleNamespace(world_view_transform=g["wvt"][v], full_proj_transform=g["full"][v], FoVx=float(g["fov"][v, 0]),
-                            FoVy=float(g["fov"][v, 1]), image_width=W, image_height=H) for v in range(V)]
-    gdict = {int(k): [(int(v), int(p)) for v, p in pairs] for k, pairs in json.loads(str(g["gdict"])).items()}
-    planes = {int(k): (row[:3].copy(), row[3:].copy()) for k, row in zip(g["plane_keys"], g["plane_rows"])}
-    disps = list(g["disps"])
-    out = SimpleNamespace(g=g, V=V, H=H, W=W, cams=cams, gdict=gdict, planes=planes, n_input=int(g["n_input"]),
-                          threshold=float(g["threshold"]), depths=list(g["depths"]), masks=list(g["masks"]), disps=disps,
-                          alphas=list(g["alphas"]), monos=[(f32(1) / d).astype(f32) for d in disps], confs=list(g["confs"]),
-                          yard=json.loads(str(g["yardstick"])), agreed=g["agreed"], visible=[a > f32(g["threshold"]) for a in g["alphas"]])
-    # the merged depth of the reference's float64 run: the rendered depth where visible, its aligned depth elsewhere
-    out.ref_merged = np.stack([np.where(out.visible[v], g["depths"][v].astype(f64), g["ref64_aligned_depth"][v]) for v in range(V)])
-    return out
 
 
 @pytest.fixture(scope="module")
 def golden():
-    return load_golden()
+    return load_depth_cues_golden()
 
 
 def _within(got, want, bound, keep=None):

@@ -17,26 +17,13 @@ import torch
 import chart_init_ref as cr
 import mesh_eval_ref as mr
 from g4splat_amd import chart_init, mesh_eval, synthetic, visibility
-from test_chart_init_cpu import check_against_golden, load_golden, pair_cloud, random_cloud
+from chart_init_ref import check_against_golden, pair_cloud, random_cloud
+from support import DEV, dev, load_chart_init_golden, same_bits
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda:0")
 f32 = np.float32
 KEYS = ("means", "scales", "quaternions", "colors")
-
-
-def _dev(a):
-    return torch.as_tensor(np.ascontiguousarray(a), device=DEV)
-
-
-def _same_bits(got, want, what=""):
-    """Equal bit for bit; a NaN has to meet a NaN (its payload is not compared)."""
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
-    nan = np.isnan(want)
-    assert np.array_equal(np.isnan(got), nan), what
-    assert np.array_equal(got[~nan].view(np.uint32), want[~nan].view(np.uint32)), (what, int((got[~nan] != want[~nan]).sum()))
 
 
 def _scene(V, H, W, seed, stretch=6.0):
@@ -54,8 +41,8 @@ def _scene(V, H, W, seed, stretch=6.0):
 def _check(points, images, masks=None, ratio_th=5.0, normalized_scales=0.5, normal_scale=1e-10, as_list=False):
     """pointmap_surfels on the device against the restatement; returns (device result as numpy, restatement)."""
     want = cr.pointmap_surfels(points, images, masks, ratio_th, normalized_scales, normal_scale, f32)
-    p, i = _dev(points), _dev(images)
-    m = None if masks is None else _dev(masks)
+    p, i = dev(points), dev(images)
+    m = None if masks is None else dev(masks)
     if as_list:
         p, i, m = list(p), list(i), (None if m is None else list(m))
     got = chart_init.pointmap_surfels(p, i, m, ratio_th, normalized_scales, normal_scale)
@@ -65,7 +52,7 @@ def _check(points, images, masks=None, ratio_th=5.0, normalized_scales=0.5, norm
         assert got[k].dtype == torch.float32 and got[k].device == DEV and got[k].is_contiguous()
         out[k] = got[k].cpu().numpy()
         assert len(out[k]) == int(want["keep"].sum()), (k, len(out[k]), int(want["keep"].sum()))
-        _same_bits(out[k], want[k], k)
+        same_bits(out[k], want[k], k, nan_payload=False)
     return out, want
 
 
@@ -74,7 +61,7 @@ def test_one_cell(hip_lib):
     img = np.array([[[[0.1, 0.2, 0.3], [1.5, 0.5, -0.5]], [[0.9, 0.8, 0.7], [0.4, 0.4, 0.4]]]], f32)
     got, want = _check(pts, img)
     assert len(got["means"]) == 2 and want["keep"].tolist() == [True, True]
-    _same_bits(got["scales"][:, 2], np.full(2, f32(1e-10)))
+    same_bits(got["scales"][:, 2], np.full(2, f32(1e-10)), nan_payload=False)
     assert (got["quaternions"][:, 0] >= 0).all() and (got["colors"] >= 0).all() and (got["colors"] <= 1).all()
 
 
@@ -93,7 +80,7 @@ def test_workgroups_straddle_halves_and_views(hip_lib):
     assert per_half % 256 != 0 and per_half % 64 != 0 and (kept > 0).all() and (kept < per_half).all()
     again, _w = _check(pts, img, as_list=True)  # lists of views, and a second run: the same bits
     for k in KEYS:
-        assert got[k].tobytes() == again[k].tobytes()
+        same_bits(got[k], again[k], k)
 
 
 @pytest.mark.parametrize("V", [1, 2])
@@ -149,7 +136,7 @@ def test_masks(hip_lib):
     for full in (np.ones(pts.shape[:3], bool), np.zeros(pts.shape[:3], bool)):  # an all-false mask removes nothing
         got, _w = _check(pts, img, full)
         for k in KEYS:
-            assert got[k].tobytes() == free[k].tobytes()
+            same_bits(got[k], free[k], k)
     single = np.zeros(pts.shape[:3], bool)
     single[1, 36, 28] = True  # the last pixel of the last view: one face_2 touches it
     got, want = _check(pts, img, single, ratio_th=1e30)
@@ -187,42 +174,42 @@ def test_depth_form_equals_point_form_over_depths_to_points(hip_lib):
     depths[1, 5, 5], depths[2, 7, 3] = np.nan, 0.0
     images = rng.uniform(0, 1, (V, H, W, 3)).astype(f32)
     masks = rng.random((V, H, W)) < 0.5
-    d, i, m = _dev(depths), _dev(images), _dev(masks)
+    d, i, m = dev(depths), dev(images), dev(masks)
     points = torch.stack([visibility.depths_to_points(d[v], cams[v]).reshape(H, W, 3) for v in range(V)])
-    _same_bits(points[0].cpu().numpy(), cr.depth_points(depths[0], visibility.ray_record(cams[0], W, H)))
+    same_bits(points[0], cr.depth_points(depths[0], visibility.ray_record(cams[0], W, H)), nan_payload=False)
     for mask in (None, m):
         a = chart_init.depthmap_surfels(d, cams, i, mask, ratio_th=4.0)
         b = chart_init.pointmap_surfels(points, i, mask, ratio_th=4.0)
         assert 0 < a["means"].shape[0] < 2 * V * (H - 1) * (W - 1)
         for k in KEYS:
-            _same_bits(a[k].cpu().numpy(), b[k].cpu().numpy(), k)
+            same_bits(a[k], b[k], k, nan_payload=False)
         c = chart_init.depthmap_surfels([x[None] for x in d], cams, list(i), None if mask is None else list(mask), ratio_th=4.0)
         for k in KEYS:  # lists of views, depth maps as [1,H,W]
-            assert c[k].cpu().numpy().tobytes() == a[k].cpu().numpy().tobytes()
+            same_bits(c[k], a[k], k)
 
 
 def test_golden_through_the_device(hip_lib):
-    g = load_golden()
+    g = load_chart_init_golden()
     got, want = _check(g["points"], g["images"], None, float(g["ratio_th"]), float(g["normalized_scales"]), float(g["normal_scale"]))
     check_against_golden(g, dict(got, keep=want["keep"]), 2.0)
     # the reference-named entry points: pa data ignores its masks, charts data divides by its scale factor
-    p, i = _dev(g["points"]), list(_dev(g["images"]))
+    p, i = dev(g["points"]), list(dev(g["images"]))
     none = [torch.zeros((1, 9, 7), device=DEV), torch.zeros((1, 9, 7), device=DEV)]
     pa = chart_init.get_gaussian_parameters_from_pa_data(p, i, normal_scale=float(g["normal_scale"]), visibility_masks=none)
     for k in KEYS:
-        assert pa[k].cpu().numpy().tobytes() == got[k].tobytes()
+        same_bits(pa[k], got[k], k)
     confs = torch.rand((2, 9, 7), device=DEV, generator=torch.Generator(DEV).manual_seed(1))
     charts = chart_init.get_gaussian_parameters_from_charts_data({"pts": p * 2.0, "confs": confs, "scale_factor": 2.0}, i,
                                                                  conf_th=0.5, normal_scale=2e-10)
     masked, _w = _check(g["points"], g["images"], (confs > 0.5).cpu().numpy())
     for k in KEYS:
-        assert charts[k].cpu().numpy().tobytes() == masked[k].tobytes()
+        same_bits(charts[k], masked[k], k)
     vis = [torch.ones((1, 9, 7), device=DEV), torch.zeros((1, 9, 7), device=DEV)]
     charts = chart_init.get_gaussian_parameters_from_charts_data({"pts": p * 2.0, "confs": confs, "scale_factor": 2.0}, i,
                                                                  conf_th=0.5, normal_scale=2e-10, visibility_masks=vis)
     masked, _w = _check(g["points"], g["images"], ((confs * torch.cat(vis)) > 0.1).cpu().numpy())
     for k in KEYS:
-        assert charts[k].cpu().numpy().tobytes() == masked[k].tobytes()
+        same_bits(charts[k], masked[k], k)
 
 
 # ---- the index pick -----------------------------------------------------------------------------------------------------------
@@ -230,7 +217,7 @@ def test_golden_through_the_device(hip_lib):
                                          ("three per voxel", random_cloud())])
 def test_index_pick_equals_the_restatement(hip_lib, name, cloud):
     cloud = np.ascontiguousarray(cloud, f32).reshape(-1, 3)
-    pts = _dev(cloud)
+    pts = dev(cloud)
     idx, factor = chart_init.voxel_downsample_gaussians({"means": pts}, voxel_size=0.1)
     want = cr.voxel_pick_indices(cloud, 0.1)
     assert idx.dtype == torch.int64 and idx.device == DEV
@@ -244,7 +231,7 @@ def test_index_pick_equals_the_restatement(hip_lib, name, cloud):
     _u, inverse, counts = np.unique(cells[:, ::-1], axis=0, return_inverse=True, return_counts=True)
     alone = np.nonzero(counts == 1)[0]
     assert np.array_equal(inverse.reshape(-1)[got[alone]], alone)
-    _same_bits(down[alone], cloud[got[alone]])
+    same_bits(down[alone], cloud[got[alone]], nan_payload=False)
     if name == "one voxel":
         assert len(got) == 1
     if name == "three per voxel":
@@ -259,8 +246,8 @@ def test_initial_gaussians_render(hip_lib, cap):
     W, H = 64, 48
     rng = np.random.default_rng(10)
     cams = _cameras(3, W, H)
-    depths = [_dev((2.5 + 0.02 * rng.standard_normal((H, W))).astype(f32)) for _ in cams]
-    images = [_dev(rng.uniform(0, 1, (H, W, 3)).astype(f32)) for _ in cams]
+    depths = [dev((2.5 + 0.02 * rng.standard_normal((H, W))).astype(f32)) for _ in cams]
+    images = [dev(rng.uniform(0, 1, (H, W, 3)).astype(f32)) for _ in cams]
     means, scales, quats, colors = chart_init.initial_gaussians(depths[:2], cams[:2], images[:2], depths[2:], cams[2:], images[2:],
                                                                 max_gaussians_num=100 if cap else 10_000_000,
                                                                 use_downsample_gaussians=True)

@@ -14,12 +14,12 @@ import torch
 
 import chart_losses_ref as ref
 from g4splat_amd import losses
+from support import DEV
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "chart_losses.npz")
 CASES = ["ragged", "m1", "m0", "row", "half", "flat"]
 MAPS = ("rend_normal", "surf_normal", "surf_depth", "prior_depth", "prior_normal", "prior_curv")
-DEV = "cuda:0"
 TIGHT = 3.5e-6  # ten times the worst gradient error measured (3.4e-7, surf_depth at 1200x1600 against eager)
 
 

@@ -2,7 +2,6 @@
 of the contract (tests/consistency_ref.py): confident maps, images, point states, counts and anchors are compared exactly.
 The restatement itself is pinned to what the reference's scripts wrote in tests/test_consistency_cpu.py."""
 import ctypes
-import math
 from types import SimpleNamespace
 
 import numpy as np
@@ -11,71 +10,40 @@ import torch
 
 import consistency_ref as cr
 from g4splat_amd import consistency
-from test_consistency_cpu import load_golden
+from support import DEV, dev, devs, hosts, load_consistency_golden, pinhole_camera, same_bits
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda:0")
 f32 = np.float32
-
-
-def _dev(a):
-    return torch.as_tensor(np.ascontiguousarray(a), device=DEV)
-
-
-def _devs(arrays):
-    return [_dev(a) for a in arrays]
-
-
-def _camera(W, H, fx, fy, t=(0.0, 0.0, 0.0)):
-    """A camera looking down +z from -t: world_view_transform = identity with the translation in its last row."""
-    M = np.eye(4, dtype=np.float32)
-    M[3, :3] = t
-    return SimpleNamespace(world_view_transform=M, full_proj_transform=M, FoVx=2.0 * math.atan(W / (2.0 * fx)),
-                           FoVy=2.0 * math.atan(H / (2.0 * fy)))
-
-
-def _np(tensors):
-    return [t.cpu().numpy() for t in tensors]
-
-
-def _bits(t):
-    return t.cpu().numpy().tobytes()  # NaN coordinates compare equal to themselves
-
-
-def _same(got, want):
-    assert len(got) == len(want)
-    for v, (a, b) in enumerate(zip(got, want)):
-        assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b), v
 
 
 def _solve_points(cams, depths, images, points, n_input, threshold):
     """The library's (images_out, confident maps) as numpy, with the inputs checked to be untouched."""
-    args = (_devs(depths), _devs(images), _dev(np.asarray(points, f32).reshape(-1, 3)))
+    args = (devs(depths), devs(images), dev(np.asarray(points, f32).reshape(-1, 3)))
     before = [[t.clone() for t in args[0]], [t.clone() for t in args[1]], args[2].clone()]
     outs, confs = consistency.solve_point_inconsistency(cams, *args, n_input, threshold)
     assert all(o.dtype == torch.float32 and o.device == DEV for o in outs) and all(c.dtype == torch.uint8 for c in confs)
-    assert all(_bits(a) == _bits(b) for a, b in zip(args[0] + args[1] + [args[2]], before[0] + before[1] + [before[2]]))
-    return _np(outs), _np(confs)
+    same_bits(args[0] + args[1] + [args[2]], before[0] + before[1] + [before[2]], "inputs")  # NaN coordinates included
+    return hosts(outs), hosts(confs)
 
 
 def _check_points(cams, depths, images, points, n_input, threshold):
     """Both outputs and the point states of a scene equal the restatement's; returns the restatement's."""
     outs, confs = _solve_points(cams, depths, images, points, n_input, threshold)
     want_outs, want_confs = cr.point_solver(cams, depths, images, points, n_input, threshold)
-    _same(outs, want_outs)
-    _same(confs, want_confs)
-    got = consistency.point_states(cams, _devs(depths), _devs(images), _dev(np.asarray(points, f32).reshape(-1, 3)), n_input,
+    same_bits(outs, want_outs)
+    same_bits(confs, want_confs)
+    got = consistency.point_states(cams, devs(depths), devs(images), dev(np.asarray(points, f32).reshape(-1, 3)), n_input,
                                    threshold)
     want = cr.point_states(cams, depths, images, points, n_input, threshold)
     assert got[0].dtype == torch.bool and got[1].dtype == torch.bool and got[2].dtype == torch.uint8
-    _same(_np(got), list(want))
+    same_bits(hosts(got), list(want))
     return want_outs, want_confs, want
 
 
 @pytest.fixture(scope="module")
 def golden():
-    return load_golden()
+    return load_consistency_golden()
 
 
 @pytest.fixture(scope="module")
@@ -93,29 +61,29 @@ def restated(golden):
 def test_point_solver_on_the_golden_scene(hip_lib, golden, restated):
     g, I = golden, golden.n_input
     outs, confs = _solve_points(g.cams, g.depths, g.float_images, g.points, I, g.threshold)
-    _same(outs, restated.outs)
-    _same(confs, restated.confs)
+    same_bits(outs, restated.outs)
+    same_bits(confs, restated.confs)
     # what the reference's script wrote, on the agreed set
     conf = np.stack(confs) * 255
     assert np.array_equal(conf[g.point_conf_agreed], g.point_conf[g.point_conf_agreed])
-    png = np.stack(_np([consistency.images_to_uint8(_dev(o)) for o in outs[I:]]))
+    png = np.stack(hosts([consistency.images_to_uint8(dev(o)) for o in outs[I:]]))
     assert np.array_equal(png[g.point_png_agreed], g.point_png[g.point_png_agreed])
     assert sum(int((c == 0).sum()) for c in confs) > 900 and sum(int((a != b).any(-1).sum()) for a, b in zip(outs, g.float_images)) > 1000
     # a second run is bit-identical, and so is one over [3,H,W] images (a camera's original_image)
     again = _solve_points(g.cams, g.depths, g.float_images, g.points, I, g.threshold)
-    _same(again[0], outs)
-    _same(again[1], confs)
+    same_bits(again[0], outs)
+    same_bits(again[1], confs)
     chw = _solve_points(g.cams, g.depths, [np.ascontiguousarray(im.transpose(2, 0, 1)) for im in g.float_images], g.points, I,
                         g.threshold)
-    _same(chw[0], outs)
-    _same(chw[1], confs)
+    same_bits(chw[0], outs)
+    same_bits(chw[1], confs)
 
 
 def test_point_states_on_the_golden_scene(hip_lib, golden, restated):
     g = golden
-    args = (g.cams, _devs(g.depths), _devs(g.float_images), _dev(g.points), g.n_input, g.threshold)
+    args = (g.cams, devs(g.depths), devs(g.float_images), dev(g.points), g.n_input, g.threshold)
     got = consistency.point_states(*args)
-    _same(_np(got), list(restated.states))
+    same_bits(hosts(got), list(restated.states))
     seen, visible, colours = restated.states
     assert (~seen).sum() == 11454 and visible.all()  # every point lies on its own view's surface
     assert not colours[seen | ~visible].any()
@@ -124,13 +92,13 @@ def test_point_states_on_the_golden_scene(hip_lib, golden, restated):
 
 
 def _solve_planes(cams, depths, images, masks, points, gdict, anchors, threshold):
-    args = (_devs(depths), _devs(images), _devs(masks), _devs(points))
+    args = (devs(depths), devs(images), devs(masks), devs(points))
     before = [[t.clone() for t in a] for a in args]
     outs, anchor_of_plane, counts = consistency.solve_plane_inconsistency(cams, *args, gdict, anchors, threshold)
     assert all(o.dtype == torch.uint8 and o.device == DEV for o in outs) and counts.dtype == torch.int64
     for a, b in zip(args, before):  # the inputs are only read
         assert all(torch.equal(x, y) for x, y in zip(a, b))
-    return _np(outs), anchor_of_plane, counts.numpy()
+    return hosts(outs), anchor_of_plane, counts.numpy()
 
 
 def _check_planes(cams, depths, images, masks, points, gdict, anchors, threshold, resolve=None):
@@ -139,7 +107,7 @@ def _check_planes(cams, depths, images, masks, points, gdict, anchors, threshold
                                                           resolve=resolve)
     assert counts.shape == want_counts.shape and np.array_equal(counts, want_counts)
     assert anchor_of_plane == want_anchor and list(anchor_of_plane) == list(want_anchor)
-    _same(outs, want_outs)
+    same_bits(outs, want_outs)
     return outs, anchor_of_plane, counts
 
 
@@ -147,19 +115,19 @@ def test_plane_solver_on_the_golden_scene(hip_lib, golden, restated):
     g = golden
     scene = (g.cams, g.depths, g.images, g.masks, g.clouds, g.gdict, g.anchors, g.threshold)
     outs, anchor_of_plane, counts = _solve_planes(*scene)
-    _same(outs, restated.b_outs)
+    same_bits(outs, restated.b_outs)
     assert np.array_equal(counts, restated.counts) and counts.tolist() == g.stats["counts"]
     assert anchor_of_plane == restated.anchor_of_plane and [anchor_of_plane[k] for k in g.gdict] == g.stats["anchors"]
     png = np.stack(outs[g.n_input:])
     assert np.array_equal(png[g.plane_png_agreed], g.plane_png[g.plane_png_agreed])
     assert sum(int((a != b).any(-1).sum()) for a, b in zip(outs, g.images)) > 1500
     again = _solve_planes(*scene)
-    _same(again[0], outs)
+    same_bits(again[0], outs)
     assert again[1] == anchor_of_plane and np.array_equal(again[2], counts)
     # int64 masks with the same ids, and points as [H,W,3]
     wide = _solve_planes(g.cams, g.depths, g.images, [m.astype(np.int64) for m in g.masks],
                          [c.reshape(m.shape + (3,)) for c, m in zip(g.clouds, g.masks)], g.gdict, g.anchors, g.threshold)
-    _same(wide[0], outs)
+    same_bits(wide[0], outs)
 
 
 # ---- edge scene -----------------------------------------------------------------------------------------------------------
@@ -212,7 +180,7 @@ def _edge_scene():
     add("only_inpainted", _at(11.5, 1.5), depth_out=1.0, pixel=(11, 1))
     add("nowhere", _at(12.5, 1.5), pixel=(12, 1))
     add("both", _at(13.5, 1.5), depth_in=1.0, depth_out=1.0, pixel=(13, 1))
-    cams = [_camera(EW, EH, EF, EF), _camera(EW, EH, EF, EF)]
+    cams = [pinhole_camera(EW, EH, EF, EF), pinhole_camera(EW, EH, EF, EF)]
     return cams, [d_in, d_out], images, np.asarray(specs, np.float64).astype(f32), names
 
 
@@ -262,7 +230,7 @@ def test_largest_index_wins_across_waves_and_workgroups(hip_lib, n):
     seen_point = 1 if n > 1 else None
     points = np.tile(np.array([[50.0, 50.0, -1.0]], f32), (n, 1))  # everything else is behind every camera
     rng = np.random.default_rng(n)
-    cams = [_camera(EW, EH, EF, EF)]
+    cams = [pinhole_camera(EW, EH, EF, EF)]
     depths, images = [np.full((EH, EW), FAR, f32)], [rng.random((EH, EW, 3)).astype(f32)]
     if seen_point is not None:
         points[seen_point] = _at(3.5, 6.5)
@@ -271,10 +239,10 @@ def test_largest_index_wins_across_waves_and_workgroups(hip_lib, n):
         points[i] = _at(2.5 + 3 * k, 1.5 + k)
         d = np.full((EH, EW), FAR, f32)
         d[1 + k, 2 + 3 * k] = 1.0
-        cams.append(_camera(EW, EH, EF, EF))
+        cams.append(pinhole_camera(EW, EH, EF, EF))
         depths.append(d)
         images.append(rng.random((EH, EW, 3)).astype(f32))
-    cams.append(_camera(1, 1, 0.5, 0.5))  # u = x / 2 + 0.5 in [0, 1) for every point above
+    cams.append(pinhole_camera(1, 1, 0.5, 0.5))  # u = x / 2 + 0.5 in [0, 1) for every point above
     depths.append(np.ones((1, 1), f32))
     images.append(rng.random((1, 1, 3)).astype(f32))
     outs, confs, (seen, visible, colours) = _check_points(cams, depths, images, points, 1, ETHRESH)
@@ -294,11 +262,11 @@ def test_no_points_and_no_inpainted_views(hip_lib, golden):
     scene = (g.cams[:3], g.depths[:3], g.float_images[:3])
     for points, n_input in ((np.zeros((0, 3), f32), 1), (g.points, 3), (np.zeros((0, 3), f32), 3), (np.zeros((0, 3), f32), 0)):
         outs, confs, states = _check_points(*scene, points, n_input, g.threshold)
-        _same(outs, scene[2])  # nothing but the fills
+        same_bits(outs, scene[2])  # nothing but the fills
         assert all((c == 1).all() for c in confs) and len(states[0]) == len(points)
-    outs, confs = consistency.solve_point_inconsistency([], [], [], _dev(g.points), 0)
+    outs, confs = consistency.solve_point_inconsistency([], [], [], dev(g.points), 0)
     assert outs == [] and confs == []
-    seen, visible, colours = consistency.point_states([], [], [], _dev(g.points), 0)
+    seen, visible, colours = consistency.point_states([], [], [], dev(g.points), 0)
     assert seen.shape == (len(g.points),) and not seen.any() and not visible.any() and tuple(colours.shape) == (len(g.points), 3)
 
 
@@ -316,24 +284,24 @@ def test_chunked_view_list_equals_the_single_call(hip_lib, golden, restated, mon
     """Two views per call: the input views in chunks of their own first, then the inpainted views, the state carried along."""
     g = golden
     whole = _solve_points(g.cams, g.depths, g.float_images, g.points, n_input, g.threshold)
-    states = consistency.point_states(g.cams, _devs(g.depths), _devs(g.float_images), _dev(g.points), n_input, g.threshold)
+    states = consistency.point_states(g.cams, devs(g.depths), devs(g.float_images), dev(g.points), n_input, g.threshold)
     monkeypatch.setattr(consistency, "MAX_VIEWS_PER_CALL", 2)
     assert consistency._view_chunks(5, n_input) == {1: [(0, 1, 1), (1, 3, 0), (3, 5, 0)], 3: [(0, 2, 2), (2, 3, 1), (3, 5, 0)]}[n_input]
     chunked = _solve_points(g.cams, g.depths, g.float_images, g.points, n_input, g.threshold)
-    _same(chunked[0], whole[0])
-    _same(chunked[1], whole[1])
-    chunked_states = consistency.point_states(g.cams, _devs(g.depths), _devs(g.float_images), _dev(g.points), n_input, g.threshold)
+    same_bits(chunked[0], whole[0])
+    same_bits(chunked[1], whole[1])
+    chunked_states = consistency.point_states(g.cams, devs(g.depths), devs(g.float_images), dev(g.points), n_input, g.threshold)
     assert all(torch.equal(a, b) for a, b in zip(states, chunked_states))
     if n_input == g.n_input:
-        _same(whole[0], restated.outs)
+        same_bits(whole[0], restated.outs)
     else:
-        _same(whole[0], cr.point_solver(g.cams, g.depths, g.float_images, g.points, n_input, g.threshold)[0])
+        same_bits(whole[0], cr.point_solver(g.cams, g.depths, g.float_images, g.points, n_input, g.threshold)[0])
 
 
 def test_views_of_different_sizes(hip_lib):
     """A 16 x 8 input view, a 5 x 3 and a 16 x 8 inpainted view over one cloud of 300 points; the small view is offset."""
     rng = np.random.default_rng(5)
-    cams = [_camera(EW, EH, EF, EF), _camera(5, 3, 2.0, 2.0, (0.1, -0.2, 0.3)), _camera(EW, EH, EF, EF, (0.25, 0.0, 0.0))]
+    cams = [pinhole_camera(EW, EH, EF, EF), pinhole_camera(5, 3, 2.0, 2.0, (0.1, -0.2, 0.3)), pinhole_camera(EW, EH, EF, EF, (0.25, 0.0, 0.0))]
     sizes = [(EH, EW), (3, 5), (EH, EW)]
     depths = [np.where(rng.random(s) < 0.5, 1.0, 1.25).astype(f32) for s in sizes]
     images = [rng.random(s + (3,)).astype(f32) for s in sizes]
@@ -357,7 +325,7 @@ def _chain_scene():
     view 2, plane 1 = [(1, -7)] in view 0, plane 2 = [(2, 30)] in view 1: a pixel of view 2 reads view 1 (step 2), which read view
     0 (step 1), which read view 2's ORIGINAL (step 0).  Plane 3 = [(1, 900)] lies at depth 100: no anchor sees it."""
     rng = np.random.default_rng(21)
-    cams = [_camera(EW, EH, EF, EF) for _ in range(3)]
+    cams = [pinhole_camera(EW, EH, EF, EF) for _ in range(3)]
     depths = [np.full((EH, EW), d, f32) for d in (2.0, 4.0, 1.0)]
     images = [rng.integers(0, 256, (EH, EW, 3)).astype(np.uint8) for _ in range(3)]
     masks = [np.full((EH, EW), 30, np.int32), np.full((EH, EW), -7, np.int32), np.full((EH, EW), 30, np.int32)]
@@ -380,8 +348,8 @@ def test_hand_made_chain_of_three_views(hip_lib):
     assert steps == [(0, 30, 2), (1, -7, 0), (2, 30, 1)]
     src = cr.plane_sources(cams, depths, masks, points, steps, ETHRESH)
     lengths = [np.zeros(EH * EW, np.int64) for _ in range(3)]
-    _same(cr.resolve_chains(images, src, lengths), outs)
-    _same(cr.repaint_in_place(images, src, len(steps)), outs)  # the literal sequential repaint
+    same_bits(cr.resolve_chains(images, src, lengths), outs)
+    same_bits(cr.repaint_in_place(images, src, len(steps)), outs)  # the literal sequential repaint
     assert (lengths[2] == 3).sum() > 30 and (lengths[1] == 2).sum() > 30
     # (y, x) of view 2 <- (y, x + 1) of view 1 <- (y, x + 2) of view 0 <- (y, x + 3) of view 2, untouched by the earlier steps
     assert lengths[2][2 * EW + 4] == 3 and np.array_equal(outs[2][2, 4], images[2][2, 7])
@@ -398,7 +366,7 @@ def test_read_inside_a_step_sees_the_colours_before_the_step(hip_lib):
     """One view anchored in itself, its points one pixel to the right: pixel x reads pixel x + 1, which the same step repaints.
     It must get the neighbour's ORIGINAL colour."""
     rng = np.random.default_rng(3)
-    cams, depths = [_camera(EW, EH, EF, EF)], [np.ones((EH, EW), f32)]
+    cams, depths = [pinhole_camera(EW, EH, EF, EF)], [np.ones((EH, EW), f32)]
     images = [rng.integers(0, 256, (EH, EW, 3)).astype(np.uint8)]
     masks, points = [np.full((EH, EW), 4, np.int64)], [_grid_points(1.0, 1)]
     outs, anchor_of_plane, counts = _check_planes(cams, depths, images, masks, points, {0: [(0, 4)]}, [0], ETHRESH)
@@ -410,10 +378,10 @@ def test_empty_dict_and_no_anchors(hip_lib):
     cams, depths, images, masks, points, gdict = _chain_scene()
     outs, anchor_of_plane, counts = _check_planes(cams, depths, images, masks, points, {}, [0, 1, 2], ETHRESH)
     assert anchor_of_plane == {} and tuple(counts.shape) == (0, 3)
-    _same(outs, images)
+    same_bits(outs, images)
     outs, anchor_of_plane, counts = _check_planes(cams, depths, images, masks, points, gdict, [], ETHRESH)
     assert set(anchor_of_plane.values()) == {-1} and tuple(counts.shape) == (5, 0)
-    _same(outs, images)
+    same_bits(outs, images)
     outs, anchor_of_plane, counts = consistency.solve_plane_inconsistency([], [], [], [], [], {0: []}, [])
     assert outs == [] and anchor_of_plane == {0: -1} and tuple(counts.shape) == (1, 0)
 
@@ -422,7 +390,7 @@ def test_plane_views_of_different_sizes(hip_lib):
     """A 16 x 8 view of depth 1 and a 5 x 3 view of depth 2; the small view's points lie at depth 1, so its plane is anchored in
     the large view (step 0), and the large view's at depth 2, so its plane is anchored in the small one (step 1)."""
     rng = np.random.default_rng(9)
-    cams = [_camera(EW, EH, EF, EF), _camera(5, 3, 2.0, 2.0)]
+    cams = [pinhole_camera(EW, EH, EF, EF), pinhole_camera(5, 3, 2.0, 2.0)]
     depths = [np.ones((EH, EW), f32), np.full((3, 5), 2.0, f32)]
     images = [rng.integers(0, 256, (EH, EW, 3)).astype(np.uint8), rng.integers(0, 256, (3, 5, 3)).astype(np.uint8)]
     masks = [rng.choice([0, 3, 8], (EH, EW)).astype(np.int32), rng.choice([0, 3], (3, 5)).astype(np.int32)]
@@ -451,7 +419,7 @@ def test_plane_counts_past_the_grid_cap(hip_lib):
     BW, BH, BF = 300, 220, 256.0
     assert BW * BH > one_pass and (BH - 1) * BW >= one_pass
     rng = np.random.default_rng(66)
-    cams = [_camera(BW, BH, BF, BF), _camera(5, 3, 2.0, 2.0), _camera(BW, BH, BF, BF)]
+    cams = [pinhole_camera(BW, BH, BF, BF), pinhole_camera(5, 3, 2.0, 2.0), pinhole_camera(BW, BH, BF, BF)]
     depths = [np.ones((BH, BW), f32), np.full((3, 5), 4.0, f32), np.full((BH, BW), 2.0, f32)]
     images = [rng.integers(0, 256, d.shape + (3,)).astype(np.uint8) for d in depths]
     masks = [rng.choice([0, 3, 8], (BH, BW)).astype(np.int32), rng.choice([0, 3], (3, 5)).astype(np.int32),
@@ -478,7 +446,7 @@ def test_plane_counts_past_the_grid_cap(hip_lib):
 # ---- argument errors ------------------------------------------------------------------------------------------------------------
 def test_python_arguments_are_checked_before_any_launch(hip_lib, golden):
     g = golden
-    depths, images, points = _devs(g.depths), _devs(g.float_images), _dev(g.points)
+    depths, images, points = devs(g.depths), devs(g.float_images), dev(g.points)
 
     def point_call(**changes):
         a = dict(cameras=g.cams, depths=depths, images=images, points=points, n_input_views=1)
@@ -490,7 +458,7 @@ def test_python_arguments_are_checked_before_any_launch(hip_lib, golden):
     with pytest.raises(ValueError, match=r"images\[2\] must have shape"):
         point_call(images=images[:2] + [images[2][:, :10]] + images[3:])
     with pytest.raises(RuntimeError, match=r"images\[1\] must be torch.float32"):
-        point_call(images=images[:1] + [_dev(g.images[1])] + images[2:])
+        point_call(images=images[:1] + [dev(g.images[1])] + images[2:])
     with pytest.raises(RuntimeError, match=r"images\[0\] must be a tensor on cuda"):
         point_call(images=[images[0].cpu()] + images[1:])
     with pytest.raises(RuntimeError, match="depth must be a tensor on cuda"):
@@ -500,7 +468,7 @@ def test_python_arguments_are_checked_before_any_launch(hip_lib, golden):
     with pytest.raises(ValueError, match="n_input_views must be in 0 .. 5"):
         point_call(n_input_views=6)
 
-    u8, masks, clouds = _devs(g.images), _devs(g.masks), _devs(g.clouds)
+    u8, masks, clouds = devs(g.images), devs(g.masks), devs(g.clouds)
 
     def plane_call(**changes):
         a = dict(cameras=g.cams, depths=depths, images=u8, plane_masks=masks, points=clouds, global_3Dplane_ID_dict=g.gdict,

@@ -21,37 +21,12 @@ import torch
 
 import depth_cues_ref as dr
 from g4splat_amd import depth_cues, visibility
-from test_depth_cues_cpu import load_golden
+from support import DEV, dev, devs, hosts, load_depth_cues_golden, same_bits
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda:0")
 f32, f64 = np.float32, np.float64
 SPAN = 4096  # ALIGN_SPAN of csrc/tsdf/depth_cues.hip: 256 threads of 16 pixels
-
-
-def _dev(a):
-    return torch.as_tensor(np.ascontiguousarray(a), device=DEV)
-
-
-def _devs(arrays):
-    return [_dev(a) for a in arrays]
-
-
-def _np(tensors):
-    return [t.cpu().numpy() for t in tensors]
-
-
-def _same_bits(got, want, what=""):
-    """Equal bit for bit; a NaN has to meet a NaN (its payload is not compared)."""
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
-    if got.dtype.kind != "f":
-        assert np.array_equal(got, want), what
-        return
-    nan = np.isnan(want)
-    assert np.array_equal(np.isnan(got), nan), what
-    assert np.array_equal(got[~nan].view(np.uint32), want[~nan].view(np.uint32)), (what, int((got[~nan] != want[~nan]).sum()))
 
 
 def _within_one_ulp(got, want, what=""):
@@ -66,7 +41,7 @@ def _within_one_ulp(got, want, what=""):
 
 @pytest.fixture(scope="module")
 def golden():
-    return load_golden()
+    return load_depth_cues_golden()
 
 
 def _scene(sizes, seed):
@@ -83,10 +58,10 @@ def _scene(sizes, seed):
 
 def _check_coeffs(disps, depths, masks, domain):
     code = {"disparity": dr.DISPARITY, "depth": dr.DEPTH}[domain]
-    aligned, coeffs, counts = depth_cues.align_disparities(_devs(disps), _devs(depths), _devs(masks), domain)
-    again = depth_cues.align_disparities(_devs(disps), _devs(depths), _devs(masks), domain)
+    aligned, coeffs, counts = depth_cues.align_disparities(devs(disps), devs(depths), devs(masks), domain)
+    again = depth_cues.align_disparities(devs(disps), devs(depths), devs(masks), domain)
     assert coeffs.dtype == torch.float32 and counts.dtype == torch.int32 and coeffs.device == DEV
-    assert coeffs.cpu().numpy().tobytes() == again[1].cpu().numpy().tobytes()  # two runs, the same bits
+    same_bits(coeffs, again[1], "two runs")
     got, n = coeffs.cpu().numpy(), counts.cpu().numpy()
     for v in range(len(disps)):
         alpha, beta, count = dr.align_coeffs(disps[v], depths[v], masks[v], code, f32)
@@ -96,7 +71,7 @@ def _check_coeffs(disps, depths, masks, domain):
         _within_one_ulp(got[v, 0], alpha, f"view {v} alpha")
         _within_one_ulp(got[v, 1], beta, f"view {v} beta")
         # the aligned map, from the device's own coefficients
-        _same_bits(aligned[v].cpu().numpy(), dr.aligned(got[v, 0], got[v, 1], disps[v], code, f32), f"aligned {v}")
+        same_bits(aligned[v], dr.aligned(got[v, 0], got[v, 1], disps[v], code, f32), f"aligned {v}", nan_payload=False)
     return got
 
 
@@ -176,9 +151,9 @@ def _check_refill(sizes, n_input, seed=17):
     """refill_unseen_regions against the restatement: counts exactly, coefficients within one unit, and -- fed the device's
     coefficients -- every depth bit for bit.  Returns the unfilled regions."""
     targets, monos, masks, confs = _refill_scene(sizes, seed)
-    args = _devs(targets), _devs(monos), _devs(masks), _devs(confs)
+    args = devs(targets), devs(monos), devs(masks), devs(confs)
     got, coeffs, counts = depth_cues.refill_unseen_regions(*args, n_input)
-    assert all(torch.equal(a, _dev(b)) for a, b in zip(args[0], targets))  # the inputs are only read
+    assert all(torch.equal(a, dev(b)) for a, b in zip(args[0], targets))  # the inputs are only read
     coeffs, counts = coeffs.cpu().numpy(), counts.cpu().numpy()
     assert coeffs.shape == (len(sizes), 2) and counts.shape == (len(sizes),)
     regions = []
@@ -187,7 +162,7 @@ def _check_refill(sizes, n_input, seed=17):
         region = (masks[v] == 0) & ~confs[v]
         regions.append(region)
         if v < n_input:
-            _same_bits(g, targets[v], f"input view {v}")
+            same_bits(g, targets[v], f"input view {v}", nan_payload=False)
             assert not coeffs[v].any() and counts[v] == 0
             continue
         alpha, beta, n = dr.align_coeffs(monos[v], targets[v], confs[v], dr.INVERSE_SOURCE, f32)
@@ -197,7 +172,7 @@ def _check_refill(sizes, n_input, seed=17):
         _within_one_ulp(coeffs[v, 0], alpha, f"refill {v} alpha")
         _within_one_ulp(coeffs[v, 1], beta, f"refill {v} beta")
         filled = dr.aligned(coeffs[v, 0], coeffs[v, 1], monos[v], dr.INVERSE_SOURCE, f32)
-        _same_bits(g, np.where(region, filled, targets[v]), f"refill {v}")
+        same_bits(g, np.where(region, filled, targets[v]), f"refill {v}", nan_payload=False)
     return regions, coeffs
 
 
@@ -229,7 +204,7 @@ def test_cue_maps_equal_the_restatement(golden, sizes):
     disps, warps, _m = _scene(sizes, 3)
     rng = np.random.default_rng(9)
     alphas = [np.where(rng.random(d.shape) < 0.7, 0.97, 0.4).astype(f32) for d in disps]
-    args = _devs(disps), _devs(warps), _devs(alphas)
+    args = devs(disps), devs(warps), devs(alphas)
     before = [[t.clone() for t in a] for a in args]
     cues = depth_cues.view_geometry_cues(cams, *args, visible_threshold=0.9)
     for a, b in zip(args, before):
@@ -246,7 +221,7 @@ def test_cue_maps_equal_the_restatement(golden, sizes):
         for name in ("mono_depth", "aligned_depth", "depth", "normal_world", "normal_cam"):
             got = getattr(cues, name)[v]
             assert got.shape == ((H, W, 3) if name.startswith("normal") else (H, W))
-            _same_bits(got.cpu().numpy(), want[name], f"{name} {v}")
+            same_bits(got, want[name], f"{name} {v}", nan_payload=False)
         if H < 3 or W < 3:
             assert not cues.normal_world[v].any() and not cues.normal_cam[v].any()
         else:
@@ -275,14 +250,14 @@ def _plane_scene(golden, sizes, seed):
 def test_plane_depths_and_refill_equal_the_restatement(golden, sizes):
     cams, depths, masks, gdict, planes = _plane_scene(golden, sizes, 21)
     V = len(sizes)
-    args = _devs(depths), _devs(masks)
+    args = devs(depths), devs(masks)
     out, replaced, zeroed = depth_cues.apply_global_planes(cams, *args, gdict, planes)
-    assert all(torch.equal(a, _dev(b)) for a, b in zip(args[0], depths))  # the inputs are only read
+    assert all(torch.equal(a, dev(b)) for a, b in zip(args[0], depths))  # the inputs are only read
     want, want_replaced, want_zeroed, touched, _valid = dr.apply_global_planes(cams, depths, masks, gdict, planes, f32)
     assert replaced.dtype == torch.int32 and np.array_equal(replaced.cpu().numpy(), want_replaced)
     assert np.array_equal(zeroed.cpu().numpy(), want_zeroed)
     for v in range(V):
-        _same_bits(out[v].cpu().numpy(), want[v], f"plane depth {v}")
+        same_bits(out[v], want[v], f"plane depth {v}", nan_payload=False)
         assert np.array_equal(out[v].cpu().numpy()[~touched[v]], depths[v][~touched[v]])  # ids 0 and 12 keep their depth
     if max(H * W for H, W in sizes) > 100:
         assert want_replaced.sum() > 0 and want_zeroed.sum() > 0
@@ -292,12 +267,12 @@ def test_plane_depths_and_refill_equal_the_restatement(golden, sizes):
     monos = [(1.0 / rng.uniform(0.2, 2.0, s)).astype(f32) for s in sizes]
     targets = [rng.uniform(1.0, 4.0, s).astype(f32) for s in sizes]
     confs = [rng.random(s) < 0.5 for s in sizes]
-    got, coeffs, counts = depth_cues.refill_unseen_regions(_devs(targets), _devs(monos), _devs(masks), _devs(confs), n_input)
+    got, coeffs, counts = depth_cues.refill_unseen_regions(devs(targets), devs(monos), devs(masks), devs(confs), n_input)
     coeffs = coeffs.cpu().numpy()
     for v in range(V):
         g = got[v].cpu().numpy()
         if v < n_input:
-            _same_bits(g, targets[v], f"input view {v}")
+            same_bits(g, targets[v], f"input view {v}", nan_payload=False)
             continue
         alpha, beta, n = dr.align_coeffs(monos[v], targets[v], confs[v], dr.INVERSE_SOURCE, f32)
         assert int(counts[v]) == n
@@ -305,30 +280,30 @@ def test_plane_depths_and_refill_equal_the_restatement(golden, sizes):
         _within_one_ulp(coeffs[v, 1], beta, f"refill {v} beta")
         region = (masks[v] == 0) & ~confs[v]
         filled = dr.aligned(coeffs[v, 0], coeffs[v, 1], monos[v], dr.INVERSE_SOURCE, f32)
-        _same_bits(g, np.where(region, filled, targets[v]), f"refill {v}")
+        same_bits(g, np.where(region, filled, targets[v]), f"refill {v}", nan_payload=False)
 
 
 def test_plane_aligned_depth_of_a_whole_image(golden):
     n, c = golden.planes[6]
     cam = golden.cams[1]
-    depth, valid = depth_cues.plane_aligned_depth(_dev(n), _dev(c), cam, (45, 67))
+    depth, valid = depth_cues.plane_aligned_depth(dev(n), dev(c), cam, (45, 67))
     z, ok = dr.plane_depth_image(n, c, cam, 45, 67, f32)
     assert valid.dtype == torch.bool and np.array_equal(valid.cpu().numpy(), ok) and ok.any() and not ok.all()
-    _same_bits(depth.cpu().numpy(), np.where(ok, z, f32(0)), "plane_aligned_depth")
+    same_bits(depth, np.where(ok, z, f32(0)), "plane_aligned_depth", nan_payload=False)
 
 
 # ---- the id search of the plane depths ----
 def _check_planes(cams, depths, masks, gdict, planes):
     """apply_global_planes against the restatement: depths bit for bit, both counts exactly, untouched pixels keep their bits."""
-    out, replaced, zeroed = depth_cues.apply_global_planes(cams, _devs(depths), _devs(masks), gdict, planes)
+    out, replaced, zeroed = depth_cues.apply_global_planes(cams, devs(depths), devs(masks), gdict, planes)
     want, want_replaced, want_zeroed, touched, _valid = dr.apply_global_planes(cams, depths, masks, gdict, planes, f32)
     print("replaced", want_replaced.tolist(), "zeroed", want_zeroed.tolist())
     assert replaced.dtype == zeroed.dtype == torch.int32
     assert np.array_equal(replaced.cpu().numpy(), want_replaced) and np.array_equal(zeroed.cpu().numpy(), want_zeroed)
     for v in range(len(cams)):
         got = out[v].cpu().numpy()
-        _same_bits(got, want[v], f"plane depth {v}")
-        _same_bits(got[~touched[v]], depths[v][~touched[v]], f"untouched {v}")
+        same_bits(got, want[v], f"plane depth {v}", nan_payload=False)
+        same_bits(got[~touched[v]], depths[v][~touched[v]], f"untouched {v}", nan_payload=False)
     return out, replaced, zeroed, (want_replaced, want_zeroed, touched)
 
 
@@ -363,10 +338,10 @@ def test_plane_depth_clamp_in_both_signs_at_zero_and_through_the_camera():
     assert not out[0].cpu().numpy()[s.mask == 3].any()
     for pid in (1, 2):  # each plane alone, over the whole image
         n, c = (np.array(x, f32) for x in s.planes[pid])
-        depth, valid = depth_cues.plane_aligned_depth(_dev(n), _dev(c), s.cam, (s.H, s.W))
+        depth, valid = depth_cues.plane_aligned_depth(dev(n), dev(c), s.cam, (s.H, s.W))
         z, ok = dr.plane_depth_image(*s.planes[pid], s.cam, s.H, s.W, f32)
         assert ok.any() and not ok.all() and np.array_equal(valid.cpu().numpy(), ok)
-        _same_bits(depth.cpu().numpy(), np.where(ok, z, f32(0)), f"clamped plane {pid}")
+        same_bits(depth, np.where(ok, z, f32(0)), f"clamped plane {pid}", nan_payload=False)
 
 
 # ---- the float mask at its edges ----
@@ -389,7 +364,7 @@ def test_float_mask_at_equality_nan_and_infinities(golden, threshold):
             with np.errstate(invalid="ignore"):
                 assert ((a[idx] > t) == seen).all()
         alphas.append(a.reshape(d.shape))
-    cues = depth_cues.view_geometry_cues(cams, _devs(disps), _devs(warps), _devs(alphas), visible_threshold=threshold)
+    cues = depth_cues.view_geometry_cues(cams, devs(disps), devs(warps), devs(alphas), visible_threshold=threshold)
     coeffs, counts = cues.coeffs.cpu().numpy(), cues.counts.cpu().numpy()
     for v in range(len(sizes)):
         with np.errstate(invalid="ignore"):
@@ -403,7 +378,7 @@ def test_float_mask_at_equality_nan_and_infinities(golden, threshold):
         want = dr.cue_maps(cams[v], disps[v], warps[v], alphas[v], threshold, coeffs[v, 0], coeffs[v, 1], f32)
         assert np.array_equal(want["visibility"], vis)
         for name in ("mono_depth", "aligned_depth", "depth", "normal_world", "normal_cam"):
-            _same_bits(getattr(cues, name)[v].cpu().numpy(), want[name], f"{name} {v}")
+            same_bits(getattr(cues, name)[v], want[name], f"{name} {v}", nan_payload=False)
 
 
 # ---- nothing is written behind the workspaces the two larger layouts ask for ----
@@ -419,7 +394,7 @@ def test_align_workspace_is_enough(hip_lib, shift):
     from g4splat_amd import _lib
     sizes = [(1, 64 * SPAN + 1), (45, 67)]
     disps, depths, masks = _scene(sizes, 17)
-    src, tgt, msk = _devs(disps), _devs(depths), [m.view(torch.uint8) for m in _devs(masks)]
+    src, tgt, msk = devs(disps), devs(depths), [m.view(torch.uint8) for m in devs(masks)]
     c_sizes = _lib.array(_lib.c_i, [x for H, W in sizes for x in (W, H)])
     nbytes = int(hip_lib.g4s_depth_align_workspace(len(sizes), c_sizes))
     assert nbytes >= (65 + 1) * 5 * 8
@@ -431,8 +406,9 @@ def test_align_workspace_is_enough(hip_lib, shift):
     assert rc == 0, hip_lib.g4s_last_error()
     torch.cuda.synchronize()
     assert (tail == 0xA5).all().item(), "bytes behind the advertised workspace were written"
-    _aligned, want_coeffs, want_counts = depth_cues.align_disparities(src, tgt, _devs(masks), "disparity")
-    assert coeffs.cpu().numpy().tobytes() == want_coeffs.cpu().numpy().tobytes() and torch.equal(counts, want_counts)
+    _aligned, want_coeffs, want_counts = depth_cues.align_disparities(src, tgt, devs(masks), "disparity")
+    same_bits(coeffs, want_coeffs, "coefficients")
+    assert torch.equal(counts, want_counts)
     assert np.isfinite(coeffs.cpu().numpy()).all() and counts.cpu().numpy().tolist() == [int(m.sum()) for m in masks]
 
 
@@ -446,7 +422,7 @@ def test_plane_depths_workspace_is_enough(hip_lib, golden, id_scene, shift):
     view_offset, ids, entry_plane, rows, _keys = depth_cues.plane_table(s.gdict, s.planes, V)
     assert view_offset[-1] == len(ids) == sum(dr.ID_RUNS) and len(rows) == 5
     records = np.concatenate([depth_cues.plane_camera_record(c, W, H) for c, (H, W) in zip(cams, s.sizes)])
-    depth, masks = _devs(s.depths), _devs(s.masks)
+    depth, masks = devs(s.depths), devs(s.masks)
     out = [torch.zeros_like(d) for d in depth]
     counts = torch.full((2, V), -1, dtype=torch.int32, device=DEV)
     c_sizes = _lib.array(_lib.c_i, [x for H, W in s.sizes for x in (W, H)])
@@ -463,7 +439,7 @@ def test_plane_depths_workspace_is_enough(hip_lib, golden, id_scene, shift):
     want, replaced, zeroed = depth_cues.apply_global_planes(cams, depth, masks, s.gdict, s.planes)
     assert torch.equal(counts[0], replaced) and torch.equal(counts[1], zeroed) and int(replaced.sum()) > 0
     for v in range(V):
-        _same_bits(out[v].cpu().numpy(), want[v].cpu().numpy(), f"plane depth {v}")
+        same_bits(out[v], want[v], f"plane depth {v}", nan_payload=False)
 
 
 def _bounded(got, want, bound, keep=None, what=""):
@@ -475,22 +451,22 @@ def _bounded(got, want, bound, keep=None, what=""):
 
 def test_golden_cues_match_the_reference(golden):
     g = golden
-    cues = depth_cues.view_geometry_cues(g.cams, _dev(np.stack(g.disps)), _devs(g.depths), _devs(g.alphas), g.threshold)
+    cues = depth_cues.view_geometry_cues(g.cams, dev(np.stack(g.disps)), devs(g.depths), devs(g.alphas), g.threshold)
     _bounded(cues.coeffs.cpu().numpy(), g.g["ref64_coeffs"], 2 * g.yard["coeffs"], what="coeffs")
-    _bounded(np.stack(_np(cues.aligned_depth)), g.g["ref64_aligned_depth"], 2 * g.yard["aligned_depth"], what="aligned_depth")
-    _bounded(np.stack(_np(cues.depth)), g.ref_merged, 2 * g.yard["depth"], what="depth")
-    _bounded(np.stack(_np(cues.normal_world[g.n_input:])), g.g["ref64_normal_world"], 2 * g.yard["normal_world"], what="normal_world")
-    _bounded(np.stack(_np(cues.normal_cam[g.n_input:])), g.g["ref64_normal_cam"], 2 * g.yard["normal_cam"], what="normal_cam")
-    assert np.array_equal(np.stack(_np(cues.visibility)), np.stack(g.visible))
+    _bounded(np.stack(hosts(cues.aligned_depth)), g.g["ref64_aligned_depth"], 2 * g.yard["aligned_depth"], what="aligned_depth")
+    _bounded(np.stack(hosts(cues.depth)), g.ref_merged, 2 * g.yard["depth"], what="depth")
+    _bounded(np.stack(hosts(cues.normal_world[g.n_input:])), g.g["ref64_normal_world"], 2 * g.yard["normal_world"], what="normal_world")
+    _bounded(np.stack(hosts(cues.normal_cam[g.n_input:])), g.g["ref64_normal_cam"], 2 * g.yard["normal_cam"], what="normal_cam")
+    assert np.array_equal(np.stack(hosts(cues.visibility)), np.stack(g.visible))
     assert np.array_equal(cues.counts.cpu().numpy(), [int(m.sum()) for m in g.visible])
     # the reference-named single-view wrappers
     for v in range(g.n_input, g.V):
-        disp, warp, vis = _dev(g.disps[v]), _dev(g.depths[v]), _dev(g.visible[v])
+        disp, warp, vis = dev(g.disps[v]), dev(g.depths[v]), dev(g.visible[v])
         aligned, alpha, beta = depth_cues.depth_linear_align(disp, warp, vis, return_alpha_beta=True)
         assert isinstance(alpha, float) and isinstance(beta, float)
         assert torch.equal(aligned, depth_cues.depth_linear_align(disp, warp, vis)) and torch.equal(aligned, cues.aligned_depth[v])
         _bounded([alpha, beta], g.g["ref64_coeffs"][v], 2 * g.yard["coeffs"], what=f"depth_linear_align {v}")
-        a2, alpha2, beta2 = depth_cues.depth_linear_align_2(_dev(g.monos[v]), warp, vis, return_alpha_beta=True)
+        a2, alpha2, beta2 = depth_cues.depth_linear_align_2(dev(g.monos[v]), warp, vis, return_alpha_beta=True)
         _bounded([alpha2, beta2], g.g["ref64_coeffs2"][v], 2 * g.yard["coeffs2"], what=f"depth_linear_align_2 {v}")
         _bounded(a2.cpu().numpy(), g.g["ref64_align2"][v - g.n_input], 2 * g.yard["align2"], what=f"align2 {v}")
 
@@ -499,26 +475,26 @@ def test_golden_refined_depths_match_the_reference(golden):
     g = golden
     for i, (key, v) in enumerate(g.g["plane_full_pairs"]):
         n, c = g.planes[int(key)]
-        depth, valid = depth_cues.plane_aligned_depth(_dev(n), _dev(c), g.cams[int(v)], (g.H, g.W))
+        depth, valid = depth_cues.plane_aligned_depth(dev(n), dev(c), g.cams[int(v)], (g.H, g.W))
         keep = g.g["full_agreed"][i]
         assert np.array_equal(valid.cpu().numpy()[keep], g.g["plane_full_valid"][i][keep])
         _bounded(depth.cpu().numpy(), g.g["ref64_plane_full"][i], 2 * g.yard["plane_full"], keep, f"plane_aligned_depth {i}")
-    depths, masks = _devs(g.depths), _devs(g.masks)
+    depths, masks = devs(g.depths), devs(g.masks)
     planed, replaced, zeroed = depth_cues.apply_global_planes(g.cams, depths, masks, g.gdict, g.planes)
-    planed_np = np.stack(_np(planed))
+    planed_np = np.stack(hosts(planed))
     touched, valid = g.g["touched"], g.g["valid"]
     assert np.array_equal((planed_np > 0)[touched & g.agreed], valid[touched & g.agreed])
     assert np.array_equal(planed_np[~touched], np.stack(g.depths)[~touched])
     assert g.agreed.all()  # so the counts are the reference's
     assert np.array_equal(replaced.cpu().numpy(), valid.sum((1, 2))) and np.array_equal(zeroed.cpu().numpy(), (touched & ~valid).sum((1, 2)))
     _bounded(planed_np, g.g["ref64_planed"], 2 * g.yard["planed"], g.agreed, "planed")
-    refined, points = depth_cues.refine_depths_with_planes(g.cams, depths, masks, _devs(g.confs), _devs(g.monos), g.gdict, g.planes,
+    refined, points = depth_cues.refine_depths_with_planes(g.cams, depths, masks, devs(g.confs), devs(g.monos), g.gdict, g.planes,
                                                            g.n_input, return_points=True)
-    _bounded(np.stack(_np(refined)), g.g["ref64_refined"], 2 * g.yard["refined"], g.agreed, "refined")
+    _bounded(np.stack(hosts(refined)), g.g["ref64_refined"], 2 * g.yard["refined"], g.agreed, "refined")
     for v in range(g.n_input):
         assert torch.equal(refined[v], planed[v])
     for v in range(g.V):
         assert points[v].shape == (g.H * g.W, 3) and torch.equal(points[v], visibility.depths_to_points(refined[v], g.cams[v]))
-    only = depth_cues.refine_depths_with_planes(g.cams, depths, masks, _devs(g.confs), _devs(g.monos), g.gdict, g.planes, g.n_input)
+    only = depth_cues.refine_depths_with_planes(g.cams, depths, masks, devs(g.confs), devs(g.monos), g.gdict, g.planes, g.n_input)
     assert all(torch.equal(a, b) for a, b in zip(only, refined))
-    assert all(torch.equal(a, _dev(b)) for a, b in zip(depths, g.depths))  # the inputs are only read
+    assert all(torch.equal(a, dev(b)) for a, b in zip(depths, g.depths))  # the inputs are only read

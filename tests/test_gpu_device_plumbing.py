@@ -6,9 +6,9 @@ import pytest
 import torch
 
 from g4splat_amd import _device, _lib, visibility
+from support import DEV
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
 
 
 def _camera():

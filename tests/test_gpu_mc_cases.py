@@ -11,10 +11,10 @@ import mc_cases
 import tsdf_ref
 import unbounded_ref as ur
 from g4splat_amd import mesh as mesh_mod
+from support import DEV, same_bits, words
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda:0")
 _REF = {}
 
 
@@ -65,10 +65,6 @@ def _load(case, seed, grow=False):
     return vol
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def _check_sparse(name, vol, far=False):
     _case, (rv, rc, rt) = _sparse(name)
     mesh = vol.extract_triangle_mesh()
@@ -80,15 +76,14 @@ def _check_sparse(name, vol, far=False):
     assert tris.min() >= 0 and tris.max() < len(verts)
     dv, dc = np.abs(verts - rv), np.abs(cols - rc)
     print(f"\n{name}: V={len(verts)} F={len(tris)} max|dv|={dv.max():.3g} max|dc|={dc.max():.3g} "
-          f"unequal bits: verts {(_bits(verts) != _bits(rv)).sum()}, colours {(_bits(cols) != _bits(rc)).sum()}")
+          f"unequal bits: verts {(words(verts) != words(rv)).sum()}, colours {(words(cols) != words(rc)).sum()}")
     if far:
         assert (dv <= 2 * np.spacing(np.abs(rv))).all(), (dv / np.spacing(np.abs(rv))).max()
     else:
         assert np.abs(rv).max() < 4.0 and dv.max() <= 1e-6
     assert dc.max() <= 1e-6
     again = vol.extract_triangle_mesh()
-    for a, b in zip(mesh, again):
-        assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+    same_bits(tuple(again), tuple(mesh), "second run")
     return mesh
 
 
@@ -133,12 +128,10 @@ def test_dense_cubes_match_the_restatement(hip_lib, name):
     assert np.array_equal(tris, rt)
     assert tris.min() >= 0 and tris.max() < len(verts)
     dv = np.abs(verts - rv)
-    print(f"\n{name}: V={len(verts)} F={len(tris)} max|dv|={dv.max():.3g} unequal bits: {(_bits(verts) != _bits(rv)).sum()}")
+    print(f"\n{name}: V={len(verts)} F={len(tris)} max|dv|={dv.max():.3g} unequal bits: {(words(verts) != words(rv)).sum()}")
     assert np.isfinite(verts).all() and dv.max() <= 1e-6
     again = mesh_mod.dense_marching_cubes(t, R, (0.0, 0.0, 0.0), 1.0)
     dev = mesh_mod.dense_marching_cubes(t, R, (0.0, 0.0, 0.0), 1.0, to_host=False)
     assert dev[0].is_cuda and dev[1].is_cuda
-    for a, b, c in zip((verts, tris), again, dev):
-        c = c.cpu().numpy()
-        assert a.dtype == b.dtype == c.dtype
-        assert np.array_equal(a.view(np.uint8), b.view(np.uint8)) and np.array_equal(a.view(np.uint8), c.view(np.uint8))
+    same_bits(tuple(again), (verts, tris), "second run")
+    same_bits(tuple(dev), (verts, tris), "device result")

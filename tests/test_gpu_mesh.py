@@ -10,10 +10,10 @@ import torch
 import tsdf_ref
 from g4splat_amd import mesh as mesh_mod
 from g4splat_amd import synthetic
+from support import DEV, dev, device_camera, devs, same_bits
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda:0")
 V, T = 0.04, 0.16
 
 
@@ -39,8 +39,7 @@ def _gpu_volume(views, initial_blocks=100000):
     vol = mesh_mod.TSDFVolume(V, T, 10.0, DEV, initial_blocks=initial_blocks)
     counts = []
     for cam, _i, _e, depth, rgb, mask in views:
-        t = lambda a: None if a is None else torch.as_tensor(a, device=DEV)
-        counts.append(vol.integrate(t(depth)[None], t(rgb), cam, t(mask)))
+        counts.append(vol.integrate(dev(depth)[None], dev(rgb), cam, dev(mask)))
     torch.cuda.synchronize()
     return vol, counts
 
@@ -84,8 +83,7 @@ def test_extraction_matches_the_numpy_restatement_and_is_bit_reproducible(hip_li
     assert np.abs(mesh.vertices - rv).max() <= 1e-6
     assert np.abs(mesh.vertex_colors - rc).max() <= 1e-6
     again = vol.extract_triangle_mesh()
-    for a, b in zip(mesh, again):
-        assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+    same_bits(tuple(again), tuple(mesh), "second run")
     assert mesh.vertices.dtype == np.float32 and mesh.triangles.dtype == np.int32
     assert len(np.unique(mesh.triangles)) == len(mesh.vertices)  # no unreferenced vertex
 
@@ -142,25 +140,17 @@ def _room_model():
     sc = synthetic.scene_room(N_SURFELS, seed=4, size=ROOM, scale_mean=SCALE_MEAN, scale_sigma=0.2)
     cols = FACE_RGB[_face_of(sc.means3D.astype(np.float64))]
     m = GaussianModel(sh_degree=3)
-    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=DEV)
-    m.create_from_parameters(t(sc.means3D), t(sc.scales), t(sc.rotations), t(cols))
+    m.create_from_parameters(*devs((sc.means3D, sc.scales, sc.rotations, cols)))
     with torch.no_grad():
         m._opacity.fill_(math.log(0.97 / 0.03))
     m.active_sh_degree = 0
     return m
 
 
-def _device_camera(cam):
-    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=DEV)
-    return SimpleNamespace(image_width=cam.image_width, image_height=cam.image_height, FoVx=cam.FoVx, FoVy=cam.FoVy,
-                           world_view_transform=t(cam.world_view_transform), full_proj_transform=t(cam.full_proj_transform),
-                           camera_center=t(cam.camera_center), znear=cam.znear, zfar=cam.zfar)
-
-
 def test_gaussian_extractor_meshes_the_rendered_room(hip_lib):
     from g4splat_amd.gaussian_renderer import render
     model = _room_model()
-    cams = [_device_camera(c) for c in synthetic.room_cameras(8, 320, 240)]
+    cams = [device_camera(c) for c in synthetic.room_cameras(8, 320, 240)]
     pipe = SimpleNamespace(depth_ratio=1.0, compute_cov3D_python=False, convert_SHs_python=False)
     ex = mesh_mod.GaussianExtractor(model, render, pipe)
     ex.reconstruction(cams)

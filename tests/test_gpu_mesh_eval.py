@@ -13,16 +13,11 @@ import tsdf_ref
 from g4splat_amd import mesh as mesh_mod
 from g4splat_amd import mesh_eval as me
 from g4splat_amd import ply_io
+from support import DEV, devs, hosts, same_bits
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda:0")
 f32 = np.float32
-
-
-def _bytes_equal(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
 def _search(cloud, query):
@@ -41,9 +36,10 @@ def _check_search(cloud, query):
     d2, idx = _search(cloud, query)
     want_d2, want_idx = ref.nn_search(cloud, query)
     assert np.array_equal(idx, want_idx), np.nonzero(idx != want_idx)[0][:8]
-    assert _bytes_equal(d2, want_d2)
+    same_bits(d2, want_d2)
     dist, index = me.nearest_neighbors(cloud, query)  # the public form: sqrt in float32
-    assert _bytes_equal(dist.cpu().numpy(), np.sqrt(want_d2)) and np.array_equal(index.cpu().numpy(), want_idx)
+    same_bits(dist, np.sqrt(want_d2))
+    assert np.array_equal(index.cpu().numpy(), want_idx)
     return d2, idx
 
 
@@ -125,7 +121,7 @@ def test_search_swapped_and_repeated(hip_lib):
     first = _check_search(a, b)
     _check_search(b, a)
     again = _search(a, b)
-    assert _bytes_equal(first[0], again[0]) and _bytes_equal(first[1], again[1])
+    same_bits(first[:2], again[:2])
 
 
 def test_search_refuses_an_empty_reference(hip_lib):
@@ -138,7 +134,7 @@ def test_search_refuses_an_empty_reference(hip_lib):
 # ---- down-sample ----------------------------------------------------------------------------------------------------
 def _check_down_sample(points, voxel):
     got = me.voxel_down_sample(points, voxel).cpu().numpy()
-    assert _bytes_equal(got, ref.voxel_down_sample(points, voxel))
+    same_bits(got, ref.voxel_down_sample(points, voxel))
     return got
 
 
@@ -175,12 +171,12 @@ def test_down_sample_refuses_non_finite_points(hip_lib, bad):
 # ---- sampler --------------------------------------------------------------------------------------------------------
 def _check_sampler(mesh, u, cum=None):
     """cum = None: the device's own cumulative areas, downloaded for the restatement."""
-    dm = mesh_mod.DeviceMesh(*(torch.as_tensor(np.ascontiguousarray(a), device=DEV) for a in mesh))
+    dm = mesh_mod.DeviceMesh(*devs(mesh))
     cum = me.cumulative_areas(dm) if cum is None else torch.as_tensor(cum, device=DEV)
-    got = [t.cpu().numpy() for t in me.sample_surface(dm, len(u), u=torch.as_tensor(u, device=DEV), cum_area=cum)]
+    got = hosts(me.sample_surface(dm, len(u), u=torch.as_tensor(u, device=DEV), cum_area=cum))
     want = ref.sample_surface(u, cum.cpu().numpy(), mesh[2], mesh[0])
     for name, g, w in zip(("points", "normals", "face"), got, want):
-        assert _bytes_equal(g, w), name
+        same_bits(g, w, name)
     return got
 
 
@@ -220,7 +216,7 @@ N_SAMPLES = 3000
 
 def _evaluate_both_ways(pred, trgt, device_meshes, threshold=0.05, down_sample=0.02):
     """(library's metrics, restatement's on the same samples and the device's own cumulative areas)."""
-    wrap = (lambda m: mesh_mod.DeviceMesh(*(torch.as_tensor(np.ascontiguousarray(a), device=DEV) for a in m))) if device_meshes \
+    wrap = (lambda m: mesh_mod.DeviceMesh(*devs(m))) if device_meshes \
         else (lambda m: mesh_mod.TriangleMesh(*m))
     g = torch.Generator(device=DEV)
     g.manual_seed(50)

@@ -13,28 +13,14 @@ import mesh_ops_ref as ref
 import tsdf_ref
 from g4splat_amd import mesh as mesh_mod
 from g4splat_amd import ply_io, synthetic
+from support import DEV, device_camera, devs, hosts, same_bits
 
 pytestmark = pytest.mark.gpu
-
-DEV = torch.device("cuda:0")
-
-
-def _bytes_equal(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
 def _assert_mesh_equal(got, want):
     for name, g, w in zip(("vertices", "vertex_colors", "triangles"), got, want):
-        assert _bytes_equal(g, w), (name, np.shape(g), np.shape(w))
-
-
-def _upload(mesh):
-    return mesh_mod.DeviceMesh(*(torch.as_tensor(np.ascontiguousarray(a), device=DEV) for a in mesh))
-
-
-def _download(mesh):
-    return tuple(a.cpu().numpy() for a in mesh)
+        same_bits(g, w, name)
 
 
 # ---- inputs -------------------------------------------------------------------------------------------------------
@@ -100,7 +86,7 @@ def test_clustering_matches_the_restatement_and_is_bit_reproducible(hip_lib, big
     cluster_sizes = sizes[labels == np.arange(len(labels))]
     assert len(mesh[2]) >= 200_000 and len(cluster_sizes) >= 200
     assert cluster_sizes.max() > 10_000 and (cluster_sizes == 1).sum() >= 1 and len(np.unique(cluster_sizes)) > 30
-    dm = _upload(mesh)
+    dm = mesh_mod.DeviceMesh(*devs(mesh))
     torch.cuda.synchronize()
     t0 = time.time()
     got_l, got_s = mesh_mod.cluster_connected_triangles(dm)
@@ -126,10 +112,10 @@ def test_post_process_mesh_matches_the_restatement(hip_lib, big_mesh, k):
     if k == 10_000:
         assert n_clusters < k
     want = ref.post_process_mesh(mesh, k)
-    got = mesh_mod.post_process_mesh(_upload(mesh), cluster_to_keep=k)
+    got = mesh_mod.post_process_mesh(mesh_mod.DeviceMesh(*devs(mesh)), cluster_to_keep=k)
     assert isinstance(got, mesh_mod.DeviceMesh) and all(a.device == DEV for a in got)
     assert len(want[2]) > 0
-    _assert_mesh_equal(_download(got), want)
+    _assert_mesh_equal(hosts(got), want)
     if k == 5:
         _assert_mesh_equal(mesh_mod.post_process_mesh(mesh_mod.TriangleMesh(*mesh), cluster_to_keep=k), want)
 
@@ -141,20 +127,20 @@ def test_filter_mesh_matches_the_restatement(hip_lib, big_mesh):
     thr = float(np.sort(valid.max(1))[len(valid) // 2])  # a length that occurs: the median longest edge (<= keeps it)
     want = ref.filter_mesh(mesh, thr)
     assert 0.3 < len(want[2]) / len(mesh[2]) < 0.7
-    got = mesh_mod.filter_mesh(_upload(mesh), length_threshold=thr)
-    _assert_mesh_equal(_download(got), want)
-    _assert_mesh_equal(_download(mesh_mod.filter_mesh(_upload(mesh))), ref.filter_mesh(mesh))  # the default 0.05
+    got = mesh_mod.filter_mesh(mesh_mod.DeviceMesh(*devs(mesh)), length_threshold=thr)
+    _assert_mesh_equal(hosts(got), want)
+    _assert_mesh_equal(hosts(mesh_mod.filter_mesh(mesh_mod.DeviceMesh(*devs(mesh)))), ref.filter_mesh(mesh))  # the default 0.05
 
 
 def test_compaction_handles_empty_results_and_out_of_range_indices(hip_lib):
     rng = np.random.default_rng(1)
     verts, cols = rng.normal(size=(8, 3)).astype(np.float32), rng.uniform(0, 1, (8, 3)).astype(np.float32)
     tris = np.array([[7, 5, 6], [0, 1, 2], [5, 9, 7], [2, 2, 2], [-1, 3, 4]], np.int32)
-    dm = _upload((verts, cols, tris))
+    dm = mesh_mod.DeviceMesh(*devs((verts, cols, tris)))
     for keep in ([1, 0, 1, 1, 1], [0, 0, 0, 0, 0], [1, 1, 1, 1, 1]):
         k = torch.tensor(keep, dtype=torch.uint8, device=DEV)
-        _assert_mesh_equal(_download(mesh_mod.compact_mesh(dm, k)), ref.compact((verts, cols, tris), np.array(keep, bool)))
-        _assert_mesh_equal(_download(mesh_mod.compact_mesh(dm, k, compact_vertices=False)),
+        _assert_mesh_equal(hosts(mesh_mod.compact_mesh(dm, k)), ref.compact((verts, cols, tris), np.array(keep, bool)))
+        _assert_mesh_equal(hosts(mesh_mod.compact_mesh(dm, k, compact_vertices=False)),
                            ref.compact((verts, cols, tris), np.array(keep, bool), compact_vertices=False))
     empty = mesh_mod.post_process_mesh(mesh_mod.TriangleMesh(np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32),
                                                              np.zeros((0, 3), np.int32)))
@@ -170,7 +156,7 @@ def test_device_residency(hip_lib, sphere_volume):
     assert isinstance(host, mesh_mod.TriangleMesh) and isinstance(dev, mesh_mod.DeviceMesh)
     assert all(isinstance(a, torch.Tensor) and a.device == DEV for a in dev)
     assert len(host.triangles) > 10_000
-    _assert_mesh_equal(_download(dev), host)
+    _assert_mesh_equal(hosts(dev), host)
     cam = synthetic.look_at_camera((6, 0, 0), (0, 0, 0), (0, 1, 0), math.radians(30), 160, 120)
     outs = [mesh_mod.cull_observed_faces(dev, [cam], 6.0), mesh_mod.join_meshes([dev, dev]),
             mesh_mod.post_process_mesh(dev, cluster_to_keep=1), mesh_mod.filter_mesh(dev, 0.03)]
@@ -178,11 +164,11 @@ def test_device_residency(hip_lib, sphere_volume):
         assert isinstance(out, mesh_mod.DeviceMesh) and all(a.device == DEV for a in out)
         assert out.vertices.dtype == torch.float32 and out.triangles.dtype == torch.int32
     assert 0 < outs[0].triangles.size(0) < dev.triangles.size(0)  # the half facing the camera is nearer than 6
-    _assert_mesh_equal(_download(outs[1]), ref.join_meshes([tuple(host), tuple(host)]))
+    _assert_mesh_equal(hosts(outs[1]), ref.join_meshes([tuple(host), tuple(host)]))
     assert all(isinstance(a, torch.Tensor) and a.device == DEV for a in mesh_mod.cluster_connected_triangles(dev))
     back = mesh_mod.cull_observed_faces(host, [cam], 6.0)
     assert isinstance(back, mesh_mod.TriangleMesh)
-    _assert_mesh_equal(back, _download(outs[0]))
+    _assert_mesh_equal(back, hosts(outs[0]))
 
 
 # ---- the rendered room (builders as in tests/test_gpu_mesh.py) -------------------------------------------------------
@@ -215,19 +201,11 @@ def _room_model():
     sc = synthetic.scene_room(N_SURFELS, seed=4, size=ROOM, scale_mean=SCALE_MEAN, scale_sigma=0.2)
     cols = FACE_RGB[_face_of(sc.means3D.astype(np.float64))]
     m = GaussianModel(sh_degree=3)
-    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=DEV)
-    m.create_from_parameters(t(sc.means3D), t(sc.scales), t(sc.rotations), t(cols))
+    m.create_from_parameters(*devs((sc.means3D, sc.scales, sc.rotations, cols)))
     with torch.no_grad():
         m._opacity.fill_(math.log(0.97 / 0.03))
     m.active_sh_degree = 0
     return m
-
-
-def _device_camera(cam):
-    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=DEV)
-    return SimpleNamespace(image_width=cam.image_width, image_height=cam.image_height, FoVx=cam.FoVx, FoVy=cam.FoVy,
-                           world_view_transform=t(cam.world_view_transform), full_proj_transform=t(cam.full_proj_transform),
-                           camera_center=t(cam.camera_center), znear=cam.znear, zfar=cam.zfar)
 
 
 def _icosahedron(center, radius):
@@ -245,7 +223,7 @@ def _icosahedron(center, radius):
 def room(hip_lib):
     from g4splat_amd.gaussian_renderer import render
     host_cams = synthetic.room_cameras(8, 320, 240)
-    cams = [_device_camera(c) for c in host_cams]
+    cams = [device_camera(c) for c in host_cams]
     pipe = SimpleNamespace(depth_ratio=1.0, compute_cov3D_python=False, convert_SHs_python=False)
     ex = mesh_mod.GaussianExtractor(_room_model(), render, pipe)
     ex.reconstruction(cams)
@@ -266,14 +244,14 @@ def test_cull_matches_the_restatement_on_sphere_plus_room(hip_lib, room, sphere_
     keep = ref.keep_unobserved(mesh[2], obs)
     print(f"\n[mesh_ops] cull: {len(mesh[2])} faces, restatement removes {1 - keep.mean():.3f}")
     assert 0.1 <= 1 - keep.mean() <= 0.9
-    dm = _upload(mesh)
+    dm = mesh_mod.DeviceMesh(*devs(mesh))
     got_keep = mesh_mod.observed_face_mask(dm, cams, near)
     assert got_keep.device == DEV and got_keep.dtype == torch.uint8
     assert np.array_equal(got_keep.cpu().numpy().astype(bool), keep)
     want = ref.compact(mesh, keep)
-    _assert_mesh_equal(_download(mesh_mod.cull_observed_faces(dm, cams, near)), want)
+    _assert_mesh_equal(hosts(mesh_mod.cull_observed_faces(dm, cams, near)), want)
     # cameras given as device tensors, and more of them than one LDS chunk holds (the same nine, repeated)
-    dev_cams = [_device_camera(c) for c in cams]
+    dev_cams = [device_camera(c) for c in cams]
     many = [dev_cams[i % 9] for i in range(150)]
     assert np.array_equal(mesh_mod.observed_face_mask(dm, many, near).cpu().numpy().astype(bool), keep)
     only_last = mesh_mod.observed_face_mask(dm, [dev_cams[0]] * 70 + [dev_cams[8]], near).cpu().numpy().astype(bool)
@@ -297,13 +275,12 @@ def test_multires_export_of_the_rendered_room(hip_lib, room, tmp_path):
     assert trunc0 == pytest.approx(TRUNC0) and trunc1 == pytest.approx(4 * TRUNC0)
     assert voxel0 == pytest.approx(TRUNC0 / MESH_RES) and before0 == after0 > 50_000
     assert 0 < after1 < before1  # the far walls come from the second level, the near ones were culled from it
-    v, c, t = _download(joined)
+    v, c, t = hosts(joined)
     assert len(t) == after0 + after1
     # the first level is the head of the result, unchanged
     level0 = ex.extract_mesh_bounded(voxel_size=voxel0, sdf_trunc=5.0 * voxel0, depth_trunc=trunc0)
     V0 = len(level0.vertices)
-    assert _bytes_equal(t[:after0], level0.triangles) and _bytes_equal(v[:V0], level0.vertices)
-    assert _bytes_equal(c[:V0], level0.vertex_colors)
+    same_bits([t[:after0], v[:V0], c[:V0]], [level0.triangles, level0.vertices, level0.vertex_colors])
     # the tail is the second level after the restatement's cull, bit for bit
     level1 = ex.extract_mesh_bounded(voxel_size=voxel1, sdf_trunc=5.0 * voxel1, depth_trunc=trunc1)
     assert len(level1.triangles) == before1
@@ -322,22 +299,23 @@ def test_multires_export_of_the_rendered_room(hip_lib, room, tmp_path):
     assert far.sum() > 0
     # floaters: five icosahedra (20 faces each) mid-room disappear, the walls stay
     centres = np.array([(0.4 * i - 0.8, 0.3, 0.1 * i) for i in range(5)])
-    floaters = [_upload(_icosahedron(ctr, 0.05)) for ctr in centres]
+    floaters = [mesh_mod.DeviceMesh(*devs(_icosahedron(ctr, 0.05))) for ctr in centres]
     with_floaters = mesh_mod.join_meshes([joined] + floaters)
     assert with_floaters.triangles.size(0) == len(t) + 100
     t0 = time.time()
     post = mesh_mod.post_process_mesh(with_floaters, cluster_to_keep=1)
     torch.cuda.synchronize()
-    pv, pc, pt = _download(post)
+    pv, pc, pt = hosts(post)
     print(f"[mesh_ops] post_process_mesh: {time.time() - t0:.2f} s, {len(pt)} of {len(t)} wall triangles remain")
     assert len(pt) >= 0.95 * len(t)
-    fv = _download(with_floaters)[0]
+    fv = hosts(with_floaters)[0]
     near_floater = lambda p: (np.linalg.norm(p[:, None, :].astype(np.float64) - centres[None], axis=2) < 0.06).any(1)
     assert near_floater(fv).sum() == 60 and near_floater(pv).sum() == 0  # the floaters' vertices are gone
     assert len(np.unique(pt)) == len(pv) and pt.min() == 0 and pt.max() == len(pv) - 1
     path = str(tmp_path / "multires_tsdf_post.ply")
     ply_io.write_triangle_mesh(path, post)
     rv, rc, rt = ply_io.read_triangle_mesh(path)
-    assert _bytes_equal(rv, pv) and _bytes_equal(rt, pt) and np.abs(rc - pc).max() <= 0.5 / 255 + 1e-6
+    same_bits([rv, rt], [pv, pt])
+    assert np.abs(rc - pc).max() <= 0.5 / 255 + 1e-6
     filtered = mesh_mod.filter_mesh(joined, length_threshold=3 * voxel0)  # drops the coarse level's long edges only
     assert after0 <= filtered.triangles.size(0) < len(t)

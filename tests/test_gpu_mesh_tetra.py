@@ -11,19 +11,11 @@ import tetra_ref as tr
 import view_tap_ref
 from g4splat_amd import mesh as mesh_mod
 from g4splat_amd import ply_io, synthetic
+from support import DEV, dev, device_camera, same_bits
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda:0")
 TRUNC = 0.1
-
-
-def _dev(a):
-    return torch.as_tensor(np.ascontiguousarray(a), device=DEV)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 @pytest.fixture(scope="module")
@@ -35,7 +27,7 @@ def scene():
 
 
 def _gpu_views(views, rgb=True):
-    return [((Wv, Pm), _dev(d), _dev(c) if rgb else None) for Wv, Pm, d, c in views]
+    return [((Wv, Pm), dev(d), dev(c) if rgb else None) for Wv, Pm, d, c in views]
 
 
 def _stacks(scene):
@@ -49,12 +41,12 @@ def test_adaptive_tsdf_equals_the_restatement_bit_for_bit(hip_lib, scene, stack,
     views, pts = _stacks(scene)[stack], scene.points[-n:] if n > 1 else scene.points[:1]
     want_t, want_c, used = tr.adaptive_tsdf(pts, views, TRUNC)
     assert n > 1 or (used.any() and want_t[0] != -1)
-    got_t, got_c = (o.cpu().numpy() for o in mesh_mod.adaptive_tsdf(_dev(pts), _gpu_views(views), TRUNC, return_rgb=True))
+    got_t, got_c = (o.cpu().numpy() for o in mesh_mod.adaptive_tsdf(dev(pts), _gpu_views(views), TRUNC, return_rgb=True))
     assert got_t.shape == (n,) and got_c.shape == (n, 3)
-    assert np.array_equal(_bits(got_t), _bits(want_t)), np.abs(got_t - want_t).max()
-    assert np.array_equal(_bits(got_c), _bits(want_c)), np.abs(got_c - want_c).max()
-    only_t = mesh_mod.adaptive_tsdf(_dev(pts), _gpu_views(views, rgb=False), TRUNC).cpu().numpy()  # without colours
-    assert np.array_equal(_bits(only_t), _bits(want_t))
+    same_bits(got_t, want_t)
+    same_bits(got_c, want_c)
+    only_t = mesh_mod.adaptive_tsdf(dev(pts), _gpu_views(views, rgb=False), TRUNC).cpu().numpy()  # without colours
+    same_bits(only_t, want_t)
     assert n < 4 or ((got_t[-4:] == -1).all() and not used[-4:].any())  # unseen keeps -1
     if stack == "none":
         assert (got_t == -1).all() and (got_c == 0).all()
@@ -83,10 +75,10 @@ def test_adaptive_tsdf_on_maps_two_pixels_wide(hip_lib, scene, crop, floor):
     want_t, want_c, used = tr.adaptive_tsdf(scene.points, views, TRUNC)
     print(crop, "accepted per view:", used.sum(0))
     assert (used.sum(0) >= floor).all()  # from the restatement alone
-    got = mesh_mod.adaptive_tsdf(_dev(scene.points), _gpu_views(views), TRUNC, return_rgb=True)
+    got = mesh_mod.adaptive_tsdf(dev(scene.points), _gpu_views(views), TRUNC, return_rgb=True)
     got_t, got_c = (o.cpu().numpy() for o in got)
-    assert np.array_equal(_bits(got_t), _bits(want_t)), np.abs(got_t - want_t).max()
-    assert np.array_equal(_bits(got_c), _bits(want_c)), np.abs(got_c - want_c).max()
+    same_bits(got_t, want_t)
+    same_bits(got_c, want_c)
 
 
 def _sphere_field(p, centre, radius):
@@ -94,7 +86,7 @@ def _sphere_field(p, centre, radius):
 
 
 def _gpu_mtet(points, tets, sdf):
-    e, f = mesh_mod.marching_tetrahedra(_dev(points), _dev(tets), _dev(sdf))
+    e, f = mesh_mod.marching_tetrahedra(dev(points), dev(tets), dev(sdf))
     assert e.dtype == torch.int32 and f.dtype == torch.int32 and e.is_cuda and f.is_cuda
     return e.cpu().numpy(), f.cpu().numpy()
 
@@ -167,10 +159,10 @@ def test_marching_tetrahedra_of_more_than_65536_points(hip_lib):
 def test_marching_tetrahedra_takes_a_view_at_an_odd_offset(hip_lib, lattice17):
     """tets as a view that starts 4 bytes into its storage: the front-end hands the kernels an aligned copy."""
     p, tets, sdf, (want_e, want_f) = lattice17
-    flat = torch.cat([torch.zeros(1, dtype=torch.int32, device=DEV), _dev(tets).reshape(-1)])
+    flat = torch.cat([torch.zeros(1, dtype=torch.int32, device=DEV), dev(tets).reshape(-1)])
     view = flat[1:].reshape(-1, 4)
     assert view.data_ptr() % 16 == 4
-    e, f = mesh_mod.marching_tetrahedra(_dev(p), view, _dev(sdf))
+    e, f = mesh_mod.marching_tetrahedra(dev(p), view, dev(sdf))
     assert np.array_equal(e.cpu().numpy(), want_e) and np.array_equal(f.cpu().numpy(), want_f)
 
 
@@ -190,11 +182,11 @@ def test_out_of_range_tets_are_refused(hip_lib, lattice17):
         t = tets[:300].copy()
         t[123, 2] = bad
         with pytest.raises(RuntimeError, match="outside"):
-            mesh_mod.marching_tetrahedra(_dev(p), _dev(t), _dev(sdf))
+            mesh_mod.marching_tetrahedra(dev(p), dev(t), dev(sdf))
     with pytest.raises(RuntimeError, match="outside"):
-        mesh_mod.bisect_surface(_dev(p), _dev(np.array([[0, len(p)]], np.int32)), _dev(sdf), [], TRUNC)
+        mesh_mod.bisect_surface(dev(p), dev(np.array([[0, len(p)]], np.int32)), dev(sdf), [], TRUNC)
     with pytest.raises(RuntimeError, match="integer"):
-        mesh_mod.bisect_surface(_dev(p), _dev(np.array([[0.0, 1.0]], np.float32)), _dev(sdf), [], TRUNC)
+        mesh_mod.bisect_surface(dev(p), dev(np.array([[0.0, 1.0]], np.float32)), dev(sdf), [], TRUNC)
     with pytest.raises(RuntimeError, match="HIP device"):
         mesh_mod.adaptive_tsdf(torch.zeros(4, 3), [], TRUNC)
 
@@ -205,9 +197,9 @@ def sphere_mesh(hip_lib, scene):
     p, tets = tr.kuhn_lattice(13)
     p = ((p / np.float32(12)) * np.float32(3.0) - np.float32(1.5)).astype(np.float32)
     views = _gpu_views(scene.full, rgb=False)
-    pts = _dev(p)
+    pts = dev(p)
     sdf = mesh_mod.adaptive_tsdf(pts, views, TRUNC)
-    edges, faces = mesh_mod.marching_tetrahedra(pts, _dev(tets), sdf)
+    edges, faces = mesh_mod.marching_tetrahedra(pts, dev(tets), sdf)
     return SimpleNamespace(p=p, pts=pts, views=views, sdf=sdf, edges=edges, faces=faces)
 
 
@@ -226,12 +218,13 @@ def test_bisection_equals_eight_explicit_rounds(hip_lib, scene, sphere_mesh):
         r = torch.where(low[:, None], r, mid)
         ls = torch.where(low, ms, ls)
     want = ((l + r) / 2).cpu().numpy()
-    assert got.shape == (E, 3) and np.array_equal(_bits(got.cpu().numpy()), _bits(want))
+    assert got.shape == (E, 3)
+    same_bits(got, want)
     ref = tr.bisect(m.p, m.edges.cpu().numpy(), m.sdf.cpu().numpy(), scene.full, TRUNC, steps=8)
-    assert np.array_equal(_bits(got.cpu().numpy()), _bits(ref))
+    same_bits(got, ref)
     # steps = 0: the edge midpoints
     mid0 = mesh_mod.bisect_surface(m.pts, m.edges, m.sdf, m.views, TRUNC, steps=0).cpu().numpy()
-    assert np.array_equal(_bits(mid0), _bits(((m.pts[e[:, 0]] + m.pts[e[:, 1]]) / 2).cpu().numpy()))
+    same_bits(mid0, (m.pts[e[:, 0]] + m.pts[e[:, 1]]) / 2)
     # every vertex, the rim crossings included, stays on its edge: a midpoint of two floats lies between them
     ends = np.stack([m.p[m.edges.cpu().numpy()[:, 0]], m.p[m.edges.cpu().numpy()[:, 1]]])
     g = got.cpu().numpy()
@@ -253,30 +246,24 @@ def _room_model(n=20000):
     sc = synthetic.scene_room(n, seed=4, size=(6.0, 4.0, 3.0), scale_mean=0.12, scale_sigma=0.2)
     rng = np.random.default_rng(1)
     m = GaussianModel(sh_degree=3)
-    m.create_from_parameters(_dev(sc.means3D), _dev(sc.scales), _dev(sc.rotations),
-                             _dev(rng.uniform(0.2, 0.9, (n, 3)).astype(np.float32)))
+    m.create_from_parameters(dev(sc.means3D), dev(sc.scales), dev(sc.rotations),
+                             dev(rng.uniform(0.2, 0.9, (n, 3)).astype(np.float32)))
     with torch.no_grad():
         m._opacity.fill_(math.log(0.97 / 0.03))
     m.active_sh_degree = 2
     return m
 
 
-def _device_camera(cam):
-    return SimpleNamespace(image_width=cam.image_width, image_height=cam.image_height, FoVx=cam.FoVx, FoVy=cam.FoVy,
-                           world_view_transform=_dev(cam.world_view_transform), full_proj_transform=_dev(cam.full_proj_transform),
-                           camera_center=_dev(cam.camera_center), znear=cam.znear, zfar=cam.zfar)
-
-
 def test_extract_mesh_tetra_end_to_end(hip_lib, tmp_path):
     from g4splat_amd.gaussian_renderer import render
     model = _room_model()
-    cams = [_device_camera(c) for c in synthetic.room_cameras(6, 160, 120)]
+    cams = [device_camera(c) for c in synthetic.room_cameras(6, 160, 120)]
     pipe = SimpleNamespace(depth_ratio=1.0, compute_cov3D_python=False, convert_SHs_python=False)
     ex = mesh_mod.GaussianExtractor(model, render, pipe)
     ex.reconstruction(cams)
     n_points = 9 * int(20000 * 0.1)
     k = int(round(n_points ** (1 / 3))) - 1
-    lattice_cells = _dev(tr.kuhn_lattice(k)[1])  # any cells over the points will do for the plumbing
+    lattice_cells = dev(tr.kuhn_lattice(k)[1])  # any cells over the points will do for the plumbing
     runs = [dict(cells=lattice_cells)]
     try:
         import scipy  # noqa: F401

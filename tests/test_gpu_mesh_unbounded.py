@@ -14,19 +14,11 @@ import unbounded_ref as ur
 import view_tap_ref
 from g4splat_amd import mesh as mesh_mod
 from g4splat_amd import ply_io, synthetic
+from support import DEV, dev, same_bits
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = torch.device("cuda:0")
-
-
-def _dev(a):
-    return torch.as_tensor(np.ascontiguousarray(a), device=DEV)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 @pytest.fixture(scope="module")
@@ -40,11 +32,11 @@ def scene():
 
 
 def _gpu_views(views):
-    return [(M, _dev(d), _dev(c)) for M, d, c in views]
+    return [(M, dev(d), dev(c)) for M, d, c in views]
 
 
 def _gpu_sample(points, views, frame, contracted, rgb):
-    out = mesh_mod.unbounded_tsdf(_dev(points), _gpu_views(views), frame["center"], frame["radius"], frame["voxel_size"],
+    out = mesh_mod.unbounded_tsdf(dev(points), _gpu_views(views), frame["center"], frame["radius"], frame["voxel_size"],
                                   contracted=contracted, return_rgb=rgb)
     return tuple(o.cpu().numpy() for o in out) if rgb else out.cpu().numpy()
 
@@ -56,10 +48,10 @@ def test_sample_equals_the_restatement_bit_for_bit(hip_lib, scene, contracted):
     want_t, want_c, _m, used = ur.sample(pts, scene.full, f["center"], f["radius"], f["voxel_size"], contracted)
     assert used.any(1).sum() > 500
     got_t, got_c = _gpu_sample(pts, scene.full, f, contracted, True)
-    assert np.array_equal(_bits(got_t), _bits(want_t)), np.abs(got_t - want_t).max()
-    assert np.array_equal(_bits(got_c), _bits(want_c)), np.abs(got_c - want_c).max()
+    same_bits(got_t, want_t)
+    same_bits(got_c, want_c)
     only_t = _gpu_sample(pts, scene.full, f, contracted, False)  # the kernel without colours: the same tsdf
-    assert np.array_equal(_bits(only_t), _bits(want_t))
+    same_bits(only_t, want_t)
 
 
 @pytest.mark.parametrize("crop", ["one_column", "one_row", "one_pixel", "mixed"])
@@ -78,8 +70,8 @@ def test_sample_on_maps_one_pixel_wide(hip_lib, scene, crop):
     print(crop, "accepted per view:", used.sum(0))
     assert (used.sum(0) >= 8).all()  # from the restatement alone
     got_t, got_c = _gpu_sample(pts, views, f, False, True)
-    assert np.array_equal(_bits(got_t), _bits(want_t)), np.abs(got_t - want_t).max()
-    assert np.array_equal(_bits(got_c), _bits(want_c)), np.abs(got_c - want_c).max()
+    same_bits(got_t, want_t)
+    same_bits(got_c, want_c)
 
 
 def _stacks(scene):
@@ -100,7 +92,7 @@ def test_grid_equals_sample_on_the_explicit_lattice(hip_lib, scene, N, stack):
     grid = mesh_mod.unbounded_tsdf_grid(N, R, _gpu_views(views), f["center"], f["radius"], f["voxel_size"], DEV).cpu().numpy()
     assert grid.shape == (N ** 3,)
     want = _gpu_sample(ur.lattice_points(N, R), views, f, True, False)
-    assert np.array_equal(_bits(grid), _bits(want)), np.abs(grid - want).max()
+    same_bits(grid, want)
     if not views:
         assert (grid == 1.0).all()
     else:
@@ -118,7 +110,7 @@ def lattice33(scene):
 def test_dense_cubes_of_the_lattice_match_the_restatement(hip_lib, scene, lattice33):
     f, R, N = scene.frame, 1.9, 33
     field = lattice33.cpu().numpy()
-    assert np.array_equal(_bits(field), _bits(ur.lattice(N, R, scene.full, f["center"], f["radius"], f["voxel_size"])))
+    same_bits(field, ur.lattice(N, R, scene.full, f["center"], f["radius"], f["voxel_size"]))
     verts, tris = mesh_mod.dense_marching_cubes(lattice33, R, f["center"], f["radius"])
     rv, rt = ur.dense_cubes(field, N, R, f["center"], f["radius"])
     assert len(rt) > 300 and verts.dtype == np.float32 and tris.dtype == np.int32
@@ -128,8 +120,7 @@ def test_dense_cubes_of_the_lattice_match_the_restatement(hip_lib, scene, lattic
     _rt, rc, _m, _u = ur.sample(rv, scene.full, f["center"], f["radius"], f["voxel_size"], False)
     assert np.abs(cols - rc).max() <= 1e-6
     again = mesh_mod.dense_marching_cubes(lattice33, R, f["center"], f["radius"])
-    for a, b in zip((verts, tris), again):
-        assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+    same_bits(tuple(again), (verts, tris), "second run")
     dv, dt = mesh_mod.dense_marching_cubes(lattice33, R, f["center"], f["radius"], to_host=False)
     assert dv.is_cuda and dt.is_cuda and np.array_equal(dv.cpu().numpy(), verts) and np.array_equal(dt.cpu().numpy(), tris)
 
@@ -138,21 +129,21 @@ def test_dense_cubes_of_analytic_fields(hip_lib):
     N, R = 33, 1.0
     y = ur.lattice_points(N, R).astype(np.float64)
     field = (np.linalg.norm(y, axis=1) - 0.5).astype(np.float32)
-    verts, tris = mesh_mod.dense_marching_cubes(_dev(field).reshape(N, N, N), R, (0.0, 0.0, 0.0), 1.0)
+    verts, tris = mesh_mod.dense_marching_cubes(dev(field).reshape(N, N, N), R, (0.0, 0.0, 0.0), 1.0)
     rv, rt = ur.dense_cubes(field, N, R, (0.0, 0.0, 0.0), 1.0)
     assert np.array_equal(tris, rt) and np.abs(verts - rv).max() <= 1e-6
     assert len(tris) > 1000 and ur.closed_manifold(len(verts), tris) == 2
     assert np.abs(np.linalg.norm(verts.astype(np.float64), axis=1) - 0.5).max() < 2.0 / 32
     # un-contraction and the clamp of world units
     shell = (np.linalg.norm(y * 1.9, axis=1) - 1.5).astype(np.float32)  # the lattice over [-1.9, 1.9]^3
-    verts, tris = mesh_mod.dense_marching_cubes(_dev(shell), 1.9, (1.0, 2.0, 3.0), 20.0, max_range=32.0)
+    verts, tris = mesh_mod.dense_marching_cubes(dev(shell), 1.9, (1.0, 2.0, 3.0), 20.0, max_range=32.0)
     rv, rt = ur.dense_cubes(shell, N, 1.9, (1.0, 2.0, 3.0), 20.0, max_range=32.0)
     assert np.array_equal(tris, rt) and np.abs(verts - rv).max() <= 1e-6 and np.abs(verts).max() == 32.0
     # N = 2: one cube, one negative corner
     for corner in (0, 5, 7):
         cube = np.ones(8, np.float32)
         cube[corner] = -0.25
-        verts, tris = mesh_mod.dense_marching_cubes(_dev(cube), 0.5, (0.0, 0.0, 0.0), 1.0)
+        verts, tris = mesh_mod.dense_marching_cubes(dev(cube), 0.5, (0.0, 0.0, 0.0), 1.0)
         rv, rt = ur.dense_cubes(cube, 2, 0.5, (0.0, 0.0, 0.0), 1.0)
         assert verts.shape == (3, 3) and tris.shape == (1, 3)
         assert np.array_equal(tris, rt) and np.abs(verts - rv).max() <= 1e-6
@@ -170,12 +161,12 @@ def test_extract_mesh_unbounded_end_to_end(hip_lib, tmp_path):
         up = (0, 0, 1) if abs(e[1]) > 0 else (0, 1, 0)
         cam = synthetic.look_at_camera(e, (0, 0, 0), up, math.radians(50), W, H)
         intr, E = mesh_mod.camera_intrinsics(cam), mesh_mod.camera_extrinsic(cam)
-        depths.append(_dev(tsdf_ref.sphere_depth(E, intr, W, H, (0, 0, 0), 1.0))[None])
-        rgbs.append(_dev(rng.uniform(0, 1, (3, H, W)).astype(np.float32)))
+        depths.append(dev(tsdf_ref.sphere_depth(E, intr, W, H, (0, 0, 0), 1.0))[None])
+        rgbs.append(dev(rng.uniform(0, 1, (3, H, W)).astype(np.float32)))
         cams.append(cam)
     xyz = rng.normal(size=(5000, 3))
     xyz /= np.linalg.norm(xyz, axis=1, keepdims=True)
-    gaussians = SimpleNamespace(get_xyz=_dev(xyz.astype(np.float32)))
+    gaussians = SimpleNamespace(get_xyz=dev(xyz.astype(np.float32)))
     ex = mesh_mod.GaussianExtractor(gaussians, None, None)
     ex.viewpoint_stack, ex.depthmaps, ex.rgbmaps = cams, depths, rgbs
     ex.estimate_bounding_sphere()

@@ -264,7 +264,7 @@ def test_render_with_the_filter_on_matches_the_torch_getters(hip_lib):
     getters (torch), within the bars tests/test_gpu_render.py holds the HIP path to."""
     from g4splat_amd import synthetic
     from g4splat_amd.gaussian_renderer import render
-    from test_gpu_render import _loss
+    from render_scenes import render_loss
     dev = torch.device("cuda:0")
     W, H, P = 64, 48, 200
     cam = synthetic.look_at_camera((0.4, -0.3, -2.6), (0, 0, 0), (0, 1, 0), 1.0, W, H)
@@ -284,7 +284,7 @@ def test_render_with_the_filter_on_matches_the_torch_getters(hip_lib):
         m.active_sh_degree = 1
         m.compute_mip_filter(_mip_cameras([cam]), znear=ZNEAR, filter_variance=2.0)
         out = render(cam, m, SimpleNamespace(depth_ratio=0.5, compute_cov3D_python=False), torch.tensor([0.1, 0.2, 0.3], device=dev))
-        _loss(out).backward()
+        render_loss(out).backward()
         outs.append(out)
         models.append(m)
     torch.cuda.synchronize()
@@ -310,9 +310,9 @@ def test_graphed_training_step_follows_the_mip_filter(hip_lib):
     from g4splat_amd.gaussian_renderer import render
     from g4splat_amd.graphed import TrainStepGraph
     from g4splat_amd.losses import geometry_regularizers, photometric_loss
-    from test_gpu_train import H, W, _cams, _model
+    from render_scenes import TRAIN_H as H, TRAIN_W as W, train_cams, train_model
     dev = torch.device("cuda", 0)
-    cams = _cams(dev)[:3]
+    cams = train_cams(dev)[:3]
     mip_cams = _mip_cameras(cams)
     g = torch.Generator(device=dev).manual_seed(3)
     gts = [torch.rand((3, H, W), device=dev, generator=g) for _ in cams]
@@ -323,7 +323,7 @@ def test_graphed_training_step_follows_the_mip_filter(hip_lib):
         return loss + 0.05 * normal_mean + 100.0 * dist_mean
 
     def fresh():
-        m = _model(0, dev, jitter=True)
+        m = train_model(0, dev, jitter=True)
         m.set_mip_filter(True)
         m.compute_mip_filter(mip_cams, znear=ZNEAR, filter_variance=VARIANCE)
         m.training_setup(capturable=True)

@@ -8,49 +8,17 @@ import torch
 
 import plane_masks_ref as R
 from g4splat_amd import plane_masks as pm
-from test_plane_masks_cpu import MAPS, load_golden
+from plane_masks_ref import unit_normals
+from support import PLANE_MASK_MAPS as MAPS, dev, host, load_plane_masks_golden, same_bits, twice
 
 pytestmark = pytest.mark.gpu
 
 SPAN = R.SPAN
-DEV = "cuda"
-
-
-def dev(a, dtype=None):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(DEV)
-
-
-def host(t):
-    return t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
-
-
-def twice(fn):
-    """fn() run twice: the first result, after asserting that the second has the same bits."""
-    a, b = fn(), fn()
-
-    def same(x, y):
-        if isinstance(x, (list, tuple)):
-            assert len(x) == len(y)
-            for p, q in zip(x, y):
-                same(p, q)
-        elif x is None:
-            assert y is None
-        else:
-            x, y = host(x), host(y)
-            assert x.shape == y.shape and x.tobytes() == y.tobytes()
-    same(a, b)
-    return a
-
-
-def unit_normals(rng, H, W, n_dirs=5, noise=0.2):
-    dirs = rng.normal(size=(n_dirs, 3))
-    n = dirs[rng.integers(0, n_dirs, (H, W))] + noise * rng.normal(size=(H, W, 3))
-    return (n / np.linalg.norm(n, axis=2, keepdims=True)).astype(np.float32)
 
 
 @pytest.fixture(scope="module")
 def golden():
-    return load_golden()
+    return load_plane_masks_golden()
 
 
 def test_span_constant_is_the_kernels():
@@ -64,7 +32,7 @@ def check_kmeans(views, inits, **kw):
         labels, centres, counts, n_iter = R.kmeans_normals(normals, init, **kw)
         assert got[3][v] == n_iter, (v, got[3][v], n_iter)
         assert host(got[0][v]).dtype == np.int8 and (host(got[0][v]) == labels).all(), v
-        assert host(got[1][v]).tobytes() == centres.tobytes(), v
+        same_bits(got[1][v], centres, f"centres of view {v}")
         assert host(got[2][v]).tolist() == counts.tolist(), v
     return got
 
@@ -217,7 +185,8 @@ def check_join(views, max_planes=100):
         if areas is None:
             assert got[v].normal is None and got[v].areas is None, v
         else:
-            assert got[v].areas.tolist() == areas.tolist() and got[v].normal.tobytes() == normal.tobytes(), v
+            assert got[v].areas.tolist() == areas.tolist(), v
+            same_bits(got[v].normal, normal, f"normals of view {v}")
     return got
 
 
@@ -298,6 +267,6 @@ def test_golden_normals_cluster_and_excavate_planes(golden):
     for v, (_c, _n, (seg, normal, areas, _count)) in enumerate(want):
         seg_mask, got_normal, got_areas = got[v]
         assert (host(seg_mask) == seg).all() and got_areas.tolist() == areas.tolist()
-        assert got_normal.tobytes() == normal.tobytes()
+        same_bits(got_normal, normal, f"normals of view {v}")
     one = pm.excavate_planes(dev(views[0]), dev(masks[0]), min_size_ratio=ratio, init=seeds[0])
     assert (one.seg_mask == got[0].seg_mask).all()

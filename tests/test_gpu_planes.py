@@ -2,8 +2,6 @@
 (tests/planes_ref.py): labels, counts, membership words, dicts and indices are compared exactly.  The restatement itself is
 pinned to the reference's code in tests/test_planes_cpu.py."""
 import ctypes
-import math
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -11,35 +9,22 @@ import torch
 
 import planes_ref as pr
 from g4splat_amd import planes
-from test_planes_cpu import load_golden
+from support import DEV, dev, load_planes_golden, pinhole_camera, same_bits
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda:0")
 f32 = np.float32
-
-
-def _dev(a):
-    return torch.as_tensor(np.ascontiguousarray(a), device=DEV)
-
-
-def _camera(W, H, fx, fy, t=(0.0, 0.0, 0.0)):
-    """A camera looking down +z from -t: world_view_transform = identity with the translation in its last row."""
-    M = np.eye(4, dtype=np.float32)
-    M[3, :3] = t
-    return SimpleNamespace(world_view_transform=M, full_proj_transform=M, FoVx=2.0 * math.atan(W / (2.0 * fx)),
-                           FoVy=2.0 * math.atan(H / (2.0 * fy)))
 
 
 @pytest.fixture(scope="module")
 def golden():
-    return load_golden()
+    return load_planes_golden()
 
 
 @pytest.fixture(scope="module")
 def golden_labels(hip_lib, golden):
     """The library's labels of the golden scene (one launch over the five views) and the restatement's, computed once."""
-    got = planes.front_point_labels(golden.cams, _dev(golden.points), [_dev(m) for m in golden.masks], golden.depth_thresh)
+    got = planes.front_point_labels(golden.cams, dev(golden.points), [dev(m) for m in golden.masks], golden.depth_thresh)
     want = np.stack([pr.front_labels(golden.points, c, m, golden.depth_thresh) for c, m in zip(golden.cams, golden.masks)])
     return got, want
 
@@ -54,7 +39,7 @@ def test_labels_of_the_golden_scene(golden, golden_labels):
         assert (got[v] != 0).sum() > 500
     # every view in a launch of its own gives the same rows (the chunked path of a long view list)
     for v in (0, 3):
-        one = planes.front_point_labels(golden.cams[v:v + 1], _dev(golden.points), [_dev(golden.masks[v])], golden.depth_thresh)
+        one = planes.front_point_labels(golden.cams[v:v + 1], dev(golden.points), [dev(golden.masks[v])], golden.depth_thresh)
         assert np.array_equal(one.cpu().numpy()[0], want[v])
     ids = planes.plane_point_indices(golden_labels[0][1], int(want[1].max()))
     assert ids.dtype == torch.int64 and np.array_equal(ids.cpu().numpy(), np.nonzero(want[1] == want[1].max())[0])
@@ -116,7 +101,7 @@ def _edge_views():
     mask = (1 + x % 3 + 3 * (y % 2)).astype(np.int32) * 7 - 50  # -43 .. -8: negative, non-contiguous ids
     mask[3, 11] = 0
     small = np.array([[5, 0, 9], [9, 9, 5], [0, 5, 2 ** 31 - 1]], np.int32)  # a second view of another size
-    return [_camera(EW, EH, EF, EF), _camera(3, 3, 2.0, 2.0, (0.1, -0.2, 0.3))], [mask, small]
+    return [pinhole_camera(EW, EH, EF, EF), pinhole_camera(3, 3, 2.0, 2.0, (0.1, -0.2, 0.3))], [mask, small]
 
 
 @pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 4099])
@@ -125,7 +110,7 @@ def test_labels_of_the_edge_cloud(hip_lib, n, depth_thresh):
     pts, names = _edge_cloud()
     pts = pts[:n]
     cams, masks = _edge_views()
-    got = planes.front_point_labels(cams, _dev(pts), [_dev(m) for m in masks], depth_thresh).cpu().numpy()
+    got = planes.front_point_labels(cams, dev(pts), [dev(m) for m in masks], depth_thresh).cpu().numpy()
     want = np.stack([pr.front_labels(pts, c, m, depth_thresh) for c, m in zip(cams, masks)])
     assert np.array_equal(got, want)
     assert got[0, 0] == 0 and got[1, 0] == 0  # point 0 never carries a label
@@ -166,7 +151,7 @@ def _random_membership(G, rng, N=N_SETS, tail=None):
         if tail is not None:
             head = labels[:tail]
             head[head == target.index(G - 1) + 1] = 0
-        member.assign(_dev(labels), target)
+        member.assign(dev(labels), target)
         for p, t in enumerate(target):
             if t >= 0:
                 want[t] |= labels == p + 1
@@ -197,7 +182,7 @@ def test_counts_and_assign_against_numpy_sets(hip_lib, G, P):
     labels[5::101] = -1
     # runs of equal labels next to scattered ones: both ends of the wave-level aggregation
     labels[200:400] = 1
-    sizes, counts = member.overlap(_dev(labels), P)
+    sizes, counts = member.overlap(dev(labels), P)
     assert sizes == [int((labels == p).sum()) for p in range(1, P + 1)]
     assert counts == [[int(((labels == p) & want[g]).sum()) for g in range(G)] for p in range(1, P + 1)]
     # row overlap, row merge, row to indices
@@ -224,7 +209,7 @@ def test_counts_beyond_the_workgroup_table(hip_lib):
     for row in (0, 4100, G - 1):
         assert member.row_counts(row) == (rows @ rows[row]).tolist()
     labels = rng.integers(0, 3, N_SETS).astype(np.int32)
-    sizes, counts = member.overlap(_dev(labels), 2)
+    sizes, counts = member.overlap(dev(labels), 2)
     assert sizes == [int((labels == p).sum()) for p in (1, 2)]
     assert counts == [(rows @ (labels == p).astype(np.int64)).tolist() for p in (1, 2)]
 
@@ -249,7 +234,7 @@ def test_overlap_past_the_grid_cap(hip_lib, P, G):
     labels[::97] = P + 1
     labels[5::101] = -1
     labels[ONE_PASS + 250: ONE_PASS + 290] = P  # a run of the tail's label across the last wave boundary
-    sizes, counts = member.overlap(_dev(labels), P)
+    sizes, counts = member.overlap(dev(labels), P)
     want_sizes, want_counts = pr.overlap_counts(labels, P, want)
     assert sizes == want_sizes and counts == want_counts
     assert sizes[P - 1] == int((labels[ONE_PASS:] == P).sum()) >= 40 and not (labels[:ONE_PASS] == P).any()
@@ -265,7 +250,7 @@ def test_row_counts_past_the_grid_cap_with_a_workgroup_table(hip_lib):
     rng = np.random.default_rng(130)
     member, want = _random_membership(G, rng, N_PAST, tail=ONE_PASS)
     half = rng.integers(0, 2, N_PAST).astype(np.int32)
-    member.assign(_dev(half), [0])
+    member.assign(dev(half), [0])
     want[0] |= half == 1
     for row in (0, G - 1):
         got = member.row_counts(row)
@@ -295,7 +280,7 @@ def test_row_counts_past_the_grid_cap_with_the_global_table(hip_lib):
         for p, k in enumerate(order):
             target[p] = rows[k]
             some[k] |= labels == p + 1
-        member.assign(_dev(labels), target)
+        member.assign(dev(labels), target)
     assert member.G == G and member.n_words >= 129
     assert some[-1, ONE_PASS:].any() and not some[-1, :ONE_PASS].any() and (some.sum(0) > 1).any()
     for k, row in enumerate(rows):
@@ -318,7 +303,7 @@ def test_overlap_at_the_switch_between_the_workgroup_and_the_global_table(hip_li
     labels[::97] = P + 1
     labels[5::101] = -1
     labels[200:400] = P  # the last table row, in runs
-    sizes, counts = member.overlap(_dev(labels), P)
+    sizes, counts = member.overlap(dev(labels), P)
     want_sizes, want_counts = pr.overlap_counts(labels, P, want)
     assert sizes == want_sizes and counts == want_counts
     assert sizes[P - 1] >= 200 and min(sizes) > 0
@@ -332,7 +317,7 @@ def test_row_counts_at_the_switch_between_the_workgroup_and_the_global_table(hip
     rng = np.random.default_rng(G)
     member, want = _random_membership(G, rng)
     labels = rng.integers(0, 4, N_SETS).astype(np.int32)  # a thousand points spread over G rows leave most rows empty:
-    member.assign(_dev(labels), [0, 4100, G - 1])        # the rows asked for below get a quarter of the points each
+    member.assign(dev(labels), [0, 4100, G - 1])        # the rows asked for below get a quarter of the points each
     for p, row in enumerate((0, 4100, G - 1)):
         want[row] |= labels == p + 1
     _check_words(member, want)
@@ -351,7 +336,7 @@ def test_membership_grows_across_a_word(hip_lib):
     for step in range(5):
         labels = rng.integers(0, 31, N_SETS).astype(np.int32)
         G = want.shape[0]
-        member.assign(_dev(labels), list(range(G, G + 30)))
+        member.assign(dev(labels), list(range(G, G + 30)))
         want = np.concatenate([want, np.stack([labels == p for p in range(1, 31)])])
         assert member.G == G + 30
     _check_words(member, want)
@@ -360,7 +345,7 @@ def test_membership_grows_across_a_word(hip_lib):
 
 # ---- end to end ----------------------------------------------------------------------------------------------------------------
 def _run(golden, previous=None):
-    idx, ids = planes.get_global_3Dplane(golden.cams, _dev(golden.points), [_dev(m) for m in golden.masks], previous, 0.5,
+    idx, ids = planes.get_global_3Dplane(golden.cams, dev(golden.points), [dev(m) for m in golden.masks], previous, 0.5,
                                          golden.depth_thresh)
     assert all(i.dtype == torch.int64 and i.device.type == "cuda" for i in idx)
     return [i.cpu().numpy() for i in idx], ids
@@ -373,7 +358,7 @@ def test_golden_dict_and_index_sets(hip_lib, golden):
 
 
 def test_golden_resume_path(hip_lib, golden):
-    idx3, ids3 = planes.get_global_3Dplane(golden.cams[:3], _dev(golden.points), [_dev(m) for m in golden.masks[:3]], None,
+    idx3, ids3 = planes.get_global_3Dplane(golden.cams[:3], dev(golden.points), [dev(m) for m in golden.masks[:3]], None,
                                            0.5, golden.depth_thresh)
     assert ids3 == golden.ids3
     idx, ids = _run(golden, ids3)
@@ -394,8 +379,8 @@ def test_seventy_stripes_push_G_over_a_word_and_an_empty_plane_of_view_zero_stay
     mask0 = np.repeat(row[None], H, 0)
     mask0[:, 142:] = 999  # no point projects there: an empty plane of view 0
     mask1 = np.repeat(row[None], H, 0)
-    cams = [_camera(W, H, F, F), _camera(W, H, F, F, (2.0 / F, 0.0, 0.0))]
-    idx, ids = planes.get_global_3Dplane(cams, _dev(pts), [_dev(mask0), _dev(mask1)])
+    cams = [pinhole_camera(W, H, F, F), pinhole_camera(W, H, F, F, (2.0 / F, 0.0, 0.0))]
+    idx, ids = planes.get_global_3Dplane(cams, dev(pts), [dev(mask0), dev(mask1)])
     ref_idx, ref_ids = pr.get_global_3Dplane(pts, cams, [mask0, mask1])
     assert ids == ref_ids
     assert len(idx) == len(ref_idx) and all(np.array_equal(a.cpu().numpy(), b) for a, b in zip(idx, ref_idx))
@@ -403,14 +388,14 @@ def test_seventy_stripes_push_G_over_a_word_and_an_empty_plane_of_view_zero_stay
     # view 1's first stripe sees only column 0 and lies inside view 0's first; every other stripe stays alone
     assert len(ids) == 140 and ids[0] == [(0, 4), (1, 4)] and sum(len(pairs) == 1 for pairs in ids.values()) == 139
     # with a lower threshold the halves merge
-    idx, ids = planes.get_global_3Dplane(cams, _dev(pts), [_dev(mask0), _dev(mask1)], None, 0.4)
+    idx, ids = planes.get_global_3Dplane(cams, dev(pts), [dev(mask0), dev(mask1)], None, 0.4)
     ref_idx, ref_ids = pr.get_global_3Dplane(pts, cams, [mask0, mask1], None, 0.4)
     assert ids == ref_ids and len(ids) < 72 and [(0, 999)] in ids.values()
     assert all(np.array_equal(a.cpu().numpy(), b) for a, b in zip(idx, ref_idx))
 
 
 def test_two_runs_are_identical_byte_for_byte(hip_lib, golden, golden_labels):
-    pts, masks = _dev(golden.points), [_dev(m) for m in golden.masks]
+    pts, masks = dev(golden.points), [dev(m) for m in golden.masks]
     again = planes.front_point_labels(golden.cams, pts, masks, golden.depth_thresh)
     assert torch.equal(again, golden_labels[0])
     runs = []
@@ -424,8 +409,9 @@ def test_two_runs_are_identical_byte_for_byte(hip_lib, golden, golden_labels):
             read.append((ids, sizes, counts))
         read.append([provider.row_counts(g) for g in range(provider.member.G)])
         idx, ids = _run(golden)
-        runs.append((read, provider.member.words.cpu().numpy().tobytes(), ids, [i.tobytes() for i in idx]))
-    assert runs[0] == runs[1]
+        runs.append((read, ids, [provider.member.words] + list(idx)))
+    assert runs[0][:2] == runs[1][:2]
+    same_bits(runs[1][2], runs[0][2], "second run")
 
 
 # ---- argument validation ------------------------------------------------------------------------------------------------------

@@ -5,47 +5,24 @@ runs it: the block-sum scan, the instance expansion, the count scan and the tile
 for bit.  And one frame pair through the rasterizer: the tile ranges are cleared by the preprocess kernel's workgroups,
 so a tile that a frame leaves empty must read (0, 0) whatever the frame before left in the same image chunk."""
 import os
-import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 from common import hip_state, run_hip, scene_inputs
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(os.path.dirname(HERE), "g4splat_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else shutil.which("hipcc")
-
-
-def makefile_cxxflags():
-    """CXXFLAGS of g4splat_amd/csrc/Makefile, with $(ARCH) resolved from the same file."""
-    text = open(os.path.join(CSRC, "Makefile")).read()
-    arch = re.search(r"^ARCH\s*\?=\s*(\S+)", text, re.M).group(1)
-    flags = re.search(r"^CXXFLAGS\s*=\s*(.+)$", text, re.M).group(1).replace("$(ARCH)", arch).split()
-    assert "--offload-arch=gfx950" in flags and "-ffp-contract=off" in flags, flags
-    return flags
-
-
-def build_harness(tmp_path):
-    exe = str(tmp_path / "preblend_edges")
-    cmd = [HIPCC] + makefile_cxxflags() + [os.path.join(HERE, "hip_unit", "preblend_edges.hip"), os.path.join(CSRC, "binning.hip"),
-                                           "-o", exe]
-    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert res.returncode == 0, res.stdout
-    return exe
+from support import HIPCC, build_harness
 
 
 @pytest.mark.skipif(HIPCC is None, reason="hipcc not installed")
 def test_preblend_harness_compiles_and_links(tmp_path):
     """No GPU needed: the harness builds against every launcher it calls."""
-    assert os.path.getsize(build_harness(tmp_path)) > 0
+    assert os.path.getsize(build_harness(tmp_path, "preblend_edges", "binning.hip")) > 0
 
 
 @pytest.mark.gpu
 def test_preblend_kernels_against_host_restatements(tmp_path):
-    exe = build_harness(tmp_path)
+    exe = build_harness(tmp_path, "preblend_edges", "binning.hip")
     res = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
     print(res.stdout[-6000:])
     assert res.returncode == 0 and "preblend_edges OK" in res.stdout, res.stdout[-20000:]

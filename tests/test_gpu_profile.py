@@ -12,7 +12,7 @@ from g4splat_amd import _lib
 from g4splat_amd.losses import geometry_regularizers, photometric_loss
 from g4splat_amd.render_maps import render_maps
 from oracle import losses_ref
-from test_gpu_render_maps import NAMES, _allmap, _camera
+from render_scenes import MAP_NAMES, allmap, maps_camera
 
 pytestmark = pytest.mark.gpu
 
@@ -33,8 +33,8 @@ def test_groups_count_the_calls_made_in_them(hip_lib):
     rn, sn, rd = (torch.randn(s, generator=g).to(dev) for s in ((3, H, W), (3, H, W), (1, H, W)))
     geo = [t.clone().requires_grad_(True) for t in (rn, sn, rd.abs())]
     x = img.clone().requires_grad_(True)
-    am = torch.tensor(_allmap(W, H, 5), device=dev, requires_grad=True)
-    cam = _camera(W, H, dev="cuda:0")
+    am = torch.tensor(allmap(W, H, 5), device=dev, requires_grad=True)
+    cam = maps_camera(W, H, dev="cuda:0")
     host = _adam_inputs(dev, 7)    # g4s_adam_step: p, g, m, v of the 5-element segment
     devi = _adam_inputs(dev, 7)    # g4s_adam_step_device: the same
     lr_dev = torch.full((2,), LR, dtype=torch.float64, device=dev)
@@ -56,7 +56,7 @@ def test_groups_count_the_calls_made_in_them(hip_lib):
         _lib.call("g4s_adam_step_device", 2, seg(devi[0]), seg(devi[1]), seg(devi[2]), seg(devi[3]), numel, _lib.ptr(lr_dev),
                   _lib.ptrs(steps), _lib.ptr(coef), BETA1, BETA2, EPS, stream)
         out = render_maps(am, cam, 0.5)
-        sum(out[k].sum() for k in NAMES).backward()
+        sum(out[k].sum() for k in MAP_NAMES).backward()
     finally:
         hip_lib.g4s_profile_enable(0)
     torch.cuda.synchronize()

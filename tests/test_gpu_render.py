@@ -6,7 +6,7 @@ import pytest
 import torch
 
 from cpu_rasterizer import oracle_backend
-from test_render_cpu import KEYS, _camera, _model
+from render_scenes import RENDER_KEYS, render_camera, render_loss, render_model
 from g4splat_amd import synthetic
 from g4splat_amd.gaussian_renderer import render
 
@@ -21,25 +21,20 @@ def _to(cam, dev):
     return SimpleNamespace(**d)
 
 
-def _loss(out):
-    return (out["render"] ** 2).mean() + out["rend_dist"].mean() + (1 - (out["rend_normal"] * out["surf_normal"]).sum(0)).mean() \
-        + 0.1 * out["surf_depth"].mean()
-
-
 def test_render_matches_oracle_driven_render(hip_lib):
-    cam, pipe = _camera(), SimpleNamespace(depth_ratio=0.5, compute_cov3D_python=False)
-    ref_model, hip_model = _model(seed=2), _model(seed=2)
+    cam, pipe = render_camera(), SimpleNamespace(depth_ratio=0.5, compute_cov3D_python=False)
+    ref_model, hip_model = render_model(seed=2), render_model(seed=2)
     with oracle_backend():
         ref = render(cam, ref_model, pipe, torch.tensor([0.1, 0.2, 0.3]))
-    _loss(ref).backward()
+    render_loss(ref).backward()
     dev = torch.device("cuda:0")
     for name in ("_xyz", "_features_dc", "_features_rest", "_scaling", "_rotation", "_opacity"):
         setattr(hip_model, name, torch.nn.Parameter(getattr(hip_model, name).detach().to(dev)))
     out = render(_to(cam, dev), hip_model, pipe, torch.tensor([0.1, 0.2, 0.3], device=dev))
-    assert set(out) == KEYS
-    _loss(out).backward()
+    assert set(out) == RENDER_KEYS
+    render_loss(out).backward()
     torch.cuda.synchronize()
-    for k in KEYS - {"viewspace_points"}:
+    for k in RENDER_KEYS - {"viewspace_points"}:
         a, b = out[k].detach().cpu(), ref[k].detach()
         if a.dtype.is_floating_point:
             assert (a - b).abs().max() <= 2e-4, k
@@ -349,7 +344,7 @@ def test_scene_file_in_the_reference_layout_loads_and_renders(hip_lib):
         ref = render(cam, host, pipe, bg)
     out = render(_to(cam, dev), gpu, pipe, bg.to(dev))
     assert int(ref["visibility_filter"].sum()) > 50
-    for k in KEYS - {"viewspace_points"}:
+    for k in RENDER_KEYS - {"viewspace_points"}:
         a, b = out[k].detach().cpu(), ref[k].detach()
         if a.dtype.is_floating_point:
             # (5e-5: rend_depth = depth sum / alpha sum amplifies the rasterizer's ~3e-7 absolute differences a hundredfold

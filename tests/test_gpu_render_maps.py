@@ -9,52 +9,24 @@ import numpy as np
 import pytest
 import torch
 
-from g4splat_amd import synthetic
 from g4splat_amd.render_maps import render_maps
 from oracle.render_maps_ref import render_maps as maps_ref
+from render_scenes import MAP_NAMES, allmap, maps_camera
 
 pytestmark = pytest.mark.gpu
 
-NAMES = ("rend_alpha", "rend_normal", "rend_normal_cam", "rend_depth", "rend_dist", "surf_depth", "surf_normal",
-         "surf_normal_cam")
-
-
-def _camera(W, H, eye=(0.3, -0.2, -3.0), dev="cpu"):
-    cam = synthetic.look_at_camera(eye, (0, 0, 0), (0, 1, 0), 1.0, W, H)
-    return SimpleNamespace(image_width=W, image_height=H,
-                           world_view_transform=torch.tensor(cam.world_view_transform, device=dev),
-                           full_proj_transform=torch.tensor(cam.full_proj_transform, device=dev))
-
-
-def _allmap(W, H, seed, holes=True):
-    """A plausible allmap: smooth depth field with steps, alpha in (0,1], unnormalised normals."""
-    rng = np.random.default_rng(seed)
-    yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
-    alpha = np.clip(rng.uniform(0.2, 1.0, (H, W)) + 0.1 * np.sin(xx / 7), 0.05, 1.0).astype(np.float32)
-    depth = (2.5 + 0.4 * np.sin(xx / 9.0) * np.cos(yy / 5.0) + 0.05 * rng.normal(size=(H, W))).astype(np.float32)
-    depth[yy > 0.7 * H] += 1.0  # a depth discontinuity
-    n = rng.normal(size=(3, H, W)).astype(np.float32) * alpha
-    med = (depth + 0.02 * rng.normal(size=(H, W))).astype(np.float32)
-    dist = rng.uniform(0, 0.1, (H, W)).astype(np.float32)
-    am = np.stack([depth * alpha, alpha, n[0], n[1], n[2], med, dist]).astype(np.float32)
-    if holes and H > 4 and W > 4:
-        am[1, 2, 3] = 0.0; am[0, 2, 3] = 0.0          # 0/0 -> nan -> 0
-        am[1, 3, 1] = 0.0; am[0, 3, 1] = 0.5          # x/0 -> +inf -> 0
-        am[5, 1, 2] = np.nan                           # nan median
-        am[5, 4, 4] = np.inf
-    return am
 
 
 def _run_both(W, H, seed, ratio, grad_seed=1, holes=True):
-    am = _allmap(W, H, seed, holes)
+    am = allmap(W, H, seed, holes)
     ref_in = torch.tensor(am, requires_grad=True)
-    ref = maps_ref(ref_in, _camera(W, H), ratio)
+    ref = maps_ref(ref_in, maps_camera(W, H), ratio)
     hip_in = torch.tensor(am, device="cuda:0", requires_grad=True)
-    out = render_maps(hip_in, _camera(W, H, dev="cuda:0"), ratio)
+    out = render_maps(hip_in, maps_camera(W, H, dev="cuda:0"), ratio)
     g = torch.Generator().manual_seed(grad_seed)
-    cots = {k: torch.randn(ref[k].shape, generator=g) for k in NAMES}
-    sum((ref[k] * cots[k]).sum() for k in NAMES).backward()
-    sum((out[k] * cots[k].to("cuda:0")).sum() for k in NAMES).backward()
+    cots = {k: torch.randn(ref[k].shape, generator=g) for k in MAP_NAMES}
+    sum((ref[k] * cots[k]).sum() for k in MAP_NAMES).backward()
+    sum((out[k] * cots[k].to("cuda:0")).sum() for k in MAP_NAMES).backward()
     torch.cuda.synchronize()
     return ref, out, ref_in.grad, hip_in.grad.cpu()
 
@@ -62,7 +34,7 @@ def _run_both(W, H, seed, ratio, grad_seed=1, holes=True):
 @pytest.mark.parametrize("W,H,ratio", [(96, 64, 0.0), (96, 64, 1.0), (133, 77, 0.37), (64, 4, 0.5), (5, 9, 0.25)])
 def test_maps_forward_backward_match_reference(hip_lib, W, H, ratio):
     ref, out, g_ref, g_hip = _run_both(W, H, seed=W + H, ratio=ratio)
-    for k in NAMES:
+    for k in MAP_NAMES:
         a, b = out[k].detach().cpu(), ref[k].detach()
         assert a.shape == b.shape, k
         assert (a - b).abs().max() <= 1e-4, (k, float((a - b).abs().max()))
@@ -89,10 +61,10 @@ def test_maps_match_the_reference_render_tail(hip_lib, case):
                           full_proj_transform=torch.tensor(z[f"c{case}_fpt"], device="cuda:0"))
     am = torch.tensor(z[f"c{case}_allmap"], device="cuda:0", requires_grad=True)
     out = render_maps(am, cam, float(ratio))
-    for m in NAMES:
+    for m in MAP_NAMES:
         d = np.abs(out[m].detach().cpu().numpy() - z[f"c{case}_{m}"]).max()
         assert d <= 1e-5, (m, float(d))
-    sum((out[m] * torch.tensor(z[f"c{case}_cot_{m}"], device="cuda:0")).sum() for m in NAMES).backward()
+    sum((out[m] * torch.tensor(z[f"c{case}_cot_{m}"], device="cuda:0")).sum() for m in MAP_NAMES).backward()
     got, want = am.grad.cpu().numpy(), z[f"c{case}_dL_dallmap"]
     assert np.array_equal(np.isnan(got), np.isnan(want))
     got, want = np.nan_to_num(got), np.nan_to_num(want)
@@ -104,7 +76,7 @@ def test_maps_match_the_reference_render_tail(hip_lib, case):
 def test_maps_degenerate_sizes(hip_lib, W, H):
     """No interior pixel (or exactly one): surf_normal is all-zero border / a single normal."""
     ref, out, g_ref, g_hip = _run_both(W, H, seed=5, ratio=0.5, holes=False)
-    for k in NAMES:
+    for k in MAP_NAMES:
         assert (out[k].detach().cpu() - ref[k].detach()).abs().max() <= 1e-4, k
     assert (g_hip - g_ref).abs().max() <= 1e-3 * g_ref.abs().max() + 1e-6
 
@@ -112,8 +84,8 @@ def test_maps_degenerate_sizes(hip_lib, W, H):
 def test_maps_partial_gradients_and_determinism(hip_lib):
     """Only some outputs used (the other cotangents arrive as None); same inputs -> bitwise same gradients."""
     W, H = 80, 56
-    am = _allmap(W, H, 3)
-    cam_c, cam_g = _camera(W, H), _camera(W, H, dev="cuda:0")
+    am = allmap(W, H, 3)
+    cam_c, cam_g = maps_camera(W, H), maps_camera(W, H, dev="cuda:0")
     ref_in = torch.tensor(am, requires_grad=True)
     ref = maps_ref(ref_in, cam_c, 0.5)
     (1 - (ref["rend_normal"] * ref["surf_normal"]).sum(0)).mean().backward()
@@ -130,7 +102,7 @@ def test_maps_partial_gradients_and_determinism(hip_lib):
 
 
 def test_maps_errors(hip_lib):
-    cam = _camera(8, 8, dev="cuda:0")
+    cam = maps_camera(8, 8, dev="cuda:0")
     with pytest.raises(RuntimeError):
         render_maps(torch.zeros((7, 8, 8)), cam, 0.5)           # host tensor: no CPU path
     with pytest.raises(RuntimeError):
@@ -144,14 +116,14 @@ def test_maps_speed_vs_eager_torch(hip_lib, capsys):
     import json
     import time
     W, H = 1600, 1200
-    am = torch.tensor(_allmap(W, H, 11), device="cuda:0")
-    cam = _camera(W, H, dev="cuda:0")
-    cots = {k: torch.randn((c, H, W), device="cuda:0") for k, c in zip(NAMES, (1, 3, 3, 1, 1, 1, 3, 3))}
+    am = torch.tensor(allmap(W, H, 11), device="cuda:0")
+    cam = maps_camera(W, H, dev="cuda:0")
+    cots = {k: torch.randn((c, H, W), device="cuda:0") for k, c in zip(MAP_NAMES, (1, 3, 3, 1, 1, 1, 3, 3))}
 
     def step(fn):
         x = am.clone().requires_grad_(True)
         out = fn(x, cam, 0.5)
-        torch.autograd.backward([out[k] for k in NAMES], [cots[k] for k in NAMES])
+        torch.autograd.backward([out[k] for k in MAP_NAMES], [cots[k] for k in MAP_NAMES])
         return x.grad
 
     def wall(fn, n=20):

@@ -28,11 +28,11 @@ import torch
 
 import rows_ref as rr
 from g4splat_amd import _lib, parallel
+from support import DEV, same_bits
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
-DEV = torch.device("cuda", 0)
 PAD = 257            # sentinel floats behind every buffer
 SENTINEL = f32(12345.0)
 PRODUCT = (3, 48, 1, 2, 4, 2)
@@ -55,13 +55,13 @@ class _Pair:
 
     def same(self, what):
         for i, (d, h) in enumerate(zip(self.got(), self.host)):
-            rr.same_bits(d, h.numpy(), (what, "segment", i))
+            same_bits(d, h, (what, "segment", i), nan_payload=False)
 
     def untouched(self, what, lo=0, hi=0):
         """The device rows outside [lo, hi) are what they were."""
         for i, (d, s) in enumerate(zip(self.got(), self.start)):
-            rr.same_bits(d[:lo], s[:lo], (what, "rows below the shard", i))
-            rr.same_bits(d[hi:], s[hi:], (what, "rows above the shard", i))
+            same_bits(d[:lo], s[:lo], (what, "rows below the shard", i), nan_payload=False)
+            same_bits(d[hi:], s[hi:], (what, "rows above the shard", i), nan_payload=False)
 
 
 def _padded(data):
@@ -75,12 +75,12 @@ def _same_buffer(d, h, n, bw, what):
     bits, never a NaN's), so that a failure names the column."""
     torch.cuda.synchronize()
     got, want = d.cpu().numpy(), h.numpy()
-    rr.same_bits(got[n * bw:], np.full(PAD, SENTINEL, f32), (what, "behind the buffer"))
-    rr.same_bits(got, want, what)
+    same_bits(got[n * bw:], np.full(PAD, SENTINEL, f32), (what, "behind the buffer"), nan_payload=False)
+    same_bits(got, want, what, nan_payload=False)
     if bw <= 301:
         g, w = got[:n * bw].reshape(n, bw), want[:n * bw].reshape(n, bw)
         for c in range(bw):
-            rr.same_bits(np.ascontiguousarray(g[:, c]), np.ascontiguousarray(w[:, c]), (what, "column", c))
+            same_bits(g[:, c], w[:, c], (what, "column", c), nan_payload=False)
 
 
 def _check_pack_modes(segs, idx, rng, what):
@@ -136,7 +136,7 @@ def _check_accumulate(segs, buf, srcs, lo, hi, paths, what, truth_srcs=None):
         pair.D.accumulate(d[:m * bw].view(m, bw), srcs, lo, hi, path, own_pos)
         pair.same((what, path, own_pos))
         pair.untouched((what, path, own_pos), lo, hi)
-        rr.same_bits(d.cpu().numpy(), h.numpy(), (what, path, own_pos, "the buffer"))  # (_HostRows only reads it)
+        same_bits(d, h, (what, path, own_pos, "the buffer"), nan_payload=False)  # (_HostRows only reads it)
         out[(path, own_pos)] = pair.got()
     return out
 
@@ -210,7 +210,7 @@ def test_rows_of_241_floats_are_refused_and_left_alone(hip_lib, widths):
         assert _raw_accumulate(hip_lib, pair.dev, widths, srcs, d, lo, hi, own_pos) == UNSUPPORTED
         assert "wider than 240" in _lib.last_error()
         pair.untouched(("241", own_pos))
-    rr.same_bits(d.cpu().numpy(), buf)
+    same_bits(d, buf, nan_payload=False)
 
 
 # ---- grid cap of the pack kernel ----------------------------------------------------------------------------------------
@@ -248,7 +248,7 @@ def test_two_and_three_launches_equal_a_launch_per_source(hip_lib, nsrc):
     buf, srcs = rr.source_buffer(sources, sum(PRODUCT), rng)
     got = _check_accumulate(segs, buf, srcs, lo, hi, [("per_source", 0), ("one_launch", 0)], nsrc)
     for a, b in zip(got[("per_source", 0)], got[("one_launch", 0)]):  # kernel against kernel, as the header words it
-        rr.same_bits(b, a, nsrc)
+        same_bits(b, a, nsrc, nan_payload=False)
 
 
 def test_ordered_form_at_every_position_of_eight_sources(hip_lib):
@@ -259,7 +259,7 @@ def test_ordered_form_at_every_position_of_eight_sources(hip_lib):
     buf, srcs = rr.source_buffer(sources, sum(PRODUCT), rng)
     got = _check_accumulate(segs, buf, srcs, lo, hi, [("rank", k) for k in range(9)] + [("one_launch", 0)], "ordered")
     for a, b in zip(got[("rank", 0)], got[("one_launch", 0)]):  # own_position 0 is g4s_accumulate_rows
-        rr.same_bits(a, b, "position 0")
+        same_bits(a, b, "position 0", nan_payload=False)
 
 
 def test_ordered_form_refuses_what_it_cannot_order(hip_lib):
@@ -275,7 +275,7 @@ def test_ordered_form_refuses_what_it_cannot_order(hip_lib):
     assert "own_position" in _lib.last_error()
     assert _raw_accumulate(hip_lib, pair.dev, PRODUCT, srcs[:3], d, lo, hi, -1) == INVALID
     pair.untouched("position outside 0..nsrc")
-    rr.same_bits(d.cpu().numpy(), buf)
+    same_bits(d, buf, nan_payload=False)
     # (nine sources with the owner's rows first are two launches)
     _check_accumulate(pair.start, buf, srcs, lo, hi, [("rank", 0), ("one_launch", 0)], "nine sources, position 0")
 
@@ -316,4 +316,4 @@ def test_unsorted_sources_write_nothing_outside_the_shard(hip_lib):
         h, d = _padded(buf)
         assert _raw_accumulate(hip_lib, pair.dev, PRODUCT, srcs, d, lo, hi, own_pos) == 0, _lib.last_error()
         pair.untouched(("unsorted", own_pos), lo, hi)
-        rr.same_bits(d.cpu().numpy(), h.numpy(), "the buffer")
+        same_bits(d, h, "the buffer", nan_payload=False)

@@ -7,27 +7,18 @@ import subprocess
 
 import pytest
 
-from test_gpu_binning_ops import CSRC, HERE, HIPCC, makefile_cxxflags
-
-
-def build_harness(tmp_path):
-    exe = str(tmp_path / "scan_ops")
-    cmd = [HIPCC] + makefile_cxxflags() + [os.path.join(HERE, "hip_unit", "scan_ops.hip"), os.path.join(CSRC, "tsdf", "scan.hip"),
-                                           "-o", exe]
-    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert res.returncode == 0, res.stdout
-    return exe
+from support import HIPCC, build_harness
 
 
 @pytest.mark.skipif(HIPCC is None, reason="hipcc not installed")
 def test_scan_harness_compiles_and_links(tmp_path):
     """No GPU needed: scan.hip must stand on its own -- a dependency on another translation unit breaks the link here."""
-    assert os.path.getsize(build_harness(tmp_path)) > 0
+    assert os.path.getsize(build_harness(tmp_path, "scan_ops", "tsdf/scan.hip")) > 0
 
 
 @pytest.mark.gpu
 def test_scan_u32_against_a_host_loop(tmp_path):
-    exe = build_harness(tmp_path)
+    exe = build_harness(tmp_path, "scan_ops", "tsdf/scan.hip")
     for kind in ("seeded", "ones"):  # one program run each, under its own time limit; nothing runs after a failure
         res = subprocess.run([shutil.which("timeout"), "-k", "10", "60", exe, kind], stdout=subprocess.PIPE,
                              stderr=subprocess.STDOUT, text=True)

@@ -21,47 +21,16 @@ from g4splat_amd.gaussian_model import GaussianModel
 from g4splat_amd.gaussian_renderer import render
 from g4splat_amd.losses import photometric_loss
 from oracle import losses_ref
+from render_scenes import TRAIN_H, TRAIN_P, TRAIN_W, train_cams, train_model
 
 pytestmark = pytest.mark.gpu
-W, H, P, ITERS = 96, 64, 400, 40
-
-
-def _cams(dev):
-    out = []
-    for i in range(4):
-        a = 0.6 * i - 0.9
-        cam = synthetic.look_at_camera((2.6 * np.sin(a), 0.3 * (i - 1.5), -2.6 * np.cos(a)), (0, 0, 0), (0, 1, 0), 1.0, W, H)
-        out.append(SimpleNamespace(image_width=W, image_height=H, FoVx=cam.FoVx, FoVy=cam.FoVy,
-                                   world_view_transform=torch.tensor(cam.world_view_transform, device=dev),
-                                   full_proj_transform=torch.tensor(cam.full_proj_transform, device=dev),
-                                   camera_center=torch.tensor(cam.camera_center, device=dev), znear=0.01, zfar=100.0))
-    return out
-
-
-def _model(seed, dev, jitter):
-    rng = np.random.default_rng(seed)
-    pts = rng.uniform(-0.9, 0.9, (P, 3)).astype(np.float32)
-    cols = rng.uniform(0, 1, (P, 3)).astype(np.float32)
-    sc = rng.uniform(0.06, 0.2, (P, 2)).astype(np.float32)
-    rot = rng.normal(size=(P, 4)).astype(np.float32)
-    if jitter:  # the trainee starts away from the scene that produced the targets
-        j = np.random.default_rng(seed + 1)
-        pts = pts + j.normal(0, 0.03, pts.shape).astype(np.float32)
-        cols = np.clip(cols + j.normal(0, 0.2, cols.shape), 0, 1).astype(np.float32)
-        sc = sc * j.uniform(0.7, 1.3, sc.shape).astype(np.float32)
-    m = GaussianModel(sh_degree=3)
-    t = lambda a: torch.tensor(a, device=dev)
-    m.create_from_parameters(t(pts), t(sc), t(rot), t(cols))
-    with torch.no_grad():
-        m._opacity += 2.5
-    m.active_sh_degree = 1
-    return m
+W, H, P, ITERS = TRAIN_W, TRAIN_H, TRAIN_P, 40
 
 
 def _train(dev, targets):
     hip = dev.type == "cuda"
-    cams = _cams(dev)
-    model = _model(0, dev, jitter=True)
+    cams = train_cams(dev)
+    model = train_model(0, dev, jitter=True)
     model.training_setup()
     pipe = SimpleNamespace(depth_ratio=0.0, compute_cov3D_python=False)
     bg = torch.tensor([0.0, 0.0, 0.0], device=dev)
@@ -94,9 +63,9 @@ def test_hip_training_tracks_cpu_checker_training(hip_lib):
     # targets: renders of the un-jittered scene by the CPU checker
     pipe = SimpleNamespace(depth_ratio=0.0, compute_cov3D_python=False)
     with torch.no_grad():
-        truth = _model(0, cpu, jitter=False)
+        truth = train_model(0, cpu, jitter=False)
         with oracle_backend():
-            targets = [render(c, truth, pipe, torch.zeros(3))["render"] for c in _cams(cpu)]
+            targets = [render(c, truth, pipe, torch.zeros(3))["render"] for c in train_cams(cpu)]
     l_cpu, f_cpu, m_cpu = _train(cpu, targets)
     l_gpu, f_gpu, m_gpu = _train(gpu, targets)
     assert l_cpu[-4:].mean() < 0.8 * l_cpu[:4].mean(), "the optimisation must make progress"
@@ -106,7 +75,7 @@ def test_hip_training_tracks_cpu_checker_training(hip_lib):
         assert 10 * np.log10(1.0 / max(mse, 1e-12)) > 45.0
     # parameters drifted apart by far less than they moved (on average: Adam with eps = 1e-15 turns a noise-level
     # gradient into a full +-lr step, so individual barely-constrained coordinates may take opposite signs)
-    start = _model(0, cpu, True)._xyz
+    start = train_model(0, cpu, True)._xyz
     moved = (m_cpu._xyz.detach() - start).abs().mean()
     drift = (m_gpu._xyz.detach().cpu() - m_cpu._xyz.detach()).abs().mean()
     assert drift <= 0.1 * moved, (float(drift), float(moved))
@@ -116,8 +85,8 @@ def test_hip_training_tracks_cpu_checker_training(hip_lib):
 def test_densify_on_gpu_then_keep_training(hip_lib):
     """prune / clone / split on HIP tensors with FusedAdam's state, followed by more iterations of the product path."""
     dev = torch.device("cuda:0")
-    cams = _cams(dev)
-    model = _model(0, dev, jitter=True)
+    cams = train_cams(dev)
+    model = train_model(0, dev, jitter=True)
     model.training_setup()
     from g4splat_amd.optim import FusedAdam
     assert isinstance(model.optimizer, FusedAdam)
@@ -375,7 +344,7 @@ def test_training_iteration_replayed_from_a_hip_graph_equals_the_eager_loop():
     from g4splat_amd.graphed import TrainStepGraph
     from g4splat_amd.losses import geometry_regularizers
     dev = torch.device("cuda", 0)
-    cams = _cams(dev)[:3]
+    cams = train_cams(dev)[:3]
     g = torch.Generator(device=dev).manual_seed(3)
     gts = [torch.rand((3, H, W), device=dev, generator=g) for _ in cams]
 
@@ -385,7 +354,7 @@ def test_training_iteration_replayed_from_a_hip_graph_equals_the_eager_loop():
         return loss + 0.05 * normal_mean + 100.0 * dist_mean
 
     def fresh():
-        m = _model(0, dev, jitter=True)
+        m = train_model(0, dev, jitter=True)
         m.training_setup(capturable=True)
         return m
 

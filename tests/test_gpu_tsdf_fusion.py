@@ -13,20 +13,12 @@ import tsdf_cases as tc
 import tsdf_ref
 from g4splat_amd import _lib
 from g4splat_amd import mesh as mesh_mod
+from support import DEV, dev, host, words
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda:0")
 NAMES = list(tc.CASES)
 POISON = (float("nan"), 1.0, 1e9)  # tsdf, weight, colour of a pool slot nobody may have written
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _t(a):
-    return None if a is None else torch.as_tensor(a, device=DEV)
 
 
 def _poison(vol, first_block=0):
@@ -51,14 +43,14 @@ def _volume(case, initial_blocks, poison):
 def _pool(vol, n=None):
     """The first n slots of the pool (default: all) on the host as bits: tsdf [n,512], weight [n,512], colour [n,1536]."""
     n = vol.pool_blocks if n is None else n
-    return tuple(_bits(buf[:n * per].cpu().numpy()).reshape(n, per)
+    return tuple(words(host(buf[:n * per])).reshape(n, per)
                  for buf, per in zip((vol.tsdf, vol.weight, vol.color), (512, 512, 1536)))
 
 
 def _poison_intact(vol, first_block):
     """Every slot from first_block on still holds the poison, bit for bit (compared on the device)."""
     for buf, val, per in zip((vol.tsdf, vol.weight, vol.color), POISON, (512, 512, 1536)):
-        want = int(_bits(np.float32(val)).astype(np.int64).item())
+        want = int(words(np.float32(val)).astype(np.int64).item())
         if not (buf[first_block * per:].view(torch.int32).to(torch.int64) & 0xFFFFFFFF == want).all().item():
             return False
     return True
@@ -75,7 +67,7 @@ def _fuse(name, initial_blocks=None, poison=True):
     out = []
     for i, (v, s) in enumerate(zip(case.views, steps)):
         table_before = (vol.keys, vol.slots)
-        counts = vol.integrate(_t(v.depth)[None], _t(v.rgb), v.cam, _t(v.mask))
+        counts = vol.integrate(dev(v.depth)[None], dev(v.rgb), v.cam, dev(v.mask))
         torch.cuda.synchronize()
         assert counts == s.counts, (name, i)
         if counts[0] == 0:
@@ -86,15 +78,15 @@ def _fuse(name, initial_blocks=None, poison=True):
         n_new = s.counts[1]
         want = [np.concatenate([w, np.zeros((n_new, w.shape[1]), np.uint32)]) for w in want]
         for w, new in zip(want, (s.tsdf, s.weight, s.color)):
-            w[s.touched_slots] = _bits(new).reshape(len(s.touched_slots), w.shape[1])
+            w[s.touched_slots] = words(new).reshape(len(s.touched_slots), w.shape[1])
         pool = _pool(vol, vol.num_blocks)
         for what, got, w in zip(("tsdf", "weight", "colour"), pool, want):
             assert np.array_equal(got, w), (name, i, what, int((got != w).sum()))
         if poison:
             assert _poison_intact(vol, vol.num_blocks), (name, i, "a slot beyond the table was written")
         tsdf, weight, color = vol.voxels()
-        assert np.array_equal(_bits(tsdf), want[0][slots]) and np.array_equal(_bits(weight), want[1][slots])
-        assert np.array_equal(_bits(color).reshape(-1, 1536), want[2][slots])
+        assert np.array_equal(words(tsdf), want[0][slots]) and np.array_equal(words(weight), want[1][slots])
+        assert np.array_equal(words(color).reshape(-1, 1536), want[2][slots])
         out.append((keys.tobytes(), slots.tobytes()) + tuple(g.tobytes() for g in pool))
     return vol, out
 
@@ -130,12 +122,12 @@ def test_pool_edges(hip_lib, name):
     for blocks, grows in ((n1, 0), (n1 - 1, 1)):
         vol = _volume(first_view, blocks, poison=True)
         v = first_view.views[0]
-        assert vol.integrate(_t(v.depth), _t(v.rgb), v.cam, _t(v.mask)) == (n1, n1)
+        assert vol.integrate(dev(v.depth), dev(v.rgb), v.cam, dev(v.mask)) == (n1, n1)
         torch.cuda.synchronize()
         assert vol.grows == grows and vol.num_blocks == n1
         assert vol.pool_blocks == (n1 if grows == 0 else max(n1, 2 * (n1 - 1)))
         for g, new in zip(_pool(vol, n1), (steps[0].tsdf, steps[0].weight, steps[0].color)):
-            assert np.array_equal(g[steps[0].touched_slots], _bits(new).reshape(n1, -1))
+            assert np.array_equal(g[steps[0].touched_slots], words(new).reshape(n1, -1))
         assert _poison_intact(vol, n1)
     big_vol, big = _fuse(name)
     small_vol, small = _fuse(name, initial_blocks=1)
@@ -162,7 +154,7 @@ def test_workspace_is_enough(hip_lib, name):
     # g4s_tsdf_workspace() adds for that, so its last array ends within 255 bytes of the canary
     buf = torch.full((1 + nbytes + tail,), 0xA5, dtype=torch.uint8, device=DEV)
     ws = buf[1:]
-    depth, rgb, mask = _t(v.depth), _t(v.rgb), _t(v.mask)
+    depth, rgb, mask = dev(v.depth), dev(v.rgb), dev(v.mask)
     n = s.counts[0]
     pool = n + 3
     tsdf = torch.full((pool * 512,), POISON[0], device=DEV)
@@ -195,6 +187,6 @@ def test_workspace_is_enough(hip_lib, name):
     for _ in range(2):
         ref.integrate(v.depth, v.rgb, v.intr, v.E, v.mask)
     for got, want, per, p in zip((tsdf, weight, color), (ref.tsdf, ref.weight, ref.color), (512, 512, 1536), POISON):
-        got = _bits(got.cpu().numpy()).reshape(pool, per)
-        assert np.array_equal(got[:n], _bits(want).reshape(n, per))
-        assert (got[n:] == _bits(np.float32(p))).all()
+        got = words(host(got)).reshape(pool, per)
+        assert np.array_equal(got[:n], words(want).reshape(n, per))
+        assert (got[n:] == words(np.float32(p))).all()

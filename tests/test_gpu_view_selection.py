@@ -13,21 +13,13 @@ import torch
 
 import view_selection_ref as sr
 from g4splat_amd import _lib, synthetic, view_selection as vs
+from support import DEV, dev, same_bits
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda:0")
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 P_EDGE = 4097
 P_MAX = 64 * 129 + 1  # 130 words: a full chunk of the count kernel (OVERLAP_CHUNK = 128 words) and a second of two words
-
-
-def _dev(a):
-    return torch.as_tensor(np.ascontiguousarray(a), device=DEV)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _world(cam, c):
@@ -84,7 +76,7 @@ def test_bits_and_counts_across_the_chunk_boundary_of_the_count_kernel(hip_lib, 
 def _check_table(scene, P, C):
     cams, pts, masks = scene
     want = masks[:C, :P]
-    table = vs.Covisibility(_dev(pts[:P]), cams[:C])
+    table = vs.Covisibility(dev(pts[:P]), cams[:C])
     W = (P + 63) // 64
     assert table.words.dtype == torch.int64 and tuple(table.words.shape) == (C, W)
     words = table.words.cpu().numpy().view(np.uint64).reshape(C, W)
@@ -126,7 +118,7 @@ def test_counts_of_given_words_equal_the_matrix_product_of_their_bits(hip_lib, C
         (17, 127): (3, 1, 1, 127), (17, 128): (3, 1, 1, 128), (17, 129): (3, 2, 2, 1), (70, 17541): (15, 136, 138, 5),
         (1040, 257): (2145, 1, 3, 1)}[(C, n_words)]  # what the case is for
     words = sr.random_words(C, n_words, 7 * C + n_words)
-    dev_words = _dev(words.view(np.int64))
+    dev_words = dev(words.view(np.int64))
     counts = torch.empty((C, C), dtype=torch.int32, device=DEV)
     with torch.cuda.device(DEV):
         _lib.call("g4s_view_overlap", C, n_words, _lib.ptr(dev_words), _lib.ptr(counts), None, 0, _lib.stream(DEV))
@@ -141,7 +133,7 @@ def test_counts_of_given_words_equal_the_matrix_product_of_their_bits(hip_lib, C
 def test_a_camera_that_sees_nothing(hip_lib, scene):
     cams, pts, masks = scene
     away = synthetic.look_at_camera((50.0, 0.0, 0.0), (100.0, 0.0, 0.0), (0.0, 0.0, 1.0), math.radians(55.0), 32, 24)
-    table = vs.Covisibility(_dev(pts), [cams[0], away, cams[1]])
+    table = vs.Covisibility(dev(pts), [cams[0], away, cams[1]])
     got = table.counts.cpu().numpy()
     assert not got[1].any() and not got[:, 1].any() and got[0, 2] == (masks[0] & masks[1]).sum() > 0
     assert table.ratio(0, 1) == 0 and table.ratio(1, 1) == 0 and not table.mask(1).any()
@@ -150,11 +142,12 @@ def test_a_camera_that_sees_nothing(hip_lib, scene):
 
 def test_reference_named_covisibility_helpers(hip_lib, scene):
     cams, pts, masks = scene
-    dp = _dev(pts)
+    dp = dev(pts)
     m = vs.get_visible_points_mask(cams[3], dp)
     assert m.dtype == torch.bool and np.array_equal(m.cpu().numpy(), masks[3])
     both = vs.get_covisible_points(cams[3], cams[4], dp)
-    assert np.array_equal(_bits(both.cpu().numpy()), _bits(pts[masks[3] & masks[4]])) and len(both) > 10
+    same_bits(both, pts[masks[3] & masks[4]])
+    assert len(both) > 10
     ratio = sr.ratio_of(sr.counts(masks[3:5]))(0, 1)
     assert vs.covisibility_check_by_gs(cams[3], cams[4], dp) == ratio
     from types import SimpleNamespace
@@ -172,12 +165,12 @@ def _clouds(M, N, seed):
 
 def _check_sampling(clouds, k, first):
     want_idx, want_pts, want_dist = sr.fps_batch(clouds, k, first)
-    idx, pts, dist = vs.farthest_point_indices(_dev(clouds), k, first, return_dist=True)
+    idx, pts, dist = vs.farthest_point_indices(dev(clouds), k, first, return_dist=True)
     M, N = clouds.shape[:2]
     assert idx.dtype == torch.int32 and tuple(idx.shape) == (M, k) and tuple(pts.shape) == (M, k, 3) and tuple(dist.shape) == (M, N)
     assert np.array_equal(idx.cpu().numpy(), want_idx)
-    assert np.array_equal(_bits(pts.cpu().numpy()), _bits(want_pts))
-    assert np.array_equal(_bits(dist.cpu().numpy()), _bits(want_dist))
+    same_bits(pts, want_pts)
+    same_bits(dist, want_dist)
     return want_idx, want_dist
 
 
@@ -220,16 +213,16 @@ def test_sampling_past_the_grid_cap(hip_lib):
 
 
 def test_farthest_point_sample_keeps_the_reference_quirk_and_draws_on_the_device(hip_lib):
-    small = _dev(np.random.default_rng(1).normal(size=(10, 3)).astype(np.float32))
+    small = dev(np.random.default_rng(1).normal(size=(10, 3)).astype(np.float32))
     assert vs.farthest_point_sample(small, 10) is small and vs.farthest_point_sample(small, 12) is small
     cloud = np.random.default_rng(2).normal(size=(300, 3)).astype(np.float32)
-    got = vs.farthest_point_sample(_dev(cloud), 7, first_index=299)
-    assert np.array_equal(_bits(got.cpu().numpy()), _bits(cloud[sr.fps(cloud, 7, 299)[0]]))
+    got = vs.farthest_point_sample(dev(cloud), 7, first_index=299)
+    same_bits(got, cloud[sr.fps(cloud, 7, 299)[0]])
     torch.manual_seed(3)
     first = int(torch.randint(0, 300, (1,), device=DEV))
     torch.manual_seed(3)
-    got = vs.farthest_point_sample(_dev(cloud), 7)
-    assert np.array_equal(_bits(got.cpu().numpy()), _bits(cloud[sr.fps(cloud, 7, first)[0]]))
+    got = vs.farthest_point_sample(dev(cloud), 7)
+    same_bits(got, cloud[sr.fps(cloud, 7, first)[0]])
 
 
 # ---- end to end on the golden scene ------------------------------------------------------------------------------------------
@@ -242,7 +235,7 @@ def gold():
 
 
 def test_select_need_inpaint_views_equals_the_reference(hip_lib, gold):
-    pts = _dev(gold["points"])
+    pts = dev(gold["points"])
     for name, case in gold["selection"].items():
         random.seed(case["seed"])
         ids = vs.select_need_inpaint_views(gold["cams"], case["rates"], pts, case["select_num"], case["low"], case["high"],
@@ -252,8 +245,8 @@ def test_select_need_inpaint_views_equals_the_reference(hip_lib, gold):
 
 
 def test_get_novel_cams_lookat_points_equals_the_reference(hip_lib, gold, monkeypatch):
-    clouds = _dev(np.load(os.path.join(GOLDEN, "visibility_grid.npz"))["clouds"])
-    train, novel = _dev(gold["lookat_train"]), _dev(gold["lookat_novel"])
+    clouds = dev(np.load(os.path.join(GOLDEN, "visibility_grid.npz"))["clouds"])
+    train, novel = dev(gold["lookat_train"]), dev(gold["lookat_novel"])
     fps_num = int(gold["lookat_fps_num"])
     torch.manual_seed(9)
     a = vs.get_novel_cams_lookat_points(train, clouds, novel, fps_num)
@@ -261,15 +254,15 @@ def test_get_novel_cams_lookat_points_equals_the_reference(hip_lib, gold, monkey
     b = vs.get_novel_cams_lookat_points(train, clouds, novel, fps_num)
     assert tuple(a.shape) == (len(gold["lookat_novel"]), 3) and torch.equal(a, b)
     # with the reference's recorded draws: the reference's points
-    monkeypatch.setattr(vs, "draw_lookat_indices", lambda *args: (_dev(gold["lookat_first"]), _dev(gold["lookat_ids"])))
+    monkeypatch.setattr(vs, "draw_lookat_indices", lambda *args: (dev(gold["lookat_first"]), dev(gold["lookat_ids"])))
     got = vs.get_novel_cams_lookat_points(train, clouds, novel, fps_num)
-    assert np.array_equal(_bits(got.cpu().numpy()), _bits(gold["lookat"]))
+    same_bits(got, gold["lookat"])
 
 
 def test_outputs_are_bit_identical_from_run_to_run(hip_lib, scene):
     cams, pts, _masks = scene
-    dp = _dev(pts)
-    clouds = _dev(_clouds(3, 65537, 5))
+    dp = dev(pts)
+    clouds = dev(_clouds(3, 65537, 5))
     runs = []
     for _ in range(2):
         table = vs.Covisibility(dp, cams)

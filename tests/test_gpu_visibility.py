@@ -11,22 +11,14 @@ import torch
 
 import visibility_ref as vr
 from g4splat_amd import ply_io, synthetic, visibility
+from support import dev, same_bits
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda:0")
 LO = np.array([-2.03, -1.97, -2.11], np.float32)
 HI = np.array([2.07, 2.01, 1.93], np.float32)
 EYES = [(3.2, 0.3, 0.2), (-0.4, 3.0, 0.5), (-3.0, -0.6, 0.9), (0.5, -0.7, -3.1), (1.9, 1.8, 1.7)]
 BACKGROUND = 5.0
-
-
-def _dev(a):
-    return torch.as_tensor(np.ascontiguousarray(a), device=DEV)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _look_at(eye, W, H, fov_deg=55.0, target=(0.0, 0.0, 0.0)):
@@ -59,7 +51,7 @@ def _case(stack, R, lo=LO, hi=HI):
     key = (stack, R, tuple(lo), tuple(hi)) if isinstance(stack, str) else None
     if key not in _cache:
         cams, depths = _stack(stack) if key else stack
-        grid = visibility.VisibilityGrid(_dev(lo), _dev(hi), R, cams, [_dev(d) for d in depths])
+        grid = visibility.VisibilityGrid(dev(lo), dev(hi), R, cams, [dev(d) for d in depths])
         bits = vr.build(lo, hi, R, list(zip(cams, depths)))
         case = SimpleNamespace(cams=cams, depths=depths, grid=grid, bits=bits, R=R)
         if key is None:
@@ -114,17 +106,17 @@ def test_sample_inside_outside_on_the_corner_and_nan(hip_lib):
     special = np.array([HI, LO, np.nextafter(HI, LO), [np.nan, 0.0, 0.0], [0.5, np.nan, -0.5], [np.nan] * 3,
                         [np.inf, -np.inf, 0.0], [1e30, 1e30, -1e30]], np.float64)
     pts = np.concatenate([inside, outside, special]).astype(np.float32)
-    got = c.grid.check_valid_camera_center(_dev(pts))
+    got = c.grid.check_valid_camera_center(dev(pts))
     assert got.dtype == torch.bool and got.shape == (len(pts),)
     want = vr.sample(c.bits, pts, LO, HI, 33)
     assert np.array_equal(got.cpu().numpy(), want) and 0.2 < want.mean() < 0.9
     # leading dimensions are kept, an empty batch works
-    assert c.grid.check_valid_camera_center(_dev(pts[:12]).reshape(3, 4, 3)).shape == (3, 4)
-    assert c.grid.check_valid_camera_center(_dev(pts[:0])).shape == (0,)
+    assert c.grid.check_valid_camera_center(dev(pts[:12]).reshape(3, 4, 3)).shape == (3, 4)
+    assert c.grid.check_valid_camera_center(dev(pts[:0])).shape == (0,)
 
 
 def _march(c, cam, depth, expect_S=None):
-    d = _dev(depth)
+    d = dev(depth)
     before = d.clone()
     (got,) = c.grid.render_visibility_map([cam], [d])
     assert torch.equal(d, before)  # the caller's depth map is not touched
@@ -134,7 +126,7 @@ def _march(c, cam, depth, expect_S=None):
         assert expect_S(S), S
     want = vr.march(c.bits, LO, HI, c.R, depth, cam)
     assert got.dtype == torch.float32 and got.shape == depth.shape
-    assert np.array_equal(_bits(got.cpu().numpy()), _bits(want))
+    same_bits(got, want)
     return want, S
 
 
@@ -185,7 +177,7 @@ def test_march_a_one_pixel_map(hip_lib):
         want, _S = _march(c, cam, np.full((1, 1), value, np.float32))
         assert want.shape == (1, 1)
     # [1,H,W] maps are accepted
-    (m,) = c.grid.render_visibility_map([c.cams[0]], [_dev(c.depths[0])[None]])
+    (m,) = c.grid.render_visibility_map([c.cams[0]], [dev(c.depths[0])[None]])
     assert m.shape == c.depths[0].shape
 
 
@@ -204,7 +196,7 @@ def cloud():
 @pytest.mark.parametrize("mode", ["free", "surface"])
 def test_view_counts_equal_the_restatement(hip_lib, cloud, mode, skip_view):
     cams, depths = _stack("mixed")
-    got = visibility.view_counts(_dev(cloud), cams, [_dev(d) for d in depths], mode, 0.1, skip_view)
+    got = visibility.view_counts(dev(cloud), cams, [dev(d) for d in depths], mode, 0.1, skip_view)
     want = vr.view_counts(cloud, list(zip(cams, depths)), vr.FREE if mode == "free" else vr.SURFACE, 0.1, skip_view)
     assert got.dtype == torch.int32 and np.array_equal(got.cpu().numpy(), want)
     assert want.max() >= 2 and (want == 0).any()
@@ -214,17 +206,17 @@ def test_view_counts_equal_the_restatement(hip_lib, cloud, mode, skip_view):
 
 
 def test_view_counts_without_views_or_points(hip_lib, cloud):
-    assert not visibility.view_counts(_dev(cloud), [], []).any()
+    assert not visibility.view_counts(dev(cloud), [], []).any()
     cams, depths = _stack("one")
-    assert visibility.view_counts(_dev(cloud[:0]), cams, [_dev(d) for d in depths]).shape == (0,)
+    assert visibility.view_counts(dev(cloud[:0]), cams, [dev(d) for d in depths]).shape == (0,)
 
 
 def test_depths_to_points_and_the_fused_pixel_counts(hip_lib):
     cams, depths = _stack("mixed")
-    dd = [_dev(d) for d in depths]
+    dd = [dev(d) for d in depths]
     for i in (0, 1):
         pts = visibility.depths_to_points(dd[i], cams[i])
-        assert np.array_equal(_bits(pts.cpu().numpy()), _bits(vr.depths_to_points(depths[i], cams[i])))
+        same_bits(pts, vr.depths_to_points(depths[i], cams[i]))
         for mode in ("free", "surface"):
             fused = visibility.pixel_view_counts(cams[i], dd[i], cams, dd, mode, 0.1, skip_view=i)
             explicit = visibility.view_counts(pts, cams, dd, mode, 0.1, skip_view=i)
@@ -234,9 +226,9 @@ def test_depths_to_points_and_the_fused_pixel_counts(hip_lib):
 
 def test_reference_named_wrappers_equal_their_restatements(hip_lib, cloud):
     cams, depths = _stack("five")
-    dd = [_dev(d) for d in depths]
-    free = visibility.check_valid_camera_center_by_depth(cams, dd, _dev(cloud))
-    surf = visibility.get_visible_mask_for_input_views(cams, dd, _dev(cloud), depth_threshold=0.05)
+    dd = [dev(d) for d in depths]
+    free = visibility.check_valid_camera_center_by_depth(cams, dd, dev(cloud))
+    surf = visibility.get_visible_mask_for_input_views(cams, dd, dev(cloud), depth_threshold=0.05)
     assert free.dtype == torch.bool and surf.dtype == torch.bool
     assert np.array_equal(free.cpu().numpy(), vr.check_valid_camera_center_by_depth(cams, depths, cloud))
     assert np.array_equal(surf.cpu().numpy(), vr.get_visible_mask_for_input_views(cams, depths, cloud, 0.05))
@@ -246,9 +238,9 @@ def test_reference_named_wrappers_equal_their_restatements(hip_lib, cloud):
 @pytest.mark.parametrize("explicit", [False, True])
 def test_build_visibility_masks(hip_lib, explicit):
     cams, depths = _stack("mixed")
-    dd = [_dev(d)[None] for d in depths]  # [1,H,W], as the reference passes them
+    dd = [dev(d)[None] for d in depths]  # [1,H,W], as the reference passes them
     host_pts = [vr.depths_to_points(d, c) for c, d in zip(cams, depths)] if explicit else None
-    dev_pts = [_dev(p) for p in host_pts] if explicit else None
+    dev_pts = [dev(p) for p in host_pts] if explicit else None
     times = visibility.build_visibility_masks(cams, dd, dev_pts, 0.1, return_origin_masks=True)
     want_times = vr.build_visibility_masks(cams, depths, host_pts, 0.1, return_origin_masks=True)
     for k in (1, 2):
@@ -266,8 +258,8 @@ def test_compaction_in_flat_index_order(hip_lib, tmp_path):
     c = _case("five", 33)
     centres = vr.grid_centers(LO, HI, 33)
     vis, inv = c.grid.get_all_visible_pnts(), c.grid.invisible_points()
-    assert np.array_equal(_bits(vis.cpu().numpy()), _bits(centres[c.bits]))
-    assert np.array_equal(_bits(inv.cpu().numpy()), _bits(centres[~c.bits]))
+    same_bits(vis, centres[c.bits])
+    same_bits(inv, centres[~c.bits])
     bound = [float(v) for v in c.grid.get_visible_boundary()]
     assert bound == [float(v) for v in np.concatenate([centres[c.bits].min(0), centres[c.bits].max(0)])]
     path = str(tmp_path / "invisible.ply")
@@ -282,7 +274,7 @@ def test_compaction_of_all_visible_and_all_invisible_grids(hip_lib, tmp_path):
     c = _case("one", 5, lo, hi)
     assert c.bits.all()
     _check_grid(c)
-    assert np.array_equal(_bits(c.grid.get_all_visible_pnts().cpu().numpy()), _bits(vr.grid_centers(lo, hi, 5)))
+    same_bits(c.grid.get_all_visible_pnts(), vr.grid_centers(lo, hi, 5))
     assert c.grid.invisible_points().shape == (0, 3)
     path = str(tmp_path / "none.ply")
     c.grid.vis_invisible_pnts(path)  # nothing invisible: nothing is written, as in the reference
@@ -290,7 +282,7 @@ def test_compaction_of_all_visible_and_all_invisible_grids(hip_lib, tmp_path):
     # no view: nothing is seen
     c = _case("none", 33)
     assert c.grid.get_all_visible_pnts() is None and c.grid.get_visible_boundary() is None
-    assert np.array_equal(_bits(c.grid.invisible_points().cpu().numpy()), _bits(vr.grid_centers(LO, HI, 33)))
+    same_bits(c.grid.invisible_points(), vr.grid_centers(LO, HI, 33))
 
 
 # ---- end to end on the analytic sphere ----------------------------------------------------------------------------------
@@ -300,17 +292,17 @@ def test_ring_of_views_sees_everything_but_the_sphere(hip_lib):
     past the sphere, by the views at +-135 degrees)."""
     lo, hi, R = np.full(3, -3.5, np.float32), np.full(3, 3.5, np.float32), 64
     cams = [_look_at((3.0 * math.cos(a), 3.0 * math.sin(a), 0.0), 128, 96, 70.0) for a in np.arange(8) * math.pi / 4]
-    depths = [_dev(vr.sphere_depth(c, 128, 96, 1.0, 8.0)) for c in cams]
-    grid = visibility.VisibilityGrid(_dev(lo), _dev(hi), R, cams, depths)
+    depths = [dev(vr.sphere_depth(c, 128, 96, 1.0, 8.0)) for c in cams]
+    grid = visibility.VisibilityGrid(dev(lo), dev(hi), R, cams, depths)
     centres = vr.grid_centers(lo, hi, R)
     dense = grid.visibility_grid.cpu().numpy().reshape(-1) > 0.5
     inner = np.linalg.norm(centres, axis=1) < 0.9
     assert inner.sum() > 1000 and not dense[inner].any()
     assert 0.3 < dense.mean() < 0.99
-    eyes = _dev(np.stack([c.camera_center for c in cams]))
+    eyes = dev(np.stack([c.camera_center for c in cams]))
     assert grid.check_valid_camera_center(eyes).all()
     assert visibility.check_valid_camera_center_by_depth(cams, depths, eyes).all()
-    assert not grid.check_valid_camera_center(_dev(np.zeros((1, 3), np.float32))).any()
+    assert not grid.check_valid_camera_center(dev(np.zeros((1, 3), np.float32))).any()
 
 
 def test_novel_view_is_visible_on_the_lit_side_and_not_behind_the_sphere(hip_lib):
@@ -321,13 +313,13 @@ def test_novel_view_is_visible_on_the_lit_side_and_not_behind_the_sphere(hip_lib
     cell = 8.0 / R
     E = np.array([3.5, 0.0, 0.0])
     cam_e = _look_at(tuple(E), 128, 96, 100.0)
-    grid = visibility.VisibilityGrid(_dev(lo), _dev(hi), R, [cam_e], [_dev(vr.sphere_depth(cam_e, 128, 96, 1.0, 9.0))])
+    grid = visibility.VisibilityGrid(dev(lo), dev(hi), R, [cam_e], [dev(vr.sphere_depth(cam_e, 128, 96, 1.0, 9.0))])
     W, H = 64, 48
     cam_n = _look_at((1.0, 2.2, 0.0), W, H, 60.0)
     depth = vr.sphere_depth(cam_n, W, H, 1.0, 4.0)
-    (got,) = grid.render_visibility_map([cam_n], [_dev(depth)])
+    (got,) = grid.render_visibility_map([cam_n], [dev(depth)])
     got = got.cpu().numpy().reshape(-1)
-    S = grid.n_samples(_dev(depth))
+    S = grid.n_samples(dev(depth))
     assert S > 30
 
     o, _D = vr.ray_record(cam_n, W, H, np.float64)

@@ -5,18 +5,14 @@ import numpy as np
 import pytest
 
 import knn_clouds
-
-
-def assert_same_bits(got, want):
-    assert got.dtype == np.float32 and want.dtype == np.float32
-    np.testing.assert_array_equal(got.view(np.uint32), want.view(np.uint32))
+from support import same_bits
 
 
 @pytest.mark.parametrize("P", [1, 2, 3, 4])
 def test_oracle_knn_fewer_than_three_neighbours(oracle_mod, P):
     pts = np.random.default_rng(P).normal(size=(P, 3)).astype(np.float32)
     want = knn_clouds.knn_mean3_numpy(pts)
-    assert_same_bits(oracle_mod.distCUDA2(pts), want)
+    same_bits(oracle_mod.distCUDA2(pts), want)
     if P < 3:  # two or three FLT_MAX terms are left over: their sum overflows
         assert np.isposinf(want).all()
     elif P == 3:  # one FLT_MAX term: (d0 + d1) + FLT_MAX rounds to FLT_MAX
@@ -29,7 +25,7 @@ def test_oracle_knn_fewer_than_three_neighbours(oracle_mod, P):
 def test_oracle_knn_normal_cloud(oracle_mod, P):
     pts = np.random.default_rng(P).normal(size=(P, 3)).astype(np.float32)
     pts[P // 2] = pts[3]  # a duplicate: distance 0 takes part
-    assert_same_bits(oracle_mod.distCUDA2(pts), knn_clouds.knn_mean3_numpy(pts))
+    same_bits(oracle_mod.distCUDA2(pts), knn_clouds.knn_mean3_numpy(pts))
 
 
 @pytest.mark.parametrize("name", knn_clouds.DEGENERATE)
@@ -37,9 +33,9 @@ def test_oracle_knn_degenerate_clouds(oracle_mod, name):
     pts = knn_clouds.degenerate_cloud(name, 2000, seed=7)
     assert 1700 <= pts.shape[0] <= 2000
     want = knn_clouds.knn_mean3_numpy(pts)
-    assert_same_bits(oracle_mod.distCUDA2(pts), want)
+    same_bits(oracle_mod.distCUDA2(pts), want)
     q = np.arange(0, pts.shape[0], 7, dtype=np.int32)
-    assert_same_bits(oracle_mod.distCUDA2_queries(pts, q), want[q])
+    same_bits(oracle_mod.distCUDA2_queries(pts, q), want[q])
     if name == "coincident":
         assert (want == 0).all()
     if name == "nonfinite":

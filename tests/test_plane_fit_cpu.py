@@ -2,9 +2,6 @@
 GPU: the constrained solver against scipy's SLSQP and numpy's SVD, the replay of sklearn's RANSAC loop against sklearn, the
 argument checks, the size queries, and the restatement against the reference's recorded results (tests/golden/plane_fit.npz,
 written by tests/golden/make_golden_plane_fit.py)."""
-import json
-import os
-import types
 
 import numpy as np
 import pytest
@@ -12,42 +9,13 @@ import torch
 
 import plane_fit_ref as R
 from g4splat_amd import plane_fit as pf
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-KEYS = (10, 11, 12)
-
-
-def load_golden():
-    return np.load(os.path.join(HERE, "golden", "plane_fit.npz"))
-
-
-def golden_scene(g):
-    """(cams, depths, normals, masks, confs, gdict) of the golden scene as numpy arrays."""
-    cams = [types.SimpleNamespace(world_view_transform=g["wvt"][v], full_proj_transform=g["full"][v], FoVx=float(g["fov"][v, 0]),
-                                  FoVy=float(g["fov"][v, 1])) for v in range(len(g["wvt"]))]
-    gdict = {int(k): [tuple(p) for p in pairs] for k, pairs in json.loads(str(g["gdict"])).items()}
-    return cams, list(g["depths"]), list(g["normals"]), list(g["masks"].astype(np.int32)), list(g["confs"]), gdict
-
-
-def within_yardstick(g, key, normal, centre, factor=2.0):
-    """The plane lies within `factor` times the recorded yardstick of EVERY one of the reference's eight results: the angle
-    between the normals, and the offset along the normal at the common point.  Returns the two largest figures."""
-    angle_bar, offset_bar = factor * g[f"yardstick_{key}"]
-    common = g[f"common_{key}"]
-    normal, centre = np.asarray(normal, np.float64), np.asarray(centre, np.float64)
-    worst_angle = worst_offset = 0.0
-    for rn, rc in zip(g[f"ref_normal_{key}"], g[f"ref_centre_{key}"]):
-        n = normal * (1.0 if np.dot(normal, rn) >= 0 else -1.0)
-        worst_angle = max(worst_angle, float(np.arccos(min(1.0, np.dot(n, rn)))))
-        worst_offset = max(worst_offset, abs(float(np.dot(n, common - centre)) - float(np.dot(rn, common - rc))))
-    print(f"plane {key}: angle {worst_angle:.3e} (bar {angle_bar:.3e}), offset {worst_offset:.3e} (bar {offset_bar:.3e})")
-    assert worst_angle <= angle_bar and worst_offset <= offset_bar, (key, worst_angle, angle_bar, worst_offset, offset_bar)
-    return worst_angle, worst_offset
+from plane_fit_ref import within_yardstick
+from support import PLANE_FIT_KEYS as KEYS, load_plane_fit_golden, plane_fit_scene
 
 
 @pytest.fixture(scope="module")
 def golden():
-    return load_golden()
+    return load_plane_fit_golden()
 
 
 # ---- the solver ---------------------------------------------------------------------------------------------------------------
@@ -308,7 +276,7 @@ def test_size_queries_and_refusals_are_host_code(hip_lib):
 @pytest.fixture(scope="module")
 def restated_scene(golden):
     """The restated fit loop over the golden scene, computed once: {key: fields of plane_fit_ref.fit_global_planes}."""
-    return R.fit_global_planes(*golden_scene(golden))
+    return R.fit_global_planes(*plane_fit_scene(golden))
 
 
 @pytest.mark.parametrize("key", KEYS)

@@ -1,7 +1,6 @@
 """The plane-mask stage without a GPU: the numpy restatement (tests/plane_masks_ref.py) against sklearn's recorded k-means and
 the reference's recorded cluster merges (tests/golden/plane_masks.npz), against scipy.ndimage for the opening and the
 components, hand-worked joins, and the wrappers' refusals, which come before any library call."""
-import os
 
 import numpy as np
 import pytest
@@ -9,18 +8,12 @@ import torch
 
 import plane_masks_ref as R
 from g4splat_amd import plane_masks as pm
-
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "plane_masks.npz")
-MAPS = ("small", "large")
-
-
-def load_golden():
-    return dict(np.load(GOLDEN))
+from support import PLANE_MASK_MAPS as MAPS, load_plane_masks_golden
 
 
 @pytest.fixture(scope="module")
 def golden():
-    return load_golden()
+    return load_plane_masks_golden()
 
 
 @pytest.fixture(scope="module")

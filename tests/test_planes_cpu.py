@@ -3,40 +3,18 @@ g4splat_amd/planes.py against vectors recorded from the reference's own code (te
 labels on the agreed set, dicts and index sets exactly, the resume path, the hand-made merge cases, the JSON round trip.
 No GPU: the GPU tests (tests/test_gpu_planes.py) hold the library to the restatement bit for bit."""
 import json
-import os
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 
 import planes_ref as pr
 from g4splat_amd import planes
-
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "global_planes.npz")
-
-
-def load_golden():
-    g = np.load(GOLDEN)
-    cams = [SimpleNamespace(world_view_transform=g["wvt"][i], full_proj_transform=g["full"][i], FoVx=float(g["fov"][i, 0]),
-                            FoVy=float(g["fov"][i, 1])) for i in range(len(g["wvt"]))]
-    masks = [m for m in g["masks"]]
-
-    def as_dict(key):
-        return {int(k): [(int(v), int(p)) for v, p in pairs] for k, pairs in json.loads(str(g[key])).items()}
-
-    def ragged(key):
-        flat, offs = g[key].astype(np.int64), g[key + "_offsets"]
-        return [flat[a:b] for a, b in zip(offs[:-1], offs[1:])]
-
-    return SimpleNamespace(g=g, cams=cams, masks=masks, points=g["points"], depth_thresh=float(g["depth_thresh"]),
-                           ids=as_dict("ids"), ids3=as_dict("ids3"), resume_ids=as_dict("resume_ids"), idx=ragged("idx"),
-                           resume_idx=ragged("resume_idx"), hand_cases=json.loads(str(g["hand_cases"])),
-                           hand_results=json.loads(str(g["hand_results"])), stats=json.loads(str(g["stats"])))
+from support import load_planes_golden
 
 
 @pytest.fixture(scope="module")
 def golden():
-    return load_golden()
+    return load_planes_golden()
 
 
 @pytest.fixture(scope="module")

@@ -2,16 +2,14 @@
 driven on the CPU through the oracle-backed rasterizer and map stand-ins (the product's are HIP-only)."""
 from types import SimpleNamespace
 
-import numpy as np
 import torch
 
 import pytest
 
 from cpu_rasterizer import oracle_backend
-from g4splat_amd import synthetic
-from g4splat_amd.gaussian_model import GaussianModel
 from g4splat_amd.gaussian_renderer import render, render_gslist
 from oracle.render_maps_ref import depth_to_normal
+from render_scenes import RENDER_KEYS, render_camera, render_model
 
 
 @pytest.fixture(autouse=True)
@@ -20,36 +18,13 @@ def _oracle_backend():
     with oracle_backend():
         yield
 
-KEYS = {"render", "viewspace_points", "visibility_filter", "radii", "rend_alpha", "rend_normal", "rend_normal_cam",
-        "rend_dist", "surf_depth", "surf_normal", "surf_normal_cam", "rend_depth"}
-
-
-def _camera(W=80, H=56):
-    cam = synthetic.look_at_camera((0.3, -0.2, -3.0), (0, 0, 0), (0, 1, 0), 1.0, W, H)
-    return SimpleNamespace(image_width=W, image_height=H, FoVx=cam.FoVx, FoVy=cam.FoVy,
-                           world_view_transform=torch.tensor(cam.world_view_transform),
-                           full_proj_transform=torch.tensor(cam.full_proj_transform),
-                           camera_center=torch.tensor(cam.camera_center), znear=0.01, zfar=100.0)
-
-
-def _model(P=300, seed=0):
-    rng = np.random.default_rng(seed)
-    m = GaussianModel(sh_degree=3)
-    pts = torch.tensor(rng.uniform(-1, 1, (P, 3)).astype(np.float32))
-    m.create_from_parameters(pts, torch.tensor(rng.uniform(0.05, 0.2, (P, 2)).astype(np.float32)),
-                             torch.tensor(rng.normal(size=(P, 4)).astype(np.float32)),
-                             torch.tensor(rng.uniform(0, 1, (P, 3)).astype(np.float32)))
-    with torch.no_grad():
-        m._opacity += 2.0
-    m.active_sh_degree = 1
-    return m
 
 
 def test_render_dict_and_gradients():
-    cam, model = _camera(), _model()
+    cam, model = render_camera(), render_model()
     pipe = SimpleNamespace(depth_ratio=0.5, compute_cov3D_python=False, convert_SHs_python=False)
     out = render(cam, model, pipe, torch.tensor([0.1, 0.2, 0.3]))
-    assert set(out) == KEYS
+    assert set(out) == RENDER_KEYS
     H, W = 56, 80
     assert out["render"].shape == (3, H, W) and out["rend_alpha"].shape == (1, H, W)
     assert out["rend_normal"].shape == (3, H, W) and out["surf_normal"].shape == (3, H, W)
@@ -73,7 +48,7 @@ def test_render_dict_and_gradients():
 
 def test_python_cov3d_path_matches_kernel_path():
     """pipe.compute_cov3D_python: T built in python (render(), :64-75) must reproduce the in-kernel T."""
-    cam, model = _camera(), _model(P=120, seed=3)
+    cam, model = render_camera(), render_model(P=120, seed=3)
     model.get_covariance = lambda mod=1: _covariance(model, mod)
     bg = torch.zeros(3)
     a = render(cam, model, SimpleNamespace(depth_ratio=0.0, compute_cov3D_python=False), bg)
@@ -99,7 +74,7 @@ def _covariance(model, mod):
 
 
 def test_depth_to_normal_of_a_plane():
-    cam = _camera(64, 48)
+    cam = render_camera(64, 48)
     depth = torch.full((1, 48, 64), 2.0)
     n = depth_to_normal(cam, depth)
     inner = n[1:-1, 1:-1]
@@ -112,14 +87,14 @@ def test_depth_to_normal_of_a_plane():
 def test_render_gslist_equals_render_of_the_union():
     """render_gslist (2dgs/gaussian_renderer/__init__.py:169-363): two models rendered together == one model holding
     both sets; dictionary keys of the reference; gradients reach both models."""
-    cam = _camera()
-    a, b = _model(P=120, seed=5), _model(P=80, seed=6)
+    cam = render_camera()
+    a, b = render_model(P=120, seed=5), render_model(P=80, seed=6)
     pipe = SimpleNamespace(depth_ratio=0.5, compute_cov3D_python=False)
     bg = torch.tensor([0.2, 0.1, 0.3])
     out = render_gslist(cam, [a, b], pipe, bg)
-    assert set(out) == (KEYS - {"rend_normal_cam", "surf_normal_cam"}) | {"model_start_indices"}
+    assert set(out) == (RENDER_KEYS - {"rend_normal_cam", "surf_normal_cam"}) | {"model_start_indices"}
     assert out["model_start_indices"] == [0, 120, 200]
-    both = _model(P=200, seed=0)
+    both = render_model(P=200, seed=0)
     with torch.no_grad():
         for name in ("_xyz", "_features_dc", "_features_rest", "_scaling", "_rotation", "_opacity"):
             getattr(both, name).copy_(torch.cat([getattr(a, name), getattr(b, name)], dim=0))

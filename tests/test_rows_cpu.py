@@ -8,6 +8,7 @@ import torch
 
 import rows_ref as rr
 from g4splat_amd import parallel
+from support import same_bits
 
 f32 = np.float32
 WIDTHS = (3, 5, 1)
@@ -22,7 +23,7 @@ def _host(segs):
 
 def _same_rows(rows, segs, what):
     for i, (r, s) in enumerate(zip(rows, segs)):
-        rr.same_bits(r.numpy(), s, (what, "segment", i))
+        same_bits(r, s, (what, "segment", i), nan_payload=False)
 
 
 @pytest.mark.parametrize("row_major, index_col", [(False, False), (True, False), (True, True)])
@@ -43,10 +44,10 @@ def test_pack_and_unpack_equal_the_restatement(row_major, index_col):
         got = flat[:n * bw].view(n, bw).numpy()
         assert np.array_equal(np.ascontiguousarray(got[:, W]).view(np.int32), idx.astype(np.int32))
         assert np.array_equal(want.view(np.int32)[:n * bw].reshape(n, bw)[:, W], idx.astype(np.int32))
-        rr.same_bits(np.ascontiguousarray(got[:, :W]), np.ascontiguousarray(want[:n * bw].reshape(n, bw)[:, :W]), "pack")
-        rr.same_bits(flat[n * bw:].numpy(), want[n * bw:], "behind the buffer")
+        same_bits(got[:, :W], want[:n * bw].reshape(n, bw)[:, :W], "pack", nan_payload=False)
+        same_bits(flat[n * bw:], want[n * bw:], "behind the buffer", nan_payload=False)
     else:
-        rr.same_bits(flat.numpy(), want, ("pack", mode))
+        same_bits(flat, want, ("pack", mode), nan_payload=False)
     _same_rows(rows, segs, "pack leaves the rows alone")
     # unpack: modes 1, 3 (an index column, if any, is passed over: the indices come from idx)
     if not index_col:
@@ -56,7 +57,7 @@ def test_pack_and_unpack_equal_the_restatement(row_major, index_col):
         t = torch.from_numpy(buf.copy())
         ops.unpack(torch.from_numpy(idx), t.view(n, W) if row_major else t, row_major=row_major)
         _same_rows(rows, want_segs, ("unpack", mode | 1))
-        rr.same_bits(t.numpy(), buf, "unpack leaves the buffer alone")
+        same_bits(t, buf, "unpack leaves the buffer alone", nan_payload=False)
         assert any(not np.array_equal(a.view(np.uint32), b.view(np.uint32)) for a, b in zip(want_segs, segs))
 
 
@@ -70,10 +71,9 @@ def test_accumulate_equals_the_sequence_of_float32_additions(path, own_pos):
     t = torch.from_numpy(buf.copy())
     ops.accumulate(t, srcs, lo, hi, path, own_pos)
     _same_rows(rows, want, (path, own_pos))
-    assert np.array_equal(t.numpy().view(np.uint32), buf.view(np.uint32))
+    same_bits(t, buf, "the buffer")
     for s, w in zip(segs, want):  # nothing outside the shard moves
-        assert np.array_equal(s[:lo].view(np.uint32), w[:lo].view(np.uint32))
-        assert np.array_equal(s[hi:].view(np.uint32), w[hi:].view(np.uint32))
+        same_bits([s[:lo], s[hi:]], [w[:lo], w[hi:]], "outside the shard")
     # the row no source holds: an own -0.0 stays what it is when the owner's rows come first, and is +0.0 behind a zero
     assert (want[0][14] == 0).all() and bool(np.signbit(want[0][14]).all()) == (own_pos == 0)
     assert np.isnan(want[0][15][0]) and want[0][15][1] == np.inf and want[0][15][2] == -np.inf
@@ -93,8 +93,8 @@ def test_one_accumulating_unpack_per_source_is_the_same_sequence():
         rr.pack_rows(m15, None, c, buf[o:o + c].copy().reshape(-1), 15)
         rr.pack_rows(m7, index[o:o + c].astype(np.int64), c, np.ascontiguousarray(buf[o:o + c, :W]).reshape(-1), 7)
     for a, b, c_ in zip(m15, m7, want):
-        rr.same_bits(a, c_, "mode 15")
-        rr.same_bits(b, c_, "mode 7")
+        same_bits(a, c_, "mode 15", nan_payload=False)
+        same_bits(b, c_, "mode 7", nan_payload=False)
 
 
 def test_restated_accumulation_skips_rows_outside_the_shard():
@@ -110,7 +110,7 @@ def test_restated_accumulation_skips_rows_outside_the_shard():
     want = [s.copy() for s in segs]
     rr.accumulate_rows(want, buf, [(3, 7)], lo, hi, 0)
     for a, b in zip(got, want):
-        rr.same_bits(a, b)
+        same_bits(a, b, nan_payload=False)
 
 
 # ---- the builders --------------------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@ import torch
 
 import view_selection_ref as sr
 from g4splat_amd import _lib, view_selection as vs
+from support import same_bits
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -104,7 +105,8 @@ def test_restated_lookat_points_equal_the_reference_given_its_draws(gold):
     assert np.array_equal(sr.nearest_train_indices(gold["lookat_train"], gold["lookat_novel"]), gold["lookat_closest"])
     got = sr.lookat_points(gold["lookat_train"], clouds, gold["lookat_novel"], int(gold["lookat_fps_num"]), gold["lookat_first"],
                            gold["lookat_ids"])
-    assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), gold["lookat"].view(np.uint32))
+    assert got.dtype == np.float32
+    same_bits(got, gold["lookat"])
     t, c = torch.tensor(gold["lookat_train"]), torch.tensor(gold["lookat_novel"])
     assert np.array_equal(vs.nearest_train_indices(t, c).numpy(), gold["lookat_closest"])
     # a tie goes to the smallest index

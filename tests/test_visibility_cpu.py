@@ -2,13 +2,13 @@
 tests/golden/visibility_grid.npz (made by tests/golden/make_golden_visibility.py), and the host-side pieces of
 g4splat_amd.visibility.  No GPU: the kernels are compared with the restatement in tests/test_gpu_visibility.py."""
 import os
-import types
 
 import numpy as np
 import pytest
 import torch
 
 import visibility_ref as vr
+from support import golden_cameras, same_bits
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "visibility_grid.npz")
 DECISIONS = ("grid32", "grid48", "maps32", "maps48", "centres32", "centres48", "free", "surface", "times", "masks1", "masks2")
@@ -17,8 +17,7 @@ DECISIONS = ("grid32", "grid48", "maps32", "maps48", "centres32", "centres48", "
 @pytest.fixture(scope="module")
 def golden():
     g = dict(np.load(GOLDEN))
-    cams = [types.SimpleNamespace(world_view_transform=w, full_proj_transform=f, FoVx=float(a[0]), FoVy=float(a[1]))
-            for w, f, a in zip(g["wvt"], g["full"], g["fov"])]
+    cams = golden_cameras(g)
     g["cams"], g["views"] = cams, list(zip(cams, g["depths"]))
     return g
 
@@ -86,7 +85,7 @@ def test_fused_masks_equal_the_explicit_ones(golden):
 def test_linspace_is_torchs_bit_for_bit():
     for S in range(1, 701):
         want = torch.linspace(0, 1, S, dtype=torch.float32).numpy()
-        assert np.array_equal(vr.linspace_t(S).view(np.uint32), want.view(np.uint32)), S
+        same_bits(vr.linspace_t(S), want, S)
 
 
 def test_point_to_voxel_clamps_at_and_beyond_both_corners():

@@ -14,7 +14,7 @@ f32 = np.float32
 FREE, SURFACE = 0, 1
 
 
-def _np(a, ft):
+def _as(a, ft):
     if hasattr(a, "detach"):
         a = a.detach().cpu().numpy()
     return np.asarray(a, ft)
@@ -28,8 +28,8 @@ def focal(cam, W, H, dtype=f32):
 def project(points, cam, W, H, dtype=f32):
     """(z [n], u [n], v [n], in_image [n]) of points [n,3] in a view whose map is W x H."""
     ft = dtype
-    p = _np(points, ft).reshape(-1, 3)
-    M = _np(cam.world_view_transform, ft).reshape(4, 4)
+    p = _as(points, ft).reshape(-1, 3)
+    M = _as(cam.world_view_transform, ft).reshape(4, 4)
     fx, fy = focal(cam, W, H, ft)
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         c = [((p[:, 0] * M[0, j] + p[:, 1] * M[1, j]) + p[:, 2] * M[2, j]) + M[3, j] for j in range(3)]
@@ -44,7 +44,7 @@ def view_pass(points, view, mode=FREE, depth_threshold=0.1, dtype=f32):
     """bool [n]: the predicate of `mode` for every point in one view."""
     ft = dtype
     cam, depth = view
-    depth = _np(depth, ft)
+    depth = _as(depth, ft)
     depth = depth.reshape(depth.shape[-2:])
     H, W = depth.shape
     z, u, v, inside = project(points, cam, W, H, ft)
@@ -65,7 +65,7 @@ def view_pass(points, view, mode=FREE, depth_threshold=0.1, dtype=f32):
 
 def view_counts(points, views, mode=FREE, depth_threshold=0.1, skip_view=None, dtype=f32):
     """int32 [n]: the number of views, skip_view left out, that pass."""
-    n = _np(points, dtype).reshape(-1, 3).shape[0]
+    n = _as(points, dtype).reshape(-1, 3).shape[0]
     counts = np.zeros(n, np.int32)
     for vi, view in enumerate(views):
         if skip_view is not None and vi == skip_view:
@@ -77,7 +77,7 @@ def view_counts(points, views, mode=FREE, depth_threshold=0.1, skip_view=None, d
 # ---- the grid ---------------------------------------------------------------------------------------------------------
 def grid_frame(bbox_min, bbox_max, R, dtype=f32):
     """(bbox_min, extent, grid_size), each [3]."""
-    lo, hi = _np(bbox_min, dtype).reshape(3), _np(bbox_max, dtype).reshape(3)
+    lo, hi = _as(bbox_min, dtype).reshape(3), _as(bbox_max, dtype).reshape(3)
     extent = hi - lo
     return lo, extent, extent / dtype(R)
 
@@ -118,7 +118,7 @@ def voxel_index(points, bbox_min, bbox_max, R, dtype=f32):
     """int64 [n] flat index of the voxel of each point; ([n,3] per-axis indices come with it)."""
     ft = dtype
     lo, extent, _c = grid_frame(bbox_min, bbox_max, R, ft)
-    p = _np(points, ft).reshape(-1, 3)
+    p = _as(points, ft).reshape(-1, 3)
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         g = ((p - lo[None]) / extent[None]) * ft(R)
         g = np.fmin(np.fmax(g, ft(0)), ft(R - 1))
@@ -134,8 +134,8 @@ def sample(bits, points, bbox_min, bbox_max, R, dtype=f32):
 # ---- rays -------------------------------------------------------------------------------------------------------------
 def ray_record(cam, W, H, dtype=f32):
     """(o [3], D [3,3]) computed in double, rounded to dtype: dir = D @ (x, y, 1), point = o + t dir."""
-    wvt = _np(cam.world_view_transform, np.float64).reshape(4, 4)
-    full = _np(cam.full_proj_transform, np.float64).reshape(4, 4)
+    wvt = _as(cam.world_view_transform, np.float64).reshape(4, 4)
+    full = _as(cam.full_proj_transform, np.float64).reshape(4, 4)
     c2w = np.linalg.inv(wvt.T)
     ndc2pix = np.array([[W / 2, 0, 0, W / 2], [0, H / 2, 0, H / 2], [0, 0, 0, 1]], np.float64).T
     intr = ((c2w.T @ full) @ ndc2pix)[:3, :3].T
@@ -153,7 +153,7 @@ def ray_dirs(cam, W, H, dtype=f32):
 
 def depths_to_points(depth, cam, dtype=f32):
     """[H*W,3]: o + depth * dir per pixel."""
-    depth = _np(depth, dtype)
+    depth = _as(depth, dtype)
     H, W = depth.shape[-2:]
     o, _D = ray_record(cam, W, H, dtype)
     with np.errstate(invalid="ignore", over="ignore"):
@@ -186,7 +186,7 @@ def n_samples(depth, min_grid_size):
 def march(bits, bbox_min, bbox_max, R, depth, cam, S=None, dtype=f32):
     """float32 [H,W], 0 / 1: the ray march of a depth map through the grid."""
     ft = dtype
-    depth = _np(depth, ft)
+    depth = _as(depth, ft)
     depth = depth.reshape(depth.shape[-2:])
     H, W = depth.shape
     if S is None:
@@ -240,9 +240,9 @@ def build_visibility_masks(cameras, depths, points=None, depth_threshold=0.1, le
     views = list(zip(cameras, depths))
     out = []
     for i, (cam, depth) in enumerate(views):
-        depth = _np(depth, dtype)
+        depth = _as(depth, dtype)
         H, W = depth.shape[-2:]
-        pts = depths_to_points(depth, cam, dtype) if points is None else _np(points[i], dtype).reshape(-1, 3)
+        pts = depths_to_points(depth, cam, dtype) if points is None else _as(points[i], dtype).reshape(-1, 3)
         n = view_counts(pts, views, SURFACE, depth_threshold, i, dtype).reshape(1, H, W)
         out.append(n.astype(f32) if return_origin_masks else (n >= least_num_views).astype(f32))
     return out
