@@ -182,6 +182,9 @@ SIGNATURES = {
     "g4s_chart_surfels_count": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_f, c_p, c_p, c_sz, c_p]),
     "g4s_chart_surfels_emit": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_f, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "g4s_voxel_downsample_emit_index": (c_i, [c_i, c_i, c_p, c_p, c_sz, c_p]),
+    "g4s_warp_init_workspace": (c_sz, [c_i, c_p, c_i]),
+    "g4s_warp_init_count": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_f, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_warp_init_emit": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "g4s_kmeans_normals_workspace": (c_sz, [c_i, c_p]),
     "g4s_kmeans_normals": (c_i, [c_i, c_p, c_p, c_i, c_p, c_i, ctypes.c_double, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "g4s_normal_components_workspace": (c_sz, [c_i, c_p]),

@@ -1,8 +1,8 @@
 """Gaussian initialisation from depth charts (include/g4s_render_maps.h, "Chart surfels"; csrc/tsdf/chart_init.hip).
 
-The trainer's first act (2d-gaussian-splatting/train_with_refine_depth.py, "Initialize gaussians", the path that is not the
-warp initialiser): one surfel on every face of the triangulated pixel grids that is not elongated, and the voxel pick of
-surfel indices.
+The trainer's first act (2d-gaussian-splatting/train_with_refine_depth.py, "Initialize gaussians") on its chart path: one
+surfel on every face of the triangulated pixel grids that is not elongated, and the voxel pick of surfel indices.  The
+other path, the warp initialiser, is warp_init.py; initial_gaussians takes it on request.
 
   pointmap_surfels, depthmap_surfels     the surfels of point maps, or of depth maps whose points are formed in the kernel.
   get_gaussian_parameters_from_pa_data, get_gaussian_parameters_from_charts_data   matcha/dm_scene/charts.py, by name.
@@ -169,14 +169,15 @@ MAX_INIT_INPUT_VIEWS = 50
 MAX_INIT_EXTRA_VIEWS = 30
 
 
-def select_init_views(n_input, n_extra):
+def select_init_views(n_input, n_extra, warp=False):
     """The trainer's view sub-selection as two index lists: with more than 50 input views, 50 of them by
     np.linspace(0, n_input - 1, 50, dtype=int); with more than 30 extra (inpainted) views, its hard-coded 0-9, 15-24 and
-    30 .. n_extra - 1."""
+    30 .. n_extra - 1.  warp: the warp initialiser takes every input view (the trainer's warp_max_init_gs_input_view_num
+    is None); the extra views are chosen as before."""
     n_input, n_extra = int(n_input), int(n_extra)
     if n_input < 0 or n_extra < 0:
         raise ValueError("view counts must not be negative")
-    if n_input > MAX_INIT_INPUT_VIEWS:
+    if n_input > MAX_INIT_INPUT_VIEWS and not warp:
         input_ids = [int(i) for i in np.linspace(0, n_input - 1, MAX_INIT_INPUT_VIEWS, dtype=int)]
     else:
         input_ids = list(range(n_input))
@@ -188,12 +189,25 @@ def select_init_views(n_input, n_extra):
 
 
 def initial_gaussians(input_depths, input_cameras, input_images, extra_depths=None, extra_cameras=None, extra_images=None,
-                      max_gaussians_num=10_000_000, use_downsample_gaussians=False):
+                      max_gaussians_num=10_000_000, use_downsample_gaussians=False, downsample_gaussians_type="voxel",
+                      warp_depth_error_thresh=0.01, warp_downsample_pixel_grid_size=-1):
     """The trainer's initial Gaussians from the plane-aware depths: (means [M,3], scales [M,2], quaternions [M,4], colors
     [M,3]), ready for GaussianModel.create_from_parameters.  The surfels of the input views, then those of the extra views
     (ratio_th 5, normalized_scales 0.5, normal_scale 1e-10); if there are more than max_gaussians_num and
     use_downsample_gaussians is set, the voxel pick at 1 cm; scales[:, :2] times the downsample factor.  The views are
-    taken as given: select_init_views is the caller's."""
+    taken as given: select_init_views is the caller's.
+
+    With use_downsample_gaussians and downsample_gaussians_type "warp" (the trainer's default type) the warp initialiser
+    runs instead: warp_init.warp_surfels over the input views followed by the extra views, images [3,H,W]."""
+    if downsample_gaussians_type not in ("voxel", "warp"):
+        raise ValueError(f"downsample_gaussians_type must be 'voxel' or 'warp' (got {downsample_gaussians_type!r})")
+    if use_downsample_gaussians and downsample_gaussians_type == "warp":
+        from .warp_init import warp_surfels
+        more = extra_depths is not None and len(extra_depths) > 0
+        return warp_surfels(list(input_depths) + (list(extra_depths) if more else []),
+                            list(input_cameras) + (list(extra_cameras) if more else []),
+                            list(input_images) + (list(extra_images) if more else []),
+                            depth_error_thresh=warp_depth_error_thresh, downsample_pixel_grid_size=warp_downsample_pixel_grid_size)
     params = depthmap_surfels(input_depths, input_cameras, input_images)
     if extra_depths is not None and len(extra_depths) > 0:
         extra = depthmap_surfels(extra_depths, extra_cameras, extra_images)

@@ -1,4 +1,4 @@
-// The generic exclusive scan of scan.hip, shared by tsdf.hip, unbounded.hip, mesh_ops.hip and plane_masks.hip.
+// The generic exclusive scan of scan.hip, shared by tsdf.hip, unbounded.hip, mesh_ops.hip, chart_init.hip, warp_init.hip and plane_masks.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

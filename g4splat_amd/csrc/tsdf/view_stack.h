@@ -1,5 +1,5 @@
 // What the units over a stack of views share.  All of them -- the two fields (unbounded.hip, tetra.hip) and, through
-// vis_view.h, visibility.hip, planes.hip, consistency.hip, view_select.hip, depth_cues.hip, chart_init.hip, plane_masks.hip --: the tail of a
+// vis_view.h, visibility.hip, planes.hip, consistency.hip, view_select.hip, depth_cues.hip, chart_init.hip, warp_init.hip, plane_masks.hip --: the tail of a
 // view record, the host checks of a view stack, and the staging of the view table into the caller's workspace with its size.
 // The two fields alone: the bilinear tap and the point-sample kernel; a field differs in its matrices, in which points a view
 // accepts and in its running-mean update, and those stay in its unit.

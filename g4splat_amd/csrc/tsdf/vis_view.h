@@ -1,7 +1,8 @@
 // What the units over the Visibility section's views share.  visibility.hip, planes.hip, consistency.hip, view_select.hip: the
 // head of a view record -- world -> camera rotation, translation, focal lengths, then view_stack.h's maps --, its fill from
 // the host arrays, THE projection of include/g4s_render_maps.h ("Projection of a point p into a view"), its truncating tap and
-// the SURFACE test.  visibility.hip, depth_cues.hip, chart_init.hip: the ray record with THE back-projection.  There is no
+// the SURFACE test.  visibility.hip, depth_cues.hip, chart_init.hip, warp_init.hip: the ray record with THE back-projection
+// (warp_init.hip reads both halves: it projects the points it back-projects).  There is no
 // second one of any of them.  The host checks and the table's staging that all six share are view_stack.h's.
 #pragma once
 #include "view_stack.h"

@@ -973,6 +973,68 @@ int g4s_voxel_downsample_emit_index(int n, int n_voxels, long long* index_out, c
                                     void* stream);
 
 /* =====================================================================================================================
+ * Warp surfels (g4splat_amd/csrc/tsdf/warp_init.hip).
+ *
+ * The trainer's default first act with --use_downsample_gaussians (2d-gaussian-splatting/train_with_refine_depth.py,
+ * "Initialize gaussians", downsample_gaussians_type "warp"; scene/gaussian_model.py
+ * get_gaussian_parameters_by_warp_from_depths): one surfel per pixel that no EARLIER view already explains under
+ * depth-consistent warping.  tests/warp_init_ref.py restates this section in numpy.  The rules of the Visibility section
+ * apply: float32, round-to-nearest-even, correctly rounded / and sqrt, no fused multiply-add, left to right as written.
+ * NOT the min / max of that section: every min, max and clamp here propagates a NaN, as torch.min and torch.clamp do
+ * (min(a, b) = a if a is a NaN or a < b, else b; max(t, lo) = lo if t < lo, else t).
+ *
+ * Inputs.  V views in order.  View v has world_view_transform, focal {fx, fy}, a ray record rays[12 v .. 12 v + 11], a depth
+ *   map [H_v,W_v] and an image [3,H_v,W_v], all as in the Visibility section; sizes may differ between views.  Scalars:
+ *   depth_error_thresh, min_scale, max_scale and the grid g (g <= 0 means 1).  Limit: the lattice cells of all views, the sum
+ *   of ceil(H_v / g) ceil(W_v / g), stay below 2^31.
+ * Points.  P_v(y,x) is THE back-projection of pixel (y,x) at its depth (g4s_depth_to_points), whatever the depth is: a
+ *   non-positive depth still yields a point, and such points are neighbours like any other (the reference's behaviour).
+ * Candidates.  Pixel (y,x) of view v is a candidate iff y % g == 0 && x % g == 0 && depth > 0 (a NaN depth is none).
+ * Covered.  A candidate p of view i is covered iff for some j < i: with (z, u, v) THE projection of P_i(p) into view j (there
+ *   is no second projection), u >= 0 && u <= W_j - 1 && v >= 0 && v <= H_j - 1 && z > 0 -- the borders are closed, which is
+ *   not the Visibility section's "in image" --, d = depth_j[rint(v)][rint(u)] with round half to even (torch.round), d > 0,
+ *   and SURFACE as written there: |z - d| / (z + 1e-6) < depth_error_thresh.
+ * Scale.  dist(a, b) = sqrt((dx*dx + dy*dy) + dz*dz) of the difference.  s = min(min(min(r, l), d), u) * 0.5 over the
+ *   distances from P(y,x) to its right, left, lower and upper neighbour point, times float(g) when g > 0.  At a border the
+ *   missing neighbour's distance is the opposite one's (the reference's edge replication).  A NaN distance gives a NaN s.
+ *   If W_v == 1 or H_v == 1 every s of the view is 1e-3f * 0.5 (times float(g)).
+ * Keep.  A pixel is kept iff it is a candidate, is not covered and s < max_scale (a NaN s is dropped).  This is the
+ *   reference's final valid_scale_mask folded in; it changes no row and no order.
+ * Normal.  n(sy, sx) with sy = clamp(y, 1, H-2), sx = clamp(x, 1, W-2) (the reference's border copy, rows first, then
+ *   columns): n = normalize(cross(P(sy+1,sx) - P(sy-1,sx), P(sy,sx+1) - P(sy,sx-1))), cross(a, b) = (a1 b2 - a2 b1,
+ *   a2 b0 - a0 b2, a0 b1 - a1 b0), normalize(a) = a / max(sqrt((a0*a0 + a1*a1) + a2*a2), 1e-12f) per component.  If H < 3
+ *   or W < 3 the normal is (0, 0, 1).
+ * Quaternion (w, x, y, z).  The reference's own construction, not pytorch3d's, without sign standardisation:
+ *   z_axis = normalize(n); ref = (0,1,0) if |z_axis_0| > 0.9 else (1,0,0); x_axis = normalize(cross(ref, z_axis)), every
+ *   product with a zero of ref kept; y_axis = cross(z_axis, x_axis); the matrix m has the columns (x_axis, y_axis, z_axis).
+ *   q = ( sqrt(max(((1 + m00) + m11) + m22, 0)) / 2, sqrt(max(((1 + m00) - m11) - m22, 0)) / 2,
+ *         sqrt(max(((1 - m00) + m11) - m22, 0)) / 2, sqrt(max(((1 - m00) - m11) + m22, 0)) / 2 );
+ *   q_x *= sign((m21 - m12) + 1e-12f), q_y *= sign((m02 - m20) + 1e-12f), q_z *= sign((m10 - m01) + 1e-12f), sign(t) = 1 if
+ *   t > 0, -1 if t < 0, else t (in float32 the 1e-12 only decides the sign of an exact zero);
+ *   then q / max(sqrt(((q_w*q_w + q_x*q_x) + q_y*q_y) + q_z*q_z), 1e-12f) per component.
+ * Row.  means = P_v(y,x); scales = (max(s, min_scale), max(s, min_scale)); the quaternion; colors = image[:, y, x], unclamped.
+ * Order.  Views in order, the kept pixels of a view in row-major order.  No atomics: the same bits from run to run.
+ *
+ * Two phases.  count writes keep[v], one byte (0 or 1) per lattice cell [ceil(H_v / g), ceil(W_v / g)] -- cell (ly, lx) is
+ *   pixel (ly g, lx g) --, and *n_rows (host int; the one host synchronisation of the stage).  emit, with the same views, grid,
+ *   keep maps and workspace, the workspace untouched in between, writes means [n_rows,3], scales [n_rows,2], quaternions
+ *   [n_rows,4], colors [n_rows,3] float32 and nothing beyond row n_rows - 1.  Depth maps and images are only read.
+ *
+ * world_view [V,16], focal [V,2], sizes [V,2], rays [V,12] and the pointer arrays are HOST arrays.  Every argument is checked
+ * on the host before anything is launched.  The size query is pure host code and returns 0 for arguments out of range.
+ */
+size_t g4s_warp_init_workspace(int n_views, const int* sizes, int grid);
+
+int g4s_warp_init_count(int n_views, const float* world_view, const float* focal, const int* sizes, const float* const* depth,
+                        const float* rays, int grid, float depth_error_thresh, float max_scale, unsigned char* const* keep,
+                        int* n_rows, char* workspace, size_t workspace_bytes, void* stream);
+
+int g4s_warp_init_emit(int n_views, const float* world_view, const float* focal, const int* sizes, const float* const* depth,
+                       const float* rays, const float* const* images, int grid, float min_scale,
+                       const unsigned char* const* keep, int n_rows, float* means, float* scales, float* quaternions,
+                       float* colors, char* workspace, size_t workspace_bytes, void* stream);
+
+/* =====================================================================================================================
  * Plane masks (g4splat_amd/csrc/tsdf/plane_masks.hip).
  *
  * What the reference does per view in 2d-gaussian-splatting/planes/plane_excavator.py after the SAM network has run: KMeans
