@@ -93,6 +93,10 @@ SIGNATURES = {
     "g4s_anisotropy_workspace": (c_sz, [c_i]),
     "g4s_anisotropy_forward": (c_i, [c_i, c_p, c_f, c_p, c_p, c_sz, c_p]),
     "g4s_anisotropy_backward": (c_i, [c_i, c_p, c_f, c_p, c_p, c_p]),
+    "g4s_chart_match_workspace": (c_sz, [c_i, c_i, c_i]),
+    "g4s_chart_match": (c_i, [c_i, c_i, c_i, c_p, c_p, c_f, c_p, c_p, c_i, c_p, c_p]),
+    "g4s_chart_match_loss_forward": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_sz, c_p]),
+    "g4s_chart_match_loss_backward": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_sz, c_p]),
     # include/g4s_render_maps.h
     "g4s_render_maps_workspace": (c_sz, []),
     "g4s_render_maps_forward": (c_i, [c_i, c_i, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz,
