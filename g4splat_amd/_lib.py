@@ -97,6 +97,11 @@ SIGNATURES = {
     "g4s_chart_match": (c_i, [c_i, c_i, c_i, c_p, c_p, c_f, c_p, c_p, c_i, c_p, c_p]),
     "g4s_chart_match_loss_forward": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_sz, c_p]),
     "g4s_chart_match_loss_backward": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_chart_align_workspace": (c_sz, [c_i, c_i, c_i]),
+    "g4s_chart_align_normals": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "g4s_chart_align_forward": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_i, c_p, c_p, c_sz, c_p]),
+    "g4s_chart_align_backward": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_i, c_p, c_p, c_p, c_p,
+                                       c_sz, c_p]),
     # include/g4s_render_maps.h
     "g4s_render_maps_workspace": (c_sz, []),
     "g4s_render_maps_forward": (c_i, [c_i, c_i, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz,

@@ -16,6 +16,7 @@
 // into dL_dsurf_depth.
 #include "g4s_internal.h"
 #include "g4s_device.h"
+#include "chart_common.h"
 #include "../../include/g4s_losses.h"
 
 namespace g4s {
@@ -37,9 +38,6 @@ struct ChartArgs {
     float *d_rn, *d_sn, *d_sd;
     unsigned long long* acc;  // [N] fixed-point sums of the depth-order scatter
 };
-
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-__device__ __forceinline__ float signf(float v) { return v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f); }  // sign(0) = 0
 
 // The partner q = clamp(p + shift_p) of pixel (px, py).
 __device__ __forceinline__ long long shifted_pixel(const ChartArgs& a, long long p, int px, int py) {

@@ -197,6 +197,95 @@ int g4s_chart_match_loss_backward(int n, int height, int width, const float* cam
                                   const float* grad_out1, float* dL_ddepths, char* workspace, size_t workspace_bytes,
                                   void* stream);
 
+/*
+ * Chart alignment losses: the depth, gradient, normal and curvature terms of MAtCha's chart alignment, fused
+ * (ParallelAligner.loss and .optimize, matcha/dm_scene/parallel_aligner.py:422-458, 713-722, 757-788, with
+ * depths_to_points_parallel, depth2normal_parallel and normal2curv_parallel, matcha/dm_utils/rendering.py:249-322, 409-436,
+ * and img_grad, matcha/dm_utils/image.py:4-9).
+ *
+ * n charts of one size H x W, N = H W, p = (y, x).  Every operation below is one float32 operation, in this order, with no
+ * fused multiply-add (the unit is compiled with -ffp-contract=off); divisions and square roots are IEEE.
+ *   cameras   device float [n][12]: the ray record o[3], D[3][3] of each view, the first 12 floats of the matcher's record
+ *   depths and every other map: float32 on the device
+ * Points:     dir_k = (D[k][0] x + D[k][1] y) + D[k][2],   q_k = d dir_k + o_k                    (as for the matcher)
+ * Normals nu [n,H,W,3]: for an interior pixel (1 <= y <= H-2, 1 <= x <= W-2)
+ *               a = q(y+1,x) - q(y-1,x)  (the reference's "dx", a ROW difference),   b = q(y,x+1) - q(y,x-1),   formed as
+ *               a_k = (d(y+1,x) - d(y-1,x)) dir_k(y+1,x) + d(y-1,x) (D[k][1] + D[k][1]),
+ *               b_k = (d(y,x+1) - d(y,x-1)) dir_k(y,x+1) + d(y,x-1) (D[k][0] + D[k][0])
+ *               (the two rays differ by exactly 2 D[k][1], 2 D[k][0]: the same differences, but with the rounding of
+ *               their own size, not of the points'; subtracting the float32 points loses four to five bits, which on
+ *               noisy depths puts the float32 curvature mean a float32 ulp from its float64 value),
+ *               c = a x b = (a_1 b_2 - a_2 b_1, a_2 b_0 - a_0 b_2, a_0 b_1 - a_1 b_0),  L = sqrt((c_0 c_0 + c_1 c_1) + c_2 c_2),
+ *               nu = c / (L < 1e-12 ? 1e-12 : L)      (F.normalize; a NaN stays)
+ *             every border pixel is exactly 0; a map with H < 3 or W < 3 has no interior.
+ * Curvature kappa [n,H,W]:  lap_c = (((nu_u - nu_p) + (nu_l - nu_p)) + (nu_b - nu_p)) + (nu_r - nu_p), the neighbours above,
+ *             left, below, right in this order, replicate padding (a neighbour outside the map is p itself): the stencil
+ *             and order of the chart-prior section;  kappa = (|lap_0| + |lap_1|) + |lap_2|.  (optimize passes a mask of ones
+ *             shaped like the normals, so the reference's curvature has three equal channels; the mean is the same.)
+ * out4 (device float[4]) receives four UNWEIGHTED means; the caller applies the weights:
+ *   out4[0] = mean over n N of            m_p (c_p |d_p - r_p| - lambda log c_p)                            l.435-458
+ *             r: reference_depths (the target); c: confidence, the ACTIVATED 1 + exp(_confidence) (NULL: the term is
+ *             |d - r|); lambda: confidence_weighting (0.2 in the reference); m: masks (NULL: 1)
+ *   out4[1] = mean over 2 n (H-1)(W-1) of |gm (D_k d - D_k d0)|,  k = row, column                           l.760-766
+ *             D_row d = d(y+1,x) - d(y,x),  D_col d = d(y,x+1) - d(y,x), both for y < H-1 and x < W-1; each pixel adds its
+ *             row term and its column term; d0: initial_depths (the aligner's _depths, NOT r); gm: gradient_masks
+ *             [n,H-1,W-1] (NULL: 1), applied per view (for gm >= 0 this is gm |D_k d - D_k d0|)
+ *   out4[2] = mean over n N of            1 - ((nu0_0 nu_0 + nu0_1 nu_1) + nu0_2 nu_2)                      l.776-780
+ *             a border pixel contributes exactly 1
+ *   out4[3] = mean over n N of            |kappa0 - kappa|                                                  l.782-788
+ *   nu0 = initial_normals [n,H,W,3] and kappa0 = initial_curvatures [n,H,W]: what g4s_chart_align_normals makes of the
+ *   initial depths, computed once by the caller.
+ *   flags: G4S_CHART_ALIGN_GRADIENT | _NORMAL | _CURVATURE switch terms 1, 2, 3 on; a term that is off leaves exactly 0
+ *   in its slot, reads none of its inputs (they may be NULL) and does no work.
+ *   Sums are reduced in a fixed order and in double (the float32 terms of 256 consecutive pixels of one view in a tree
+ *   per block, one block finishes over the block partials): bit-reproducible, and a mean is as good as its terms.
+ * The backward takes the cotangents of the four means (device float[4]) and writes EVERY element of dL_ddepths [n,H,W]
+ * and, if confidence is given, of dL_dconfidence [n,H,W].  It reproduces autograd at the kinks: sign(0) = 0 for d - r, for
+ * gm (D_k d - D_k d0), for each lap_c and for kappa0 - kappa; the clamp at 1e-12 passes the gradient at equality and gives
+ * G / 1e-12 below it.  With k0 = g0 / float(n N), k2, k3 alike and k1 = g1 / float(2 n (H-1)(W-1)), dL/dd_p is the sum, in
+ * this order, of
+ *   depth:     ((k0 m_p) c_p) sign(d_p - r_p),     and dL/dc_p = (k0 m_p) (|d_p - r_p| - lambda / c_p)
+ *   gradient:  k1 s,  s = 0 - s_row(y,x) - s_col(y,x) + s_row(y-1,x) + s_col(y,x-1) over the stencils that exist (at most
+ *              four memberships), s_k = gm sign(gm (D_k d - D_k d0))
+ *   normal and curvature:  dir(p) . dL/dq(p) = (dir_0 dq_0 + dir_1 dq_1) + dir_2 dq_2, where
+ *              w_p,c = sign(kappa_p - kappa0_p) sign(lap_p,c),   G_p = k3 (sum over the four neighbours nb, in the order
+ *              above, of (w_nb - w_p)) - k2 nu0_p   for an interior p (all its neighbours lie inside; border normals are
+ *              constants; the stencil is a graph Laplacian: its adjoint is the same stencil),
+ *              dL/dc = G / L - c (((c_0 G_0 + c_1 G_1) + c_2 G_2) / ((L L) L))    (G / 1e-12 where L < 1e-12),
+ *              A = b x dL/dc,  B = dL/dc x a  (0 off the interior),
+ *              dq(p') = 0 + A(y'-1,x') - A(y'+1,x') + B(y',x'-1) - B(y',x'+1), a neighbour outside the map skipped.
+ * Every step is a gather from a fixed neighbourhood: no atomics, no fixed-point sums, no range limit on the values.
+ *
+ * Launches per call: g4s_chart_align_normals 1 or 2; forward 3 (normals, terms, reduce; 2 with the normal and curvature
+ * terms off); backward 3 (normals, A and B, gather; 2 with the curvature term off, 1 with the normal term off as well).
+ * The normals, A and B pass through three [n,H,W,3] maps of the workspace.  No allocation, no host synchronisation:
+ * forward and backward can be captured in a HIP graph.
+ *
+ * g4s_chart_align_normals   normals [n,H,W,3] and curv_out [n,H,W] of `depths`; either may be NULL.  With depths NULL,
+ *                           `normals` is READ and only curv_out is written (the curvature of any normal map).
+ * All refuse (G4S_ERR_INVALID_ARGUMENT, with a message) n, H or W <= 0 and sizes whose [n,H,W,3] maps have 2^31 elements
+ * or more (g4s_chart_align_workspace is 0 for them); the two loss calls also a workspace smaller than
+ * g4s_chart_align_workspace, and the gradient term with H < 2 or W < 2 -- the reference's mean over an empty tensor is NaN
+ * there.
+ */
+#define G4S_CHART_ALIGN_GRADIENT 1
+#define G4S_CHART_ALIGN_NORMAL 2
+#define G4S_CHART_ALIGN_CURVATURE 4
+size_t g4s_chart_align_workspace(int n, int height, int width);
+int g4s_chart_align_normals(int n, int height, int width, const float* cameras, const float* depths, float* normals,
+                            float* curv_out, void* stream);
+int g4s_chart_align_forward(int n, int height, int width, const float* cameras, const float* depths,
+                            const float* reference_depths, const float* confidence, const float* masks,
+                            const float* initial_depths, const float* gradient_masks, const float* initial_normals,
+                            const float* initial_curvatures, float confidence_weighting, int flags, float* out4,
+                            char* workspace, size_t workspace_bytes, void* stream);
+int g4s_chart_align_backward(int n, int height, int width, const float* cameras, const float* depths,
+                             const float* reference_depths, const float* confidence, const float* masks,
+                             const float* initial_depths, const float* gradient_masks, const float* initial_normals,
+                             const float* initial_curvatures, float confidence_weighting, int flags,
+                             const float* grad_out4, float* dL_ddepths, float* dL_dconfidence, char* workspace,
+                             size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
