@@ -20,6 +20,13 @@ class G4sPackedRows(ctypes.Structure):  # g4s_packed_rows
     _fields_ = [("rows", ctypes.c_void_p), ("block_offs", ctypes.c_void_p), ("capacity", ctypes.c_longlong)]
 
 
+class G4sChartDeformShape(ctypes.Structure):  # g4s_chart_deform_shape
+    _fields_ = [("n", ctypes.c_int), ("height", ctypes.c_int), ("width", ctypes.c_int), ("levels", ctypes.c_int),
+                ("channels", ctypes.c_int), ("level_height", ctypes.c_int * 8), ("level_width", ctypes.c_int * 8),
+                ("bins", ctypes.c_int), ("layers", ctypes.c_int), ("layer_size", ctypes.c_int), ("scene_radius", ctypes.c_float),
+                ("deformation_radius", ctypes.c_float)]
+
+
 class G4sLayout(ctypes.Structure):
     _fields_ = [(n, ctypes.c_size_t) for n in (
         "rec", "clamped", "depth_sorted", "tiles_touched", "geom_bytes", "entries", "qhit", "binning_bytes", "ranges",
@@ -102,6 +109,11 @@ SIGNATURES = {
     "g4s_chart_align_forward": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_i, c_p, c_p, c_sz, c_p]),
     "g4s_chart_align_backward": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_i, c_p, c_p, c_p, c_p,
                                        c_sz, c_p]),
+    "g4s_chart_deform_workspace": (c_sz, [ctypes.POINTER(G4sChartDeformShape)]),
+    "g4s_chart_deform_forward": (c_i, [ctypes.POINTER(G4sChartDeformShape), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz,
+                                       c_p]),
+    "g4s_chart_deform_backward": (c_i, [ctypes.POINTER(G4sChartDeformShape), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                        c_p, c_p, c_sz, c_p]),
     # include/g4s_render_maps.h
     "g4s_render_maps_workspace": (c_sz, []),
     "g4s_render_maps_forward": (c_i, [c_i, c_i, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz,

@@ -286,6 +286,86 @@ int g4s_chart_align_backward(int n, int height, int width, const float* cameras,
                              const float* grad_out4, float* dL_ddepths, float* dL_dconfidence, char* workspace,
                              size_t workspace_bytes, void* stream);
 
+/*
+ * Chart deformation: the trainable half of MAtCha's chart alignment, fused -- the chart encodings, the depth encoding, the
+ * per-chart MLP and the deformed depths (ParallelAligner.verts_deformations, .verts, .deformed_depths,
+ * matcha/dm_scene/parallel_aligner.py:341-413; MultiResChartsEncoding, ChartsEncoding, DepthEncoding,
+ * matcha/dm_deformation/encodings.py:49-179; DeformationMultiMLP, MultiLinear, matcha/dm_deformation/multi_mlp.py:33-242) in the
+ * configuration charts_alignment.py runs: depth encoding mode 'add' (or none), plain DeformationMultiMLP, output dimension 1
+ * along the rays, not in disparity space, no final non-linearity.
+ *
+ * n charts of one size H x W, N = H W, pixel p = (r, c) = (p / W, p % W).  Every operation below is one float32 operation, in
+ * this order; a product-sum written fma(a, b, s) is ONE fused operation, everything else is unfused (-ffp-contract=off).
+ *   levels[l]       device float [n][C][h_l][w_l], l < L: the reference's parameter layout.  E = L C.
+ *   depth_encoding  device float [n][E][B] (bins = 0: absent, and depth_coords is not read)
+ *   weights[j], biases[j], j < layers: device float [n][out_j][in_j], [n][out_j]; in_0 = E, out_j = layer_size = S for
+ *                   j < layers - 1, out of the last layer 1
+ *   depth_coords    device float [n][N] in [0, 1];  cameras  device float [n][12], the ray record o[3], D[3][3] of each view;
+ *   initial_depths  device float [n][N]
+ * Positions.  lin_K[i] = float(2 i - (K - 1)) / float(K - 1) (-1 for K = 1): the correctly rounded torch.linspace(-1, 1, K)[i];
+ *             torch's own float32 linspace is off it by an ulp or two at some i.  Pixel (r, c) samples at u_x = lin_H[r],
+ *             u_y = lin_W[c]: the reference builds _pts_uv as (lin_H[r], lin_W[c]) and grid_sample reads component 0 as x, the
+ *             WIDTH axis, so the pixel's ROW runs along a level's width.  Kept.
+ * Taps(u, size):  t = ((u + 1) size - 1) / 2, clamped to [0, size - 1] (padding_mode='border', align_corners=False),
+ *             i0 = floor(t), i1 = min(i0 + 1, size - 1), w0 = (floor(t) + 1) - t, w1 = t - floor(t).  Where i1 is clamped w1 is
+ *             exactly 0 (grid_sample skips that tap; here it adds v 0, which differs only for a non-finite v).
+ * Chart encoding of channel e = l C + ch:  (x0, x1, wx0, wx1) = Taps(u_x, w_l), (y0, y1, wy0, wy1) = Taps(u_y, h_l), v = levels[l][i][ch],
+ *             enc_e = ((v[y0][x0] (wx0 wy0) + v[y0][x1] (wx1 wy0)) + v[y1][x0] (wx0 wy1)) + v[y1][x1] (wx1 wy1)
+ * Depth encoding (an image of height B and width 1 sampled at x = 0):  (b0, b1, w0, w1) = Taps(-1 + 2 depth_coords[i][p], B),
+ *             x_e = enc_e + (q[b0] w0 + q[b1] w1),  q = depth_encoding[i][e]         (mode 'add'; x_e = enc_e without)
+ * MLP.        a_0 = x / scene_radius  (the reference's centre terms are exactly 0 and its input scale exactly 1);
+ *             layer j < layers - 1:  z_o = b_o, then z_o = fma(W[o][k], a[k], z_o) over k in the order
+ *                 k = 16 t + 4 g + s  for t = 0 .. in/16 - 1, s = 0..3, g = 0..3 (g fastest)
+ *             -- the order in which the accumulator registers of one 16x16x4 MFMA tile feed the next product (an MFMA is a
+ *             k-ordered fma chain) --, a = z > 0 ? z : 0;
+ *             last layer:  p_g = fma chain from 0 over k = 16 t + 4 g + s (t, then s) for g = 0..3,
+ *                 out = ((p_0 + p_1) + (p_2 + p_3)) + b;       delta = out deformation_radius
+ * Deformed depth.  The reference forms verts = _verts + delta normalize(_rays), rays = verts - centre, and takes the view-space
+ *             z.  Here, from the initial depth d0 and the ray record: dir_k = (D[k][0] c + D[k][1] r) + D[k][2],
+ *                 depth = d0 + delta (sign(d0) / sqrt((dir_0 dir_0 + dir_1 dir_1) + dir_2 dir_2)),   exactly d0 where d0 = 0
+ *             (the view-space z of dir is 1, so ray_hat . z = sign(d0) / |dir|).  No float32 points are subtracted: as for the
+ *             normals above, that keeps the four to five bits the points' rounding would take.  normalize's clamp at 1e-12
+ *             is not modelled for 0 < |d0| |dir| < 1e-12.
+ * Supported envelope (anything else is refused with a message that names the limit): L <= G4S_CHART_DEFORM_MAX_LEVELS, C a
+ *   multiple of 4, E in {16, 32, 64}, S in {32, 64}, 2 <= layers <= 4, 0 <= B <= 4096, every level 1 x 1 to 2^24 texels,
+ *   n H W < 2^31, scene_radius > 0.
+ * The backward takes dL/ddepths [n][N] on the device and writes EVERY element of the gradients, in the parameters' layouts.
+ *   It recomputes the activations (the forward saves nothing).  With gz = (g s) deformation_radius, s the factor of delta
+ *   above (gz = 0 where d0 = 0), ReLU passes the cotangent where z > 0, and da = W^T dz is the same fma chain over the output
+ *   index (from 0).  A workgroup serves G4S_CHART_DEFORM_WG_PIXELS consecutive pixels of one chart in tiles of
+ *   G4S_CHART_DEFORM_TILE.  Sums over pixels have three levels, each in index order: a tile's dW[o][k] is the fma chain, from
+ *   0, of dz_o(p) a_k(p) over its pixels (pixels past the end add exact zeros) and its db_o the plain sum of dz_o(p); the tile
+ *   sums are added to the workgroup's running sum in tile order; a chart's workgroup sums are added in workgroup order.
+ *   dL/dx = da_0 / scene_radius [n][N][E] passes through the workspace.  The encodings GATHER from it: a texel sums, over
+ *   the pixels whose taps reach it (rows, then columns, in index order; a pixel's taps in the order above), dL/dx_e times the
+ *   tap's weight; a depth bin likewise over a workgroup's pixels in index order (tap b0, then b1), the workgroups' sums added
+ *   in order.  No atomics, no fixed-point sums, no range limit: outputs and gradients are bit-identical from run to run.
+ * Launches: forward 1; backward 3 + L (+1 with a depth encoding).  No allocation, no host synchronisation, nothing read
+ * back: both can be captured in a HIP graph.  Workspace (backward only; the forward ignores it): n N E floats for dL/dx and
+ * n ceil(N / G4S_CHART_DEFORM_WG_PIXELS) partials of (all weights + biases + E B) floats.
+ */
+#define G4S_CHART_DEFORM_TILE 64
+#define G4S_CHART_DEFORM_WG_PIXELS 4096
+#define G4S_CHART_DEFORM_MAX_LEVELS 8
+typedef struct g4s_chart_deform_shape {
+    int n, height, width;
+    int levels, channels; /* L, C */
+    int level_height[G4S_CHART_DEFORM_MAX_LEVELS], level_width[G4S_CHART_DEFORM_MAX_LEVELS];
+    int bins;             /* B; 0: no depth encoding */
+    int layers, layer_size;
+    float scene_radius, deformation_radius;
+} g4s_chart_deform_shape;
+size_t g4s_chart_deform_workspace(const g4s_chart_deform_shape* shape); /* 0 for a shape outside the envelope */
+int g4s_chart_deform_forward(const g4s_chart_deform_shape* shape, const float* const* levels, const float* depth_encoding,
+                             const float* const* weights, const float* const* biases, const float* depth_coords,
+                             const float* cameras, const float* initial_depths, float* depths, float* delta,
+                             char* workspace, size_t workspace_bytes, void* stream);
+int g4s_chart_deform_backward(const g4s_chart_deform_shape* shape, const float* const* levels, const float* depth_encoding,
+                              const float* const* weights, const float* const* biases, const float* depth_coords,
+                              const float* cameras, const float* initial_depths, const float* dL_ddepths,
+                              float* const* dL_dlevels, float* dL_ddepth_encoding, float* const* dL_dweights,
+                              float* const* dL_dbiases, char* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
