@@ -114,6 +114,14 @@ SIGNATURES = {
                                        c_p]),
     "g4s_chart_deform_backward": (c_i, [ctypes.POINTER(G4sChartDeformShape), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                         c_p, c_p, c_sz, c_p]),
+    "g4s_chart_confidence_forward": (c_i, [ctypes.c_longlong, c_p, c_p, c_p, c_p]),
+    "g4s_chart_confidence_backward": (c_i, [ctypes.c_longlong, c_p, c_p, c_p, c_p]),
+    "g4s_chart_deform_reg_workspace": (c_sz, [ctypes.POINTER(G4sChartDeformShape), c_i]),
+    "g4s_chart_deform_reg_forward_workspace": (c_sz, [ctypes.POINTER(G4sChartDeformShape), c_i]),
+    "g4s_chart_deform_reg_forward": (c_i, [ctypes.POINTER(G4sChartDeformShape), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p,
+                                           c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_chart_deform_reg_backward": (c_i, [ctypes.POINTER(G4sChartDeformShape), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p,
+                                            c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
     # include/g4s_render_maps.h
     "g4s_render_maps_workspace": (c_sz, []),
     "g4s_render_maps_forward": (c_i, [c_i, c_i, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz,

@@ -145,6 +145,41 @@ class _Deform(torch.autograd.Function):
         return (None, None) + tuple(gr.reshape(s).to(dt) for gr, (s, dt) in zip(grads, ctx.meta))
 
 
+REG_NORM, REG_TV = 1, 2  # G4S_CHART_DEFORM_REG_NORM, _TV
+
+
+class _DeformReg(torch.autograd.Function):
+    """The weighted deformation with the encoding regularisers (g4s_chart_deform_reg_*): (depths [n,H,W], reg [2])."""
+
+    @staticmethod
+    def forward(ctx, module, flags, encoding_weights, *params):
+        m = module
+        p = [t.detach().float().contiguous() for t in params]
+        with torch.cuda.device(m.device):
+            depths = torch.empty((m.n, m.height, m.width), dtype=torch.float32, device=m.device)
+            reg = torch.empty(2, dtype=torch.float32, device=m.device)
+            launch(m.device, "g4s_chart_deform_reg_forward", *m._call_head(p), _lib.ptr(encoding_weights), int(flags), _lib.ptr(depths),
+                   _lib.ptr(None), _lib.ptr(reg), workspace=m.reg_workspace_bytes(flags, forward=True) if flags & REG_NORM else None)
+        ctx.weighted = encoding_weights is not None
+        ctx.save_for_backward(*([encoding_weights] if ctx.weighted else []), *p)
+        ctx.module, ctx.flags = m, int(flags)
+        ctx.meta = [(t.shape, t.dtype) for t in params]
+        return depths, reg
+
+    @staticmethod
+    def backward(ctx, g, greg):
+        m, p = ctx.module, list(ctx.saved_tensors)
+        w = p.pop(0) if ctx.weighted else None
+        with torch.cuda.device(m.device):
+            g = g.detach().float().contiguous()  # the cotangents stay on the device
+            greg = greg.detach().float().contiguous()
+            grads = [torch.empty_like(t) for t in p]
+            lv, de, ws, bs = m._split(grads)
+            launch(m.device, "g4s_chart_deform_reg_backward", *m._call_head(p), _lib.ptr(w), ctx.flags, _lib.ptr(g), _lib.ptr(greg),
+                   _lib.ptrs(lv), _lib.ptr(de), _lib.ptrs(ws), _lib.ptrs(bs), workspace=m.reg_workspace_bytes(ctx.flags))
+        return (None, None, None) + tuple(gr.reshape(s).to(dt) for gr, (s, dt) in zip(grads, ctx.meta))
+
+
 class ChartDeformation(torch.nn.Module):
     """The trainable half of ParallelAligner: charts_encoding, depth_encoding and deformation under the reference's parameter
     names, and deformed_depths() [n,H,W] with gradients to every one of them.  `depths` are the aligner's `_depths` (constants,
@@ -318,6 +353,36 @@ class ChartDeformation(torch.nn.Module):
         gradients are bit-identical from run to run."""
         self._check_device()
         return _Deform.apply(self, False, *self._params())
+
+    def reg_workspace_bytes(self, flags, forward=False):
+        """The workspace of the weighted pair's backward: a double per workgroup, the plain pair's, then n H W floats (the norm's
+        cotangent per pixel); forward=True: what the forward needs with the norm bit, the doubles alone.  A refusal (the total
+        variation with fewer than 2 bins) raises ValueError with the library's message."""
+        size = _lib.load().g4s_chart_deform_reg_forward_workspace if forward else _lib.load().g4s_chart_deform_reg_workspace
+        nbytes = size(ctypes.byref(self._shape), int(flags))
+        if nbytes == 0:
+            raise ValueError(f"chart deform: {_lib.last_error()}")
+        return nbytes
+
+    def deformed_depths_and_regularizers(self, encoding_weights=None, norm=False, tv=False):
+        """(depths float32 [n,H,W], reg float32 [2]) in one library call, its backward a second.  encoding_weights [n,H,W]
+        (detached; the reference's 1 - exp(-(confidence - 1)^2 / 2)) multiply the chart encoding of each pixel before the
+        depth encoding is added; reg[0] is the mean norm of the unweighted chart encoding over all pixels
+        (regularize_chart_encodings_norms), reg[1] the mean |q[b+1] - q[b]| of the depth encoding
+        (use_total_variation_on_depth_encodings); a term not asked for is exactly 0.  Both outputs are differentiable in every
+        parameter; values and gradients are bit-identical from run to run, and with no weights and no terms the depths and
+        their gradients are bit-identical to deformed_depths()."""
+        flags = (REG_NORM if norm else 0) | (REG_TV if tv else 0)
+        if tv and self._B < 2:
+            raise ValueError(f"chart deform: the total variation needs at least 2 depth bins (got {self._B}; the reference's mean "
+                             "over an empty tensor is NaN)")
+        self._check_device()
+        if encoding_weights is not None:
+            _dev, w = _stack(encoding_weights, "encoding_weights", self.device)
+            if tuple(w.shape) != (self.n, self.height, self.width):
+                raise ValueError(f"encoding_weights must have the shape {(self.n, self.height, self.width)} (got {tuple(w.shape)})")
+            encoding_weights = w.detach().float().contiguous()
+        return _DeformReg.apply(self, flags, encoding_weights, *self._params())
 
     @torch.no_grad()
     def deformations(self):

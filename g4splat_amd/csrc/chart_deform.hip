@@ -26,6 +26,12 @@
 // folds a chart's partials in workgroup order.  dL/dx [n, H W, E] goes to the workspace; the encoding grids GATHER from it
 // (per texel the rectangle of pixels whose taps can reach it; per depth bin a walk over the pixels in index order, in
 // workgroup-sized pieces that the same fold finishes).  No atomics, no fixed-point sums.
+//
+// The forward, backward, fold and level kernels carry a compile-time switch REG ("Chart alignment: confidence, weighted
+// encodings, encoding regularisers" of the header: g4s_chart_deform_reg_*).  REG = false is the plain pair's code, unchanged;
+// REG = true adds the per-pixel encoding weight, the norm of the unweighted chart encoding (formed in the gather, reduced
+// per workgroup in double) and, in the backward, the norm's and the total variation's cotangents.  The confidence
+// activation (g4s_chart_confidence_*) lives here too.
 #include "g4s_internal.h"
 #include "g4s_device.h"
 #include "chart_common.h"
@@ -72,7 +78,16 @@ struct DeformArgs {
     float* db[CD_MAX_LAYERS];
     float* dlevel[CD_MAX_LEVELS];
     float* ddenc;
+    // REG only
+    const float* encw;  // [n,N] or NULL: the weight of the chart encoding
+    int flags;          // G4S_CHART_DEFORM_REG_NORM | _TV
+    const float* dreg;  // [2]: dL/dreg
+    float* coef;        // [n,N]: (dL/dreg[0] / r(p)) / (n N), 0 where r(p) = 0
+    double* rpart;      // [n wgs]: a workgroup's sum of r(p)
+    float* reg_out;     // [2]
 };
+
+constexpr int CD_REG_NORM = G4S_CHART_DEFORM_REG_NORM, CD_REG_TV = G4S_CHART_DEFORM_REG_TV;
 
 __device__ __forceinline__ int cd_in(const DeformArgs& a, int l) { return l == 0 ? a.E : a.S; }
 __device__ __forceinline__ int cd_out(const DeformArgs& a, int l) { return l == a.NL - 1 ? 1 : a.S; }
@@ -109,15 +124,22 @@ __device__ __forceinline__ float cd_ray_scale(const float* __restrict__ c, int y
     return signf(d0) / len;
 }
 
-// The lane's share of its pixel's input: x[t][r] = a0 of channel 16 t + 4 g + r, t < ET.
-template <int ET>
-__device__ __forceinline__ void cd_gather(const DeformArgs& a, int chart, int p, int g, float (&x)[ET][4]) {
+// The lane's share of its pixel's input: x[t][r] = a0 of channel 16 t + 4 g + r, t < ET.  REG: the chart encoding is
+// multiplied by the pixel's weight before the depth encoding is added, and ss takes the fma chain of the lane's unweighted
+// enc_e^2 in the order t, r.
+template <int ET, bool REG>
+__device__ __forceinline__ void cd_gather(const DeformArgs& a, int chart, int p, int g, float (&x)[ET][4], float& ss) {
     const int row = p / a.W, col = p % a.W;
     const float ux = cd_lin(row, a.H), uy = cd_lin(col, a.W);  // the reference's transposed indexing: the ROW drives x
     Taps td{};
     if (a.denc) {
         const float y = -1.0f + 2.0f * a.coords[(size_t)chart * a.N + p];
         td = cd_taps(y, a.B);
+    }
+    float wgt = 1.0f;
+    if constexpr (REG) {
+        ss = 0.0f;
+        if (a.encw) wgt = a.encw[(size_t)chart * a.N + p];
     }
 #pragma unroll
     for (int t = 0; t < ET; t++) {
@@ -131,6 +153,10 @@ __device__ __forceinline__ void cd_gather(const DeformArgs& a, int chart, int p,
         for (int r = 0; r < 4; r++) {
             const float* __restrict__ v = base + (size_t)r * h * w;
             float s = ((v[ty.i0 * w + tx.i0] * w00 + v[ty.i0 * w + tx.i1] * w01) + v[ty.i1 * w + tx.i0] * w10) + v[ty.i1 * w + tx.i1] * w11;
+            if constexpr (REG) {
+                ss = fmaf(s, s, ss);
+                if (a.encw) s = s * wgt;
+            }
             if (a.denc) {
                 const float* __restrict__ q = a.denc + ((size_t)chart * a.E + e0 + r) * a.B;
                 s = s + (q[td.i0] * td.w0 + q[td.i1] * td.w1);
@@ -138,6 +164,13 @@ __device__ __forceinline__ void cd_gather(const DeformArgs& a, int chart, int p,
             x[t][r] = s / a.R;
         }
     }
+}
+
+// r(p) = sqrt((s_0 + s_1) + (s_2 + s_3)) of the four lanes' chains, in every lane of the pixel
+__device__ __forceinline__ float cd_norm(float ss) {
+    ss = ss + __shfl_xor(ss, 16, 64);
+    ss = ss + __shfl_xor(ss, 32, 64);
+    return sqrtf(ss);
 }
 
 // ---- the network -----------------------------------------------------------------------------------------------------------
@@ -220,9 +253,11 @@ __device__ __forceinline__ void cd_hidden(const DeformArgs& a, const Image& im, 
 }
 
 // grid n * wgs; block 256
-template <int ET, int ST>
+template <int ET, int ST, bool REG>
 __global__ void __launch_bounds__(256) chart_deform_fwd_kernel(DeformArgs a) {
     __shared__ float s_p[CD_MAX_PARAMS];
+    __shared__ double s_r[REG ? CD_TILE : 1];
+    double racc = 0.0;  // REG: the sum of r(p) over this lane's pixels, in tile order
     const int chart = (int)blockIdx.x / a.wgs, first = ((int)blockIdx.x % a.wgs) * CD_WG_PIXELS;
     const int last = first + CD_WG_PIXELS < a.N ? first + CD_WG_PIXELS : a.N;
     const Image& im = a.im;
@@ -233,8 +268,14 @@ __global__ void __launch_bounds__(256) chart_deform_fwd_kernel(DeformArgs a) {
     for (int base = first; base < last; base += CD_TILE) {
         const int p = base + 16 * wv + pl;
         const int pc = p < last ? p : last - 1;  // a lane past the end repeats the last pixel and stores nothing
-        float x[ET][4], h[CD_MAX_LAYERS - 1][ST][4];
-        cd_gather<ET>(a, chart, pc, g, x);
+        float x[ET][4], h[CD_MAX_LAYERS - 1][ST][4], ss;
+        cd_gather<ET, REG>(a, chart, pc, g, x, ss);
+        if constexpr (REG) {
+            if (a.flags & CD_REG_NORM) {
+                const float r = cd_norm(ss);
+                if (p < last) racc = racc + (double)r;
+            }
+        }
         cd_hidden<ET, ST>(a, im, s_p, pl, g, x, h);
         float out = 0.0f;
 #pragma unroll
@@ -248,10 +289,21 @@ __global__ void __launch_bounds__(256) chart_deform_fwd_kernel(DeformArgs a) {
             if (a.delta) a.delta[at] = delta;
         }
     }
+    if constexpr (REG) {
+        if (a.flags & CD_REG_NORM) {  // the workgroup's sum: the 64 pixel slots of a tile in index order
+            if (g == 0) s_r[16 * wv + pl] = racc;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                double s = s_r[0];
+                for (int j = 1; j < CD_TILE; j++) s = s + s_r[j];
+                a.rpart[blockIdx.x] = s;
+            }
+        }
+    }
 }
 
 // grid n * wgs; block 256.  Leaves dL/dx of its pixels in a.dx and one partial of the weight and bias gradients.
-template <int ET, int ST>
+template <int ET, int ST, bool REG>
 __global__ void __launch_bounds__(256) chart_deform_bwd_kernel(DeformArgs a) {
     __shared__ float s_p[CD_MAX_PARAMS];
     __shared__ float s_act[64 * CD_PITCH], s_dz[64 * CD_PITCH], s_gz[CD_TILE];
@@ -281,8 +333,14 @@ __global__ void __launch_bounds__(256) chart_deform_bwd_kernel(DeformArgs a) {
         const int p = base + 16 * wv + pl;
         const bool valid = p < last;
         const int pc = valid ? p : last - 1;
-        float x[ET][4], h[CD_MAX_LAYERS - 1][ST][4];
-        cd_gather<ET>(a, chart, pc, g, x);
+        float x[ET][4], h[CD_MAX_LAYERS - 1][ST][4], ss;
+        cd_gather<ET, REG>(a, chart, pc, g, x, ss);
+        if constexpr (REG) {
+            if (a.flags & CD_REG_NORM) {  // the norm's cotangent per pixel, for the level kernels
+                const float r = cd_norm(ss);
+                if (g == 0 && valid) a.coef[(size_t)chart * a.N + p] = r > 0.0f ? (a.dreg[0] / r) / (float)((long long)a.n * a.N) : 0.0f;
+            }
+        }
         cd_hidden<ET, ST>(a, im, s_p, pl, g, x, h);
         const size_t at = (size_t)chart * a.N + pc;
         const float d0 = a.d0[at];
@@ -455,6 +513,7 @@ __global__ void __launch_bounds__(256) chart_deform_denc_kernel(DeformArgs a) {
 
 // Element j of a chart's packed gradients: its partials summed in workgroup order, written where the parameter's own
 // gradient tensor has it.  grid (ceil(gcount / 256), n)
+template <bool REG>
 __global__ void __launch_bounds__(256) chart_deform_fold_kernel(DeformArgs a) {
     const int j = (int)blockIdx.x * 256 + (int)threadIdx.x, chart = (int)blockIdx.y;
     if (j >= a.gcount) return;
@@ -462,6 +521,14 @@ __global__ void __launch_bounds__(256) chart_deform_fold_kernel(DeformArgs a) {
     float s = part[0];
     for (int k = 1; k < a.wgs; k++) s = s + part[(size_t)k * a.gcount];
     if (a.denc && j >= a.goff_denc) {
+        if constexpr (REG) {
+            if (a.flags & CD_REG_TV) {  // (sign(q[b] - q[b-1]) - sign(q[b+1] - q[b])) (dL/dreg[1] / (n E (B - 1)))
+                const int k = j - a.goff_denc, b = k % a.B;
+                const float* __restrict__ q = a.denc + (size_t)chart * a.E * a.B + k;
+                const float sl = b > 0 ? signf(q[0] - q[-1]) : 0.0f, sr = b < a.B - 1 ? signf(q[1] - q[0]) : 0.0f;
+                s = s + (sl - sr) * (a.dreg[1] / (float)((long long)a.n * a.E * (a.B - 1)));
+            }
+        }
         a.ddenc[(size_t)chart * a.E * a.B + (j - a.goff_denc)] = s;
         return;
     }
@@ -481,6 +548,9 @@ __global__ void __launch_bounds__(256) chart_deform_fold_kernel(DeformArgs a) {
 // The gradient of level `l`: one thread per texel and four channels gathers from dx over the rectangle of pixels whose taps
 // can reach the texel, rows then columns in index order, the four taps of a pixel in the forward's order.
 // grid (ceil(h w (C / 4) / 256), n)
+// REG: the pixel's term is (w(p) dL/dx_e(p)) + enc_e(p) coef(p), each part only where it is asked for; enc_e(p) is formed
+// from the pixel's four texels by the forward's expression.
+template <bool REG>
 __global__ void __launch_bounds__(256) chart_deform_level_kernel(DeformArgs a, int l) {
     const int h = a.lh[l], w = a.lw[l], c4 = a.C / 4, chart = (int)blockIdx.y;
     const int j = (int)blockIdx.x * 256 + (int)threadIdx.x;
@@ -505,8 +575,26 @@ __global__ void __launch_bounds__(256) chart_deform_level_kernel(DeformArgs a, i
             const Taps py = cd_taps(cd_lin(col, a.W), h);
             if (py.i0 != ty && py.i1 != ty) continue;
             const float4 d = *(const float4*)(a.dx + ((size_t)chart * a.N + (size_t)row * a.W + col) * a.E + l * a.C + 4 * cq);
-            const float dv[4] = {d.x, d.y, d.z, d.w};
+            float dv[4] = {d.x, d.y, d.z, d.w};
             const float wt[4] = {px.w0 * py.w0, px.w1 * py.w0, px.w0 * py.w1, px.w1 * py.w1};
+            if constexpr (REG) {
+                const size_t at = (size_t)chart * a.N + (size_t)row * a.W + col;
+                if (a.encw) {
+                    const float wgt = a.encw[at];
+#pragma unroll
+                    for (int c = 0; c < 4; c++) dv[c] = dv[c] * wgt;
+                }
+                if (a.flags & CD_REG_NORM) {
+                    const float cf = a.coef[at];
+#pragma unroll
+                    for (int c = 0; c < 4; c++) {
+                        const float* __restrict__ v = a.level[l] + ((size_t)chart * a.C + 4 * cq + c) * h * w;
+                        const float enc = ((v[py.i0 * w + px.i0] * wt[0] + v[py.i0 * w + px.i1] * wt[1]) + v[py.i1 * w + px.i0] * wt[2]) +
+                                          v[py.i1 * w + px.i1] * wt[3];
+                        dv[c] = dv[c] + enc * cf;
+                    }
+                }
+            }
             const bool hit[4] = {px.i0 == tx && py.i0 == ty, px.i1 == tx && py.i0 == ty, px.i0 == tx && py.i1 == ty,
                                  px.i1 == tx && py.i1 == ty};
 #pragma unroll
@@ -520,6 +608,56 @@ __global__ void __launch_bounds__(256) chart_deform_level_kernel(DeformArgs a, i
     }
 #pragma unroll
     for (int c = 0; c < 4; c++) a.dlevel[l][(((size_t)chart * a.C + 4 * cq + c) * h + ty) * w + tx] = acc[c];
+}
+
+// The two regularisers' values.  One workgroup: thread t sums, in double and in index order, the entries t, t + 256, ... of
+// the workgroups' partial sums of r(p) and of |q[b + 1] - q[b]| (a float32 difference) over (chart, e, b); thread 0 adds the
+// 256 sums in thread order.  grid 1; block 256
+__global__ void __launch_bounds__(256) chart_deform_reg_kernel(DeformArgs a) {
+    __shared__ double s_n[256], s_t[256];
+    const int tid = (int)threadIdx.x;
+    double sn = 0.0, st = 0.0;
+    if (a.flags & CD_REG_NORM) {
+        for (int k = tid; k < a.n * a.wgs; k += 256) sn = sn + a.rpart[k];
+    }
+    const long long tv_count = (long long)a.n * a.E * (a.B - 1);
+    if (a.flags & CD_REG_TV) {
+        for (long long k = tid; k < tv_count; k += 256) {
+            const float* __restrict__ q = a.denc + (k / (a.B - 1)) * a.B + k % (a.B - 1);
+            st = st + (double)fabsf(q[1] - q[0]);
+        }
+    }
+    s_n[tid] = sn;
+    s_t[tid] = st;
+    __syncthreads();
+    if (tid == 0) {
+        for (int j = 1; j < 256; j++) {
+            sn = sn + s_n[j];
+            st = st + s_t[j];
+        }
+        a.reg_out[0] = (a.flags & CD_REG_NORM) ? (float)(sn / (double)((long long)a.n * a.N)) : 0.0f;
+        a.reg_out[1] = (a.flags & CD_REG_TV) ? (float)(st / (double)tv_count) : 0.0f;
+    }
+}
+
+// conf = 1 + exp(raw); weight = 1 - exp(-((conf - 1) (conf - 1)) / 2).  grid ceil(count / 256); block 256
+__global__ void __launch_bounds__(256) chart_confidence_fwd_kernel(long long count, const float* __restrict__ raw,
+                                                                   float* __restrict__ conf, float* __restrict__ weight) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const float c = 1.0f + expf(raw[i]);
+    conf[i] = c;
+    if (weight) {
+        const float cw = c - 1.0f;
+        weight[i] = 1.0f - expf(-(cw * cw) / 2.0f);
+    }
+}
+
+__global__ void __launch_bounds__(256) chart_confidence_bwd_kernel(long long count, const float* __restrict__ raw,
+                                                                   const float* __restrict__ dconf, float* __restrict__ draw) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    draw[i] = dconf[i] * expf(raw[i]);
 }
 
 }  // namespace g4s
@@ -620,15 +758,15 @@ static int cd_inputs(DeformArgs& a, const g4s_chart_deform_shape* shape, const f
     return G4S_OK;
 }
 
-#define CD_LAUNCH(kernel, a, grid, s)                                                                    \
+#define CD_LAUNCH(kernel, REG, a, grid, s)                                                                  \
     do {                                                                                                 \
         const int et_ = (a).E / 16, st_ = (a).S / 16;                                                    \
-        if (et_ == 1 && st_ == 2) hipLaunchKernelGGL((kernel<1, 2>), grid, dim3(256), 0, s, a);          \
-        else if (et_ == 2 && st_ == 2) hipLaunchKernelGGL((kernel<2, 2>), grid, dim3(256), 0, s, a);     \
-        else if (et_ == 4 && st_ == 2) hipLaunchKernelGGL((kernel<4, 2>), grid, dim3(256), 0, s, a);     \
-        else if (et_ == 1 && st_ == 4) hipLaunchKernelGGL((kernel<1, 4>), grid, dim3(256), 0, s, a);     \
-        else if (et_ == 2 && st_ == 4) hipLaunchKernelGGL((kernel<2, 4>), grid, dim3(256), 0, s, a);     \
-        else hipLaunchKernelGGL((kernel<4, 4>), grid, dim3(256), 0, s, a);                               \
+        if (et_ == 1 && st_ == 2) hipLaunchKernelGGL((kernel<1, 2, REG>), grid, dim3(256), 0, s, a);          \
+        else if (et_ == 2 && st_ == 2) hipLaunchKernelGGL((kernel<2, 2, REG>), grid, dim3(256), 0, s, a);     \
+        else if (et_ == 4 && st_ == 2) hipLaunchKernelGGL((kernel<4, 2, REG>), grid, dim3(256), 0, s, a);     \
+        else if (et_ == 1 && st_ == 4) hipLaunchKernelGGL((kernel<1, 4, REG>), grid, dim3(256), 0, s, a);     \
+        else if (et_ == 2 && st_ == 4) hipLaunchKernelGGL((kernel<2, 4, REG>), grid, dim3(256), 0, s, a);     \
+        else hipLaunchKernelGGL((kernel<4, 4, REG>), grid, dim3(256), 0, s, a);                               \
     } while (0)
 
 extern "C" int g4s_chart_deform_forward(const g4s_chart_deform_shape* shape, const float* const* levels,
@@ -643,7 +781,7 @@ extern "C" int g4s_chart_deform_forward(const g4s_chart_deform_shape* shape, con
     (void)workspace; (void)workspace_bytes;  // the forward needs none
     a.depths = depths; a.delta = delta;
     const dim3 grid((unsigned)(a.n * a.wgs));
-    CD_LAUNCH(chart_deform_fwd_kernel, a, grid, s);
+    CD_LAUNCH(chart_deform_fwd_kernel, false, a, grid, s);
     return stage_done("chart_deform_forward", s);
 }
 
@@ -673,12 +811,131 @@ extern "C" int g4s_chart_deform_backward(const g4s_chart_deform_shape* shape, co
     a.partials = (float*)(w + cd_dx_bytes(a));
     a.g = dL_ddepths; a.ddenc = dL_ddepth_encoding;
     const dim3 grid((unsigned)(a.n * a.wgs));
-    CD_LAUNCH(chart_deform_bwd_kernel, a, grid, s);
+    CD_LAUNCH(chart_deform_bwd_kernel, false, a, grid, s);
     if (a.denc) hipLaunchKernelGGL(chart_deform_denc_kernel, grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL(chart_deform_fold_kernel, dim3((unsigned)((a.gcount + 255) / 256), (unsigned)a.n), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(chart_deform_fold_kernel<false>, dim3((unsigned)((a.gcount + 255) / 256), (unsigned)a.n), dim3(256), 0, s, a);
     for (int l = 0; l < a.L; l++) {
         const int threads = a.lh[l] * a.lw[l] * (a.C / 4);
-        hipLaunchKernelGGL(chart_deform_level_kernel, dim3((unsigned)((threads + 255) / 256), (unsigned)a.n), dim3(256), 0, s, a, l);
+        hipLaunchKernelGGL(chart_deform_level_kernel<false>, dim3((unsigned)((threads + 255) / 256), (unsigned)a.n), dim3(256), 0, s, a, l);
     }
     return stage_done("chart_deform_backward", s);
+}
+
+// ---- the weighted deformation with the encoding regularisers, and the confidence -------------------------------------
+static size_t cd_coef_bytes(const DeformArgs& a) { return align_up((size_t)a.n * a.N * 4); }
+static size_t cd_rpart_bytes(const DeformArgs& a) { return align_up((size_t)a.n * a.wgs * 8); }
+
+static int cd_reg_flags(const DeformArgs& a, int reg_flags) {
+    if (reg_flags & ~(CD_REG_NORM | CD_REG_TV))
+        return fail(G4S_ERR_INVALID_ARGUMENT, "chart deform: reg_flags has bits 0 (norm) and 1 (total variation) only, got %d", reg_flags);
+    if ((reg_flags & CD_REG_TV) && a.B < 2)
+        return fail(G4S_ERR_INVALID_ARGUMENT, "chart deform: the total variation needs at least 2 depth bins, got %d", a.B);
+    return G4S_OK;
+}
+
+extern "C" size_t g4s_chart_deform_reg_workspace(const g4s_chart_deform_shape* shape, int reg_flags) {
+    DeformArgs a;
+    if (cd_shape(a, shape) || cd_reg_flags(a, reg_flags)) return 0;
+    return cd_rpart_bytes(a) + cd_dx_bytes(a) + cd_partial_bytes(a) + cd_coef_bytes(a) + 256;
+}
+
+extern "C" size_t g4s_chart_deform_reg_forward_workspace(const g4s_chart_deform_shape* shape, int reg_flags) {
+    DeformArgs a;
+    if (cd_shape(a, shape) || cd_reg_flags(a, reg_flags)) return 0;
+    return cd_rpart_bytes(a) + 256;
+}
+
+// rpart, then the plain pair's dx and partials, then coef; the forward has rpart only (forward_only)
+static int cd_reg_workspace(DeformArgs& a, const g4s_chart_deform_shape* shape, int reg_flags, char* workspace, size_t workspace_bytes,
+                            bool forward_only) {
+    const size_t need = forward_only ? g4s_chart_deform_reg_forward_workspace(shape, reg_flags)
+                                     : g4s_chart_deform_reg_workspace(shape, reg_flags);
+    if (!workspace || workspace_bytes < need) return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
+    char* w = align_ptr(workspace);
+    a.rpart = (double*)w;
+    if (forward_only) return G4S_OK;
+    a.dx = (float*)(w + cd_rpart_bytes(a));
+    a.partials = (float*)(w + cd_rpart_bytes(a) + cd_dx_bytes(a));
+    a.coef = (float*)(w + cd_rpart_bytes(a) + cd_dx_bytes(a) + cd_partial_bytes(a));
+    return G4S_OK;
+}
+
+extern "C" int g4s_chart_deform_reg_forward(const g4s_chart_deform_shape* shape, const float* const* levels,
+                                            const float* depth_encoding, const float* const* weights, const float* const* biases,
+                                            const float* depth_coords, const float* cameras, const float* initial_depths,
+                                            const float* encoding_weights, int reg_flags, float* depths, float* delta,
+                                            float* reg_out, char* workspace, size_t workspace_bytes, void* stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    clear_error();
+    DeformArgs a;
+    if (int rc = cd_inputs(a, shape, levels, depth_encoding, weights, biases, depth_coords, cameras, initial_depths)) return rc;
+    if (int rc = cd_reg_flags(a, reg_flags)) return rc;
+    if (!depths || (reg_flags && !reg_out)) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (reg_flags & CD_REG_NORM) {  // the partial sums of r(p): the head of the workspace
+        if (int rc = cd_reg_workspace(a, shape, reg_flags, workspace, workspace_bytes, true)) return rc;
+    }
+    a.depths = depths; a.delta = delta; a.encw = encoding_weights; a.flags = reg_flags; a.reg_out = reg_out;
+    const dim3 grid((unsigned)(a.n * a.wgs));
+    CD_LAUNCH(chart_deform_fwd_kernel, true, a, grid, s);
+    if (reg_out) hipLaunchKernelGGL(chart_deform_reg_kernel, dim3(1), dim3(256), 0, s, a);
+    return stage_done("chart_deform_reg_forward", s);
+}
+
+extern "C" int g4s_chart_deform_reg_backward(const g4s_chart_deform_shape* shape, const float* const* levels,
+                                             const float* depth_encoding, const float* const* weights, const float* const* biases,
+                                             const float* depth_coords, const float* cameras, const float* initial_depths,
+                                             const float* encoding_weights, int reg_flags, const float* dL_ddepths,
+                                             const float* dL_dreg, float* const* dL_dlevels, float* dL_ddepth_encoding,
+                                             float* const* dL_dweights, float* const* dL_dbiases, char* workspace,
+                                             size_t workspace_bytes, void* stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    clear_error();
+    DeformArgs a;
+    if (int rc = cd_inputs(a, shape, levels, depth_encoding, weights, biases, depth_coords, cameras, initial_depths)) return rc;
+    if (int rc = cd_reg_flags(a, reg_flags)) return rc;
+    if (!dL_ddepths || !dL_dlevels || !dL_dweights || !dL_dbiases || (a.B > 0 && !dL_ddepth_encoding) || (reg_flags && !dL_dreg))
+        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    for (int l = 0; l < a.L; l++) {
+        if (!dL_dlevels[l]) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+        a.dlevel[l] = dL_dlevels[l];
+    }
+    for (int l = 0; l < a.NL; l++) {
+        if (!dL_dweights[l] || !dL_dbiases[l]) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+        a.dw[l] = dL_dweights[l]; a.db[l] = dL_dbiases[l];
+    }
+    if (int rc = cd_reg_workspace(a, shape, reg_flags, workspace, workspace_bytes, false)) return rc;
+    a.g = dL_ddepths; a.ddenc = dL_ddepth_encoding; a.encw = encoding_weights; a.flags = reg_flags; a.dreg = dL_dreg;
+    const dim3 grid((unsigned)(a.n * a.wgs));
+    CD_LAUNCH(chart_deform_bwd_kernel, true, a, grid, s);
+    if (a.denc) hipLaunchKernelGGL(chart_deform_denc_kernel, grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(chart_deform_fold_kernel<true>, dim3((unsigned)((a.gcount + 255) / 256), (unsigned)a.n), dim3(256), 0, s, a);
+    for (int l = 0; l < a.L; l++) {
+        const int threads = a.lh[l] * a.lw[l] * (a.C / 4);
+        hipLaunchKernelGGL(chart_deform_level_kernel<true>, dim3((unsigned)((threads + 255) / 256), (unsigned)a.n), dim3(256), 0, s, a, l);
+    }
+    return stage_done("chart_deform_reg_backward", s);
+}
+
+extern "C" int g4s_chart_confidence_forward(long long count, const float* raw, float* confidence, float* encoding_weights,
+                                            void* stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    clear_error();
+    if (count <= 0 || count > 2147483647ll)
+        return fail(G4S_ERR_INVALID_ARGUMENT, "chart confidence: the element count must be 1 to 2^31 - 1, got %lld", count);
+    if (!raw || !confidence) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    hipLaunchKernelGGL(chart_confidence_fwd_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, count, raw, confidence,
+                       encoding_weights);
+    return stage_done("chart_confidence_forward", s);
+}
+
+extern "C" int g4s_chart_confidence_backward(long long count, const float* raw, const float* dL_dconfidence, float* dL_draw,
+                                             void* stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    clear_error();
+    if (count <= 0 || count > 2147483647ll)
+        return fail(G4S_ERR_INVALID_ARGUMENT, "chart confidence: the element count must be 1 to 2^31 - 1, got %lld", count);
+    if (!raw || !dL_dconfidence || !dL_draw) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    hipLaunchKernelGGL(chart_confidence_bwd_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, count, raw, dL_dconfidence,
+                       dL_draw);
+    return stage_done("chart_confidence_backward", s);
 }

@@ -366,6 +366,74 @@ int g4s_chart_deform_backward(const g4s_chart_deform_shape* shape, const float* 
                               float* const* dL_dlevels, float* dL_ddepth_encoding, float* const* dL_dweights,
                               float* const* dL_dbiases, char* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * Chart alignment: confidence, weighted encodings, encoding regularisers -- what the reference's `strong` alignment
+ * configuration adds to the deformation above (weight_encodings_with_confidence, regularize_chart_encodings_norms,
+ * use_total_variation_on_depth_encodings; matcha/dm_scene/parallel_aligner.py:341-363, 806-822), and the activation of the
+ * learnable confidence.  Everything of "Chart deformation" holds unless stated otherwise; every operation is one float32
+ * operation in the order written, unless it says double.
+ *
+ * Confidence (g4s_chart_confidence_*), element-wise over count = n H W elements, one launch each:
+ *   forward:   conf = 1 + expf(raw);   optionally (encoding_weights != NULL)  cw = conf - 1,  w = 1 - expf(-(cw cw) / 2)
+ *              -- cw is taken from the ROUNDED 1 + exp, as the reference takes it (lines 350-351): raw <= -17 gives conf = 1,
+ *              cw = 0 and w = 0 exactly; raw >= 3 gives w = 1 exactly.
+ *   backward:  dL/draw = dL/dconf expf(raw).  The reference detaches w: it has no gradient.
+ *   Refused: count outside 1 .. 2^31 - 1, a NULL raw, confidence, dL_dconfidence or dL_draw.
+ *
+ * Deformation with weights and regularisers (g4s_chart_deform_reg_*): the arguments of the plain pair, and
+ *   encoding_weights  device float [n][N] or NULL;  reg_flags: G4S_CHART_DEFORM_REG_NORM | G4S_CHART_DEFORM_REG_TV
+ *   reg_out   (forward)  device float [2]: the norm term, the total variation; 0 for a term not asked for.  Required when
+ *             reg_flags != 0; with reg_flags = 0 it may be NULL (then the forward is 1 launch) or is written with zeros.
+ *   dL_dreg   (backward) device float [2], read on the device only; required when reg_flags != 0.
+ * Weighted input.  With w = encoding_weights[i][p]:  x_e = (enc_e w) + (q[b0] w0 + q[b1] w1); only the chart encoding is
+ *   weighted, the depth encoding is added afterwards (lines 355-363).  Without weights x_e is the plain pair's.
+ * Norm term: the mean over all n N pixels of r(p) = sqrtf((s_0 + s_1) + (s_2 + s_3)), where s_g is the fma chain, from 0, of
+ *   fma(enc_e, enc_e, s_g) over the channels e = 16 t + 4 g + s (t, then s) -- the channels lane group g holds, as in the last
+ *   layer.  enc_e is the UNWEIGHTED chart encoding without the depth encoding (line 812).  Sum over the pixels in double:
+ *   pixel slot j < 64 of a workgroup adds r of its pixels j, j + 64, ... in that order; the workgroup adds its 64 slots in
+ *   index order; thread t < 256 of the final workgroup adds the workgroups' sums t, t + 256, ... of all charts (chart-major)
+ *   and thread 0 adds the 256 results in thread order.  reg_out[0] = float(sum / double(n N)).
+ *   Cotangent into enc_e:  enc_e coef(p),  coef(p) = (dL_dreg[0] / r(p)) / float(n N), and coef(p) = 0 exactly where
+ *   r(p) = 0 (torch's subgradient).
+ * Total variation: the mean over n E (B - 1) of fabsf(q[b + 1] - q[b]) (a float32 difference, then double): thread t < 256
+ *   adds the entries t, t + 256, ... of the index ((i E + e) (B - 1) + b), thread 0 adds the 256 results in thread order.
+ *   reg_out[1] = float(sum / double(n E (B - 1))).  Backward: dL/dq[b] of the depth path, then
+ *   + (sign(q[b] - q[b-1]) - sign(q[b+1] - q[b])) (dL_dreg[1] / float(n E (B - 1))), sign(0) = 0, a missing neighbour 0.
+ *   Refused: the TV bit with B < 2 (the reference's mean over an empty tensor is NaN).
+ * Backward.  The depth encoding's gradient takes the unweighted dL/dx.  A level's texel gathers, over the same pixels in the
+ *   same order as in the plain backward, the term  t_e(p)  times the tap weight, where t_e(p) = dL/dx_e(p), multiplied by w(p) if
+ *   there are weights, then + enc_e(p) coef(p) if the norm is asked for; enc_e(p) is formed from the pixel's four texels by
+ *   the forward's expression.  Every element of every gradient is written.  No atomics; bit-identical from run to run.
+ * Bit-identity: with encoding_weights = NULL and reg_flags = 0, depths, delta and every gradient are bit-identical to the
+ *   plain pair's (the same kernels instantiated with the additions compiled in and switched off).  A weight of exactly 1
+ *   changes nothing either.
+ * Workspace (g4s_chart_deform_reg_workspace; 0 for a refused shape or flags): one double per workgroup for the norm's partial
+ *   sums, then the plain pair's -- dL/dx [n][N][E], UNCHANGED and unweighted, and the partials -- then coef [n][N] floats,
+ *   written by the backward's first kernel and read by the level kernels.  No second [n][N][E] array.  The backward always
+ *   needs all of it.  The forward touches the workspace only with the norm bit, and then only the partial sums at its head:
+ *   it asks for g4s_chart_deform_reg_forward_workspace bytes (0 for a refused shape or flags), a few KB, and nothing the
+ *   forward leaves there is read by the backward.
+ * Launches: forward 1 (+1 when reg_out is given); backward as the plain one.  No allocation, no host synchronisation, nothing
+ *   read back: capturable in a HIP graph.
+ */
+#define G4S_CHART_DEFORM_REG_NORM 1
+#define G4S_CHART_DEFORM_REG_TV 2
+int g4s_chart_confidence_forward(long long count, const float* raw, float* confidence, float* encoding_weights, void* stream);
+int g4s_chart_confidence_backward(long long count, const float* raw, const float* dL_dconfidence, float* dL_draw, void* stream);
+size_t g4s_chart_deform_reg_workspace(const g4s_chart_deform_shape* shape, int reg_flags);
+size_t g4s_chart_deform_reg_forward_workspace(const g4s_chart_deform_shape* shape, int reg_flags);
+int g4s_chart_deform_reg_forward(const g4s_chart_deform_shape* shape, const float* const* levels, const float* depth_encoding,
+                                 const float* const* weights, const float* const* biases, const float* depth_coords,
+                                 const float* cameras, const float* initial_depths, const float* encoding_weights, int reg_flags,
+                                 float* depths, float* delta, float* reg_out, char* workspace, size_t workspace_bytes,
+                                 void* stream);
+int g4s_chart_deform_reg_backward(const g4s_chart_deform_shape* shape, const float* const* levels, const float* depth_encoding,
+                                  const float* const* weights, const float* const* biases, const float* depth_coords,
+                                  const float* cameras, const float* initial_depths, const float* encoding_weights,
+                                  int reg_flags, const float* dL_ddepths, const float* dL_dreg, float* const* dL_dlevels,
+                                  float* dL_ddepth_encoding, float* const* dL_dweights, float* const* dL_dbiases,
+                                  char* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
