@@ -122,6 +122,18 @@ SIGNATURES = {
                                            c_p, c_p, c_p, c_sz, c_p]),
     "g4s_chart_deform_reg_backward": (c_i, [ctypes.POINTER(G4sChartDeformShape), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p,
                                             c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_chart_points_workspace": (c_sz, [c_i, c_i, c_i, c_i]),
+    "g4s_chart_points_index_workspace": (c_sz, [c_i, c_i, c_i, c_i]),
+    "g4s_chart_points_project": (c_i, [c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "g4s_chart_points_sample": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "g4s_chart_points_fit": (c_i, [c_i, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_chart_points_apply": (c_i, [c_i, c_i, c_i, c_p, c_p, c_f, c_p, c_p]),
+    "g4s_chart_points_view_depths": (c_i, [c_i, c_p, ctypes.c_longlong, ctypes.c_longlong, c_p, c_p, c_f, c_p, c_p]),
+    "g4s_chart_points_index": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_chart_points_loss_forward": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_sz, c_p]),
+    "g4s_chart_points_loss_backward": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_sz,
+                                             c_p]),
+    "g4s_chart_points_sample_backward": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     # include/g4s_render_maps.h
     "g4s_render_maps_workspace": (c_sz, []),
     "g4s_render_maps_forward": (c_i, [c_i, c_i, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz,

@@ -23,6 +23,7 @@ from .chart_align import AlignmentLosses
 from .chart_deform import (ChartDeformation, ChartsEncodingParams, DepthEncodingParams, MLPParams,  # noqa: F401 (re-exported)
                            MultiResChartsEncodingParams)
 from .chart_match import MATCHING_THR_FACTOR, ChartMatcher, _camera_list, _stack, spatial_extent
+from .chart_points import ChartPoints, point_reference_loss
 from .optim import FusedAdam
 
 # the `alignment:` blocks of the reference's configs/charts_alignment/default.yaml and strong.yaml, as values
@@ -265,6 +266,9 @@ class ChartAligner(torch.nn.Module):
         conf, depths, reg = self._forward(o.weights.get("norm") is not None, o.weights.get("tv") is not None)
         terms = self.losses.terms(depths, o.reference, conf, o.masks, o.gradient_masks, o.weights.get("gradient") is not None,
                                   o.weights.get("normal") is not None, o.weights.get("curvature") is not None)
+        if o.points is not None:
+            # the all-zero masks make the fused depth term exactly 0 (value and gradient); the points' term takes its place
+            terms = torch.cat([point_reference_loss(depths, o.points, conf, self.confidence_weighting).reshape(1), terms[1:]])
         matching = hessian = None
         if o.weights.get("matching") is not None:
             if o.confidence_in_matching:
@@ -324,7 +328,7 @@ class ChartAligner(torch.nn.Module):
         self.matcher.update_references(reference_depths=depths)
         self.matcher.match(matching_thr)
 
-    def optimize(self, reference_data, masks=None, gradient_masks=None, n_iterations=600, use_gradient_loss=True,
+    def optimize(self, reference_data=None, masks=None, gradient_masks=None, n_iterations=600, use_gradient_loss=True,
                  use_hessian_loss=False, use_normal_loss=True, use_curvature_loss=False, use_matching_loss=False,
                  use_reprojection_loss=False, matching_thr=None, use_confidence_in_matching_loss=False, matching_update_iters=None,
                  gradient_loss_weight=10., hessian_loss_weight=100., normal_loss_weight=2., curvature_loss_weight=1.,
@@ -332,16 +336,35 @@ class ChartAligner(torch.nn.Module):
                  lr_update_iters=(300,), lr_update_factor=0.1, verbose=False, match_to_img=None, match_to_pix=None,
                  reprojection_loss_power=0.5, regularize_chart_encodings_norms=False, chart_encodings_norm_loss_weight=0.5,
                  use_total_variation_on_depth_encodings=False, total_variation_on_depth_encodings_weight=1.0, graph=None,
-                 prepare=True):
-        """ParallelAligner.optimize with its keywords and defaults.  graph: capture the iteration in a HIP graph and replay it
+                 prepare=True, reference_points=None):
+        """ParallelAligner.optimize with its keywords and defaults.  reference_points: the reference's other form of
+        reference_data, 3D points per chart -- a list of [N_c,3] tensors or a chart_points.ChartPoints --, given INSTEAD of
+        reference_data: the depth term becomes chart_points.point_reference_loss.  graph: capture the iteration in a HIP graph and replay it
         (None: yes on a HIP device); prepare=False keeps the current parameters and optimiser (the reference always resets).
         train_losses gets the total loss and loss_terms a dict of the named terms every max(1, n_iterations // 50) iterations
         (one read-back each); the reference divides by zero below 50 iterations."""
         shape = (self.n, self.height, self.width)
         if use_reprojection_loss:
             raise NotImplementedError("chart aligner: use_reprojection_loss is not supported (the reference's own script refuses it)")
-        if _is_points(reference_data, shape):
-            raise NotImplementedError("chart aligner: 3D points as reference_data are not supported (depth maps [n,H,W] only)")
+        if reference_points is not None:
+            if reference_data is not None:
+                raise ValueError("chart aligner: give reference_data or reference_points, not both")
+            if use_matching_loss:
+                raise NotImplementedError("Matching loss is not implemented when using points as reference.")
+            if masks is not None:
+                raise ValueError("chart aligner: masks are not supported with reference_points (the reference's masks * diff "
+                                 "cannot broadcast against points)")
+            if not isinstance(reference_points, ChartPoints):
+                reference_points = ChartPoints(self.cameras, reference_points, self.height, self.width)
+            if (reference_points.n, reference_points.height, reference_points.width) != shape:
+                raise ValueError(f"reference_points must belong to charts of shape {shape}")
+            if reference_points.n_points == 0:
+                raise ValueError("chart aligner: reference_points holds no point")
+        elif reference_data is None:
+            raise ValueError("chart aligner: reference_data (depth maps) or reference_points (3D points per chart) is needed")
+        elif _is_points(reference_data, shape):
+            raise NotImplementedError("chart aligner: 3D points as reference_data are not supported (depth maps [n,H,W] only); "
+                                      "pass them as reference_points=")
         if use_confidence_in_matching_loss and not self.use_learnable_confidence:
             raise ValueError("chart aligner: use_confidence_in_matching_loss needs use_learnable_confidence")
         if use_hessian_loss and gradient_masks is not None:
@@ -352,10 +375,15 @@ class ChartAligner(torch.nn.Module):
         graph = True if graph is None else bool(graph)
         n_iterations = int(n_iterations)
         lr_update_iters = list(lr_update_iters)
-        _dev, reference = _stack(reference_data, "reference_data", self.device)
-        if tuple(reference.shape) != shape:
-            raise ValueError(f"reference_data must have the charts' shape {shape} (got {tuple(reference.shape)})")
-        reference = reference.detach().float().contiguous()
+        if reference_points is not None:
+            reference_points.build_index()  # before any capture: the index is built once, not per replay
+            reference = torch.zeros(shape, dtype=torch.float32, device=self.device)
+            masks = torch.zeros(shape, dtype=torch.float32, device=self.device)
+        else:
+            _dev, reference = _stack(reference_data, "reference_data", self.device)
+            if tuple(reference.shape) != shape:
+                raise ValueError(f"reference_data must have the charts' shape {shape} (got {tuple(reference.shape)})")
+            reference = reference.detach().float().contiguous()
         if self.losses is None:
             self.losses = AlignmentLosses(self.cameras, self._depths, self.confidence_weighting)
         self.losses.confidence_weighting = float(self.confidence_weighting)
@@ -371,6 +399,7 @@ class ChartAligner(torch.nn.Module):
 
         o = SimpleNamespace()
         o.reference = reference
+        o.points = reference_points
         o.masks = None if masks is None else self.losses._map(masks, "masks")
         o.gradient_masks = None if gradient_masks is None or not use_gradient_loss else \
             self.losses._map(gradient_masks, "gradient_masks", (self.n, self.height - 1, self.width - 1))
@@ -459,18 +488,24 @@ def hessian_term(depths, prior):
     return total / (4 * depths.shape[0] * H * W)
 
 
-def align_charts(cameras, initial_depths, reference_depths, masks=None, scale_factor=1.0, charts_data_path=None,
-                 return_training_losses=False, graph=None, **align_config):
+def align_charts(cameras, initial_depths, reference_depths=None, masks=None, scale_factor=1.0, charts_data_path=None,
+                 return_training_losses=False, graph=None, reference_points=None, **align_config):
     """align_charts_in_parallel from the point where it has its cameras and initial depths: builds a ChartAligner from the
     configuration's architecture keywords, runs optimize with the rest (matching_thr_factor becomes matching_thr) and returns
     (verts, depths, confs[, train_losses]) -- (verts, depths[, train_losses]) without a learnable confidence, as the reference
-    does.  charts_data_path: a directory (or file) that gets charts_data.npz.  align_config: e.g. ALIGNMENT_CONFIGS["strong"]."""
+    does.  charts_data_path: a directory (or file) that gets charts_data.npz.  align_config: e.g. ALIGNMENT_CONFIGS["strong"].
+    reference_points (a list of [N_c,3] tensors or a ChartPoints, also accepted in reference_depths' place as
+    chart_points.build_charts returns it) replaces reference_depths; the matching loss is then refused as the reference refuses it."""
+    if isinstance(reference_depths, ChartPoints):
+        if reference_points is not None:
+            raise ValueError("align_charts: two sets of reference points")
+        reference_points, reference_depths = reference_depths, None
     cfg = dict(ALIGNMENT_CONFIGS["default"], **align_config)  # align_charts_in_parallel's own defaults are default.yaml's
     arch = {k: cfg.pop(k) for k in ARCHITECTURE_KEYS if k in cfg}
     factor = cfg.pop("matching_thr_factor", MATCHING_THR_FACTOR)
     aligner = ChartAligner(cameras, initial_depths, **arch)
     cfg.setdefault("matching_thr", float(factor) * aligner._spatial_extent)
-    aligner.optimize(reference_depths, masks=masks, graph=graph, **cfg)
+    aligner.optimize(reference_depths, masks=masks, graph=graph, reference_points=reference_points, **cfg)
     verts, depths, confs = aligner.outputs()
     if charts_data_path is not None:
         aligner.save_charts_data(charts_data_path, scale_factor)

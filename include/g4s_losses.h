@@ -434,6 +434,82 @@ int g4s_chart_deform_reg_backward(const g4s_chart_deform_shape* shape, const flo
                                   float* dL_ddepth_encoding, float* const* dL_dweights, float* const* dL_dbiases,
                                   char* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * Chart points: a packed list of 3D points per chart, projected into their chart and tapped in any [n,H,W] map -- the SfM fit
+ * that makes the aligner's initial depths (matcha/pointmap/depthanythingv2.py:82-117 get_points_depth_in_depthmap, 156-253
+ * fit_depth_to_point_cloud, looped by get_pointmap_from_sfm_data_with_depthanything, 634-697) and the point form of the
+ * aligner's depth term (ParallelAligner.loss, matcha/dm_scene/parallel_aligner.py:423-453).
+ *
+ * n charts of one size H x W.  Every operation below is one float32 operation, in this order, with no fused multiply-add
+ * (the unit is compiled with -ffp-contract=off), left to right as written, except where float64 is named; divisions are IEEE.
+ *   points    device float [N,3], packed: chart c owns points offsets[c] .. offsets[c+1] - 1 (offsets: device int32 [n+1],
+ *             offsets[0] = 0, ascending, offsets[n] = N).  An empty chart is legal.  N <= 2^29 - 1, n H W <= 2^31 - 2, n <= 65535.
+ *   cameras   device float [n][32]: world_view_transform V[4][4], then full_proj_transform F[4][4], row-major, in the
+ *             reference's row-vector convention.  (The matcher's [n,44] record carries projection_matrix, not the product the
+ *             reference projects with here; chart_points.camera_records makes this record from the same cameras.)
+ * Projection of point p of chart c:
+ *   z_p = ((p_0 V[0][2] + p_1 V[1][2]) + p_2 V[2][2]) + V[3][2]
+ *   q_k = ((p_0 F[0][k] + p_1 F[1][k]) + p_2 F[2][k]) + F[3][k]  (k = 0, 1, 3),   gx = q_0 / q_3,  gy = q_1 / q_3
+ *   (the reference reaches gx, gy through pytorch3d's NDC times -min(H,W)/W: the two signs and aspect factors cancel, as its
+ *   own CamerasWrapper.project_points(use_p3d_convention=True) shows)
+ *   ix = ((gx + 1) W - 1) / 2,  iy = ((gy + 1) H - 1) / 2  (grid_sample, align_corners=False)
+ *   clipped = not (q_3 > 0) or gx or gy not finite: then (ix, iy) = (-2, -2), whose taps all lie outside.  pytorch3d divides
+ *   regardless; a difference, on purpose.
+ * Tap of a map m of chart c at (ix, iy) (bilinear, zeros padding):  x0 = floor(ix), y0 = floor(iy), x1 = x0 + 1, y1 = y0 + 1,
+ *   nw = (x1 - ix)(y1 - iy),  ne = (ix - x0)(y1 - iy),  sw = (x1 - ix)(iy - y0),  se = (ix - x0)(iy - y0)
+ *   value = ((nw m(x0,y0) + ne m(x1,y0)) + sw m(x0,y1)) + se m(x1,y1), the term of a tap outside the map being +0;
+ *   fov = value > 0.
+ * Fit per chart (g4s_chart_points_fit), over all its points (a point outside the image contributes d = 0, the reference's
+ *   quirk) or, with use_fov_mask, over the points with d > 0:  t = 1 / z_p, d = the value sampled from the disparity map.
+ *   n, St, Sd, Std, Sdd and alpha, beta are those of "Depth cues" A (include/g4s_render_maps.h): float64 sums in a fixed order
+ *   -- a workgroup owns G4S_CHART_POINTS_SPAN consecutive points of ONE chart, counted from the chart's first point, thread t
+ *   adds points t, t + 256, ... of the span in ascending order, a fixed tree folds the threads, the partials are added by
+ *   index --, no float atomics, coeffs [n,2] = {alpha, beta} and counts [n] (int32) on the device, no host read-back.  A
+ *   degenerate chart (no point, one point, no variance) gives what IEEE gives: NaN or inf.  That is no error.
+ * Apply:  depth = scale (1 / (alpha + beta d)) per pixel of chart c with coeffs[c].
+ * View depths:  z of scale P:  (((scale p_0) V[0][2] + (scale p_1) V[1][2]) + (scale p_2) V[2][2]) + V[3][2], for the packed
+ *   list (chart [N]) or for n runs of per_chart points (point maps [n,H,W,3], chart = NULL).
+ * Point-reference term (g4s_chart_points_loss_*):  s_p, k_p = the values of depths, confidence at point p (k_p = 1 without a
+ *   confidence),  e_p = |s_p - z_p|,  term_p = e_p, or k_p e_p - cw log k_p (float32, the device's logf).
+ *   L = (sum of term_p) / N in float64, rounded once: spans of G4S_CHART_POINTS_SPAN consecutive points of the PACKED LIST,
+ *   threads and tree as above, one workgroup adds the span sums by index.  N = 0 is refused.
+ *   Gradient, with c = cotangent / float(N):  dL/ds_p = (c k_p) sign(s_p - z_p)  (c sign(.) without a confidence; sign(0) = 0),
+ *   dL/dk_p = c (e_p - cw / k_p).  Pixel v receives, from each tap (p, corner) that lands on it, dL/ds_p w_corner
+ *   (dL/dk_p w_corner); its gradient is their float32 sum in ascending (p, corner) order, the list cut into chunks of
+ *   G4S_CHART_POINTS_CHUNK taps from its start: each chunk summed from 0, the chunk sums added from 0 in chunk order.  Every
+ *   pixel is written.  No float atomics, no fixed-point range limit: two runs give the same bits.  No fov masking, no masks.
+ * Inverted index (g4s_chart_points_index), built once per point set:  taps int32 [4 N]: the ids 4 p + corner of the taps inside
+ *   a map, ordered by (chart pixel, p, corner); starts uint32 [n H W + 1]: pixel v owns taps[starts[v] .. starts[v+1] - 1].
+ * g4s_chart_points_sample_backward spreads any dL/dvalue [N] to the map the same way.
+ * Nothing allocates, synchronises or reads back: every call can be captured in a HIP graph.  The size queries are pure host
+ * code and return 0 for a refused shape; g4s_chart_points_workspace serves fit and both loss calls.
+ */
+#define G4S_CHART_POINTS_SPAN 4096 /* points per workgroup of the float64 sums */
+#define G4S_CHART_POINTS_CHUNK 64  /* taps per separately summed chunk of a pixel's list */
+size_t g4s_chart_points_workspace(int n, int height, int width, int n_points);
+size_t g4s_chart_points_index_workspace(int n, int height, int width, int n_points);
+int g4s_chart_points_project(int n, int height, int width, const float* cameras, int n_points, const float* points,
+                             const int* offsets, int* chart, float* z, float* ixy, unsigned char* clipped, void* stream);
+int g4s_chart_points_sample(int n, int height, int width, int n_points, const int* chart, const float* ixy, const float* map,
+                            float* values, unsigned char* fov, void* stream);
+int g4s_chart_points_fit(int n, int n_points, const int* offsets, int max_count, const float* z, const float* values,
+                         int use_fov_mask, float* coeffs, int* counts, char* workspace, size_t workspace_bytes, void* stream);
+int g4s_chart_points_apply(int n, int height, int width, const float* disparities, const float* coeffs, float scale,
+                           float* depths, void* stream);
+int g4s_chart_points_view_depths(int n, const float* cameras, long long count, long long per_chart, const int* chart,
+                                 const float* points, float scale, float* depths, void* stream);
+int g4s_chart_points_index(int n, int height, int width, int n_points, const int* chart, const float* ixy, int* taps,
+                           unsigned int* starts, char* workspace, size_t workspace_bytes, void* stream);
+int g4s_chart_points_loss_forward(int n, int height, int width, int n_points, const int* chart, const float* ixy,
+                                  const float* z, const float* depths, const float* confidence, float confidence_weighting,
+                                  float* out1, char* workspace, size_t workspace_bytes, void* stream);
+int g4s_chart_points_loss_backward(int n, int height, int width, int n_points, const int* chart, const float* ixy,
+                                   const float* z, const float* depths, const float* confidence, float confidence_weighting,
+                                   const int* taps, const unsigned int* starts, const float* grad_out1, float* dL_ddepths,
+                                   float* dL_dconfidence, char* workspace, size_t workspace_bytes, void* stream);
+int g4s_chart_points_sample_backward(int n, int height, int width, int n_points, const float* ixy, const int* taps,
+                                     const unsigned int* starts, const float* grad_values, float* dL_dmap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
