@@ -16,8 +16,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._charts import camera_list, depths_and_confidence, f32, grads_like, maps_of_shape, stack
 from ._device import launch
-from .chart_match import _camera_list, _stack
 from .visibility import ray_record
 
 GRADIENT, NORMAL, CURVATURE = 1, 2, 4  # G4S_CHART_ALIGN_*
@@ -46,10 +46,10 @@ def _normals_call(dev, n, H, W, cams, depths, normals, curv):
 def depth2normal_parallel(depths, cameras):
     """The reference's depth2normal_parallel: [n,H,W,3] float32, the normalised cross product of the central point
     differences at the interior pixels, exactly 0 on the border."""
-    dev, d = _stack(depths, "depths")
-    d = d.detach().float().contiguous()
+    dev, d = stack(depths, "depths")
+    d = f32(d)
     n, H, W = d.shape
-    cam_list = _camera_list(cameras)
+    cam_list = camera_list(cameras)
     if len(cam_list) != n:
         raise ValueError(f"{len(cam_list)} views but {n} depths")
     _workspace_bytes(n, H, W)  # the size check
@@ -67,8 +67,8 @@ def normal2curv_parallel(normals, mask=None):
     given (it broadcasts as the reference's final product does; a mask inside the stencil is not supported)."""
     if not isinstance(normals, torch.Tensor) or normals.dim() != 4 or normals.size(-1) != 3:
         raise ValueError(f"normals must be a [n,H,W,3] tensor (got {tuple(getattr(normals, 'shape', ()))})")
-    dev, _ = _stack(normals[..., 0], "normals")
-    nu = normals.detach().float().contiguous()
+    dev, _ = stack(normals[..., 0], "normals")
+    nu = f32(normals)
     n, H, W = nu.shape[:3]
     _workspace_bytes(n, H, W)
     with torch.cuda.device(dev):
@@ -86,8 +86,7 @@ class _Terms(torch.autograd.Function):
     @staticmethod
     def forward(ctx, depths, confidence, losses, reference_depths, masks, gradient_masks, flags):
         a = losses
-        d = depths.detach().float().contiguous()
-        c = None if confidence is None else confidence.detach().float().contiguous()
+        d, c, ctx.meta = depths_and_confidence(depths, confidence)
         args = (a.n, a.height, a.width, _lib.ptr(a._cams), _lib.ptr(d), _lib.ptr(reference_depths), _lib.ptr(c), _lib.ptr(masks),
                 _lib.ptr(a._initial_depths), _lib.ptr(gradient_masks), _lib.ptr(a.initial_normals), _lib.ptr(a._initial_curv),
                 float(a.confidence_weighting), int(flags))
@@ -96,7 +95,6 @@ class _Terms(torch.autograd.Function):
             launch(a.device, "g4s_chart_align_forward", *args, _lib.ptr(out), workspace=a._workspace_bytes)
         ctx.save_for_backward(d, c, reference_depths, masks, gradient_masks)
         ctx.losses, ctx.flags = a, flags
-        ctx.meta = (depths.shape, depths.dtype, None if confidence is None else (confidence.shape, confidence.dtype))
         return out
 
     @staticmethod
@@ -111,11 +109,7 @@ class _Terms(torch.autograd.Function):
                    _lib.ptr(reference_depths), _lib.ptr(c), _lib.ptr(masks), _lib.ptr(a._initial_depths), _lib.ptr(gradient_masks),
                    _lib.ptr(a.initial_normals), _lib.ptr(a._initial_curv), float(a.confidence_weighting), int(ctx.flags),
                    _lib.ptr(g4), _lib.ptr(dd), _lib.ptr(dc), workspace=a._workspace_bytes)
-        dshape, ddtype, cmeta = ctx.meta
-        dd = dd.reshape(dshape).to(ddtype)
-        if dc is not None:
-            dc = dc.reshape(cmeta[0]).to(cmeta[1])
-        return dd, dc, None, None, None, None, None
+        return (*grads_like(dd, dc, ctx.meta), None, None, None, None, None)
 
 
 class AlignmentLosses:
@@ -125,15 +119,15 @@ class AlignmentLosses:
 
     def __init__(self, cameras, initial_depths, confidence_weighting=0.2):
         self.cameras = cameras
-        cam_list = _camera_list(cameras)
-        dev, d0 = _stack(initial_depths, "initial_depths")
+        cam_list = camera_list(cameras)
+        dev, d0 = stack(initial_depths, "initial_depths")
         n, H, W = d0.shape
         if n != len(cam_list):
             raise ValueError(f"{len(cam_list)} views but {n} initial_depths")
         self._workspace_bytes = _workspace_bytes(n, H, W)
         self.device, self.n, self.height, self.width = dev, n, H, W
         self.confidence_weighting = float(confidence_weighting)
-        self._initial_depths = d0.detach().float().contiguous()
+        self._initial_depths = f32(d0)
         with torch.cuda.device(dev):
             self._cams = torch.as_tensor(ray_records(cam_list, W, H), device=dev)
             self.initial_normals = torch.empty((n, H, W, 3), dtype=torch.float32, device=dev)
@@ -147,11 +141,7 @@ class AlignmentLosses:
             return None
         if isinstance(t, torch.Tensor) and t.dtype in (torch.bool, torch.uint8):
             t = t.float()
-        _dev, m = _stack(t, name, self.device)
-        shape = (self.n, self.height, self.width) if shape is None else shape
-        if tuple(m.shape) != tuple(shape):
-            raise ValueError(f"{name} must have the shape {tuple(shape)} (got {tuple(m.shape)})")
-        return m.detach().float().contiguous()
+        return f32(maps_of_shape(t, name, (self.n, self.height, self.width) if shape is None else shape, self.device))
 
     def terms(self, depths, reference_depths, confidence=None, masks=None, gradient_masks=None, use_gradient_loss=False,
               use_normal_loss=True, use_curvature_loss=True):
@@ -161,13 +151,9 @@ class AlignmentLosses:
         [n,H,W] and gradient_masks [n,H-1,W-1] (applied per view) are treated as detached.  Value and gradients are
         bit-identical from run to run."""
         shape = (self.n, self.height, self.width)
-        _dev, d = _stack(depths, "depths", self.device)
-        if tuple(d.shape) != shape:
-            raise ValueError(f"depths must have the initial depths' shape {shape} (got {tuple(d.shape)})")
+        d = maps_of_shape(depths, "depths", shape, self.device, "the initial depths' shape")
         if confidence is not None:
-            _dev, confidence = _stack(confidence, "confidence", self.device)
-            if tuple(confidence.shape) != shape:
-                raise ValueError(f"confidence must have the depths' shape {shape} (got {tuple(confidence.shape)})")
+            confidence = maps_of_shape(confidence, "confidence", shape, self.device, "the depths' shape")
         flags = (GRADIENT if use_gradient_loss else 0) | (NORMAL if use_normal_loss else 0) | (CURVATURE if use_curvature_loss else 0)
         if use_gradient_loss and (self.height < 2 or self.width < 2):
             raise ValueError(f"chart align: the gradient term needs H >= 2 and W >= 2 (got {self.height} x {self.width}; the "

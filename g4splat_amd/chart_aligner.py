@@ -22,7 +22,8 @@ from . import _lib
 from .chart_align import AlignmentLosses
 from .chart_deform import (ChartDeformation, ChartsEncodingParams, DepthEncodingParams, MLPParams,  # noqa: F401 (re-exported)
                            MultiResChartsEncodingParams)
-from .chart_match import MATCHING_THR_FACTOR, ChartMatcher, _camera_list, _stack, spatial_extent
+from ._charts import camera_list, f32, maps_of_shape, spatial_extent
+from .chart_match import MATCHING_THR_FACTOR, ChartMatcher
 from .chart_points import ChartPoints, point_reference_loss
 from .optim import FusedAdam
 
@@ -158,7 +159,7 @@ class ChartAligner(torch.nn.Module):
             self._confidence = torch.nn.Parameter(torch.zeros((self.n, self.height, self.width), device=self.device))
         self.confidence_weighting = 0.2
         self._depths = deform._d0
-        self._spatial_extent = spatial_extent(_camera_list(cameras)) if spatial_extent_override is None else float(spatial_extent_override)
+        self._spatial_extent = spatial_extent(camera_list(cameras)) if spatial_extent_override is None else float(spatial_extent_override)
         self.losses = None  # AlignmentLosses, built on first use (it launches)
         self.matcher = None
         self.optimizer = None
@@ -380,10 +381,7 @@ class ChartAligner(torch.nn.Module):
             reference = torch.zeros(shape, dtype=torch.float32, device=self.device)
             masks = torch.zeros(shape, dtype=torch.float32, device=self.device)
         else:
-            _dev, reference = _stack(reference_data, "reference_data", self.device)
-            if tuple(reference.shape) != shape:
-                raise ValueError(f"reference_data must have the charts' shape {shape} (got {tuple(reference.shape)})")
-            reference = reference.detach().float().contiguous()
+            reference = f32(maps_of_shape(reference_data, "reference_data", shape, self.device, "the charts' shape"))
         if self.losses is None:
             self.losses = AlignmentLosses(self.cameras, self._depths, self.confidence_weighting)
         self.losses.confidence_weighting = float(self.confidence_weighting)

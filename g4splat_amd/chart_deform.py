@@ -17,7 +17,7 @@ import torch
 from . import _lib
 from ._device import launch
 from .chart_align import ray_records
-from .chart_match import _camera_list, _stack, spatial_extent
+from ._charts import camera_list, f32, maps_of_shape, spatial_extent, stack
 
 TILE_PIXELS, WORKGROUP_PIXELS, MAX_LEVELS = 64, 4096, 8  # G4S_CHART_DEFORM_TILE, _WG_PIXELS, _MAX_LEVELS
 ENCODING_WIDTHS, LAYER_SIZES, MIN_LAYERS, MAX_LAYERS, MAX_BINS = (16, 32, 64), (32, 64), 2, 4, 4096
@@ -206,13 +206,13 @@ class ChartDeformation(torch.nn.Module):
             if flag:
                 raise NotImplementedError(f"chart deform: {what} is not supported")
         self.cameras = cameras
-        cam_list = _camera_list(cameras)
+        cam_list = camera_list(cameras)
         if isinstance(depths, torch.Tensor) and depths.device.type != "cuda":  # parameters on the host: no forward there
             dev, d0 = depths.device, (depths[:, 0] if depths.dim() == 4 and depths.size(1) == 1 else depths)
             if d0.dim() != 3:
                 raise ValueError(f"depths: a stacked tensor must be [n,H,W] (got {tuple(depths.shape)})")
         else:
-            dev, d0 = _stack(depths, "depths")
+            dev, d0 = stack(depths, "depths")
         n, H, W = d0.shape
         if n != len(cam_list):
             raise ValueError(f"{len(cam_list)} views but {n} depths")
@@ -378,10 +378,7 @@ class ChartDeformation(torch.nn.Module):
                              "over an empty tensor is NaN)")
         self._check_device()
         if encoding_weights is not None:
-            _dev, w = _stack(encoding_weights, "encoding_weights", self.device)
-            if tuple(w.shape) != (self.n, self.height, self.width):
-                raise ValueError(f"encoding_weights must have the shape {(self.n, self.height, self.width)} (got {tuple(w.shape)})")
-            encoding_weights = w.detach().float().contiguous()
+            encoding_weights = f32(maps_of_shape(encoding_weights, "encoding_weights", (self.n, self.height, self.width), self.device))
         return _DeformReg.apply(self, flags, encoding_weights, *self._params())
 
     @torch.no_grad()

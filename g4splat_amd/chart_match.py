@@ -15,26 +15,12 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._device import check_dtype, drop_leading_one, hip_device, launch, same_device, to_np
+from ._charts import camera_list, f32, maps_of_shape, spatial_extent, stack  # noqa: F401 (spatial_extent: public here)
+from ._device import hip_device, launch, same_device, to_np
 from .visibility import ray_record
 
 MATCHING_THR_FACTOR = 1.0 / 20.0  # the reference's matching_thr_factor
 MAX_TERMS = 1 << 26               # the range limit of the backward: n H W max(1, weight_max)
-
-
-def _camera_list(cameras):
-    cams = list(getattr(cameras, "gs_cameras", cameras))
-    if len(cams) == 0:
-        raise ValueError("chart matcher: no views (n = 0)")
-    return cams
-
-
-def spatial_extent(cameras):
-    """CamerasWrapper.get_spatial_extent: 1.1 x the largest distance of a camera centre from the mean centre (a float,
-    computed in double on the host from world_view_transform)."""
-    cams = _camera_list(cameras)
-    c = np.stack([np.linalg.inv(np.asarray(to_np(cam.world_view_transform), np.float64).reshape(4, 4).T)[:3, 3] for cam in cams])
-    return 1.1 * float(np.linalg.norm(c - c.mean(axis=0, keepdims=True), axis=1).max())
 
 
 def camera_records(cameras, width, height):
@@ -48,38 +34,11 @@ def camera_records(cameras, width, height):
     return np.stack(rows).astype(np.float32)
 
 
-def _stack(depths, name, dev=None):
-    """[n,H,W] float32 contiguous on one HIP device from a stacked tensor or a list of maps of ONE size."""
-    if isinstance(depths, torch.Tensor):
-        if depths.dim() == 4 and depths.size(1) == 1:
-            depths = depths[:, 0]
-        if depths.dim() != 3:
-            raise ValueError(f"{name}: a stacked tensor must be [n,H,W] (got {tuple(depths.shape)})")
-        maps = None
-    else:
-        maps = [drop_leading_one(d) for d in depths]
-        if len(maps) == 0:
-            raise ValueError("chart matcher: no views (n = 0)")
-        for v, d in enumerate(maps):
-            dev = same_device(d, dev, f"{name}[{v}]")
-            if d.dim() != 2:
-                raise ValueError(f"{name}[{v}] must be [H,W] or [1,H,W] (got {tuple(d.shape)})")
-            if d.shape != maps[0].shape:
-                raise ValueError(f"{name}: the views must all have one size (view 0 is {tuple(maps[0].shape)}, view {v} is "
-                                 f"{tuple(d.shape)})")
-        depths = torch.stack(maps)
-    dev = same_device(depths, dev, name)
-    check_dtype(depths, (torch.float32, torch.float64, torch.float16, torch.bfloat16), name)
-    if depths.size(0) == 0:
-        raise ValueError("chart matcher: no views (n = 0)")
-    return dev, depths
-
-
 class _MatchLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, depths, matcher, weights, weight_max):
         m = matcher
-        d = depths.detach().float().contiguous()
+        d = f32(depths)
         with torch.cuda.device(m.device):
             out = torch.empty(1, dtype=torch.float32, device=m.device)
             launch(m.device, "g4s_chart_match_loss_forward", m.n, m.height, m.width, _lib.ptr(m._cams), _lib.ptr(d),
@@ -107,7 +66,7 @@ class ChartMatcher:
 
     def __init__(self, cameras, reference_depths=None, reference_pts=None):
         self.cameras = cameras
-        self._cam_list = _camera_list(cameras)
+        self._cam_list = camera_list(cameras)
         self.znear = 1e-6
         self.words = None
         self.matching_thr = None
@@ -125,7 +84,7 @@ class ChartMatcher:
             if pts.size(0) != wvt.size(0):
                 raise ValueError(f"{wvt.size(0)} views but {pts.size(0)} reference_pts")
             reference_depths = (torch.cat([pts, torch.ones_like(pts[..., :1])], dim=-1).flatten(1, 2) @ wvt)[..., 2].reshape(pts.shape[:3])
-        dev, depths = _stack(reference_depths, "reference_depths")
+        dev, depths = stack(reference_depths, "reference_depths")
         n, H, W = depths.shape
         if n != len(self._cam_list):
             raise ValueError(f"{len(self._cam_list)} views but {n} reference_depths")
@@ -135,7 +94,7 @@ class ChartMatcher:
         self.device, self.n, self.height, self.width = dev, n, H, W
         self.n_charts = n
         self._workspace_bytes = nws
-        self.reference_depths = depths.detach().float().contiguous()
+        self.reference_depths = f32(depths)
         self._cams = torch.as_tensor(camera_records(self._cam_list, W, H), device=dev)
         self.words, self._matches, self._errors = None, None, None
 
@@ -184,10 +143,7 @@ class ChartMatcher:
         return self._errors
 
     def _current(self, depths):
-        dev, d = _stack(depths, "depths", self.device)
-        if tuple(d.shape) != (self.n, self.height, self.width):
-            raise ValueError(f"depths must have the references' shape {(self.n, self.height, self.width)} (got {tuple(d.shape)})")
-        return d
+        return maps_of_shape(depths, "depths", (self.n, self.height, self.width), self.device, "the references' shape")
 
     @torch.no_grad()
     def compute_reprojection_errors(self, depths=None, points=None):
@@ -197,7 +153,7 @@ class ChartMatcher:
             raise NotImplementedError("chart matcher: compute_reprojection_errors takes depths, not points")
         if depths is None:
             raise ValueError("Either depths or points should be provided.")
-        d = self._current(depths).detach().float().contiguous()
+        d = f32(self._current(depths))
         shape = (self.n, self.n, self.height, self.width)
         errors = torch.empty(shape, dtype=torch.float32, device=self.device)
         fov = torch.empty(shape, dtype=torch.uint8, device=self.device)
@@ -215,10 +171,7 @@ class ChartMatcher:
         self._need_match()
         d = self._current(depths)
         if weights is not None:
-            _dev, w = _stack(weights, "weights", self.device)
-            if tuple(w.shape) != tuple(d.shape):
-                raise ValueError(f"weights must have the depths' shape {tuple(d.shape)} (got {tuple(w.shape)})")
-            weights = w.detach().float().contiguous()
+            weights = f32(maps_of_shape(weights, "weights", d.shape, self.device, "the depths' shape"))
             if weight_max is None:
                 weight_max = float(weights.abs().max())
         else:

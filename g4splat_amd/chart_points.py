@@ -18,7 +18,7 @@ import torch
 
 from . import _lib
 from ._device import check_dtype, launch, same_device, to_np
-from .chart_match import _camera_list, _stack, spatial_extent
+from ._charts import camera_list, depths_and_confidence, f32, grads_like, maps_of_shape, spatial_extent, stack
 
 SPAN = 4096  # G4S_CHART_POINTS_SPAN: points per workgroup of the float64 sums
 CHUNK = 64   # G4S_CHART_POINTS_CHUNK: taps per separately summed chunk of a pixel's list
@@ -55,7 +55,7 @@ def _point_lists(points, n):
 class _Sample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, maps, cp):
-        m = maps.detach().float().contiguous()
+        m = f32(maps)
         with torch.cuda.device(cp.device):
             values = torch.empty(cp.n_points, dtype=torch.float32, device=cp.device)
             fov = torch.empty(cp.n_points, dtype=torch.uint8, device=cp.device)
@@ -71,7 +71,7 @@ class _Sample(torch.autograd.Function):
         cp = ctx.cp
         cp.build_index()
         with torch.cuda.device(cp.device):
-            g = g.detach().float().contiguous()
+            g = f32(g)
             out = torch.empty((cp.n, cp.height, cp.width), dtype=torch.float32, device=cp.device)
             _lib.call("g4s_chart_points_sample_backward", cp.n, cp.height, cp.width, cp.n_points, _lib.ptr(cp.ixy),
                       _lib.ptr(cp._taps), _lib.ptr(cp._starts), _lib.ptr(g), _lib.ptr(out), _lib.stream(cp.device))
@@ -86,7 +86,7 @@ class ChartPoints:
 
     def __init__(self, cameras, points, height, width):
         self.cameras = cameras
-        cams = _camera_list(cameras)
+        cams = camera_list(cameras)
         lists = _point_lists(points, len(cams))
         height, width = int(height), int(width)
         if height <= 0 or width <= 0:
@@ -130,10 +130,7 @@ class ChartPoints:
         self._taps, self._starts = taps, starts
 
     def _maps(self, maps, name):
-        _dev, m = _stack(maps, name, self.device)
-        if tuple(m.shape) != (self.n, self.height, self.width):
-            raise ValueError(f"{name} must have the shape {(self.n, self.height, self.width)} (got {tuple(m.shape)})")
-        return m
+        return maps_of_shape(maps, name, (self.n, self.height, self.width), self.device)
 
     def sample(self, maps):
         """(values float32 [N], fov bool [N]) of maps [n,H,W] under the points: bilinear, zeros padding, fov = value > 0.
@@ -163,13 +160,13 @@ def fit_disparities(disparities, chart_points, use_fov_mask=False, return_counts
 @torch.no_grad()
 def aligned_depths(disparities, coeffs, scale=1.0):
     """scale * (1 / (alpha + beta disparity)) [n,H,W] with coeffs [n,2] on the device."""
-    dev, d = _stack(disparities, "disparities")
-    d = d.detach().float().contiguous()
+    dev, d = stack(disparities, "disparities")
+    d = f32(d)
     n, H, W = d.shape
     if not isinstance(coeffs, torch.Tensor) or tuple(coeffs.shape) != (n, 2):
         raise ValueError(f"coeffs must be a [{n},2] tensor (got {tuple(getattr(coeffs, 'shape', ()))})")
     same_device(coeffs, dev, "coeffs")
-    c = coeffs.detach().float().contiguous()
+    c = f32(coeffs)
     with torch.cuda.device(dev):
         out = torch.empty_like(d)
         _lib.call("g4s_chart_points_apply", n, H, W, _lib.ptr(d), _lib.ptr(c), float(scale), _lib.ptr(out), _lib.stream(dev))
@@ -179,7 +176,7 @@ def aligned_depths(disparities, coeffs, scale=1.0):
 @torch.no_grad()
 def view_depths_of_point_maps(cameras, point_maps, scale=1.0):
     """z of scale * P in each point map's own view: [n,H,W] from point maps [n,H,W,3] (a tensor or a list of [H,W,3])."""
-    cams = _camera_list(cameras)
+    cams = camera_list(cameras)
     if not isinstance(point_maps, torch.Tensor):
         point_maps = torch.stack(list(point_maps))
     if point_maps.dim() != 4 or point_maps.size(-1) != 3:
@@ -187,7 +184,7 @@ def view_depths_of_point_maps(cameras, point_maps, scale=1.0):
     if point_maps.size(0) != len(cams):
         raise ValueError(f"{len(cams)} views but {point_maps.size(0)} point maps")
     dev = same_device(point_maps, None, "point_maps")
-    p = point_maps.detach().float().contiguous()
+    p = f32(point_maps)
     n, H, W = p.shape[:3]
     with torch.cuda.device(dev):
         rec = torch.as_tensor(camera_records(cams), device=dev)
@@ -200,8 +197,7 @@ def view_depths_of_point_maps(cameras, point_maps, scale=1.0):
 class _PointLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, depths, confidence, cp, cw):
-        d = depths.detach().float().contiguous()
-        c = None if confidence is None else confidence.detach().float().contiguous()
+        d, c, ctx.meta = depths_and_confidence(depths, confidence)
         with torch.cuda.device(cp.device):
             out = torch.empty(1, dtype=torch.float32, device=cp.device)
             launch(cp.device, "g4s_chart_points_loss_forward", cp.n, cp.height, cp.width, cp.n_points, _lib.ptr(cp.chart),
@@ -209,7 +205,6 @@ class _PointLoss(torch.autograd.Function):
                    workspace=cp._workspace_bytes)
         ctx.save_for_backward(d, c)
         ctx.cp, ctx.cw = cp, cw
-        ctx.meta = (depths.shape, depths.dtype, None if confidence is None else (confidence.shape, confidence.dtype))
         return out[0]
 
     @staticmethod
@@ -224,11 +219,7 @@ class _PointLoss(torch.autograd.Function):
             launch(cp.device, "g4s_chart_points_loss_backward", cp.n, cp.height, cp.width, cp.n_points, _lib.ptr(cp.chart),
                    _lib.ptr(cp.ixy), _lib.ptr(cp.view_depths), _lib.ptr(d), _lib.ptr(c), float(ctx.cw), _lib.ptr(cp._taps),
                    _lib.ptr(cp._starts), _lib.ptr(g1), _lib.ptr(dd), _lib.ptr(dc), workspace=cp._workspace_bytes)
-        dshape, ddtype, cmeta = ctx.meta
-        dd = dd.reshape(dshape).to(ddtype)
-        if dc is not None:
-            dc = dc.reshape(cmeta[0]).to(cmeta[1])
-        return dd, dc, None, None
+        return (*grads_like(dd, dc, ctx.meta), None, None)
 
 
 def point_reference_loss(depths, chart_points, confidence=None, confidence_weighting=0.2, masks=None):
@@ -267,7 +258,7 @@ def fit_depth_to_point_cloud(disp, pts, cameras, camera_idx, return_alpha_beta=F
         raise NotImplementedError("Rasterizer implementation is not really satisfactory yet.")
     if image is not None and pt_colors is not None:
         raise NotImplementedError("Color weighting implementation is not satisfactory yet.")
-    cams = _camera_list(cameras)
+    cams = camera_list(cameras)
     if not 0 <= int(camera_idx) < len(cams):
         raise ValueError(f"camera_idx {camera_idx} is not in range({len(cams)})")
     if not isinstance(disp, torch.Tensor) or disp.dim() != 2:
@@ -286,7 +277,7 @@ def rescale_cameras(cameras, factor):
     double, full_proj_transform is the product with the camera's projection_matrix (taken from full_proj_transform where the
     camera has none); the other attributes a chart unit reads are copied."""
     out = []
-    for cam in _camera_list(cameras):
+    for cam in camera_list(cameras):
         wvt = np.asarray(to_np(cam.world_view_transform), np.float64).reshape(4, 4)
         if hasattr(cam, "projection_matrix"):
             proj = np.asarray(to_np(cam.projection_matrix), np.float64).reshape(4, 4)
@@ -308,8 +299,8 @@ def build_charts(cameras, disparities, sfm_points, point_maps=None, target_scale
     returns (rescaled cameras, initial_depths [n,H,W], reference, scale_factor).  `reference` is reference_depths [n,H,W] when
     point maps [n,H,W,3] are given (the view depths of the scaled maps) and otherwise the ChartPoints of the scaled SfM points:
     chart_aligner.align_charts takes either as its third argument."""
-    cams = _camera_list(cameras)
-    dev, disp = _stack(disparities, "disparities")
+    cams = camera_list(cameras)
+    dev, disp = stack(disparities, "disparities")
     n, H, W = disp.shape
     if n != len(cams):
         raise ValueError(f"{len(cams)} views but {n} disparities")

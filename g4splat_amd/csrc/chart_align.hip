@@ -146,17 +146,6 @@ __global__ void __launch_bounds__(256) chart_align_curv_kernel(AlignArgs a, cons
                                                        FROM_DEPTH ? nullptr : normals + 3 * (size_t)t.v * a.N, a.H, a.W, t.y, t.x, lap);
 }
 
-// Sum over a 256-thread block in double, in a fixed order (a butterfly over the wave, then the four waves); valid in
-// thread 0.  Every lane of the block has to call it.  The terms are float32, their sums are not: a mean over n N terms is
-// then as good as its terms.
-__device__ __forceinline__ double ca_block_sum(double v, double* s4) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (s4[0] + s4[1]) + (s4[2] + s4[3]);
-}
-
 // |gm t| of the row (DY = 1) or column (DY = 0) difference based at (y, x); sg: its derivative gm sign(gm t)
 template <int DY>
 __device__ __forceinline__ float ca_grad_term(const AlignArgs& a, const float* __restrict__ Dv, const float* __restrict__ D0v,
@@ -200,9 +189,10 @@ __global__ void __launch_bounds__(256) chart_align_fwd_kernel(AlignArgs a, const
             s[3] = fabsf(a.curv0[at] - ca_lap<false>(nullptr, nullptr, Nv, a.H, a.W, t.y, t.x, lap));
         }
     }
+    // The terms are float32, their sums are not: a mean over n N terms is then as good as its terms.
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        const double b = ca_block_sum((double)s[k], s_red[k]);
+        const double b = chart_block_sum_pairs((double)s[k], s_red[k]);
         if (threadIdx.x == 0) a.partials[4 * (size_t)blockIdx.x + k] = b;
     }
 }
@@ -210,21 +200,7 @@ __global__ void __launch_bounds__(256) chart_align_fwd_kernel(AlignArgs a, const
 // one block of 1024 threads folds the block partials; fixed association => bit-reproducible
 __global__ void __launch_bounds__(1024) chart_align_reduce_kernel(AlignArgs a) {
     __shared__ double s_v[4][1024];
-    double v[4] = {0, 0, 0, 0};
-    for (int i = (int)threadIdx.x; i < a.nblocks; i += 1024) {
-#pragma unroll
-        for (int k = 0; k < 4; k++) v[k] += a.partials[4 * (size_t)i + k];
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) s_v[k][threadIdx.x] = v[k];
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-#pragma unroll
-            for (int k = 0; k < 4; k++) s_v[k][threadIdx.x] += s_v[k][threadIdx.x + o];
-        }
-        __syncthreads();
-    }
+    chart_fold_partials<4>(a.partials, a.nblocks, s_v);
     if (threadIdx.x < 4) {
         const int k = (int)threadIdx.x;
         const bool on = k == 0 || (a.flags & (1 << (k - 1)));
@@ -361,12 +337,23 @@ using namespace g4s;
 static inline bool ca_size_ok(int n, int height, int width) {
     return n > 0 && height > 0 && width > 0 && (long long)n * height * width * 3 <= 2147483647ll;
 }
-static inline size_t ca_blocks(int n, int height, int width) { return (size_t)n * (((size_t)height * width + 255) / 256); }
-static inline size_t ca_map3_bytes(int n, int height, int width) { return align_up((size_t)n * height * width * 3 * 4); }
+
+struct AlignLayout { size_t partials, nrm, A, B, bytes; };
+static AlignLayout ca_layout(int n, int height, int width) {
+    WorkspaceCursor c;
+    AlignLayout L;
+    const size_t map3 = (size_t)n * height * width * 3 * 4;
+    L.partials = c.take((size_t)n * chart_view_blocks(height, width) * 4 * 8);
+    L.nrm = c.take(map3);
+    L.A = c.take(map3);
+    L.B = c.take(map3);
+    L.bytes = c.off;
+    return L;
+}
 
 extern "C" size_t g4s_chart_align_workspace(int n, int height, int width) {
     if (!ca_size_ok(n, height, width)) return 0;
-    return align_up(ca_blocks(n, height, width) * 4 * 8) + 3 * ca_map3_bytes(n, height, width) + 256;
+    return ca_layout(n, height, width).bytes + WORKSPACE_BASE_SLACK;
 }
 
 static int ca_check(int n, int height, int width) {
@@ -381,16 +368,14 @@ static int ca_check(int n, int height, int width) {
 static AlignArgs ca_args(int n, int height, int width, char* workspace) {
     AlignArgs a{};
     a.n = n; a.H = height; a.W = width; a.N = height * width;
-    a.bpv = (a.N + 255) / 256;
-    a.nblocks = (int)ca_blocks(n, height, width);
+    a.bpv = (int)chart_view_blocks(height, width);
+    a.nblocks = n * a.bpv;
     if (workspace) {
-        char* w = align_ptr(workspace);
-        const size_t m = ca_map3_bytes(n, height, width);
-        a.partials = (double*)w;
-        w += align_up((size_t)a.nblocks * 4 * 8);
-        a.nrm = (float*)w;
-        a.A = (float*)(w + m);
-        a.B = (float*)(w + 2 * m);
+        const AlignLayout L = ca_layout(n, height, width);
+        a.partials = workspace_at<double>(workspace, L.partials);
+        a.nrm = workspace_at<float>(workspace, L.nrm);
+        a.A = workspace_at<float>(workspace, L.A);
+        a.B = workspace_at<float>(workspace, L.B);
     }
     return a;
 }
@@ -426,15 +411,14 @@ static int ca_loss_args(AlignArgs& a, int n, int height, int width, const float*
     if ((flags & G4S_CHART_ALIGN_GRADIENT) && (height < 2 || width < 2))
         return fail(G4S_ERR_INVALID_ARGUMENT, "chart align: the gradient term needs H >= 2 and W >= 2 (no difference to average), got %d x %d",
                     height, width);
-    if (!cameras || !depths || !reference_depths) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (!cameras || !depths || !reference_depths) return null_pointer();
     if ((flags & G4S_CHART_ALIGN_GRADIENT) && !initial_depths)
         return fail(G4S_ERR_INVALID_ARGUMENT, "chart align: the gradient term needs initial_depths");
     if ((flags & G4S_CHART_ALIGN_NORMAL) && !initial_normals)
         return fail(G4S_ERR_INVALID_ARGUMENT, "chart align: the normal term needs initial_normals");
     if ((flags & G4S_CHART_ALIGN_CURVATURE) && !initial_curvatures)
         return fail(G4S_ERR_INVALID_ARGUMENT, "chart align: the curvature term needs initial_curvatures");
-    if (!workspace || workspace_bytes < g4s_chart_align_workspace(n, height, width))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
+    if (int rc = check_workspace(workspace, workspace_bytes, g4s_chart_align_workspace(n, height, width))) return rc;
     a = ca_args(n, height, width, workspace);
     a.flags = flags; a.lambda = confidence_weighting;
     a.ref = reference_depths; a.conf = confidence; a.mask = masks; a.depths0 = initial_depths; a.gmask = gradient_masks;
@@ -455,7 +439,7 @@ extern "C" int g4s_chart_align_forward(int n, int height, int width, const float
                               gradient_masks, initial_normals, initial_curvatures, confidence_weighting, flags, workspace,
                               workspace_bytes))
         return rc;
-    if (!out4) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (!out4) return null_pointer();
     a.out4 = out4;
     const dim3 grid((unsigned)a.nblocks), block(256);
     if (flags & (G4S_CHART_ALIGN_NORMAL | G4S_CHART_ALIGN_CURVATURE))
@@ -478,7 +462,7 @@ extern "C" int g4s_chart_align_backward(int n, int height, int width, const floa
                               gradient_masks, initial_normals, initial_curvatures, confidence_weighting, flags, workspace,
                               workspace_bytes))
         return rc;
-    if (!grad_out4 || !dL_ddepths || (confidence && !dL_dconfidence)) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (!grad_out4 || !dL_ddepths || (confidence && !dL_dconfidence)) return null_pointer();
     a.g4 = grad_out4; a.d_depths = dL_ddepths; a.d_conf = dL_dconfidence;
     const dim3 grid((unsigned)a.nblocks), block(256);
     if (flags & (G4S_CHART_ALIGN_NORMAL | G4S_CHART_ALIGN_CURVATURE)) {

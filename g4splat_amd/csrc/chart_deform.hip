@@ -682,7 +682,7 @@ static void cd_pack(DeformArgs& a) {
 }
 
 static int cd_shape(DeformArgs& a, const g4s_chart_deform_shape* sh) {
-    if (!sh) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (!sh) return null_pointer();
     if (sh->n <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "chart deform: n must be positive (no charts)");
     if (sh->width <= 0 || sh->height <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "chart deform: width, height must be positive");
     if ((long long)sh->n * sh->height * sh->width > 2147483647ll)
@@ -728,13 +728,25 @@ static int cd_shape(DeformArgs& a, const g4s_chart_deform_shape* sh) {
     return G4S_OK;
 }
 
-static size_t cd_dx_bytes(const DeformArgs& a) { return align_up((size_t)a.n * a.N * a.E * 4); }
-static size_t cd_partial_bytes(const DeformArgs& a) { return align_up((size_t)a.n * a.wgs * a.gcount * 4); }
+// The backward's workspace: dx and the partials; the regulariser pair (REG) has rpart before them -- alone the workspace of
+// its forward, `forward_bytes` -- and coef behind.
+struct DeformLayout { size_t rpart, dx, partials, coef, forward_bytes, bytes; };
+static DeformLayout cd_layout(const DeformArgs& a, bool reg) {
+    WorkspaceCursor c;
+    DeformLayout L{};
+    if (reg) L.rpart = c.take((size_t)a.n * a.wgs * 8);
+    L.forward_bytes = c.off;
+    L.dx = c.take((size_t)a.n * a.N * a.E * 4);
+    L.partials = c.take((size_t)a.n * a.wgs * a.gcount * 4);
+    if (reg) L.coef = c.take((size_t)a.n * a.N * 4);
+    L.bytes = c.off;
+    return L;
+}
 
 extern "C" size_t g4s_chart_deform_workspace(const g4s_chart_deform_shape* shape) {
     DeformArgs a;
     if (cd_shape(a, shape)) return 0;
-    return cd_dx_bytes(a) + cd_partial_bytes(a) + 256;
+    return cd_layout(a, false).bytes + WORKSPACE_BASE_SLACK;
 }
 
 // what forward and backward check alike
@@ -742,15 +754,15 @@ static int cd_inputs(DeformArgs& a, const g4s_chart_deform_shape* shape, const f
                      const float* const* weights, const float* const* biases, const float* depth_coords, const float* cameras,
                      const float* initial_depths) {
     if (int rc = cd_shape(a, shape)) return rc;
-    if (!levels || !weights || !biases || !cameras || !initial_depths) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (!levels || !weights || !biases || !cameras || !initial_depths) return null_pointer();
     if (a.B > 0 && (!depth_encoding || !depth_coords))
         return fail(G4S_ERR_INVALID_ARGUMENT, "chart deform: bins > 0 needs depth_encoding and depth_coords");
     for (int l = 0; l < a.L; l++) {
-        if (!levels[l]) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+        if (!levels[l]) return null_pointer();
         a.level[l] = levels[l];
     }
     for (int l = 0; l < a.NL; l++) {
-        if (!weights[l] || !biases[l]) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+        if (!weights[l] || !biases[l]) return null_pointer();
         a.w[l] = weights[l]; a.b[l] = biases[l];
     }
     a.denc = a.B > 0 ? depth_encoding : nullptr;
@@ -769,6 +781,45 @@ static int cd_inputs(DeformArgs& a, const g4s_chart_deform_shape* shape, const f
         else hipLaunchKernelGGL((kernel<4, 4, REG>), grid, dim3(256), 0, s, a);                               \
     } while (0)
 
+// the gradient pointers of a backward, checked and stored
+static int cd_gradients(DeformArgs& a, float* const* dL_dlevels, float* dL_ddepth_encoding, float* const* dL_dweights,
+                        float* const* dL_dbiases) {
+    if (!dL_dlevels || !dL_dweights || !dL_dbiases || (a.B > 0 && !dL_ddepth_encoding)) return null_pointer();
+    for (int l = 0; l < a.L; l++) {
+        if (!dL_dlevels[l]) return null_pointer();
+        a.dlevel[l] = dL_dlevels[l];
+    }
+    for (int l = 0; l < a.NL; l++) {
+        if (!dL_dweights[l] || !dL_dbiases[l]) return null_pointer();
+        a.dw[l] = dL_dweights[l]; a.db[l] = dL_dbiases[l];
+    }
+    a.ddenc = dL_ddepth_encoding;
+    return G4S_OK;
+}
+
+// the workspace of `need` bytes, checked, and its ranges; the regulariser's forward has rpart only (need = its own query)
+static int cd_workspace(DeformArgs& a, bool reg, char* workspace, size_t workspace_bytes, size_t need, bool forward_only = false) {
+    if (int rc = check_workspace(workspace, workspace_bytes, need)) return rc;
+    const DeformLayout L = cd_layout(a, reg);
+    if (reg) a.rpart = workspace_at<double>(workspace, L.rpart);
+    if (forward_only) return G4S_OK;
+    a.dx = workspace_at<float>(workspace, L.dx);
+    a.partials = workspace_at<float>(workspace, L.partials);
+    if (reg) a.coef = workspace_at<float>(workspace, L.coef);
+    return G4S_OK;
+}
+
+// the backward: dL/dx and the workgroups' partials, the depth encoding's share, the fold, one gather per level
+template <bool REG>
+static void cd_launch_backward(const DeformArgs& a, hipStream_t s) {
+    const dim3 grid((unsigned)(a.n * a.wgs));
+    CD_LAUNCH(chart_deform_bwd_kernel, REG, a, grid, s);
+    if (a.denc) hipLaunchKernelGGL(chart_deform_denc_kernel, grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(chart_deform_fold_kernel<REG>, dim3(blocks256(a.gcount), (unsigned)a.n), dim3(256), 0, s, a);
+    for (int l = 0; l < a.L; l++)
+        hipLaunchKernelGGL(chart_deform_level_kernel<REG>, dim3(blocks256(a.lh[l] * a.lw[l] * (a.C / 4)), (unsigned)a.n), dim3(256), 0, s, a, l);
+}
+
 extern "C" int g4s_chart_deform_forward(const g4s_chart_deform_shape* shape, const float* const* levels,
                                         const float* depth_encoding, const float* const* weights, const float* const* biases,
                                         const float* depth_coords, const float* cameras, const float* initial_depths,
@@ -777,7 +828,7 @@ extern "C" int g4s_chart_deform_forward(const g4s_chart_deform_shape* shape, con
     clear_error();
     DeformArgs a;
     if (int rc = cd_inputs(a, shape, levels, depth_encoding, weights, biases, depth_coords, cameras, initial_depths)) return rc;
-    if (!depths) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (!depths) return null_pointer();
     (void)workspace; (void)workspace_bytes;  // the forward needs none
     a.depths = depths; a.delta = delta;
     const dim3 grid((unsigned)(a.n * a.wgs));
@@ -795,36 +846,15 @@ extern "C" int g4s_chart_deform_backward(const g4s_chart_deform_shape* shape, co
     clear_error();
     DeformArgs a;
     if (int rc = cd_inputs(a, shape, levels, depth_encoding, weights, biases, depth_coords, cameras, initial_depths)) return rc;
-    if (!dL_ddepths || !dL_dlevels || !dL_dweights || !dL_dbiases || (a.B > 0 && !dL_ddepth_encoding))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    for (int l = 0; l < a.L; l++) {
-        if (!dL_dlevels[l]) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-        a.dlevel[l] = dL_dlevels[l];
-    }
-    for (int l = 0; l < a.NL; l++) {
-        if (!dL_dweights[l] || !dL_dbiases[l]) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-        a.dw[l] = dL_dweights[l]; a.db[l] = dL_dbiases[l];
-    }
-    if (!workspace || workspace_bytes < g4s_chart_deform_workspace(shape)) return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
-    char* w = align_ptr(workspace);
-    a.dx = (float*)w;
-    a.partials = (float*)(w + cd_dx_bytes(a));
-    a.g = dL_ddepths; a.ddenc = dL_ddepth_encoding;
-    const dim3 grid((unsigned)(a.n * a.wgs));
-    CD_LAUNCH(chart_deform_bwd_kernel, false, a, grid, s);
-    if (a.denc) hipLaunchKernelGGL(chart_deform_denc_kernel, grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL(chart_deform_fold_kernel<false>, dim3((unsigned)((a.gcount + 255) / 256), (unsigned)a.n), dim3(256), 0, s, a);
-    for (int l = 0; l < a.L; l++) {
-        const int threads = a.lh[l] * a.lw[l] * (a.C / 4);
-        hipLaunchKernelGGL(chart_deform_level_kernel<false>, dim3((unsigned)((threads + 255) / 256), (unsigned)a.n), dim3(256), 0, s, a, l);
-    }
+    if (!dL_ddepths) return null_pointer();
+    if (int rc = cd_gradients(a, dL_dlevels, dL_ddepth_encoding, dL_dweights, dL_dbiases)) return rc;
+    if (int rc = cd_workspace(a, false, workspace, workspace_bytes, g4s_chart_deform_workspace(shape))) return rc;
+    a.g = dL_ddepths;
+    cd_launch_backward<false>(a, s);
     return stage_done("chart_deform_backward", s);
 }
 
 // ---- the weighted deformation with the encoding regularisers, and the confidence -------------------------------------
-static size_t cd_coef_bytes(const DeformArgs& a) { return align_up((size_t)a.n * a.N * 4); }
-static size_t cd_rpart_bytes(const DeformArgs& a) { return align_up((size_t)a.n * a.wgs * 8); }
-
 static int cd_reg_flags(const DeformArgs& a, int reg_flags) {
     if (reg_flags & ~(CD_REG_NORM | CD_REG_TV))
         return fail(G4S_ERR_INVALID_ARGUMENT, "chart deform: reg_flags has bits 0 (norm) and 1 (total variation) only, got %d", reg_flags);
@@ -836,28 +866,13 @@ static int cd_reg_flags(const DeformArgs& a, int reg_flags) {
 extern "C" size_t g4s_chart_deform_reg_workspace(const g4s_chart_deform_shape* shape, int reg_flags) {
     DeformArgs a;
     if (cd_shape(a, shape) || cd_reg_flags(a, reg_flags)) return 0;
-    return cd_rpart_bytes(a) + cd_dx_bytes(a) + cd_partial_bytes(a) + cd_coef_bytes(a) + 256;
+    return cd_layout(a, true).bytes + WORKSPACE_BASE_SLACK;
 }
 
 extern "C" size_t g4s_chart_deform_reg_forward_workspace(const g4s_chart_deform_shape* shape, int reg_flags) {
     DeformArgs a;
     if (cd_shape(a, shape) || cd_reg_flags(a, reg_flags)) return 0;
-    return cd_rpart_bytes(a) + 256;
-}
-
-// rpart, then the plain pair's dx and partials, then coef; the forward has rpart only (forward_only)
-static int cd_reg_workspace(DeformArgs& a, const g4s_chart_deform_shape* shape, int reg_flags, char* workspace, size_t workspace_bytes,
-                            bool forward_only) {
-    const size_t need = forward_only ? g4s_chart_deform_reg_forward_workspace(shape, reg_flags)
-                                     : g4s_chart_deform_reg_workspace(shape, reg_flags);
-    if (!workspace || workspace_bytes < need) return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
-    char* w = align_ptr(workspace);
-    a.rpart = (double*)w;
-    if (forward_only) return G4S_OK;
-    a.dx = (float*)(w + cd_rpart_bytes(a));
-    a.partials = (float*)(w + cd_rpart_bytes(a) + cd_dx_bytes(a));
-    a.coef = (float*)(w + cd_rpart_bytes(a) + cd_dx_bytes(a) + cd_partial_bytes(a));
-    return G4S_OK;
+    return cd_layout(a, true).forward_bytes + WORKSPACE_BASE_SLACK;
 }
 
 extern "C" int g4s_chart_deform_reg_forward(const g4s_chart_deform_shape* shape, const float* const* levels,
@@ -870,9 +885,10 @@ extern "C" int g4s_chart_deform_reg_forward(const g4s_chart_deform_shape* shape,
     DeformArgs a;
     if (int rc = cd_inputs(a, shape, levels, depth_encoding, weights, biases, depth_coords, cameras, initial_depths)) return rc;
     if (int rc = cd_reg_flags(a, reg_flags)) return rc;
-    if (!depths || (reg_flags && !reg_out)) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (!depths || (reg_flags && !reg_out)) return null_pointer();
     if (reg_flags & CD_REG_NORM) {  // the partial sums of r(p): the head of the workspace
-        if (int rc = cd_reg_workspace(a, shape, reg_flags, workspace, workspace_bytes, true)) return rc;
+        if (int rc = cd_workspace(a, true, workspace, workspace_bytes, g4s_chart_deform_reg_forward_workspace(shape, reg_flags), true))
+            return rc;
     }
     a.depths = depths; a.delta = delta; a.encw = encoding_weights; a.flags = reg_flags; a.reg_out = reg_out;
     const dim3 grid((unsigned)(a.n * a.wgs));
@@ -893,26 +909,11 @@ extern "C" int g4s_chart_deform_reg_backward(const g4s_chart_deform_shape* shape
     DeformArgs a;
     if (int rc = cd_inputs(a, shape, levels, depth_encoding, weights, biases, depth_coords, cameras, initial_depths)) return rc;
     if (int rc = cd_reg_flags(a, reg_flags)) return rc;
-    if (!dL_ddepths || !dL_dlevels || !dL_dweights || !dL_dbiases || (a.B > 0 && !dL_ddepth_encoding) || (reg_flags && !dL_dreg))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    for (int l = 0; l < a.L; l++) {
-        if (!dL_dlevels[l]) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-        a.dlevel[l] = dL_dlevels[l];
-    }
-    for (int l = 0; l < a.NL; l++) {
-        if (!dL_dweights[l] || !dL_dbiases[l]) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-        a.dw[l] = dL_dweights[l]; a.db[l] = dL_dbiases[l];
-    }
-    if (int rc = cd_reg_workspace(a, shape, reg_flags, workspace, workspace_bytes, false)) return rc;
-    a.g = dL_ddepths; a.ddenc = dL_ddepth_encoding; a.encw = encoding_weights; a.flags = reg_flags; a.dreg = dL_dreg;
-    const dim3 grid((unsigned)(a.n * a.wgs));
-    CD_LAUNCH(chart_deform_bwd_kernel, true, a, grid, s);
-    if (a.denc) hipLaunchKernelGGL(chart_deform_denc_kernel, grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL(chart_deform_fold_kernel<true>, dim3((unsigned)((a.gcount + 255) / 256), (unsigned)a.n), dim3(256), 0, s, a);
-    for (int l = 0; l < a.L; l++) {
-        const int threads = a.lh[l] * a.lw[l] * (a.C / 4);
-        hipLaunchKernelGGL(chart_deform_level_kernel<true>, dim3((unsigned)((threads + 255) / 256), (unsigned)a.n), dim3(256), 0, s, a, l);
-    }
+    if (!dL_ddepths || (reg_flags && !dL_dreg)) return null_pointer();
+    if (int rc = cd_gradients(a, dL_dlevels, dL_ddepth_encoding, dL_dweights, dL_dbiases)) return rc;
+    if (int rc = cd_workspace(a, true, workspace, workspace_bytes, g4s_chart_deform_reg_workspace(shape, reg_flags))) return rc;
+    a.g = dL_ddepths; a.encw = encoding_weights; a.flags = reg_flags; a.dreg = dL_dreg;
+    cd_launch_backward<true>(a, s);
     return stage_done("chart_deform_reg_backward", s);
 }
 
@@ -922,8 +923,8 @@ extern "C" int g4s_chart_confidence_forward(long long count, const float* raw, f
     clear_error();
     if (count <= 0 || count > 2147483647ll)
         return fail(G4S_ERR_INVALID_ARGUMENT, "chart confidence: the element count must be 1 to 2^31 - 1, got %lld", count);
-    if (!raw || !confidence) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    hipLaunchKernelGGL(chart_confidence_fwd_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, count, raw, confidence,
+    if (!raw || !confidence) return null_pointer();
+    hipLaunchKernelGGL(chart_confidence_fwd_kernel, dim3(blocks256(count)), dim3(256), 0, s, count, raw, confidence,
                        encoding_weights);
     return stage_done("chart_confidence_forward", s);
 }
@@ -934,8 +935,8 @@ extern "C" int g4s_chart_confidence_backward(long long count, const float* raw, 
     clear_error();
     if (count <= 0 || count > 2147483647ll)
         return fail(G4S_ERR_INVALID_ARGUMENT, "chart confidence: the element count must be 1 to 2^31 - 1, got %lld", count);
-    if (!raw || !dL_dconfidence || !dL_draw) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    hipLaunchKernelGGL(chart_confidence_bwd_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, count, raw, dL_dconfidence,
+    if (!raw || !dL_dconfidence || !dL_draw) return null_pointer();
+    hipLaunchKernelGGL(chart_confidence_bwd_kernel, dim3(blocks256(count)), dim3(256), 0, s, count, raw, dL_dconfidence,
                        dL_draw);
     return stage_done("chart_confidence_backward", s);
 }

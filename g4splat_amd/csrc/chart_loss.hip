@@ -60,14 +60,6 @@ __device__ __forceinline__ float lap4(const float* s, int r, int c) {
     return (((s[(r - 1) * LD + c] - ctr) + (s[r * LD + c - 1] - ctr)) + (s[(r + 1) * LD + c] - ctr)) + (s[r * LD + c + 1] - ctr);
 }
 
-// sum over a 256-thread block in a fixed order; result valid in thread 0 (s4: four floats of this sum's own)
-__device__ __forceinline__ float chart_block_sum(float v, float* s4) {
-    v = wave_sum_to_lane63(v);
-    if ((threadIdx.x & 63) == 63) s4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (s4[0] + s4[1]) + (s4[2] + s4[3]);
-}
-
 __global__ void __launch_bounds__(256) chart_fwd_kernel(ChartArgs a) {
     constexpr int LD = CP_TW + 2, ROWS = CP_TH + 2;
     __shared__ float s_n[3][ROWS * LD];
@@ -110,21 +102,7 @@ __global__ void __launch_bounds__(256) chart_fwd_kernel(ChartArgs a) {
 // one block of 1024 threads folds the block partials in double; fixed association => bit-reproducible
 __global__ void __launch_bounds__(1024) chart_reduce_kernel(ChartArgs a) {
     __shared__ double s_v[5][1024];
-    double v[5] = {0, 0, 0, 0, 0};
-    for (int i = (int)threadIdx.x; i < a.nblocks; i += 1024) {
-#pragma unroll
-        for (int k = 0; k < 5; k++) v[k] += (double)a.partials[5 * (size_t)i + k];
-    }
-#pragma unroll
-    for (int k = 0; k < 5; k++) s_v[k][threadIdx.x] = v[k];
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-#pragma unroll
-            for (int k = 0; k < 5; k++) s_v[k][threadIdx.x] += s_v[k][threadIdx.x + o];
-        }
-        __syncthreads();
-    }
+    chart_fold_partials<5>(a.partials, a.nblocks, s_v);
     if (threadIdx.x < 5) a.out5[threadIdx.x] = (float)(s_v[threadIdx.x][0] / (double)a.N);
 }
 
@@ -228,16 +206,9 @@ __global__ void __launch_bounds__(256) aniso_fwd_kernel(AnisoArgs a) {
 }
 
 __global__ void __launch_bounds__(1024) aniso_reduce_kernel(AnisoArgs a) {
-    __shared__ double s_v[1024];
-    double v = 0;
-    for (int i = (int)threadIdx.x; i < a.nblocks; i += 1024) v += (double)a.partials[i];
-    s_v[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) s_v[threadIdx.x] += s_v[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) a.out1[0] = (float)(s_v[0] / (double)a.P);
+    __shared__ double s_v[1][1024];
+    chart_fold_partials<1>(a.partials, a.nblocks, s_v);
+    if (threadIdx.x == 0) a.out1[0] = (float)(s_v[0][0] / (double)a.P);
 }
 
 __global__ void __launch_bounds__(256) aniso_bwd_kernel(AnisoArgs a) {
@@ -269,9 +240,19 @@ static inline bool chart_size_ok(int width, int height) {
     return width > 0 && height > 0 && (long long)width * height <= CP_MAX_PIXELS;
 }
 
+struct ChartLayout { size_t partials, acc, bytes; };
+static ChartLayout chart_layout(int width, int height) {
+    WorkspaceCursor c;
+    ChartLayout L;
+    L.partials = c.take(chart_blocks(width, height) * 5 * 4);
+    L.acc = c.take((size_t)width * height * 8);
+    L.bytes = c.off;
+    return L;
+}
+
 extern "C" size_t g4s_chart_prior_workspace(int width, int height) {
     if (!chart_size_ok(width, height)) return 0;
-    return align_up(chart_blocks(width, height) * 5 * 4) + align_up((size_t)width * height * 8) + 256;
+    return chart_layout(width, height).bytes + WORKSPACE_BASE_SLACK;
 }
 
 static int chart_check(int width, int height, const char* workspace, size_t workspace_bytes) {
@@ -279,9 +260,7 @@ static int chart_check(int width, int height, const char* workspace, size_t work
     if ((long long)width * height > CP_MAX_PIXELS)
         return fail(G4S_ERR_INVALID_ARGUMENT, "chart prior: at most 2^22 pixels (fixed-point depth-order sums), got %lld",
                     (long long)width * height);
-    if (!workspace || workspace_bytes < g4s_chart_prior_workspace(width, height))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
-    return G4S_OK;
+    return check_workspace(workspace, workspace_bytes, g4s_chart_prior_workspace(width, height));
 }
 
 static ChartArgs chart_args(int width, int height, const float* rn, const float* sn, const float* sd, const float* pd,
@@ -293,9 +272,9 @@ static ChartArgs chart_args(int width, int height, const float* rn, const float*
     a.rn = rn; a.sn = sn; a.sd = sd; a.pd = pd; a.pn = pn; a.pc = pc; a.shifts = shifts;
     a.depth_scale = depth_scale; a.extent = scene_extent; a.log_scale = log_scale;
     a.nblocks = (int)chart_blocks(width, height);
-    char* w = align_ptr(workspace);
-    a.partials = (float*)w;
-    a.acc = (unsigned long long*)(w + align_up((size_t)a.nblocks * 5 * 4));
+    const ChartLayout L = chart_layout(width, height);
+    a.partials = workspace_at<float>(workspace, L.partials);
+    a.acc = workspace_at<unsigned long long>(workspace, L.acc);
     return a;
 }
 
@@ -307,8 +286,7 @@ extern "C" int g4s_chart_prior_forward(int width, int height, const float* rend_
     hipStream_t s = (hipStream_t)stream_;
     clear_error();
     if (int rc = chart_check(width, height, workspace, workspace_bytes)) return rc;
-    if (!rend_normal || !surf_normal || !surf_depth || !prior_depth || !prior_normal || !prior_curv || !out5)
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (!rend_normal || !surf_normal || !surf_depth || !prior_depth || !prior_normal || !prior_curv || !out5) return null_pointer();
     if (misaligned(pixel_shifts, 8)) return fail(G4S_ERR_INVALID_ARGUMENT, "pixel_shifts must be 8-byte aligned");
     ChartArgs a = chart_args(width, height, rend_normal, surf_normal, surf_depth, prior_depth, prior_normal, prior_curv,
                              depth_scale, scene_extent, log_scale, pixel_shifts, workspace);
@@ -332,7 +310,7 @@ extern "C" int g4s_chart_prior_backward(int width, int height, const float* rend
     if (int rc = chart_check(width, height, workspace, workspace_bytes)) return rc;
     if (!rend_normal || !surf_normal || !surf_depth || !prior_depth || !prior_normal || !prior_curv || !grad_out5 ||
         !dL_drend_normal || !dL_dsurf_normal || !dL_dsurf_depth)
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+        return null_pointer();
     if (misaligned(pixel_shifts, 8)) return fail(G4S_ERR_INVALID_ARGUMENT, "pixel_shifts must be 8-byte aligned");
     ChartArgs a = chart_args(width, height, rend_normal, surf_normal, surf_depth, prior_depth, prior_normal, prior_curv,
                              depth_scale, scene_extent, log_scale, pixel_shifts, workspace);
@@ -351,14 +329,23 @@ extern "C" int g4s_chart_prior_backward(int width, int height, const float* rend
     return stage_done("chart_prior_backward", s);
 }
 
+struct AnisoLayout { size_t partials, bytes; };
+static AnisoLayout aniso_layout(int P) {
+    WorkspaceCursor c;
+    AnisoLayout L;
+    L.partials = c.take((size_t)blocks256(P) * 4);
+    L.bytes = c.off;
+    return L;
+}
+
 extern "C" size_t g4s_anisotropy_workspace(int P) {
     if (P <= 0) return 0;
-    return align_up(((size_t)P + 255) / 256 * 4) + 256;
+    return aniso_layout(P).bytes + WORKSPACE_BASE_SLACK;
 }
 
 static int aniso_check(int P, const float* scaling) {
     if (P <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "anisotropy: P must be positive (the mean of no ratios is undefined)");
-    if (!scaling) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (!scaling) return null_pointer();
     if (misaligned(scaling, 8)) return fail(G4S_ERR_INVALID_ARGUMENT, "scaling must be 8-byte aligned");
     return G4S_OK;
 }
@@ -368,12 +355,12 @@ extern "C" int g4s_anisotropy_forward(int P, const float* scaling, float max_rat
     hipStream_t s = (hipStream_t)stream_;
     clear_error();
     if (int rc = aniso_check(P, scaling)) return rc;
-    if (!out1) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    if (!workspace || workspace_bytes < g4s_anisotropy_workspace(P)) return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
+    if (!out1) return null_pointer();
+    if (int rc = check_workspace(workspace, workspace_bytes, g4s_anisotropy_workspace(P))) return rc;
     AnisoArgs a{};
     a.P = P; a.scaling = (const float2*)scaling; a.max_ratio = max_ratio; a.out1 = out1;
-    a.nblocks = (P + 255) / 256;
-    a.partials = (float*)align_ptr(workspace);
+    a.nblocks = (int)blocks256(P);
+    a.partials = workspace_at<float>(workspace, aniso_layout(P).partials);
     {
         ProfScope ps(PF_CHART_PRIOR, s);
         hipLaunchKernelGGL(aniso_fwd_kernel, dim3(a.nblocks), dim3(256), 0, s, a);
@@ -387,11 +374,11 @@ extern "C" int g4s_anisotropy_backward(int P, const float* scaling, float max_ra
     hipStream_t s = (hipStream_t)stream_;
     clear_error();
     if (int rc = aniso_check(P, scaling)) return rc;
-    if (!grad_out1 || !dL_dscaling) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (!grad_out1 || !dL_dscaling) return null_pointer();
     if (misaligned(dL_dscaling, 8)) return fail(G4S_ERR_INVALID_ARGUMENT, "dL_dscaling must be 8-byte aligned");
     AnisoArgs a{};
     a.P = P; a.scaling = (const float2*)scaling; a.max_ratio = max_ratio; a.g1 = grad_out1; a.d_scaling = (float2*)dL_dscaling;
-    a.nblocks = (P + 255) / 256;
+    a.nblocks = (int)blocks256(P);
     {
         ProfScope ps(PF_CHART_PRIOR, s);
         hipLaunchKernelGGL(aniso_bwd_kernel, dim3(a.nblocks), dim3(256), 0, s, a);

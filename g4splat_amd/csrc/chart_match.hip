@@ -16,6 +16,7 @@
 // pass scales into dL/dD.  Nothing of size n n N exists except the match bits.
 #include "g4s_internal.h"
 #include "g4s_device.h"
+#include "chart_common.h"
 #include "../../include/g4s_losses.h"
 
 namespace g4s {
@@ -136,14 +137,6 @@ __device__ __forceinline__ float cm_nan_to_num(float e) {
     return e != e ? 0.0f : (e > 3.4028234663852886e38f ? 3.4028234663852886e38f : e);  // e >= 0 or NaN
 }
 
-// sum over a 256-thread block in a fixed order; valid in thread 0
-__device__ __forceinline__ float cm_block_sum(float v, float* s4) {
-    v = wave_sum_to_lane63(v);
-    if ((threadIdx.x & 63) == 63) s4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (s4[0] + s4[1]) + (s4[2] + s4[3]);
-}
-
 // grid (ceil(N / 256), n): block (b, j) owns pixels 256 b .. 256 b + 255 of source view j
 __global__ void __launch_bounds__(256) chart_match_kernel(MatchArgs a, const float* __restrict__ cams,
         const float* __restrict__ depths) {
@@ -184,22 +177,15 @@ __global__ void __launch_bounds__(256) chart_match_loss_fwd_kernel(MatchArgs a, 
             if (((word >> (p & 31)) & 1u) && r.fov) sum += cm_nan_to_num(r.e) * w;
         }
     }
-    const float b = cm_block_sum(sum, s_red);
+    const float b = chart_block_sum(sum, s_red);
     if (threadIdx.x == 0) a.partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = b;
 }
 
 // one block of 1024 threads folds the block partials in double; fixed association => bit-reproducible
 __global__ void __launch_bounds__(1024) chart_match_reduce_kernel(MatchArgs a) {
-    __shared__ double s_v[1024];
-    double v = 0;
-    for (int i = (int)threadIdx.x; i < a.nblocks; i += 1024) v += (double)a.partials[i];
-    s_v[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) s_v[threadIdx.x] += s_v[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) a.out1[0] = (float)(s_v[0] / ((double)a.n * (double)a.n * (double)a.N));
+    __shared__ double s_v[1][1024];
+    chart_fold_partials<1>(a.partials, a.nblocks, s_v);
+    if (threadIdx.x == 0) a.out1[0] = (float)(s_v[0][0] / ((double)a.n * (double)a.n * (double)a.N));
 }
 
 __global__ void __launch_bounds__(256) chart_match_loss_bwd_kernel(MatchArgs a, const float* __restrict__ cams,
@@ -247,13 +233,20 @@ using namespace g4s;
 static inline bool cm_size_ok(int n, int height, int width) {
     return n > 0 && height > 0 && width > 0 && (long long)n * height * width <= CM_MAX_TERMS;
 }
-static inline size_t cm_blocks(int n, int height, int width) {
-    return (size_t)n * (((size_t)height * width + 255) / 256);
+
+struct MatchLayout { size_t partials, acc, bytes; };
+static MatchLayout cm_layout(int n, int height, int width) {
+    WorkspaceCursor c;
+    MatchLayout L;
+    L.partials = c.take((size_t)n * chart_view_blocks(height, width) * 4);
+    L.acc = c.take((size_t)n * height * width * 8);
+    L.bytes = c.off;
+    return L;
 }
 
 extern "C" size_t g4s_chart_match_workspace(int n, int height, int width) {
     if (!cm_size_ok(n, height, width)) return 0;
-    return align_up(cm_blocks(n, height, width) * 4) + align_up((size_t)n * height * width * 8) + 256;
+    return cm_layout(n, height, width).bytes + WORKSPACE_BASE_SLACK;
 }
 
 static int cm_check(int n, int height, int width, const float* cameras, const float* depths) {
@@ -262,7 +255,7 @@ static int cm_check(int n, int height, int width, const float* cameras, const fl
     if ((long long)n * height * width > CM_MAX_TERMS)
         return fail(G4S_ERR_INVALID_ARGUMENT, "chart match: n H W max(1, weight_max) must be at most 2^26 (fixed-point tap sums), got n H W = %lld",
                     (long long)n * height * width);
-    if (!cameras || !depths) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (!cameras || !depths) return null_pointer();
     return G4S_OK;
 }
 
@@ -283,15 +276,15 @@ static MatchArgs cm_args(int n, int height, int width, char* workspace) {
     a.n = n; a.W = width; a.H = height; a.N = width * height; a.nwords = (a.N + 31) / 32;
     const double m = (double)(width < height ? width : height);
     a.fax = (float)(width / m); a.fay = (float)(height / m); a.fbx = (float)(-m / width); a.fby = (float)(-m / height);
-    a.nblocks = (int)cm_blocks(n, height, width);
+    a.nblocks = n * (int)chart_view_blocks(height, width);
     if (workspace) {
-        char* w = align_ptr(workspace);
-        a.partials = (float*)w;
-        a.acc = (unsigned long long*)(w + align_up((size_t)a.nblocks * 4));
+        const MatchLayout L = cm_layout(n, height, width);
+        a.partials = workspace_at<float>(workspace, L.partials);
+        a.acc = workspace_at<unsigned long long>(workspace, L.acc);
     }
     return a;
 }
-static inline dim3 cm_grid(const MatchArgs& a) { return dim3((unsigned)((a.N + 255) / 256), (unsigned)a.n); }
+static inline dim3 cm_grid(const MatchArgs& a) { return dim3(chart_view_blocks(a.H, a.W), (unsigned)a.n); }
 
 extern "C" int g4s_chart_match(int n, int height, int width, const float* cameras, const float* depths, float thr,
                                unsigned int* words, float* errors, int raw_errors, unsigned char* fov_mask, void* stream_) {
@@ -313,9 +306,8 @@ extern "C" int g4s_chart_match_loss_forward(int n, int height, int width, const 
     if (int rc = cm_check(n, height, width, cameras, depths)) return rc;
     if (n > 65535) return fail(G4S_ERR_INVALID_ARGUMENT, "chart match: at most 65535 views");
     if (int rc = cm_check_weights(n, height, width, weights, weight_max)) return rc;
-    if (!words || !out1) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    if (!workspace || workspace_bytes < g4s_chart_match_workspace(n, height, width))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
+    if (!words || !out1) return null_pointer();
+    if (int rc = check_workspace(workspace, workspace_bytes, g4s_chart_match_workspace(n, height, width))) return rc;
     MatchArgs a = cm_args(n, height, width, workspace);
     a.words_in = words; a.weights = weights; a.weight_max = weight_max; a.out1 = out1;
     hipLaunchKernelGGL(chart_match_loss_fwd_kernel, cm_grid(a), dim3(256), 0, s, a, cameras, depths);
@@ -332,15 +324,14 @@ extern "C" int g4s_chart_match_loss_backward(int n, int height, int width, const
     if (int rc = cm_check(n, height, width, cameras, depths)) return rc;
     if (n > 65535) return fail(G4S_ERR_INVALID_ARGUMENT, "chart match: at most 65535 views");
     if (int rc = cm_check_weights(n, height, width, weights, weight_max)) return rc;
-    if (!words || !grad_out1 || !dL_ddepths) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    if (!workspace || workspace_bytes < g4s_chart_match_workspace(n, height, width))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
+    if (!words || !grad_out1 || !dL_ddepths) return null_pointer();
+    if (int rc = check_workspace(workspace, workspace_bytes, g4s_chart_match_workspace(n, height, width))) return rc;
     MatchArgs a = cm_args(n, height, width, workspace);
     a.words_in = words; a.weights = weights; a.weight_max = weight_max; a.g1 = grad_out1; a.d_depths = dL_ddepths;
     const size_t total = (size_t)n * a.N;
     hipError_t e = hipMemsetAsync(a.acc, 0, total * 8, s);
     if (e != hipSuccess) return finish(e, "chart_match_loss_backward");
     hipLaunchKernelGGL(chart_match_loss_bwd_kernel, cm_grid(a), dim3(256), 0, s, a, cameras, depths);
-    hipLaunchKernelGGL(chart_match_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(chart_match_finish_kernel, dim3(blocks256((long long)total)), dim3(256), 0, s, a);
     return stage_done("chart_match_loss_backward", s);
 }

@@ -24,9 +24,7 @@
 #include "g4s_internal.h"
 #include "g4s_device.h"
 #include "chart_common.h"
-#include "tsdf/mesh_common.h"
 #include "tsdf/scan.h"
-#include "tsdf/wave_count.h"
 #include "../../include/g4s_losses.h"
 
 namespace g4s {
@@ -143,16 +141,11 @@ __global__ void __launch_bounds__(256) cp_moments_kernel(const int* __restrict__
         s[3] += t * dd;  // exact: two float32 factors
         s[4] += dd * dd;
     }
-    __shared__ double waves[4][CP_TERMS];
+    __shared__ double waves[CP_TERMS][4];
 #pragma unroll
     for (int k = 0; k < CP_TERMS; k++) {
-        const double w = wave_fold(s[k]);
-        if (lane_id() == 0) waves[threadIdx.x >> 6][k] = w;
-    }
-    __syncthreads();
-    if (threadIdx.x < CP_TERMS) {
-        const int k = (int)threadIdx.x;
-        partials[(cp_partial_base(offsets, c) + blockIdx.x) * CP_TERMS + k] = ((waves[0][k] + waves[1][k]) + waves[2][k]) + waves[3][k];
+        const double b = chart_block_sum_chain(s[k], waves[k]);
+        if (threadIdx.x == 0) partials[(cp_partial_base(offsets, c) + blockIdx.x) * CP_TERMS + k] = b;
     }
 }
 
@@ -244,10 +237,8 @@ __global__ void __launch_bounds__(256) cp_loss_kernel(PointArgs a, double* __res
         s += (double)(a.conf ? p.k * p.e - a.cw * logf(p.k) : p.e);
     }
     __shared__ double waves[4];
-    const double w = wave_fold(s);
-    if (lane_id() == 0) waves[threadIdx.x >> 6] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = ((waves[0] + waves[1]) + waves[2]) + waves[3];
+    const double b = chart_block_sum_chain(s, waves);
+    if (threadIdx.x == 0) partials[blockIdx.x] = b;
 }
 
 // one workgroup: thread t adds partials t, t + 256, ... in ascending order, then the same fold
@@ -256,10 +247,8 @@ __global__ void __launch_bounds__(256) cp_loss_fold_kernel(int nparts, int N, co
     double s = 0.0;
     for (int b = (int)threadIdx.x; b < nparts; b += 256) s += partials[b];
     __shared__ double waves[4];
-    const double w = wave_fold(s);
-    if (lane_id() == 0) waves[threadIdx.x >> 6] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) out1[0] = (float)((((waves[0] + waves[1]) + waves[2]) + waves[3]) / (double)N);
+    const double b = chart_block_sum_chain(s, waves);
+    if (threadIdx.x == 0) out1[0] = (float)(b / (double)N);
 }
 
 // the store pass: dL/ds_p and dL/dk_p per point

@@ -169,6 +169,13 @@ __device__ __forceinline__ float wave_sum16_to_quads(float (&v)[16], bool b3, bo
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_readlane((int)wave_sum_to_lane63(v), 63);
 }
+// The fixed float64 fold of the units that sum in a fixed order (depth_cues.hip, plane_masks.hip, the chart units):
+// lane 0 receives ((...) + lanes 32..63 folded alike): the same tree whatever the values
+__device__ __forceinline__ double wave_fold(double v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
+    return v;
+}
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
     for (int off = 32; off >= 1; off >>= 1) {
         uint32_t o = (uint32_t)__shfl_xor((int)v, off, 64);

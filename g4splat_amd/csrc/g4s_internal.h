@@ -159,6 +159,13 @@ inline ImgLayout img_layout(size_t N, size_t tiles) {
     return L;
 }
 inline char* align_ptr(char* p) { return (char*)align_up((size_t)p); }
+// What a g4s_*_workspace query adds to its layout's bytes: the entry point aligns the caller's base pointer (align_ptr).
+constexpr size_t WORKSPACE_BASE_SLACK = 256;
+// the range of a layout at byte offset `off`
+template <class T>
+T* workspace_at(char* workspace, size_t off) { return (T*)(align_ptr(workspace) + off); }
+// workgroups of 256 threads over n >= 0 items
+inline unsigned blocks256(long long n) { return (unsigned)((n + 255) / 256); }
 
 // ---- the error path (api.hip owns the calling thread's message buffer behind g4s_last_error() and alone writes it) ----
 void clear_error();
@@ -168,6 +175,11 @@ int finish(hipError_t e, const char* what);  // e, or if that is hipSuccess the 
 // environment, which also logs "[g4s] what: <error>" to stderr -- as G4S_OK or "what: <error>".
 int stage_done(const char* what, hipStream_t s, bool debug = false);
 inline bool misaligned(const void* p, size_t a) { return p != nullptr && ((size_t)p % a) != 0; }
+// argument checks: each leaves its message behind and returns the entry point's status
+inline int null_pointer() { return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer"); }
+inline int check_workspace(const char* workspace, size_t bytes, size_t need) {
+    return workspace && bytes >= need ? G4S_OK : fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
+}
 
 // ---- optional per-kernel timing with HIP events on the launch stream (api.hip; bench.py reads the groups by name) ----
 enum ProfId { PF_PREPROCESS_FWD, PF_DEPTH_SORT, PF_COUNT_SCAN, PF_EMIT, PF_TILE_SORT, PF_TILE_RANGES, PF_BLEND_FWD,

@@ -1,8 +1,9 @@
 // What the units under tsdf/ share that is not about views -- the mesh units (tsdf.hip, unbounded.hip, tetra.hip, mesh_ops.hip,
 // mesh_eval.hip) and the view-stack units (visibility.hip, planes.hip, consistency.hip, view_select.hip, depth_cues.hip,
-// chart_init.hip, plane_masks.hip): the argument checks of their entry points, the grid of a thread-per-item launch, the upload of host values
-// and the read-back of the two scan totals; for the mesh units alone, the index arithmetic of the marching-cubes table
-// (tsdf_mc_table.h).  What is about a stack of views is in view_stack.h.
+// chart_init.hip, plane_masks.hip): the argument checks of their entry points beyond those of g4s_internal.h (null_pointer,
+// check_workspace; blocks256 and workspace_at are there too), the upload of host values and the read-back of the two scan
+// totals; for the mesh units alone, the index arithmetic of the marching-cubes table (tsdf_mc_table.h).  What is about a
+// stack of views is in view_stack.h.
 #pragma once
 #include <math.h>
 #include <vector>
@@ -14,23 +15,10 @@ namespace g4s {
 // ---- argument checks: each leaves its message behind and returns the entry point's status ----
 inline bool finite_pos(float x) { return x > 0.0f && x < 3.0e38f; }
 inline bool finite(float x) { return fabsf(x) < 3.0e38f; }
-inline int null_pointer() { return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer"); }
-inline int check_workspace(const char* workspace, size_t bytes, size_t need) {
-    return workspace && bytes >= need ? G4S_OK : fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
-}
 inline bool lattice_ok(int n) { return n >= 2 && (long long)n * n * n < (1ll << 31); }
 inline int check_lattice(int n) {
     return lattice_ok(n) ? G4S_OK : fail(G4S_ERR_INVALID_ARGUMENT, "n must be at least 2 and n^3 below 2^31");
 }
-
-// workgroups of 256 threads over n >= 0 items
-inline unsigned blocks256(long long n) { return (unsigned)((n + 255) / 256); }
-
-// What a g4s_*_workspace query adds to its layout's bytes: the entry point aligns the caller's base pointer (align_ptr).
-constexpr size_t WORKSPACE_BASE_SLACK = 256;
-// the range of a layout at byte offset `off`
-template <class T>
-T* workspace_at(char* workspace, size_t off) { return (T*)(align_ptr(workspace) + off); }
 
 // host values -> device memory; synchronises, so `host` is the caller's again on return
 inline hipError_t upload(void* dev, const void* host, size_t bytes, hipStream_t stream) {

@@ -1,16 +1,10 @@
 // The wave-level fold of integer counts that the units with integer count tables (planes.hip, consistency.hip,
-// plane_masks.hip) share, and the fixed float64 fold of the units that sum in a fixed order (depth_cues.hip, plane_masks.hip).
+// plane_masks.hip) share.  The fixed float64 fold of the units that sum in a fixed order (depth_cues.hip, plane_masks.hip),
+// wave_fold, is in g4s_device.h beside the other wave sums.
 #pragma once
 #include "../g4s_device.h"
 
 namespace g4s {
-
-// lane 0 receives ((...) + lanes 32..63 folded alike): the same tree whatever the values
-__device__ __forceinline__ double wave_fold(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
 
 // table[key] += the number of active lanes that hold `key`, one atomic per distinct key of the wave.  Every lane of the wave
 // must call it (inactive ones with active = false).

@@ -154,6 +154,24 @@ def test_generated_case_within_the_float32_restatement(wide):
     within_yardstick("wide dL/dconfidence", gc, wide.s64.conf_grad, np.abs(wide.s32.conf_grad.astype(np.float64) - wide.s64.conf_grad).max())
 
 
+def test_means_fold_beyond_one_trip(hip_lib):
+    """2 x 256 x 513, all four terms on, with confidence: 2 x 513 = 1026 block partials with a ragged last block per view, so
+    two threads of the one-workgroup fold add two rows each.  The four means by the rule of the generated case above (the
+    float64 restatement, the float32 one as the yardstick); two runs, the same bits."""
+    from types import SimpleNamespace
+    cams, d0, r, cur = ref.scene(2, 256, 513, seed=23)
+    c = SimpleNamespace(name="fold", n=2, H=256, W=513, cams=cams, initial_depths=d0, reference_depths=r, depths=cur, lam=0.2,
+                        confidence=np.random.default_rng(29).uniform(1.2, 4.0, d0.shape).astype(np.float32), masks=None,
+                        gradient_masks=None)
+    a = losses_of(c)
+    with torch.no_grad():
+        m = twice(lambda: host(a.terms(dev(c.depths), dev(c.reference_depths), dev(c.confidence), use_gradient_loss=True,
+                                       use_normal_loss=True, use_curvature_loss=True)))
+    m32, m64 = (ref.means(*args, **kw) for args, kw in (ref.case_inputs(c, T) for T in (np.float32, np.float64)))
+    assert (m64 > 0).all()
+    within_yardstick("fold means", m, m64, np.abs(m32.astype(np.float64) - m64).max())
+
+
 @pytest.mark.parametrize("name", ("small", "full"))
 def test_each_term_alone(golden, name):
     """Term k with the others switched off: its mean has the bits it has with all terms on, the other slots are exactly 0,

@@ -192,6 +192,38 @@ def test_smooth_unquantised_means(hip_lib, H, W):
     assert float(got[4]) > 0
 
 
+# ---- the one-workgroup fold of the block partials beyond its first 1024 rows ----------------------------------------------
+def test_anisotropy_fold_beyond_one_trip(hip_lib):
+    """P = 256 * 1024 + 1: 1025 block partials, the last block holding one Gaussian, so one thread of the fold adds two
+    rows.  The mean against the restatement evaluated in float64, by the bar of every loss scalar here; two runs, the same
+    bits."""
+    P = 256 * 1024 + 1
+    g = torch.Generator().manual_seed(31)
+    scaling = (torch.rand((P, 2), generator=g) * torch.tensor([1.0, 0.1]) + 0.01).to(DEV)
+    got = [losses.anisotropy_loss(scaling, 5.0) for _ in range(2)]
+    want = ref.anisotropy_loss(scaling.double(), 5.0)
+    print(f"anisotropy, P = {P}: fused {float(got[0]):.9g} float64 restatement {float(want):.12g}")
+    assert float(want) > 0 and close_scalar(got[0], want)
+    assert torch.equal(got[0], got[1])
+
+
+def test_chart_prior_fold_beyond_one_trip(hip_lib):
+    """267 x 1029: 34 x 33 = 1122 tiles of 8 x 32, ragged both ways.  The five means against the restatement evaluated in
+    float64 on the same lattice inputs (every sign and clamp is exact there), by the bar of every loss scalar here; two runs,
+    the same bits."""
+    H, W = 8 * 33 + 3, 32 * 32 + 5
+    t = ref.lattice_inputs(H, W, 17, device=DEV)
+    torch.manual_seed(17)
+    shifts = losses.draw_pixel_shifts(H, W, device=DEV)
+    got = [losses.chart_prior_losses(*t, 5.0, shifts, 4.0, 20.0) for _ in range(2)]
+    want = ref.chart_prior_losses(*[x.double() for x in t], 5.0, shifts, 4.0, 20.0)
+    for k in range(5):
+        print(f"{H}x{W} mean {k}: fused {float(got[0][k]):.9g} float64 restatement {float(want[k]):.12g}")
+        assert close_scalar(got[0][k], want[k]), k
+    assert float(got[0][4]) > 0
+    assert torch.equal(got[0], got[1])
+
+
 def small_training_inputs(H=48, W=64, P=5000):
     rn, sn, sd, pd, pn, pc = ref.lattice_inputs(H, W, 12, device=DEV)
     pkg = {"rend_normal": rn.requires_grad_(True), "surf_normal": sn.requires_grad_(True), "surf_depth": sd.requires_grad_(True)}

@@ -150,6 +150,26 @@ def test_generated_case_within_the_float32_restatement(six):
         same_terms_other_order(label, v, g, six["cams"], six["cur"], six["matches"], w, 1.0, None if w is None else 3.0)
 
 
+def test_loss_fold_beyond_one_trip(hip_lib):
+    """n = 2 at 256x513: 2 x 513 = 1026 block partials with a ragged last block per view, so two threads of the one-workgroup
+    fold add two rows each.  The loss against the float64 restatement with the float32 one as the yardstick and, against the
+    float32 one, within loss_sum_bound -- the two checks of the loss in the tests above; two runs, the same bits."""
+    n, H, W, thr = 2, 256, 513, 0.12
+    cams, depths = ref.generated_scene(n, H, W, seed=5)
+    matches, _errors, _fov = ref.match(cams, depths, thr)
+    cur = (depths * (1.0 + 0.01 * np.sin(np.arange(depths.size, dtype=np.float64).reshape(depths.shape)))).astype(np.float32)
+    m = matcher_of(cams, depths, thr)
+    same_bits(host(m.words).view(np.uint32), ref.pack_words(matches), "words")
+    with torch.no_grad():
+        v = twice(lambda: host(m.loss(dev(cur))))
+    v64, v32 = (ref.loss(cams, cur, matches, ftype=t) for t in (np.float64, np.float32))
+    assert matches.any() and float(v64) > 0
+    within_yardstick("2x256x513 loss", v, v64, v32)
+    dv, bv = abs(float(v) - float(v32)), ref.loss_sum_bound(n, H * W, v32)
+    print(f"2x256x513: loss off the float32 restatement by {dv:.3e} (bound {bv:.3e})")
+    assert dv <= bv, (dv, bv)
+
+
 def test_forward_and_backward_are_bit_reproducible(six):
     m = matcher_of(six["cams"], six["depths"], six["thr"])
     twice(lambda: loss_and_grad(m, six["cur"], six["weights"], 0.37, 3.0))

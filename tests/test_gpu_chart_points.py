@@ -186,6 +186,32 @@ def test_points_behind_the_camera_are_clipped():
     assert host(values)[2:4].tolist() == [0.0, 0.0] and not host(fov)[2:4].any() and host(fov)[[0, 1, 4]].all()
 
 
+def test_loss_fold_beyond_one_trip():
+    """N = 4096 * 256 + 1 points on two charts of 16x32: 257 spans, the last of one point, so thread 0 of the loss's
+    256-thread fold adds two partials.  The value against the restatement (float32 terms, float64 sum) by the bound of
+    check_against_restatement, with and without a confidence; two runs, the same bits."""
+    H, W, N = 16, 32, 4096 * 256 + 1
+    rng = np.random.default_rng(41)
+    counts = (600_000, N - 600_000)
+    # the strips beside the image included, but every point with a tap inside: the sampled confidence stays positive
+    lists = [at_pixels(rng.uniform(-0.75, W - 0.25, k), rng.uniform(-0.75, H - 0.25, k), H, W) for k in counts]
+    cams = [grid_camera(), grid_camera()]
+    points, _offsets, chart = ref.pack(lists)
+    z, ix, iy, clipped = ref.project(cams, points, chart, H, W, f32)
+    assert not clipped.any()
+    pts = device_points(cams, lists, H, W)
+    assert pts.n_points == N
+    same_bits(pts.ixy, np.stack([ix, iy], -1), "ixy")
+    depths = rng.uniform(0.5, 3.0, (2, H, W)).astype(f32)
+    conf = (1.0 + np.exp(rng.uniform(-1, 1, (2, H, W)))).astype(f32)
+    for k in (None, conf):
+        with torch.no_grad():
+            loss = twice(lambda: host(cp.point_reference_loss(dev(depths), pts, dev(k), 0.2)))
+        want = ref.point_reference_loss(depths, chart, ix, iy, z, k, 0.2, need_grad=False).loss
+        print(f"N = {N}, confidence {k is not None}: loss {float(loss):.9g}, restatement {float(want):.9g}")
+        assert np.isfinite(want) and abs(float(loss) - float(want)) <= 4 * np.spacing(f32(abs(want))), (loss, want)
+
+
 @pytest.mark.parametrize("counts", [(0, 5, 7), (5, 0, 7), (5, 7, 0), (1, 6, 0), (0, 0, 0)])
 def test_empty_charts_and_a_chart_with_one_point(golden, counts):
     """An empty chart first, in the middle and last; one point gives NaN coefficients and no error; no point at all."""
