@@ -18,7 +18,7 @@
 //   backward: normals -> A, B of every interior pixel -> gather into dL/ddepths, dL/dconfidence   (3 launches; 1 without
 //             the normal and curvature terms)
 #include "g4s_internal.h"
-#include "g4s_device.h"
+#include "fixed_sums.h"
 #include "chart_common.h"
 #include "../../include/g4s_losses.h"
 
@@ -192,7 +192,7 @@ __global__ void __launch_bounds__(256) chart_align_fwd_kernel(AlignArgs a, const
     // The terms are float32, their sums are not: a mean over n N terms is then as good as its terms.
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        const double b = chart_block_sum_pairs((double)s[k], s_red[k]);
+        const double b = block_sum_pairs((double)s[k], s_red[k]);
         if (threadIdx.x == 0) a.partials[4 * (size_t)blockIdx.x + k] = b;
     }
 }
@@ -200,7 +200,7 @@ __global__ void __launch_bounds__(256) chart_align_fwd_kernel(AlignArgs a, const
 // one block of 1024 threads folds the block partials; fixed association => bit-reproducible
 __global__ void __launch_bounds__(1024) chart_align_reduce_kernel(AlignArgs a) {
     __shared__ double s_v[4][1024];
-    chart_fold_partials<4>(a.partials, a.nblocks, s_v);
+    fold_partials<4>(a.partials, a.nblocks, s_v);
     if (threadIdx.x < 4) {
         const int k = (int)threadIdx.x;
         const bool on = k == 0 || (a.flags & (1 << (k - 1)));

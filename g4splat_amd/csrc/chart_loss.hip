@@ -15,7 +15,7 @@
 // depend on the arrival order and the gradient is bit-identical from run to run -- and a finishing pass scales the sums
 // into dL_dsurf_depth.
 #include "g4s_internal.h"
-#include "g4s_device.h"
+#include "fixed_sums.h"
 #include "chart_common.h"
 #include "../../include/g4s_losses.h"
 
@@ -94,7 +94,7 @@ __global__ void __launch_bounds__(256) chart_fwd_kernel(ChartArgs a) {
     }
 #pragma unroll
     for (int k = 0; k < 5; k++) {
-        const float b = chart_block_sum(t[k], s_red[k]);
+        const float b = block_sum(t[k], s_red[k]);
         if (threadIdx.x == 0) a.partials[5 * (size_t)blockIdx.x + k] = b;
     }
 }
@@ -102,7 +102,7 @@ __global__ void __launch_bounds__(256) chart_fwd_kernel(ChartArgs a) {
 // one block of 1024 threads folds the block partials in double; fixed association => bit-reproducible
 __global__ void __launch_bounds__(1024) chart_reduce_kernel(ChartArgs a) {
     __shared__ double s_v[5][1024];
-    chart_fold_partials<5>(a.partials, a.nblocks, s_v);
+    fold_partials<5>(a.partials, a.nblocks, s_v);
     if (threadIdx.x < 5) a.out5[threadIdx.x] = (float)(s_v[threadIdx.x][0] / (double)a.N);
 }
 
@@ -201,13 +201,13 @@ __global__ void __launch_bounds__(256) aniso_fwd_kernel(AnisoArgs a) {
         const float2 s = a.scaling[i];
         v = fmaxf(fmaxf(s.x, s.y) / fminf(s.x, s.y), a.max_ratio) - a.max_ratio;
     }
-    const float b = chart_block_sum(v, s_red);
+    const float b = block_sum(v, s_red);
     if (threadIdx.x == 0) a.partials[blockIdx.x] = b;
 }
 
 __global__ void __launch_bounds__(1024) aniso_reduce_kernel(AnisoArgs a) {
     __shared__ double s_v[1][1024];
-    chart_fold_partials<1>(a.partials, a.nblocks, s_v);
+    fold_partials<1>(a.partials, a.nblocks, s_v);
     if (threadIdx.x == 0) a.out1[0] = (float)(s_v[0][0] / (double)a.P);
 }
 

@@ -15,7 +15,7 @@
 // as 2^36 fixed-point integers with 64-bit integer atomics (associative: bit-identical from run to run), which a finishing
 // pass scales into dL/dD.  Nothing of size n n N exists except the match bits.
 #include "g4s_internal.h"
-#include "g4s_device.h"
+#include "fixed_sums.h"
 #include "chart_common.h"
 #include "../../include/g4s_losses.h"
 
@@ -177,14 +177,14 @@ __global__ void __launch_bounds__(256) chart_match_loss_fwd_kernel(MatchArgs a, 
             if (((word >> (p & 31)) & 1u) && r.fov) sum += cm_nan_to_num(r.e) * w;
         }
     }
-    const float b = chart_block_sum(sum, s_red);
+    const float b = block_sum(sum, s_red);
     if (threadIdx.x == 0) a.partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = b;
 }
 
 // one block of 1024 threads folds the block partials in double; fixed association => bit-reproducible
 __global__ void __launch_bounds__(1024) chart_match_reduce_kernel(MatchArgs a) {
     __shared__ double s_v[1][1024];
-    chart_fold_partials<1>(a.partials, a.nblocks, s_v);
+    fold_partials<1>(a.partials, a.nblocks, s_v);
     if (threadIdx.x == 0) a.out1[0] = (float)(s_v[0][0] / ((double)a.n * (double)a.n * (double)a.N));
 }
 

@@ -22,7 +22,7 @@
 //               A pixel with more than one chunk (SfM points pile up) is summed by its whole wave, a chunk per lane.
 // Every launch is on the caller's stream; nothing allocates, synchronises or reads back.
 #include "g4s_internal.h"
-#include "g4s_device.h"
+#include "fixed_sums.h"
 #include "chart_common.h"
 #include "tsdf/scan.h"
 #include "../../include/g4s_losses.h"
@@ -141,12 +141,10 @@ __global__ void __launch_bounds__(256) cp_moments_kernel(const int* __restrict__
         s[3] += t * dd;  // exact: two float32 factors
         s[4] += dd * dd;
     }
-    __shared__ double waves[CP_TERMS][4];
+    __shared__ double waves[4][CP_TERMS];
 #pragma unroll
-    for (int k = 0; k < CP_TERMS; k++) {
-        const double b = chart_block_sum_chain(s[k], waves[k]);
-        if (threadIdx.x == 0) partials[(cp_partial_base(offsets, c) + blockIdx.x) * CP_TERMS + k] = b;
-    }
+    for (int k = 0; k < CP_TERMS; k++) moment_fold(s[k], waves, k);
+    moment_store(waves, CP_TERMS, partials + (cp_partial_base(offsets, c) + blockIdx.x) * CP_TERMS);
 }
 
 // grid = charts, 64 threads
@@ -154,21 +152,9 @@ __global__ void __launch_bounds__(64) cp_coeffs_kernel(const int* __restrict__ o
         float* __restrict__ coeffs, int* __restrict__ counts) {
     const int c = (int)blockIdx.x;
     const int nb = (offsets[c + 1] - offsets[c] + CP_SPAN - 1) / CP_SPAN;
-    double s[CP_TERMS] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int b = (int)threadIdx.x; b < nb; b += 64) {
-        const double* p = partials + (cp_partial_base(offsets, c) + b) * CP_TERMS;
-#pragma unroll
-        for (int k = 0; k < CP_TERMS; k++) s[k] += p[k];
-    }
-#pragma unroll
-    for (int k = 0; k < CP_TERMS; k++) s[k] = wave_fold(s[k]);
-    if (threadIdx.x != 0) return;
-    const double n = s[0], St = s[1], Sd = s[2], Std = s[3], Sdd = s[4];
-    const double beta = (Std - St * Sd / n) / (Sdd - Sd * Sd / n);
-    const double alpha = (St - beta * Sd) / n;
-    coeffs[2 * (size_t)c] = (float)alpha;
-    coeffs[2 * (size_t)c + 1] = (float)beta;
-    counts[c] = (int)n;
+    double s[CP_TERMS];
+    column_fold(partials + cp_partial_base(offsets, c) * CP_TERMS, (uint32_t)nb, CP_TERMS, s);
+    if (threadIdx.x == 0) scale_shift_solve(s, coeffs + 2 * (size_t)c, counts + c);
 }
 
 __global__ void __launch_bounds__(256) cp_apply_kernel(long long total, int per_chart, const float* __restrict__ disp,
@@ -237,7 +223,7 @@ __global__ void __launch_bounds__(256) cp_loss_kernel(PointArgs a, double* __res
         s += (double)(a.conf ? p.k * p.e - a.cw * logf(p.k) : p.e);
     }
     __shared__ double waves[4];
-    const double b = chart_block_sum_chain(s, waves);
+    const double b = block_sum_chain(s, waves);
     if (threadIdx.x == 0) partials[blockIdx.x] = b;
 }
 
@@ -247,7 +233,7 @@ __global__ void __launch_bounds__(256) cp_loss_fold_kernel(int nparts, int N, co
     double s = 0.0;
     for (int b = (int)threadIdx.x; b < nparts; b += 256) s += partials[b];
     __shared__ double waves[4];
-    const double b = chart_block_sum_chain(s, waves);
+    const double b = block_sum_chain(s, waves);
     if (threadIdx.x == 0) out1[0] = (float)(b / (double)N);
 }
 

@@ -131,7 +131,7 @@ extern "C" int g4s_knn_mean_dist(int P, const float* points, float* meanDists, c
     if (P < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "P < 0");
     if (P == 0) return G4S_OK;
     if (!points || !meanDists || !workspace) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL pointer");
-    if (workspace_bytes < g4s_knn_workspace(P)) return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
+    if (int rc = check_workspace(workspace, workspace_bytes, g4s_knn_workspace(P))) return rc;
     const KnnLayout L = knn_layout((size_t)P);
     char* w = align_ptr(workspace);
     knn_build_tree(L, P, points, w, s);

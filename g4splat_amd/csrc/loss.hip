@@ -12,7 +12,7 @@
 // term; a one-block kernel folds the block partials in double, in a fixed order.  HBM traffic ~ 130 B/pixel
 // per channel-pixel against ~25 full-image passes of the eager formulation.
 #include "g4s_internal.h"
-#include "g4s_device.h"
+#include "fixed_sums.h"
 #include "../../include/g4s_losses.h"
 
 namespace g4s {
@@ -37,14 +37,6 @@ struct PhotoArgs {
     float* dL_dimage;
     int nblocks;
 };
-
-// sum over a 256-thread block in a fixed order; result valid in thread 0
-__device__ __forceinline__ float block_sum256(float v, float* s4) {
-    v = wave_sum_to_lane63(v);
-    if ((threadIdx.x & 63) == 63) s4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (s4[0] + s4[1]) + (s4[2] + s4[3]);
-}
 
 __global__ void __launch_bounds__(256) ssim_fwd_kernel(PhotoArgs a) {
     __shared__ float s_x[SS_IN][SS_LD], s_y[SS_IN][SS_LD];
@@ -99,8 +91,8 @@ __global__ void __launch_bounds__(256) ssim_fwd_kernel(PhotoArgs a) {
         a.maps[(2 * 3 + ch) * N + p] = dS_de12;
         l1 = fabsf(s_x[ty + SS_R][tx + SS_R] - s_y[ty + SS_R][tx + SS_R]);
     }
-    const float bs = block_sum256(ssim, s_red[0]);
-    const float bl = block_sum256(l1, s_red[1]);
+    const float bs = block_sum(ssim, s_red[0]);
+    const float bl = block_sum(l1, s_red[1]);
     if (threadIdx.x == 0) {
         const int b = (int)((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
         a.partials[2 * b] = bs;
@@ -108,32 +100,13 @@ __global__ void __launch_bounds__(256) ssim_fwd_kernel(PhotoArgs a) {
     }
 }
 
-// one block of 1024 threads; four independent loads in flight per thread (a serial loop of dependent round trips over
-// the 22 500 block partials of a 1600x1200 frame took 24 us); fixed association => bit-reproducible
+// one block of 1024 threads folds the block partials in double, in a fixed order => bit-reproducible
 __global__ void __launch_bounds__(1024) photo_reduce_kernel(PhotoArgs a) {
-    __shared__ double s_s[1024], s_l[1024];
-    double s = 0, l = 0;
-    const float2* part = reinterpret_cast<const float2*>(a.partials);
-    for (int i0 = (int)threadIdx.x; i0 < a.nblocks; i0 += 4096) {
-        float2 v[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int i = i0 + 1024 * k;
-            v[k] = part[i < a.nblocks ? i : 0];
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (i0 + 1024 * k < a.nblocks) { s += v[k].x; l += v[k].y; }
-    }
-    s_s[threadIdx.x] = s; s_l[threadIdx.x] = l;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { s_s[threadIdx.x] += s_s[threadIdx.x + o]; s_l[threadIdx.x] += s_l[threadIdx.x + o]; }
-        __syncthreads();
-    }
+    __shared__ double s_v[2][1024];
+    fold_partials<2>(a.partials, a.nblocks, s_v);
     if (threadIdx.x == 0) {
         const double n = 3.0 * (double)a.W * (double)a.H;
-        const double ssim = s_s[0] / n, l1 = s_l[0] / n;
+        const double ssim = s_v[0][0] / n, l1 = s_v[1][0] / n;
         a.out3[0] = (float)((1.0 - (double)a.lambda) * l1 + (double)a.lambda * (1.0 - ssim));
         a.out3[1] = (float)l1;
         a.out3[2] = (float)ssim;
@@ -197,9 +170,8 @@ extern "C" int g4s_photometric_loss(int width, int height, const float* image, c
     hipStream_t s = (hipStream_t)stream_;
     clear_error();
     if (width <= 0 || height <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "width, height must be positive");
-    if (!image || !gt || !out3) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    if (!workspace || workspace_bytes < g4s_photometric_workspace(width, height))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
+    if (!image || !gt || !out3) return null_pointer();
+    if (int rc = check_workspace(workspace, workspace_bytes, g4s_photometric_workspace(width, height))) return rc;
     PhotoArgs a{};
     a.W = width; a.H = height; a.lambda = lambda_dssim; a.image = image; a.gt = gt; a.out3 = out3; a.dL_dimage = dL_dimage;
     const size_t N = (size_t)width * height;
@@ -262,36 +234,15 @@ __global__ void __launch_bounds__(256) georeg_fwd_kernel(GeoRegArgs a) {
             }
         }
     }
-    const float be = block_sum256(e, s_red[0]);
-    const float bd = block_sum256(d, s_red[1]);
+    const float be = block_sum(e, s_red[0]);
+    const float bd = block_sum(d, s_red[1]);
     if (threadIdx.x == 0) { a.partials[2 * blockIdx.x] = be; a.partials[2 * blockIdx.x + 1] = bd; }
 }
 
 __global__ void __launch_bounds__(1024) georeg_reduce_kernel(GeoRegArgs a) {
-    __shared__ double s_e[1024], s_d[1024];
-    double e = 0, d = 0;
-    const float2* part = reinterpret_cast<const float2*>(a.partials);
-    for (int i0 = (int)threadIdx.x; i0 < a.nblocks; i0 += 4096) {
-        float2 v[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int i = i0 + 1024 * k;
-            v[k] = part[i < a.nblocks ? i : 0];
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (i0 + 1024 * k < a.nblocks) { e += v[k].x; d += v[k].y; }
-    }
-    s_e[threadIdx.x] = e; s_d[threadIdx.x] = d;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { s_e[threadIdx.x] += s_e[threadIdx.x + o]; s_d[threadIdx.x] += s_d[threadIdx.x + o]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        a.out2[0] = (float)(s_e[0] / (double)a.N);
-        a.out2[1] = (float)(s_d[0] / (double)a.N);
-    }
+    __shared__ double s_v[2][1024];
+    fold_partials<2>(a.partials, a.nblocks, s_v);
+    if (threadIdx.x < 2) a.out2[threadIdx.x] = (float)(s_v[threadIdx.x][0] / (double)a.N);
 }
 
 __global__ void __launch_bounds__(256) georeg_bwd_kernel(GeoRegArgs a) {
@@ -327,13 +278,12 @@ extern "C" size_t g4s_geometry_regularizers_workspace(int width, int height) {
 }
 
 // what both directions share; vec = float4 accesses: N % 4 == 0 and every plane of the direction on a 16-byte aligned base
-static inline bool georeg_al16(const void* p) { return ((size_t)p & 15) == 0; }
 static GeoRegArgs georeg_args(int width, int height, const float* rn, const float* sn) {
     GeoRegArgs a{};
     a.N = (long long)width * height;
     a.rn = rn; a.sn = sn;
     a.nblocks = (int)((a.N + 1023) / 1024);
-    a.vec = (a.N % 4 == 0) && georeg_al16(rn) && georeg_al16(sn);
+    a.vec = (a.N % 4 == 0) && !misaligned(rn, 16) && !misaligned(sn, 16);
     return a;
 }
 
@@ -343,12 +293,11 @@ extern "C" int g4s_geometry_regularizers_forward(int width, int height, const fl
     hipStream_t s = (hipStream_t)stream_;
     clear_error();
     if (width <= 0 || height <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "width, height must be positive");
-    if (!rend_normal || !surf_normal || !rend_dist || !out2) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    if (!workspace || workspace_bytes < g4s_geometry_regularizers_workspace(width, height))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
+    if (!rend_normal || !surf_normal || !rend_dist || !out2) return null_pointer();
+    if (int rc = check_workspace(workspace, workspace_bytes, g4s_geometry_regularizers_workspace(width, height))) return rc;
     GeoRegArgs a = georeg_args(width, height, rend_normal, surf_normal);
     a.dist = rend_dist; a.out2 = out2;
-    a.vec = a.vec && georeg_al16(rend_dist);
+    a.vec = a.vec && !misaligned(rend_dist, 16);
     a.partials = (float*)align_ptr(workspace);
     {
         ProfScope ps(PF_GEO_REG, s);
@@ -365,10 +314,10 @@ extern "C" int g4s_geometry_regularizers_backward(int width, int height, const f
     clear_error();
     if (width <= 0 || height <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "width, height must be positive");
     if (!rend_normal || !surf_normal || !grad_out2 || !dL_drend_normal || !dL_dsurf_normal || !dL_drend_dist)
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+        return null_pointer();
     GeoRegArgs a = georeg_args(width, height, rend_normal, surf_normal);
     a.g2 = grad_out2; a.d_rn = dL_drend_normal; a.d_sn = dL_dsurf_normal; a.d_dist = dL_drend_dist;
-    a.vec = a.vec && georeg_al16(dL_drend_normal) && georeg_al16(dL_dsurf_normal) && georeg_al16(dL_drend_dist);
+    a.vec = a.vec && !misaligned(dL_drend_normal, 16) && !misaligned(dL_dsurf_normal, 16) && !misaligned(dL_drend_dist, 16);
     {
         ProfScope ps(PF_GEO_REG, s);
         hipLaunchKernelGGL(georeg_bwd_kernel, dim3(a.nblocks), dim3(256), 0, s, a);

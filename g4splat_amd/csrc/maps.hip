@@ -294,8 +294,8 @@ extern "C" int g4s_render_maps_forward(int width, int height, const float* allma
     if (width <= 0 || height <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "width, height must be positive");
     if (!allmap || !world_view_transform || !full_proj_transform || !rend_alpha || !rend_normal || !rend_normal_cam ||
         !rend_depth || !rend_dist || !surf_depth || !surf_normal || !surf_normal_cam)
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    if (!workspace || workspace_bytes < g4s_render_maps_workspace()) return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
+        return null_pointer();
+    if (int rc = check_workspace(workspace, workspace_bytes, g4s_render_maps_workspace())) return rc;
     {
         ProfScope ps(PF_MAPS_FWD, s);
         MapsArgs a = maps_prepare(width, height, depth_ratio, allmap, world_view_transform, full_proj_transform, workspace, s);
@@ -317,8 +317,8 @@ extern "C" int g4s_render_maps_backward(int width, int height, const float* allm
     clear_error();
     if (width <= 0 || height <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "width, height must be positive");
     if (!allmap || !surf_depth || !world_view_transform || !full_proj_transform || !dL_dallmap)
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    if (!workspace || workspace_bytes < g4s_render_maps_workspace()) return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
+        return null_pointer();
+    if (int rc = check_workspace(workspace, workspace_bytes, g4s_render_maps_workspace())) return rc;
     {
         ProfScope ps(PF_MAPS_BWD, s);
         MapsArgs a = maps_prepare(width, height, depth_ratio, allmap, world_view_transform, full_proj_transform, workspace, s);

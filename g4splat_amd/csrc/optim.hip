@@ -124,7 +124,7 @@ extern "C" int g4s_adam_step(int nseg, float* const* params, const float* const*
     }
     {
         ProfScope ps(PF_ADAM, s);
-        if (blocks4 > 0) hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((blocks4 + 255) / 256)), dim3(256), 0, s, a);
+        if (blocks4 > 0) hipLaunchKernelGGL(adam_kernel, dim3(blocks256(blocks4)), dim3(256), 0, s, a);
     }
     return stage_done("adam_step", s);
 }
@@ -152,7 +152,7 @@ extern "C" int g4s_adam_step_device(int nseg, float* const* params, const float*
     {
         ProfScope ps(PF_ADAM, s);
         hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(8), 0, s, pr);  // (the counts advance even when all segments are empty)
-        if (blocks4 > 0) hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((blocks4 + 255) / 256)), dim3(256), 0, s, a);
+        if (blocks4 > 0) hipLaunchKernelGGL(adam_kernel, dim3(blocks256(blocks4)), dim3(256), 0, s, a);
     }
     return stage_done("adam_step_device", s);
 }
@@ -181,8 +181,8 @@ extern "C" int g4s_densify_stats(int P, const float* grad_mean2D, const unsigned
     if (P < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "P must not be negative");
     if (P == 0) return G4S_OK;
     if (!grad_mean2D || !update_filter || !xyz_gradient_accum || !denom || (max_radii2D && !radii))
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    hipLaunchKernelGGL(densify_stats_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, P, grad_mean2D, update_filter,
+        return null_pointer();
+    hipLaunchKernelGGL(densify_stats_kernel, dim3(blocks256(P)), dim3(256), 0, s, P, grad_mean2D, update_filter,
                        radii, xyz_gradient_accum, denom, max_radii2D);
     return stage_done("densify_stats launch", s);
 }
@@ -238,10 +238,10 @@ extern "C" int g4s_activations_forward(int P, const float* scaling_raw, const fl
     if (P < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "P must not be negative");
     if (P == 0) return G4S_OK;
     if (!scaling_raw || !rotation_raw || !opacity_raw || !scales || !rotations || !opacities)
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+        return null_pointer();
     if (misaligned(scaling_raw, 8) || misaligned(scales, 8) || misaligned(rotation_raw, 16) || misaligned(rotations, 16))
         return fail(G4S_ERR_INVALID_ARGUMENT, "scaling / scales must be 8-byte, rotations 16-byte aligned");
-    hipLaunchKernelGGL(activations_fwd_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, P, (const float2*)scaling_raw,
+    hipLaunchKernelGGL(activations_fwd_kernel, dim3(blocks256(P)), dim3(256), 0, s, P, (const float2*)scaling_raw,
                        (const float4*)rotation_raw, opacity_raw, (float2*)scales, (float4*)rotations, opacities);
     return stage_done("activations launch", s);
 }
@@ -255,11 +255,11 @@ extern "C" int g4s_activations_backward(int P, const float* scales, const float*
     if (P == 0) return G4S_OK;
     if (!scales || !rotation_raw || !opacities || !dL_dscales || !dL_drotations || !dL_dopacities || !dL_dscaling_raw ||
         !dL_drotation_raw || !dL_dopacity_raw)
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+        return null_pointer();
     if (misaligned(scales, 8) || misaligned(dL_dscales, 8) || misaligned(dL_dscaling_raw, 8) || misaligned(rotation_raw, 16) ||
         misaligned(dL_drotations, 16) || misaligned(dL_drotation_raw, 16))
         return fail(G4S_ERR_INVALID_ARGUMENT, "scale tensors must be 8-byte, rotation tensors 16-byte aligned");
-    hipLaunchKernelGGL(activations_bwd_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, P, (const float2*)scales,
+    hipLaunchKernelGGL(activations_bwd_kernel, dim3(blocks256(P)), dim3(256), 0, s, P, (const float2*)scales,
                        (const float4*)rotation_raw, opacities, (const float2*)dL_dscales, (const float4*)dL_drotations,
                        dL_dopacities, (float2*)dL_dscaling_raw, (float4*)dL_drotation_raw, dL_dopacity_raw);
     return stage_done("activations backward launch", s);
@@ -379,10 +379,10 @@ extern "C" int g4s_activations_mip_forward(int P, const float* scaling_raw, cons
     if (P < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "P must not be negative");
     if (P == 0) return G4S_OK;
     if (!scaling_raw || !rotation_raw || !opacity_raw || !mip_filter || !scales || !rotations || !opacities)
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+        return null_pointer();
     if (misaligned(scaling_raw, 8) || misaligned(scales, 8) || misaligned(rotation_raw, 16) || misaligned(rotations, 16))
         return fail(G4S_ERR_INVALID_ARGUMENT, "scaling / scales must be 8-byte, rotations 16-byte aligned");
-    hipLaunchKernelGGL(activations_mip_fwd_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, P,
+    hipLaunchKernelGGL(activations_mip_fwd_kernel, dim3(blocks256(P)), dim3(256), 0, s, P,
                        (const float2*)scaling_raw, (const float4*)rotation_raw, opacity_raw, mip_filter, (float2*)scales,
                        (float4*)rotations, opacities);
     return stage_done("activations (mip filter) launch", s);
@@ -398,11 +398,11 @@ extern "C" int g4s_activations_mip_backward(int P, const float* scaling_raw, con
     if (P == 0) return G4S_OK;
     if (!scaling_raw || !rotation_raw || !opacity_raw || !mip_filter || !dL_dscales || !dL_drotations || !dL_dopacities ||
         !dL_dscaling_raw || !dL_drotation_raw || !dL_dopacity_raw)
-        return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+        return null_pointer();
     if (misaligned(scaling_raw, 8) || misaligned(dL_dscales, 8) || misaligned(dL_dscaling_raw, 8) ||
         misaligned(rotation_raw, 16) || misaligned(dL_drotations, 16) || misaligned(dL_drotation_raw, 16))
         return fail(G4S_ERR_INVALID_ARGUMENT, "scale tensors must be 8-byte, rotation tensors 16-byte aligned");
-    hipLaunchKernelGGL(activations_mip_bwd_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, P,
+    hipLaunchKernelGGL(activations_mip_bwd_kernel, dim3(blocks256(P)), dim3(256), 0, s, P,
                        (const float2*)scaling_raw, (const float4*)rotation_raw, opacity_raw, mip_filter,
                        (const float2*)dL_dscales, (const float4*)dL_drotations, dL_dopacities, (float2*)dL_dscaling_raw,
                        (float4*)dL_drotation_raw, dL_dopacity_raw);
@@ -418,12 +418,12 @@ extern "C" int g4s_mip_filter(int P, const float* xyz, int V, const float* camer
     if (P < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "P must not be negative");
     if (V < 1) return fail(G4S_ERR_INVALID_ARGUMENT, "at least one view");
     if (P == 0) return G4S_OK;
-    if (!xyz || !cameras || !mip_filter_out || !workspace) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (!xyz || !cameras || !mip_filter_out || !workspace) return null_pointer();
     if (misaligned(xyz, 4) || misaligned(cameras, 4) || misaligned(mip_filter_out, 4))
         return fail(G4S_ERR_INVALID_ARGUMENT, "float tensors must be 4-byte aligned");
     uint32_t* seen_max = (uint32_t*)align_ptr(workspace);
     if (hipMemsetAsync(seen_max, 0, sizeof(uint32_t), s) != hipSuccess) return fail(G4S_ERR_HIP, "memset failed");
-    const dim3 grid((unsigned)((P + 255) / 256));
+    const dim3 grid(blocks256(P));
     hipLaunchKernelGGL(mip_filter_depth_kernel, grid, dim3(256), 0, s, P, xyz, V, cameras, znear, mip_filter_out, seen_max);
     hipLaunchKernelGGL(mip_filter_scale_kernel, grid, dim3(256), 0, s, P, mip_filter_out, seen_max, scale);
     return stage_done("mip_filter launch", s);
@@ -523,8 +523,8 @@ extern "C" int g4s_compact_scan(int P, const unsigned char* keep, int* out_count
     hipStream_t s = (hipStream_t)stream_;
     clear_error();
     if (P < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "P must not be negative");
-    if (!out_count || !workspace || (P > 0 && !keep)) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
-    if (workspace_bytes < g4s_compact_workspace(P)) return fail(G4S_ERR_INVALID_ARGUMENT, "workspace too small");
+    if (!out_count || !workspace || (P > 0 && !keep)) return null_pointer();
+    if (int rc = check_workspace(workspace, workspace_bytes, g4s_compact_workspace(P))) return rc;
     if (P == 0) {
         if (hipMemsetAsync(out_count, 0, sizeof(int), s) != hipSuccess) return fail(G4S_ERR_HIP, "memset failed");
         return G4S_OK;
@@ -542,7 +542,7 @@ extern "C" int g4s_compact_gather(int P, const unsigned char* keep, const char* 
     clear_error();
     if (P < 0 || nseg < 0 || dst_row0 < 0) return fail(G4S_ERR_INVALID_ARGUMENT, "P, nseg, dst_row0 must not be negative");
     if (P == 0 || nseg == 0) return G4S_OK;
-    if (!keep || !workspace || !src || !dst || !widths) return fail(G4S_ERR_INVALID_ARGUMENT, "NULL required pointer");
+    if (!keep || !workspace || !src || !dst || !widths) return null_pointer();
     for (int i = 0; i < nseg; i++)
         if (!src[i] || !dst[i] || widths[i] <= 0) return fail(G4S_ERR_INVALID_ARGUMENT, "tensor %d: NULL pointer or width <= 0", i);
     const uint32_t* block_off = (const uint32_t*)align_ptr((char*)workspace);

@@ -14,7 +14,7 @@
 #include <math.h>
 
 #include "../g4s_internal.h"
-#include "../g4s_device.h"
+#include "../fixed_sums.h"
 #include "../../../include/g4s_render_maps.h"
 #include "mesh_common.h"
 #include "vis_view.h"
@@ -101,36 +101,17 @@ __global__ void __launch_bounds__(256) align_sums_kernel(const AlignView* __rest
     }
     __shared__ double waves[4][ALIGN_TERMS];
 #pragma unroll
-    for (int c = 0; c < ALIGN_TERMS; c++) {
-        const double w = wave_fold(s[c]);
-        if (lane_id() == 0) waves[threadIdx.x >> 6][c] = w;
-    }
-    __syncthreads();
-    if (threadIdx.x < ALIGN_TERMS) {
-        const int c = (int)threadIdx.x;
-        partials[((size_t)v.block_base + blockIdx.x) * ALIGN_TERMS + c] = ((waves[0][c] + waves[1][c]) + waves[2][c]) + waves[3][c];
-    }
+    for (int c = 0; c < ALIGN_TERMS; c++) moment_fold(s[c], waves, c);
+    moment_store(waves, ALIGN_TERMS, partials + ((size_t)v.block_base + blockIdx.x) * ALIGN_TERMS);
 }
 
 // grid = views, 64 threads
 __global__ void __launch_bounds__(64) align_coeffs_kernel(const AlignView* __restrict__ views, const double* __restrict__ partials,
                                                           float* __restrict__ coeffs, int* __restrict__ counts) {
     const AlignView& v = views[blockIdx.x];
-    double s[ALIGN_TERMS] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    for (uint32_t b = threadIdx.x; b < v.n_blocks; b += 64u) {
-        const double* p = partials + ((size_t)v.block_base + b) * ALIGN_TERMS;
-#pragma unroll
-        for (int c = 0; c < ALIGN_TERMS; c++) s[c] += p[c];
-    }
-#pragma unroll
-    for (int c = 0; c < ALIGN_TERMS; c++) s[c] = wave_fold(s[c]);
-    if (threadIdx.x != 0) return;
-    const double n = s[0], St = s[1], Sd = s[2], Std = s[3], Sdd = s[4];
-    const double beta = (Std - St * Sd / n) / (Sdd - Sd * Sd / n);
-    const double alpha = (St - beta * Sd) / n;
-    coeffs[2 * (size_t)blockIdx.x] = (float)alpha;
-    coeffs[2 * (size_t)blockIdx.x + 1] = (float)beta;
-    counts[blockIdx.x] = (int)n;
+    double s[ALIGN_TERMS];
+    column_fold(partials + (size_t)v.block_base * ALIGN_TERMS, v.n_blocks, ALIGN_TERMS, s);
+    if (threadIdx.x == 0) scale_shift_solve(s, coeffs + 2 * (size_t)blockIdx.x, counts + blockIdx.x);
 }
 
 __global__ void __launch_bounds__(256) align_apply_kernel(const AlignView* __restrict__ views, int domain,

@@ -18,7 +18,7 @@
 #include <vector>
 
 #include "../g4s_internal.h"
-#include "../g4s_device.h"
+#include "../fixed_sums.h"
 #include "../../../include/g4s_render_maps.h"
 #include "mesh_common.h"
 #include "scan.h"
@@ -378,15 +378,8 @@ __global__ void __launch_bounds__(256) pf_refit_sums_kernel(const PfPlane* __res
         s[9] += z * z;
     }
 #pragma unroll
-    for (int t = 0; t < RF_TERMS; t++) {
-        const double w = wave_fold(s[t]);
-        if (lane_id() == 0) waves[threadIdx.x >> 6][t] = w;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < RF_TERMS) {
-        const int t = (int)threadIdx.x;
-        partials[((size_t)pl.rf_base + blockIdx.x) * RF_TERMS + t] = ((waves[0][t] + waves[1][t]) + waves[2][t]) + waves[3][t];
-    }
+    for (int t = 0; t < RF_TERMS; t++) moment_fold(s[t], waves, t);
+    moment_store(waves, RF_TERMS, partials + ((size_t)pl.rf_base + blockIdx.x) * RF_TERMS);
 }
 
 // grid = planes, 64 threads
@@ -395,12 +388,7 @@ __global__ void __launch_bounds__(64) pf_refit_solve_kernel(const PfPlane* __res
                                                             double* __restrict__ coef) {
     const PfPlane& pl = planes[blockIdx.x];
     double s[RF_TERMS];
-#pragma unroll
-    for (int t = 0; t < RF_TERMS; t++) {
-        double v = 0.0;
-        for (uint32_t b = threadIdx.x; b < pl.rf_blocks; b += 64u) v += partials[((size_t)pl.rf_base + b) * RF_TERMS + t];
-        s[t] = wave_fold(v);
-    }
+    column_fold(partials + (size_t)pl.rf_base * RF_TERMS, pl.rf_blocks, RF_TERMS, s);
     if (threadIdx.x != 0) return;
     double* mo = moments + (size_t)blockIdx.x * RF_TERMS;
     double* out = coef + 4 * (size_t)blockIdx.x;

@@ -17,7 +17,7 @@
 #include <vector>
 
 #include "../g4s_internal.h"
-#include "../g4s_device.h"
+#include "../fixed_sums.h"
 #include "../../../include/g4s_render_maps.h"
 #include "mesh_common.h"
 #include "scan.h"
@@ -69,24 +69,6 @@ struct JoinView {
 // ---------------------------------------------------------------------------------------------------------------------
 // A. k-means
 
-// the sums of one term over the workgroup's threads end in waves[wave][term]
-__device__ __forceinline__ void span_fold(double s, double (*waves)[KM_STRIDE], int term) {
-    const double w = wave_fold(s);
-    if (lane_id() == 0) waves[threadIdx.x >> 6][term] = w;
-}
-__device__ __forceinline__ void span_store(const double (*waves)[KM_STRIDE], int terms, double* __restrict__ row) {
-    __syncthreads();
-    if ((int)threadIdx.x < terms) {
-        const int c = (int)threadIdx.x;
-        row[c] = ((waves[0][c] + waves[1][c]) + waves[2][c]) + waves[3][c];
-    }
-}
-// lane 0: the partials' column `c` of a view, added by index
-__device__ __forceinline__ double column_fold(const KmView& v, const double* __restrict__ partials, int c) {
-    double s = 0.0;
-    for (uint32_t b = threadIdx.x; b < v.n_blocks; b += 64u) s += partials[((size_t)v.block_base + b) * KM_STRIDE + c];
-    return wave_fold(s);
-}
 
 __global__ void __launch_bounds__(256) km_moments_kernel(const KmView* __restrict__ views, double* __restrict__ partials) {
     const KmView& v = views[blockIdx.y];
@@ -110,8 +92,8 @@ __global__ void __launch_bounds__(256) km_moments_kernel(const KmView* __restric
     }
     __shared__ double waves[4][KM_STRIDE];
 #pragma unroll
-    for (int c = 0; c < 7; c++) span_fold(s[c], waves, c);
-    span_store(waves, 7, partials + ((size_t)v.block_base + blockIdx.x) * KM_STRIDE);
+    for (int c = 0; c < 7; c++) moment_fold(s[c], waves, c);
+    moment_store(waves, 7, partials + ((size_t)v.block_base + blockIdx.x) * KM_STRIDE);
 }
 
 // grid = views, 64 threads: the absolute tolerance of the view, and its state cleared
@@ -119,8 +101,7 @@ __global__ void __launch_bounds__(64) km_tolerance_kernel(const KmView* __restri
                                                           double tol, double* __restrict__ tol_abs, int* __restrict__ state) {
     const KmView& v = views[blockIdx.x];
     double s[7];
-#pragma unroll
-    for (int c = 0; c < 7; c++) s[c] = column_fold(v, partials, c);
+    column_fold(partials + (size_t)v.block_base * KM_STRIDE, v.n_blocks, KM_STRIDE, s);
     if (threadIdx.x != 0) return;
     const double n = s[0];
     const double vx = (s[4] - s[1] * s[1] / n) / n, vy = (s[5] - s[2] * s[2] / n) / n, vz = (s[6] - s[3] * s[3] / n) / n;
@@ -179,12 +160,12 @@ __global__ void __launch_bounds__(256) km_assign_kernel(const KmView* __restrict
             s2 += (double)y[i];
             s3 += (double)z[i];
         }
-        span_fold(s0, waves, 4 * k);
-        span_fold(s1, waves, 4 * k + 1);
-        span_fold(s2, waves, 4 * k + 2);
-        span_fold(s3, waves, 4 * k + 3);
+        moment_fold(s0, waves, 4 * k);
+        moment_fold(s1, waves, 4 * k + 1);
+        moment_fold(s2, waves, 4 * k + 2);
+        moment_fold(s3, waves, 4 * k + 3);
     }
-    span_store(waves, 4 * K, partials + ((size_t)v.block_base + blockIdx.x) * KM_STRIDE);
+    moment_store(waves, 4 * K, partials + ((size_t)v.block_base + blockIdx.x) * KM_STRIDE);
 }
 
 // grid = (K, views), 64 threads: the cluster's count, and in an iteration its next centre and the squared shift
@@ -196,8 +177,7 @@ __global__ void __launch_bounds__(64) km_update_kernel(const KmView* __restrict_
     if (state[4 * (size_t)blockIdx.y] != pass) return;
     const int k = (int)blockIdx.x;
     double s[4];
-#pragma unroll
-    for (int c = 0; c < 4; c++) s[c] = column_fold(v, partials, 4 * k + c);
+    column_fold(partials + (size_t)v.block_base * KM_STRIDE + 4 * k, v.n_blocks, KM_STRIDE, s);
     if (threadIdx.x != 0) return;
     const size_t row = (size_t)blockIdx.y * K + k;
     counts[row] = (int)s[0];

@@ -172,6 +172,24 @@ def test_means_fold_beyond_one_trip(hip_lib):
     within_yardstick("fold means", m, m64, np.abs(m32.astype(np.float64) - m64).max())
 
 
+def test_means_fold_beyond_four_loads(hip_lib):
+    """2 x 1024 x 513, all four terms on, with confidence: 2 x 2052 = 4104 block partials (K = 4), so eight threads of the
+    one-workgroup fold take a second trip of four row loads of which only the first is a row.  The four means by the rule of
+    the test above; two runs, the same bits.  Measured on an MI355X: error 1.9e-8, yardstick 6.2e-8."""
+    from types import SimpleNamespace
+    cams, d0, r, cur = ref.scene(2, 1024, 513, seed=31)
+    c = SimpleNamespace(name="fold4", n=2, H=1024, W=513, cams=cams, initial_depths=d0, reference_depths=r, depths=cur, lam=0.2,
+                        confidence=np.random.default_rng(37).uniform(1.2, 4.0, d0.shape).astype(np.float32), masks=None,
+                        gradient_masks=None)
+    a = losses_of(c)
+    with torch.no_grad():
+        m = twice(lambda: host(a.terms(dev(c.depths), dev(c.reference_depths), dev(c.confidence), use_gradient_loss=True,
+                                       use_normal_loss=True, use_curvature_loss=True)))
+    m32, m64 = (ref.means(*args, **kw) for args, kw in (ref.case_inputs(c, T) for T in (np.float32, np.float64)))
+    assert (m64 > 0).all()
+    within_yardstick("fold4 means", m, m64, np.abs(m32.astype(np.float64) - m64).max())
+
+
 @pytest.mark.parametrize("name", ("small", "full"))
 def test_each_term_alone(golden, name):
     """Term k with the others switched off: its mean has the bits it has with all terms on, the other slots are exactly 0,

@@ -224,6 +224,57 @@ def test_chart_prior_fold_beyond_one_trip(hip_lib):
     assert torch.equal(got[0], got[1])
 
 
+# ---- ... and beyond its first 4096: the second trip of four row loads per thread, and that trip's ragged tail
+FOLD_MARGIN = 4.0
+FOLD_FLOOR = 9.0 * 2.0 ** -24  # the eight levels of the float32 sum over a 256-thread block and the rounding of the mean
+
+
+def fold_within_yardstick(label, got, want64, got32):
+    """The means against the float64 restatement, relative to the largest of them: at most FOLD_MARGIN times the error of the
+    float32 restatement, and never asked for less than FOLD_FLOOR -- what the float32 block sums and the final rounding may
+    cost to first order when a term is of the size of the largest mean; behind the block sums everything is float64."""
+    got, want64, got32 = (torch.as_tensor(v).detach().double().cpu().reshape(-1) for v in (got, want64, got32))
+    top = float(want64.abs().max())
+    err, yard = float((got - want64).abs().max()) / top, float((got32 - want64).abs().max()) / top
+    print(f"{label}: error {err:.3e}, yardstick {yard:.3e}, floor {FOLD_FLOOR:.3e}")
+    assert top > 0 and err <= max(FOLD_MARGIN * yard, FOLD_FLOOR), (label, err, yard)
+
+
+def test_anisotropy_fold_beyond_four_loads(hip_lib):
+    """P = 256 * 4096 + 1: 4097 block partials (K = 1), so thread 0 of the fold takes a second trip of four loads of which
+    only the first is a row.  The mean against the restatement in float64 with the float32 one as the yardstick, and by the
+    bar of every loss scalar here; two runs, the same bits.  Measured on an MI355X: error 3.9e-9, yardstick 6.4e-8."""
+    P = 256 * 4096 + 1
+    g = torch.Generator().manual_seed(37)
+    scaling = (torch.rand((P, 2), generator=g) * torch.tensor([1.0, 0.1]) + 0.01).to(DEV)
+    got = [losses.anisotropy_loss(scaling, 5.0) for _ in range(2)]
+    want, yard = ref.anisotropy_loss(scaling.double(), 5.0), ref.anisotropy_loss(scaling, 5.0)
+    print(f"anisotropy, P = {P}: fused {float(got[0]):.9g} float64 restatement {float(want):.12g}")
+    assert float(want) > 0 and close_scalar(got[0], want)
+    fold_within_yardstick(f"anisotropy, P = {P}", got[0], want, yard)
+    assert torch.equal(got[0], got[1])
+
+
+def test_chart_prior_fold_beyond_four_loads(hip_lib):
+    """1000 x 1025: 125 x 33 = 4125 tiles of 8 x 32 (K = 5), ragged across; 29 threads of the fold take a second trip of four
+    loads of which only the first is a row.  The five means against the restatement in float64 on the same lattice inputs
+    with the float32 one as the yardstick, and by the bar of every loss scalar here; two runs, the same bits.  Measured on an
+    MI355X: error 6.9e-8 of the largest mean, yardstick 2.9e-8 (the floor of 5.4e-7 decides)."""
+    H, W = 1000, 1025
+    t = ref.lattice_inputs(H, W, 19, device=DEV)
+    torch.manual_seed(19)
+    shifts = losses.draw_pixel_shifts(H, W, device=DEV)
+    got = [losses.chart_prior_losses(*t, 5.0, shifts, 4.0, 20.0) for _ in range(2)]
+    want = ref.chart_prior_losses(*[x.double() for x in t], 5.0, shifts, 4.0, 20.0)
+    yard = ref.chart_prior_losses(*t, 5.0, shifts, 4.0, 20.0)
+    for k in range(5):
+        print(f"{H}x{W} mean {k}: fused {float(got[0][k]):.9g} float64 restatement {float(want[k]):.12g}")
+        assert close_scalar(got[0][k], want[k]), k
+    assert float(got[0][4]) > 0
+    fold_within_yardstick(f"{H}x{W} means", got[0], want, yard)
+    assert torch.equal(got[0], got[1])
+
+
 def small_training_inputs(H=48, W=64, P=5000):
     rn, sn, sd, pd, pn, pc = ref.lattice_inputs(H, W, 12, device=DEV)
     pkg = {"rend_normal": rn.requires_grad_(True), "surf_normal": sn.requires_grad_(True), "surf_depth": sd.requires_grad_(True)}

