@@ -249,6 +249,11 @@ SIGNATURES = {
     "g4s_plane_fit_score": (c_i, [c_i, c_p, c_p, c_i, c_p, ctypes.c_double, c_p, c_p, c_sz, c_p]),
     "g4s_plane_fit_refit": (c_i, [c_i, c_p, c_p, c_i, c_p, c_p, ctypes.c_double, c_p, ctypes.c_double, c_p, c_p, c_p, c_p, c_sz,
                                   c_p]),
+    "g4s_mesh_raster_workspace": (c_sz, [c_i, c_i, c_i]),
+    "g4s_mesh_raster": (c_i, [c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_f, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p,
+                              c_p, c_p, c_p, c_sz, c_p]),
+    "g4s_depth_dilate_workspace": (c_sz, [c_i, c_p]),
+    "g4s_depth_dilate": (c_i, [c_i, c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_p, c_p, c_p, c_sz, c_p]),
 }
 
 _lib = None

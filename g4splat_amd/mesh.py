@@ -33,7 +33,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._device import ViewStack, default_device, device_points, hip_device, host_f32, launch, on_device, to_np
+from ._device import ViewStack, default_device, device_points, focal_lengths, hip_device, host_f32, launch, on_device, to_np
 
 VOXELS_PER_BLOCK = 512
 
@@ -589,6 +589,14 @@ def focus_point(c2ws):
     return np.linalg.solve(M.sum(0), (M @ o[:, :, None]).sum(0))[:, 0]
 
 
+def sdf_tolerance(camera, depth, tolerance_in_pixels=1.5, max_tolerance=1e8):
+    """min(tolerance_in_pixels / focal x depth, max_tolerance) with focal the mean of the camera's two focal lengths at the
+    map's size: what evaluate_tsdf's use_sdf_tolerance subtracts from a depth map (an elementwise expression on the device)."""
+    H, W = depth.shape[-2:]
+    fx, fy = focal_lengths(camera, W, H)
+    return (tolerance_in_pixels / ((fx + fy) / 2.0) * depth).clamp(max=max_tolerance)
+
+
 class GaussianExtractor:
     """mesh_utils.py:73-182 (`GaussianExtractor`): render the views, fuse them into a TSDF volume on the GPU, extract
     the mesh.  `render(camera, gaussians, pipe=, bg_color=)` is gaussian_renderer.render."""
@@ -701,7 +709,8 @@ class GaussianExtractor:
 
     @torch.no_grad()
     def extract_mesh_tetra(self, downsample_ratio=0.5, gaussian_flatness=2e-4, truncation_margin=5e-3, texture_mesh=True,
-                           cells=None, n_binary_steps=8, to_host=True, generator=None):
+                           cells=None, n_binary_steps=8, to_host=True, generator=None, use_dilated_depth=False,
+                           use_sdf_tolerance=False):
         """extract_mesh_adaptive_tsdf.py:259-377 over the maps of reconstruction() (rendered with pipe.depth_ratio = 1.0, as
         the reference's configuration does): tetra points of the Gaussians, their tetrahedralisation (`cells` [T,4] as the
         reference's cells.pt holds them, or triangulate()), the adaptive TSDF at the points with trunc = truncation_margin
@@ -710,7 +719,11 @@ class GaussianExtractor:
         Stated differences (include/g4s_render_maps.h): triangles in tet order, only the default flags of
         AdaptiveTSDF.integrate, colours from the maps rendered here.  Without texture_mesh the colours are zero.
         Two additions to the reference's signature: `generator` seeds the random subset of tetra_points, and
-        `self.tetra` keeps (points, point scales, cells, sdf, edges) of the run until the next reconstruction()."""
+        `self.tetra` keeps (points, point scales, cells, sdf, edges) of the run until the next reconstruction().
+        use_dilated_depth replaces every view's depth -- and, for the colours, rgb -- by mesh_render.dilated_depths(..., 1.5,
+        1e-3 x extent) before the sample, the bisection and the colouring; use_sdf_tolerance then subtracts
+        min(1.5 / focal x depth, 1e-3 x extent) from the depth (evaluate_tsdf, extract_mesh_adaptive_tsdf.py:168-183).  With
+        both off nothing changes."""
         extent = cameras_spatial_extent(self.viewpoint_stack)
         trunc = float(truncation_margin) * extent
         points, scale = tetra_points(self.gaussians, downsample_ratio, float(gaussian_flatness) * extent, generator=generator)
@@ -718,20 +731,45 @@ class GaussianExtractor:
             cells = triangulate(points)
         cells = torch.as_tensor(cells).to(points.device)
         views = [(cam, d, None) for cam, d in zip(self.viewpoint_stack, self.depthmaps)]
+        coloured = None
+        if use_dilated_depth and texture_mesh:
+            # the colour maps go through the dilation with the depth they belong to: rendered first, so that the stack is
+            # dilated once for the sample, the bisection and the colouring
+            coloured = self._adjusted_views([(cam, d, c) for (cam, d, _n), c in zip(views, self._flat_colour_maps())], extent,
+                                            True, use_sdf_tolerance)
+            views = [(cam, d, None) for cam, d, _c in coloured]
+        elif use_dilated_depth or use_sdf_tolerance:
+            views = self._adjusted_views(views, extent, use_dilated_depth, use_sdf_tolerance)
         sdf = adaptive_tsdf(points, views, trunc)
         edges, faces = marching_tetrahedra(points, cells, sdf)
         self.tetra = (points, scale, cells, sdf, edges)
         verts = bisect_surface(points, edges, sdf, views, trunc, steps=n_binary_steps)
         cols = torch.zeros_like(verts)
         if texture_mesh and verts.size(0) > 0:
-            degree = self.gaussians.active_sh_degree
-            self.gaussians.active_sh_degree = 0
-            try:
-                rgbs = [self.render(cam)["render"].detach() for cam in self.viewpoint_stack]
-            finally:
-                self.gaussians.active_sh_degree = degree
-            _t, cols = adaptive_tsdf(verts, [(cam, d, c) for (cam, d, _n), c in zip(views, rgbs)], trunc, return_rgb=True)
+            if coloured is None:
+                coloured = [(cam, d, c) for (cam, d, _n), c in zip(views, self._flat_colour_maps())]
+            _t, cols = adaptive_tsdf(verts, coloured, trunc, return_rgb=True)
         return _returned(DeviceMesh(verts, cols, faces), to_host)
+
+    def _flat_colour_maps(self):
+        """The colour map of every view rendered at SH degree 0."""
+        degree = self.gaussians.active_sh_degree
+        self.gaussians.active_sh_degree = 0
+        try:
+            return [self.render(cam)["render"].detach() for cam in self.viewpoint_stack]
+        finally:
+            self.gaussians.active_sh_degree = degree
+
+    @staticmethod
+    def _adjusted_views(views, extent, use_dilated_depth, use_sdf_tolerance):
+        """The views as evaluate_tsdf's two depth switches leave them (extract_mesh_adaptive_tsdf.py:168-183)."""
+        from .mesh_render import dilated_depths
+        limit = 1e-3 * extent
+        if use_dilated_depth:
+            views = [(cam, d, c) for (cam, _d, _c), (d, c) in zip(views, dilated_depths(views, 1.5, limit))]
+        if use_sdf_tolerance:
+            views = [(cam, d - sdf_tolerance(cam, d, 1.5, limit), c) for cam, d, c in views]
+        return views
 
     @torch.no_grad()
     def extract_mesh_bounded_streaming(self, viewpoint_stack, voxel_size=0.004, sdf_trunc=0.02, depth_trunc=3,

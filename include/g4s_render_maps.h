@@ -1248,6 +1248,105 @@ int g4s_plane_fit_refit(int n_planes, const int* plane_offset, const float* poin
                         const int* best, double threshold, const double* priors, double alpha, unsigned char* inlier_mask,
                         double* moments, double* coefficients, char* workspace, size_t workspace_bytes, void* stream);
 
+/* =====================================================================================================================
+ * Mesh rasteriser and dilated depth (g4splat_amd/csrc/tsdf/mesh_render.hip).
+ *
+ * What the reference asks of pytorch3d: matcha/dm_scene/meshes.py render_mesh_with_pytorch3d (a MeshRasterizer with
+ * faces_per_pixel = 1, blur_radius = 0 and a shader over vertex colours) and its one live consumer, get_dilated_depth
+ * (2d-gaussian-splatting/extract_mesh_adaptive_tsdf.py:50-137), the `use_dilated_depth` switch of the tetrahedral
+ * extraction.  One primitive serves both: a nearest-face-per-pixel z-buffer.  As above, the semantics are this library's
+ * own, stated exactly (tests/mesh_render_ref.py restates them in numpy) and NOT bit-equal to pytorch3d: float32,
+ * round-to-nearest-even, correctly rounded / and sqrt, no fused multiply-add, evaluated left to right as written; every
+ * comparison with a NaN is false; min / max are IEEE minNum / maxNum.
+ *
+ * Camera.  world_view_transform Wv, projection_matrix Pm (16 HOST floats each, row-major, row-vector @ M: M[r][c] = M[4r + c]),
+ *   an image of W x H pixels (W H < 2^31), pixel_offset off = 0.5 or 0.0, znear > 0.
+ * Vertices.  For a position p: v_c = ((p0*Wv[0][c] + p1*Wv[1][c]) + p2*Wv[2][c]) + Wv[3][c] for c = 0, 1, 2 and
+ *   q_c = ((v_0*Pm[0][c] + v_1*Pm[1][c]) + v_2*Pm[2][c]) + Pm[3][c] for c = 0, 1, 3 (the adaptive-TSDF section's sums);
+ *   z = v_2;  sx = ((1 + q_0 / q_3) * float(W)) / 2 - off,  sy = ((1 + q_1 / q_3) * float(H)) / 2 - off, in pixel-index
+ *   units: pixel (i, j) = (row, column) samples (sx, sy) = (float(j), float(i)).  off = 0.5 gives the surfel rasteriser's
+ *   pixel centres, so a mesh depth map lines up with surf_depth; off = 0 is g4s_atsdf_sample's ix = ((1 + ndc) W) / 2.
+ *   A vertex is usable iff z > znear && z < inf && |sx| < inf && |sy| < inf.
+ * Faces [F,3] int32, F < 2^31.  A face is skipped, and never used as an address, if it names an index outside [0, V); else
+ *   if one of its vertices is not usable ("behind or non-finite", stats[0]; there is no near clipping); else if
+ *   |sx| > 32768 or |sy| > 32768 for one of them ("guard band", stats[1]); else if its snapped area is 0.  stats [2] int32
+ *   (device, optional) is cleared and counts the two named kinds.  Both windings are drawn.
+ * Coverage, in integers.  X_k = rint(sx_k * 256), Y_k = rint(sy_k * 256) (exact inside the guard band);
+ *   A = (X_1 - X_0)(Y_2 - Y_0) - (Y_1 - Y_0)(X_2 - X_0), s = sign(A).  For k = 0, 1, 2 with a = (k + 1) mod 3 and
+ *   b = (k + 2) mod 3 the oriented edge opposite vertex k is (dx, dy) = s (X_b - X_a, Y_b - Y_a), and at the sample
+ *   (PX, PY) = (256 j, 256 i):  E_k = dx (PY - Y_a) - dy (PX - X_a), in 64 bits (below 2^49 inside the face's box).  The
+ *   edge owns its samples iff dy < 0 (a left edge: the interior lies towards +x) or dy == 0 && dx > 0 (a top edge: y grows
+ *   downwards and the interior lies below).  The sample is covered iff for every k: E_k > 0, or E_k == 0 and edge k owns
+ *   its samples.  Two faces that share an edge walk it in opposite directions, so exactly one owns it: a sample inside
+ *   the union of the two belongs to exactly one of them, also on the shared edge or on a shared vertex.
+ * Weights and depth.  b_k = float(s) * ((sx_b - sx_a) * (float(i) - sy_a) - (sy_b - sy_a) * (float(j) - sx_a)) from the
+ *   unsnapped coordinates, negatives replaced by 0; sum = (b_0 + b_1) + b_2; if sum == 0: b_k = float(E_k) and the sum
+ *   again.  r_k = (b_k / sum) / z_k;  t = (r_0 + r_1) + r_2;  zpix = 1 / t;  w_k = r_k / t, the perspective-correct weights.
+ *   (Weights from the snapped coordinates cost up to 6e-4 of relative depth on sliver faces.)
+ * Winner.  Per pixel the covering face of smallest zpix, then of smallest index: the minimum of the 64-bit keys
+ *   float_bits(zpix) << 32 | face, by unsigned atomic min over a [H W] buffer of all-ones in the workspace.  Integer min
+ *   is order-independent: two runs give the same bits.
+ * Resolve, per pixel.  pix_to_face [H,W] int32: the winner or -1.  zbuf [H,W]: the key's high word as float, 0 where
+ *   nothing won.  bary [H,W,3]: the winner's w_k, 0 where nothing won.  attr_out [H,W,C], C <= G4S_MESH_RASTER_MAX_CHANNELS:
+ *   (w_0 a_0 + w_1 a_1) + w_2 a_2 of attributes [V,C], background [C] (HOST) where nothing won.  normal [H,W,3]: with
+ *   u = p_1 - p_0 and v = p_2 - p_0, g = (u_1 v_2 - u_2 v_1, u_2 v_0 - u_0 v_2, u_0 v_1 - u_1 v_0) divided by
+ *   len = sqrt((g_0 g_0 + g_1 g_1) + g_2 g_2) -- zero when len is not positive, and where nothing won --; with
+ *   G4S_MESH_RASTER_FLIP_NORMALS negated iff ((d_0 g_0 + d_1 g_1) + d_2 g_2) < 0 for d_c = centre_c - ((p_0c + p_1c) + p_2c) / 3
+ *   (camera_center, 3 HOST floats); then n_c = (g_0 Wv[0][c] + g_1 Wv[1][c]) + g_2 Wv[2][c]; with
+ *   G4S_MESH_RASTER_SURFELS_CONVENTION n_0 and n_1 negated (the reference's two switches, both on by default; the reference
+ *   multiplies by sign(d . g), which zeroes the normal of a face seen exactly edge-on).  seen [F] uint8: a plain store of 1
+ *   at every winning face, nothing else written: several cameras accumulate into one array.
+ *   Every output is optional, but one must be given.
+ * Dilated depth (g4s_depth_dilate).  A stack of views of any sizes as in the adaptive-TSDF section: Pm [V,16] (HOST), depth
+ *   [H,W] and optionally rgb [3,H,W] per view (all views or none), outputs of the same shapes that share no byte with an input or with
+ *   another output (checked on the host).
+ *   Everything happens in the view space of the map's own camera, so Wv is not needed.  Per view, with off = 0:
+ *   Vertex (i, j): d = depth[i][j], valid iff d > 0 && d < inf;  nx = (2 float(j)) / float(W) - 1, ny = (2 float(i)) / float(H) - 1;
+ *   p = (((nx - Pm[2][0]) * d) / Pm[0][0], ((ny - Pm[2][1]) * d) / Pm[1][1], d).
+ *   Faces: the grid of get_manifold_meshes_from_pointmaps.  Cell (i, j), i < H - 1, j < W - 1, with a = i W + j has face
+ *   i (W - 1) + j = (a, a + W, a + 1) and face (H - 1)(W - 1) + i (W - 1) + j = (a + W + 1, a + 1, a + W): the reference's
+ *   indices.  The list is never materialised.  A face with an invalid vertex does not exist: it is neither drawn nor part
+ *   of a normal.
+ *   Vertex normal: n = 0, then n_c <- n_c + g_c over the incident faces (a, b, c) in ascending face index, g as above with
+ *   u = p_b - p_a and v = p_c - p_a; len = max(sqrt((n_0 n_0 + n_1 n_1) + n_2 n_2), 1e-6).  It points towards the camera on
+ *   a fronto-parallel patch.
+ *   focal = ((Pm[0][0] * float(W)) / 2 + (Pm[1][1] * float(H)) / 2) / 2;  delta = min((dilation_pixels / focal) * d, max_dilation);
+ *   p'_c = p_c + delta * (n_c / len).  The grid of the p' is rasterised as above with v = p' (no Wv); colours are
+ *   (w_0 a_0 + w_1 a_1) + w_2 a_2 per channel of a = min(max(rgb, 0), 1) at the face's vertices.  Where no face won, the
+ *   outputs take the input depth and rgb.
+ *   Differences from the reference, on purpose.  One pixel convention on all three sides -- back-projection, raster and the
+ *   TSDF's sampler -- where the reference has three, so dilation_pixels = 0 returns the map up to rounding.  The colour is
+ *   the interpolated vertex colour (pytorch3d's soft blend adds O(1e-4) of background).  rgb is restored wherever nothing
+ *   was drawn (the reference tests the depth for 0 after having filled it, so its rgb fill never fires).  Invalid depths
+ *   make holes instead of faces to the origin.  pytorch3d draws no sample that lies exactly on an edge; here the fill
+ *   rule is watertight.  The last row and column lie on edges the fill rule leaves out and are served by the fallback.
+ *
+ * Every argument is checked on the host before anything is launched; sizes beyond the stated limits are refused with a
+ * message.  g4s_mesh_raster reads nothing back and does not synchronise -- the list of faces too large for one thread and
+ * its length stay on the device --, so it can be captured into a graph.  g4s_depth_dilate uploads its view table like every
+ * view-stack entry point (one host synchronisation, before the first launch) and reads nothing back.
+ */
+#define G4S_MESH_RASTER_MAX_CHANNELS 16
+#define G4S_MESH_RASTER_FLIP_NORMALS 1
+#define G4S_MESH_RASTER_SURFELS_CONVENTION 2
+
+/* Bytes of device workspace of g4s_mesh_raster (0 for sizes out of range). */
+size_t g4s_mesh_raster_workspace(int n_faces, int width, int height);
+
+int g4s_mesh_raster(int n_vertices, const float* vertices, int n_faces, const int* faces, const float* world_view,
+                    const float* projection, const float* camera_center, int width, int height, float pixel_offset,
+                    float znear, int n_channels, const float* attributes, const float* background, int flags,
+                    int* pix_to_face, float* zbuf, float* bary, float* attr_out, float* normal, unsigned char* seen,
+                    int* stats, char* workspace, size_t workspace_bytes, void* stream);
+
+/* Bytes of device workspace of g4s_depth_dilate: the view table, 12 B of vertex, 8 B of key and 8 B of list per pixel
+ * (0 for sizes out of range: at most 65535 views, fewer than 2^31 pixels together). */
+size_t g4s_depth_dilate_workspace(int n_views, const int* sizes);
+
+int g4s_depth_dilate(int n_views, const float* projection, const int* sizes, const float* const* depth,
+                     const float* const* rgb, float dilation_pixels, float max_dilation, float znear,
+                     float* const* depth_out, float* const* rgb_out, char* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
